@@ -16,7 +16,7 @@ line says so: ml_trigger_rate); the configs that exercise it are in the "configs
           (SURVEY.md 8d), S = 1024 and S = 1
     cfg4  (4080,3060) [synthesised matrix] vs 16 x RS(255,223) on the same erasure patterns, 65536 frames, S = 1
           + cfg4_S1024: the same code and RS(255,223) in packet mode (S = 1024), the first 4096 frames of that stream
-          (alone: `--config 4 --S 1` / `--config 4 --S 1024`)
+          (alone: `--full --config 4 --S 1` / `--full --config 4 --S 1024`)
     cfg5  mixed (4000,2000) + (2040,1530) stream, 1:1, 10 % -- at N = 1 the whole 65536-frame stream (the strong-scaling anchor),
           one GPU's 1/8 share, and an S = 64 run whose final gather moves the decoded outputs
 
@@ -26,7 +26,7 @@ the roofline fraction they give, ML-trigger / rank-deficient rates and a bounded
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
-    ... bench.py --gpus 8 --config 5 --gather outputs      # BASELINE configs[4] on an 8-GPU node (strong scaling)
+    ... bench.py --full --gpus 8 --config 5 --gather outputs      # BASELINE configs[4] on an 8-GPU node (strong scaling)
 
 One process per GPU; frames are sharded with no data-path collective (cfg 2: weak scaling, 4096 frames per GPU; cfg 5:
 the 65536-frame mixed stream split over the ranks); RCCL is used once, for the final gather (status words, or outputs +
@@ -34,6 +34,15 @@ status words with --gather outputs).  Rank 0 prints ONE JSON line.
 
 The oracle (oracle/) is used here only (a) to time the CPU baseline and (b) to spot-check decoded frames after the timed
 region; the measured path is the HIP library behind the C ABI.
+
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: it sets up the cfg 2 batch at --S, runs W
+untimed and K timed steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+Everything described above besides that -- the S = 1 companion run, the CPU baselines, the cfg 3/4/5 block (or `--config
+3/4/5` alone), the sustained / pipelined / encoder / in-place / copy-probe / xGMI figures, the replayed PMC roofline, the
+oracle spot checks and the detail file (--detail-out) -- runs with `--full`.
+
+`--dump-outputs DIR` writes what the timed path returned in its last headline step as float32 .npy files (dump_outputs):
+two builds given the same arguments decode the same seeded inputs and can be compared output for output.
 """
 import argparse
 import json
@@ -64,6 +73,10 @@ WORKLOADS = {
     "cfg4p": dict(code=3, channel=("uniform", 0.10), frames=4096),
     "cfg5": dict(codes=(2, 1), channel=("uniform", 0.10), frames=65536),
 }
+
+
+DUMP_SEED, DUMP_FRAMES, DUMP_LANES = 20261016, 256, 16   # --dump-outputs: the fixed sample of the decoded symbols
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def alg_bytes_per_frame(n, S):
@@ -358,19 +371,24 @@ class Gpu:
                     kernel_ms={kk: (v[0] / max(v[1], 1)) for kk, v in prof.items() if v[1] > 0})
 
 
-def summarize(g, r, cw, n, k, S, steps, frames_all_ranks):
-    """Common numbers of one timed decode run."""
+def summarize(g, r, cw, n, k, S, steps, frames_all_ranks, checks=True):
+    """Common numbers of one timed decode run (checks=False: the timing figures only, no statistics or verification)."""
     torch = g.torch
     F = cw.shape[0]
-    ok_frames = r["st"] <= 1
-    verified = bool(torch.equal(r["out"][ok_frames], cw[ok_frames]))
-    resid = r["res"][r["res"] > 0].float()
     ms = r["dt"] / steps * 1e3
-    ab = alg_bytes_per_frame(n, S) * F
-    return {
+    timing = {
         "frames": F, "frames_per_s": frames_all_ranks * steps / r["dt"], "ms_per_step": ms, "steps": steps,
         "recovered_GBps": frames_all_ranks * steps / r["dt"] * k * S / 1e9,
         "kernel_ms": r["kernel_ms"], "kernels": r["names"],
+    }
+    if not checks:
+        return timing
+    ok_frames = r["st"] <= 1
+    verified = bool(torch.equal(r["out"][ok_frames], cw[ok_frames]))
+    resid = r["res"][r["res"] > 0].float()
+    ab = alg_bytes_per_frame(n, S) * F
+    return {
+        **timing,
         "alg_bytes_per_step": ab, "roofline_frac": ab / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
         "sweeps_hist": torch.bincount(r["sw"], minlength=12).cpu().numpy().tolist(),
         "ml_trigger_rate": float((r["res"] > 0).float().mean()) if F else 0.0,
@@ -396,6 +414,34 @@ def pick_samples(r, sym, era, want_ml):
     return ids, take(sym), take(era), take(r["out"]), take(r["sw"]), take(r["st"])
 
 
+def dump_outputs(path, r, rank, world):
+    """--dump-outputs: what the timed decode returned in its last step, as float32 .npy files under `path` (each value a byte or
+    a small count, exact in float32): `sweeps`, `residual` and `status` of every frame, and `decoded_sample`, a fixed seeded
+    sample of the decoded symbols -- DUMP_FRAMES frames x all n symbols x DUMP_LANES byte lanes of the S-byte packets (the whole
+    output is F x n x S bytes, 8.6 GB at the defaults).  With N > 1 every rank writes its own frames, `<name>_rank<r>.npy`."""
+    import torch
+    out = r["out"]
+    F, n = out.shape[0], out.shape[1]
+    S = out.shape[2] if out.ndim == 3 else 1
+    rng = np.random.default_rng(DUMP_SEED)
+    frames = np.sort(rng.choice(F, size=min(DUMP_FRAMES, F), replace=False))
+    lanes = np.sort(rng.choice(S, size=min(DUMP_LANES, S), replace=False))
+    fi = torch.from_numpy(frames).to(out.device)
+    li = torch.from_numpy(lanes).to(out.device)
+    arrays = {"decoded_sample": out.reshape(F, n, S).index_select(0, fi).index_select(2, li)}
+    # the status words of every frame (12 B per frame as float32) while they fit in a quarter of the budget, else of the sampled frames
+    all_frames = 12 * F <= DUMP_LIMIT_BYTES // 4
+    for key, name in (("sw", "sweeps"), ("res", "residual"), ("st", "status")):
+        arrays[name] = r[key] if all_frames else r[key].index_select(0, fi)
+    arrays = {name: a.cpu().numpy().astype(np.float32) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_LIMIT_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+
+
 def oracle_check(code_ind, S, sample):
     from ldpc_erasure_codes_amd import codes
     from oracle import oracle_py
@@ -419,7 +465,7 @@ def run_cfg2(g, args):
     h, n, k = g.code(1)
     F = args.frames
     result = {}
-    for S in ([args.S, 1] if (args.S != 1 and not args.no_s1) else [args.S]):
+    for S in ([args.S, 1] if (args.full and args.S != 1 and not args.no_s1) else [args.S]):
         steps = args.steps if S == args.S else max(args.steps, 20)
         cw, sym, era, _ = g.make_batch("cfg2", 1, S, frame0=g.rank * F, nframes=F)   # every rank its own frames
         counts = [F] * g.world
@@ -428,6 +474,12 @@ def run_cfg2(g, args):
                           after_steps=lambda out, sw, res, st: sharding.gather_status(torch.stack([sw, res, st]), counts))
         r["dt"] = sharding.max_over_ranks(r["dt"], g.dev)
         assert len(r["extra"]) == g.world
+        if S == args.S and args.dump_outputs:
+            dump_outputs(args.dump_outputs, r, g.rank, g.world)
+        if not args.full:   # a plain run: the headline's timing and nothing else
+            result[S] = summarize(g, r, cw, n, k, S, steps, g.world * F, checks=False)
+            del cw, sym, era, r
+            continue
         s = summarize(g, r, cw, n, k, S, steps, g.world * F)
         s["verified"] = s["verified"] and int(r["st"].max()) == 0   # every frame of cfg 2 decodes to its codeword
         s["sample"] = pick_samples(r, sym, era, False)
@@ -819,7 +871,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="headline only (skip the cfg 3/4/5 block)")
     ap.add_argument("--no-s1", action="store_true", help="skip the S = 1 companion runs (profiling of one batch shape)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: S = 1 companion, CPU baselines, the cfg 3/4/5 block or --config 3/4/5, sustained / "
+                         "pipelined / encoder / in-place / copy-probe figures, PMC roofline, oracle spot checks, detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed headline step's outputs to DIR/<name>.npy (float32; a fixed sample of the symbols)")
+    ap.add_argument("--detail-out", default=os.path.join(ROOT, "bench_detail.json"),
+                    help="--full: file for the whole result (the line on stdout is the compact form)")
     args = ap.parse_args()
+    if args.config != "2" and not args.full:
+        ap.error(f"--config {args.config} is a side configuration: run it with --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -828,8 +889,8 @@ def main():
         if rank == 0:
             print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}; launch with torch.distributed.run", file=sys.stderr)
         sys.exit(2)
-    want_block = args.config == "2" and world == 1 and not args.no_configs
-    do_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_block = args.full and args.config == "2" and world == 1 and not args.no_configs
+    do_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
 
     # ---- CPU legs first (forked workers must not inherit a HIP context)
     cpu = {}
@@ -957,10 +1018,11 @@ def main():
                                    f"random erasures, batch={args.frames} frames per GPU, max_sweeps=10, ML on",
                        "frames_per_gpu": args.frames, "S": args.S, "per": 0.10, "code": "n2040_k1530",
                        "sharding": f"{world} x {args.frames} independent frames, status gather over RCCL"},
-            "verified_bit_exact": main_r["verified"], "sweeps_hist": main_r["sweeps_hist"],
-            "ml_trigger_rate": main_r["ml_trigger_rate"], "kernel_ms": main_r["kernel_ms"],
-            "roofline": main_r["roofline"],
+            "kernel_ms": main_r["kernel_ms"],
         }
+        if args.full:
+            line.update({"verified_bit_exact": main_r["verified"], "sweeps_hist": main_r["sweeps_hist"],
+                         "ml_trigger_rate": main_r["ml_trigger_rate"], "roofline": main_r["roofline"]})
         if main_r.get("sustained"):
             line["sustained"] = main_r["sustained"]
         if main_r.get("pipelined"):
@@ -1007,19 +1069,19 @@ def main():
             line["cpu_baseline"] = head["cpu_baseline"]
     # ---- ONE line on stdout, short enough for the driver's tail: the required keys, `roofline`, `cpu_baseline`
     # and a flat per-config `summary` LAST; everything else (per-kernel name maps, workload prose, histograms, the ML stage's other
-    # modes, the CPU legs' sample texts) goes to the detail file written by this same run.
+    # modes, the CPU legs' sample texts) goes to the detail file written by a --full run (--detail-out; not a committed file:
+    # copy it under profiles/ deliberately when a line is recorded).
     line["non_default_knobs"] = non_default_knobs
-    detail_rel = os.path.join("profiles", "round4_bench_detail.json")
-    written = []
-    for dpath in (os.path.join(ROOT, detail_rel), os.path.join(ROOT, "gpurun_out", "round4_bench_detail.json")):
+    written = None
+    if args.full:
+        dpath = os.path.abspath(args.detail_out)
         try:
-            if os.path.isdir(os.path.dirname(dpath)):
-                with open(dpath, "w") as fh:
-                    json.dump(line, fh, indent=1)
-                written.append(os.path.relpath(dpath, ROOT))
+            with open(dpath, "w") as fh:
+                json.dump(line, fh, indent=1)
+            written = os.path.relpath(dpath, ROOT)
         except OSError as e:
             print(f"bench.py: could not write {dpath}: {e}", file=sys.stderr)
-    print(json.dumps(compact_line(line, written[0] if written else None), separators=(",", ":")))
+    print(json.dumps(compact_line(line, written), separators=(",", ":")))
 
 
 def _r(x, sig=4):
@@ -1098,7 +1160,8 @@ def compact_line(line, detail_file):
                                "sample": (cb.get("sample") or "")[:150], "single_thread": _r(cb.get("single_thread"), 4),
                                "cpu_model": cb.get("cpu_model")}
         out["gpu_over_cpu"] = _r(line.get("gpu_over_cpu"), 4)
-    out["detail_file"] = detail_file
+    if detail_file:   # (written by --full runs only)
+        out["detail_file"] = detail_file
     if line.get("non_default_knobs"):
         out["non_default_knobs"] = line["non_default_knobs"]   # a measurement under LDPC_AMD_* variables says so in the line
     sm = {}

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r3q
 rm -rf $O && mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats3 -o cfg3 -- python3 bench.py --config 3 --no-s1 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats3 -o cfg3 -- python3 bench.py --full --config 3 --no-s1 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 python3 - <<'PY'
 import csv, glob
 for f in glob.glob('gpurun_out/r3q/stats3/**/*kernel_stats.csv', recursive=True):

@@ -8,12 +8,12 @@ R=$GRAFT_REPO_ROOT
 cd $R
 O=gpurun_out/r3prof
 rm -rf $O && mkdir -p $O
-A2="--steps 10 --warmup 3 --no-cpu-baseline --no-configs --sustain-seconds 0"
-P2="--steps 2 --warmup 1 --no-cpu-baseline --no-configs --sustain-seconds 0"
-A3="--config 3 --no-s1 --steps 10 --warmup 2 --no-cpu-baseline"
-P3="--config 3 --no-s1 --steps 3 --warmup 2 --no-cpu-baseline"
-A4="--config 4 --S 1024 --steps 5 --no-cpu-baseline"
-P4="--config 4 --S 1024 --steps 3 --no-cpu-baseline"
+A2="--full --steps 10 --warmup 3 --no-cpu-baseline --no-configs --sustain-seconds 0"
+P2="--full --steps 2 --warmup 1 --no-cpu-baseline --no-configs --sustain-seconds 0"
+A3="--full --config 3 --no-s1 --steps 10 --warmup 2 --no-cpu-baseline"
+P3="--full --config 3 --no-s1 --steps 3 --warmup 2 --no-cpu-baseline"
+A4="--full --config 4 --S 1024 --steps 5 --no-cpu-baseline"
+P4="--full --config 4 --S 1024 --steps 3 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats2 -o cfg2 -- python3 bench.py $A2 > $O/bench_cfg2_stats.json 2> $O/bench_cfg2_stats.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch2 -o cfg2 -- python3 bench.py $P2 > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write2 -o cfg2 -- python3 bench.py $P2 > /dev/null 2>&1

@@ -50,7 +50,7 @@ def main():
     ap.add_argument("--workload", default="cfg2", help="bench.py workload the passes ran (cfg2, cfg3, cfg4p): bench.py replays traffic per workload")
     ap.add_argument("--valu", help="directory of a --pmc VALUBusy pass -> <tag>_valubusy.json")
     ap.add_argument("--outdir", default=None, help="where the summaries go (default: profiles/)")
-    ap.add_argument("--cmd", default="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline", help="the profiled command (for the note)")
+    ap.add_argument("--cmd", default="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline", help="the profiled command (for the note)")
     a = ap.parse_args()
     out = a.outdir or os.path.join(ROOT, "profiles")
     os.makedirs(out, exist_ok=True)
