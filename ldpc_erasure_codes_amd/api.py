@@ -45,6 +45,11 @@ EXPORTS = [
     "ldpc_amd_fec_rx_destroy", "ldpc_amd_fec_rx_push", "ldpc_amd_fec_rx_push_many", "ldpc_amd_fec_rx_flush", "ldpc_amd_fec_rx_dropped",
     "ldpc_amd_set_profiling", "ldpc_amd_get_profile", "ldpc_amd_selftest", "ldpc_amd_copy_probe", "ldpc_amd_gf_tables", "ldpc_amd_version",
 ]
+# every symbol include/ldpc_erasure_amd_wire_dev.h declares (the device-resident wire path)
+EXPORTS_WIRE_DEV = [
+    "ldpc_amd_fec_packetize_dev", "ldpc_amd_fec_rx_dev_create", "ldpc_amd_fec_rx_dev_destroy", "ldpc_amd_fec_rx_dev_push_many",
+    "ldpc_amd_fec_rx_dev_flush", "ldpc_amd_fec_rx_dev_dropped",
+]
 
 
 class LdpcAmdError(RuntimeError):
@@ -141,6 +146,15 @@ def load_library():
     L.ldpc_amd_fec_rx_push_many.argtypes = [vp, vp, C.c_long, vp, vp, vp, i32, C.POINTER(C.c_long)]
     L.ldpc_amd_fec_rx_dropped.argtypes = [vp]
     L.ldpc_amd_fec_rx_dropped.restype = C.c_long
+    # device-resident wire path (include/ldpc_erasure_amd_wire_dev.h)
+    L.ldpc_amd_fec_packetize_dev.argtypes = [vp, vp, i64, i32, i32, C.c_uint, C.c_uint, vp]
+    L.ldpc_amd_fec_rx_dev_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
+    L.ldpc_amd_fec_rx_dev_destroy.argtypes = [vp]
+    L.ldpc_amd_fec_rx_dev_destroy.restype = None
+    L.ldpc_amd_fec_rx_dev_push_many.argtypes = [vp, vp, i64, vp, vp, vp, i32, C.POINTER(i64)]
+    L.ldpc_amd_fec_rx_dev_flush.argtypes = [vp, vp, vp, C.POINTER(i32)]
+    L.ldpc_amd_fec_rx_dev_dropped.argtypes = [vp]
+    L.ldpc_amd_fec_rx_dev_dropped.restype = i64
     L.ldpc_amd_data_out.argtypes = [vp, vp, i32, C.c_long, C.POINTER(ErrorType)]
     L.ldpc_amd_set_profiling.argtypes = [vp, i32]
     L.ldpc_amd_get_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64)]
@@ -449,6 +463,24 @@ class Context:
         self._check(self._L.ldpc_amd_data_out(self._h, None, code_ind, num_frames, C.byref(st)), "data_out")
         return st.num_LDPC_errors, st.num_RS_errors
 
+    # -- device-resident wire path (include/ldpc_erasure_amd_wire_dev.h)
+    def fec_packetize_device(self, frames, fec_class=1, block0=0, out=None):
+        """frames: torch uint8 [F][n][S] on this context's device -> packets [F*n][8+S] (the bytes of fec_packetize).
+        Asynchronous on the context's stream."""
+        import torch
+        assert _is_torch(frames) and frames.dtype == torch.uint8 and frames.ndim == 3
+        F, n, S = frames.shape
+        if out is None:
+            out = torch.empty((F * n, 8 + S), dtype=torch.uint8, device=frames.device)
+        assert tuple(out.shape) == (F * n, 8 + S) and out.dtype == torch.uint8
+        self._check(self._L.ldpc_amd_fec_packetize_dev(self._h, _ptr(frames), F, n, S, fec_class, block0, _ptr(out)),
+                    "fec_packetize_dev")
+        return out
+
+    def fec_rx_device(self, n, k, S):
+        """A two-buffer reassembler whose packets and blocks stay on this context's device (FecRxDevice)."""
+        return FecRxDevice(self, n, k, S)
+
 
 # ---------------------------------------------------------------------------------------------------------
 # Host-side wire format (include/ldpc_erasure_amd_wire.h): FEC header, packetiser, two-buffer reassembler.
@@ -523,6 +555,66 @@ class FecRx:
         if self._h:
             self._L.ldpc_amd_fec_rx_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FecRxDevice:
+    """FecRx for packets already in GPU memory (include/ldpc_erasure_amd_wire_dev.h): the same blocks, erasure flags,
+    consumed and dropped counts, byte for byte.  Payload movement is asynchronous on the context's stream; the returned
+    block numbers and counts are final when a call returns.  Close it before its Context."""
+
+    def __init__(self, ctx, n, k, S):
+        self._ctx, self._L = ctx, ctx._L
+        h = C.c_void_p()
+        ctx._check(self._L.ldpc_amd_fec_rx_dev_create(ctx._h, n, k, S, C.byref(h)), "fec_rx_dev_create")
+        self._h, self.n, self.k, self.S = h, n, k, S
+
+    def _device(self):
+        import torch
+        return torch.device("cuda", self._ctx.device)
+
+    def push_many(self, packets, max_blocks):
+        """packets: torch uint8 [P][8+S] on the device.  Returns (blocks int32 [B], sym torch uint8 [B][n][S],
+        erased torch uint8 [B][n], consumed)."""
+        import torch
+        assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.shape[1] == 8 + self.S
+        sym = torch.empty((max(max_blocks, 1), self.n, self.S), dtype=torch.uint8, device=packets.device)
+        er = torch.empty((max(max_blocks, 1), self.n), dtype=torch.uint8, device=packets.device)
+        blocks = np.zeros(max(max_blocks, 1), dtype=np.int32)
+        used = C.c_int64(0)
+        nb = self._ctx._check(self._L.ldpc_amd_fec_rx_dev_push_many(self._h, _ptr(packets) if packets.numel() else None, packets.shape[0],
+                                                                    _ptr(sym), _ptr(er), blocks.ctypes.data, max_blocks, C.byref(used)),
+                              "fec_rx_dev_push_many")
+        return blocks[:nb], sym[:nb], er[:nb], used.value
+
+    def flush(self):
+        """None, or (block number, sym torch [n][S], erased torch [n]) of the block the end of the stream closes."""
+        import torch
+        sym = torch.empty((self.n, self.S), dtype=torch.uint8, device=self._device())
+        er = torch.empty(self.n, dtype=torch.uint8, device=self._device())
+        blk = C.c_int(-1)
+        rc = self._ctx._check(self._L.ldpc_amd_fec_rx_dev_flush(self._h, _ptr(sym), _ptr(er), C.byref(blk)), "fec_rx_dev_flush")
+        return (blk.value, sym, er) if rc == 1 else None
+
+    @property
+    def dropped(self):
+        return int(self._L.ldpc_amd_fec_rx_dev_dropped(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ldpc_amd_fec_rx_dev_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
     def __del__(self):
         try:

@@ -13,15 +13,16 @@ OBJ="${LDPC_AMD_OBJDIR:-$HERE/obj}"
 mkdir -p "$OBJ"
 echo "$FLAGS" > "$OBJ/flags.new"
 if ! cmp -s "$OBJ/flags.new" "$OBJ/flags" 2>/dev/null; then rm -f "$OBJ"/*.o; mv "$OBJ/flags.new" "$OBJ/flags"; fi
-COMMON="$HERE/internal.h $ROOT/include/ldpc_erasure_amd.h $ROOT/include/ldpc_erasure_amd_synth.h $ROOT/include/ldpc_erasure_amd_wire.h $ROOT/include/ldpc_erasure_amd_multi.h"
+COMMON="$HERE/internal.h $ROOT/include/ldpc_erasure_amd.h $ROOT/include/ldpc_erasure_amd_synth.h $ROOT/include/ldpc_erasure_amd_wire.h $ROOT/include/ldpc_erasure_amd_multi.h $ROOT/include/ldpc_erasure_amd_wire_dev.h"
 declare -A DEPS=(
   [kernels.hip]="$HERE/gf256_dev.h $HERE/peel_relax.inc $HERE/ml_kernel.inc $HERE/ml_pi.inc $HERE/rs_kernels.inc $HERE/fpga_kernels.inc"
   [api.cpp]="$HERE/builtin_codes_gen.inc"
   [wire.cpp]=""
   [multi.hip]=""
+  [wire_dev.hip]=""
 )
 pids=()
-for src in kernels.hip api.cpp wire.cpp multi.hip; do
+for src in kernels.hip api.cpp wire.cpp multi.hip wire_dev.hip; do
   o="$OBJ/${src%.*}.o"
   stale=0
   [ -f "$o" ] || stale=1
@@ -34,5 +35,5 @@ for src in kernels.hip api.cpp wire.cpp multi.hip; do
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/kernels.o" "$OBJ/api.o" "$OBJ/wire.o" "$OBJ/multi.o"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/kernels.o" "$OBJ/api.o" "$OBJ/wire.o" "$OBJ/multi.o" "$OBJ/wire_dev.o"
 echo "$OUT"

@@ -1,0 +1,471 @@
+// wire_dev.hip -- device-resident FEC wire path (include/ldpc_erasure_amd_wire_dev.h): the packetiser and the two-buffer
+// reassembler of csrc/wire.cpp for data that is already in GPU memory, byte for byte the host functions' output.
+//
+// Reference: OpenCL/device/ldpc_erasure_encoder_VITA_in_UDP_out.cl:84-129,168-211 (headers written in a kernel) and
+// OpenCL/device/ldpc_erasure_decoder_with_reordering_logic.cl:44-141,214-243 (reassembly in a kernel in front of the decoder).
+//
+// The reassembler's rule depends only on the headers, never on the payloads, so one push_many call is split into a PLAN and a
+// DATA MOVEMENT:
+//   (a) fec_rx_headers   every packet's header -> one dense u32, block << 16 | symbol                         (parallel)
+//   (b) fec_rx_scan      one wavefront replays ldpc_amd_fec_rx_push over the dense headers, 64 packets per step; per packet
+//                        it writes a destination (the SERIAL of the block it went to, or -1 = dropped), per close the wire
+//                        block number, and at the end the state.  The host reads the state back (the call returns it).
+//   (c) fec_rx_winners   atomicMax of the packet index into a [(closes + 2)][n] table: the host copies duplicates in stream
+//                        order, so the last one is what stays                                                   (parallel)
+//   (d) fec_rx_move<1>   closed blocks -> sym_batch / erased_batch                                              (parallel)
+//   (e) fec_rx_move<0>   the two blocks still open -> the two staging planes                                    (parallel)
+// Serials: the block that is current when the call starts is serial 0, the next one serial 1, and the t-th close of the call
+// (0-based) opens serial t + 2.  Blocks close in the order they were opened (cur closes, next becomes cur), so serial s is closed
+// slot s of the call when s < closes; serials closes and closes + 1 are the blocks still open at the end (current, next).  A
+// serial s lives in staging buffer (cb + s) & 1, cb = the current block's buffer at the start of the call (the buffers rotate
+// on every close, :241).  Serials 0 and 1 were carried in from earlier calls: their staging planes hold what those calls
+// received; every other serial starts erased.  (d) reads the staging planes of carried blocks that close; (e) rewrites the
+// plane of serial s >= 2, which is the plane of serial s - 2 -- a block (d) may read -- so (e) is a launch after (d).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+
+#include "internal.h"
+#include "../../include/ldpc_erasure_amd_wire_dev.h"
+
+using namespace ldpc_amd;
+
+namespace {
+
+constexpr int kHdr = LDPC_AMD_FEC_HEADER_BYTES;
+constexpr int kThreads = 256;
+constexpr int kScanPrefetch = 16;   // groups of 64 dense headers a scan lane holds in flight ahead of the one it works on
+
+// Result record of one scan, read back by the host (32-bit words, then the closed blocks' wire numbers).
+enum : int { R_CUR, R_NEXT, R_CCNT, R_NCNT, R_CLOSES, R_ERR, R_CONSUMED_LO, R_CONSUMED_HI, R_DROPPED_LO, R_DROPPED_HI, R_WORDS = 16 };
+
+__device__ __forceinline__ uint64_t fec_header(unsigned fec_class, unsigned block, unsigned symbol)
+{
+    // ldpc_amd_fec_header_pack: {class:8 | block:8 | symbol:16} in both halves of a 64-bit word
+    const uint64_t d = ((uint64_t)(fec_class & 0xffu) << 24) | ((uint64_t)(block & 0xffu) << 16) | (uint64_t)(symbol & 0xffffu);
+    return (d << 32) | d;
+}
+
+inline unsigned grid_for(int64_t items)
+{
+    const int64_t b = (items + kThreads - 1) / kThreads;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(b, (int64_t)1 << 20));   // grid-stride loops cover the rest
+}
+
+// ---- packetiser ------------------------------------------------------------------------------------------------------
+// Tuned path (S % 16 == 0, frames 16-byte and packets 8-byte aligned): one work item per 16-byte piece of a row; the piece is read
+// as one 16-byte load and written as two 8-byte stores (the payload sits at offset 8 of a packet of stride 8 + S); the item of
+// piece 0 also writes the header.
+__global__ __launch_bounds__(kThreads) void fec_packetize_v16(const uint4 *__restrict__ frames, int64_t rows, int n, int q,
+                                                             unsigned fec_class, unsigned block0, uint8_t *__restrict__ packets)
+{
+    const int64_t total = rows * q, plen = (int64_t)q * 16 + kHdr;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
+        const int64_t r = t / q;
+        const int c = (int)(t - r * q);
+        const uint4 v = frames[t];
+        uint2 *dst = reinterpret_cast<uint2 *>(packets + r * plen + kHdr + (int64_t)c * 16);
+        dst[0] = make_uint2(v.x, v.y);
+        dst[1] = make_uint2(v.z, v.w);
+        if (c == 0) {
+            const int64_t f = r / n;
+            *reinterpret_cast<uint64_t *>(packets + r * plen) = fec_header(fec_class, block0 + (unsigned)f, (unsigned)(r - f * n));
+        }
+    }
+}
+
+// Any S: one work item per output byte.
+__global__ __launch_bounds__(kThreads) void fec_packetize_bytes(const uint8_t *__restrict__ frames, int64_t rows, int n, int S,
+                                                               unsigned fec_class, unsigned block0, uint8_t *__restrict__ packets)
+{
+    const int64_t plen = (int64_t)S + kHdr, total = rows * plen;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
+        const int64_t r = t / plen;
+        const int o = (int)(t - r * plen);
+        uint8_t b;
+        if (o < kHdr) {
+            const int64_t f = r / n;
+            b = (uint8_t)(fec_header(fec_class, block0 + (unsigned)f, (unsigned)(r - f * n)) >> (8 * o));   // little endian
+        } else {
+            b = frames[r * S + (o - kHdr)];
+        }
+        packets[t] = b;
+    }
+}
+
+// ---- (a) headers -----------------------------------------------------------------------------------------------------
+// Only the first 32-bit half of the header is read, as the host's ldpc_amd_fec_header_unpack does (symbol = bytes 0-1,
+// block = byte 2).
+template <bool ALIGNED4>
+__global__ __launch_bounds__(kThreads) void fec_rx_headers(const uint8_t *__restrict__ packets, int64_t np, int plen,
+                                                          uint32_t *__restrict__ dense)
+{
+    for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < np; p += (int64_t)gridDim.x * kThreads) {
+        const uint8_t *h = packets + p * plen;
+        uint32_t w;
+        if (ALIGNED4) w = *reinterpret_cast<const uint32_t *>(h) & 0x00ffffffu;
+        else w = (uint32_t)h[0] | (uint32_t)h[1] << 8 | (uint32_t)h[2] << 16;
+        dense[p] = w;
+    }
+}
+
+// ---- (b) the plan scan -----------------------------------------------------------------------------------------------
+// :139 -- kd = k + round(0.8 (n-k)), km = k + round(0.2 (n-k))
+__device__ __forceinline__ bool close_rule(int c, int x, int n, int kd, int km)
+{
+    return c == n || (c > kd && x > 10) || (c > km && x > 100);
+}
+
+// One wavefront.  Every value but the lane's own packet is wave-uniform.  For a group of 64 packets from lane `start` on:
+//   isC / isN    this lane's packet goes to the current / next block (symbol < n and the block number matches);
+//   c_l, x_l     the counts after this lane's packet: the counts before the group + the ballots' inclusive prefix popcounts;
+//   bz           the lanes where :139 holds after their packet; the first of them (ffs) is where the host closes.
+// Exactness: the host's state after packet l depends on the packets before it only through (cur, next, ccnt, ncnt), and as
+// long as no close happens cur / next are fixed, so each count after packet l is exactly the count before the group plus the
+// matching packets among start..l -- the prefix popcount.  The condition after packet l is a function of those two counts
+// alone, so the first lane where it holds is the first packet after which the host closes, and every lane up to it is
+// assigned as the host assigns it.  The close rotates the state exactly as close_current does, and the lanes after it are
+// evaluated again with the new state.  A dropped packet changes no count but is still a point where :139 is tested, as on the
+// host (a block whose count reached n through the next block's packets closes at the packet after the rotation).
+// The loop is bounded: every iteration assigns at least one packet or ends its group, so a call takes at most
+// npackets + closes + groups iterations; a cap on that reports R_ERR instead of spinning on a bad stream.
+__global__ __launch_bounds__(64) void fec_rx_scan(const uint32_t *__restrict__ dense, int64_t np, int n, int kd, int km,
+                                                 int max_blocks, int cur, int nxt, int ccnt, int ncnt,
+                                                 int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    const int lane = threadIdx.x;
+    const uint64_t le = (lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1);   // lanes <= this one
+    int closes = 0, err = 0;
+    int64_t dropped = 0, consumed = np, iters = 0;
+    const int64_t iter_cap = np + (int64_t)max_blocks + (np + 63) / 64 + 1;
+    bool done = false;
+    uint32_t nb[kScanPrefetch];
+#pragma unroll
+    for (int u = 0; u < kScanPrefetch; u++) {
+        const int64_t p = (int64_t)u * 64 + lane;
+        nb[u] = p < np ? dense[p] : 0u;
+    }
+    for (int64_t base0 = 0; base0 < np && !done; base0 += 64 * kScanPrefetch) {
+        uint32_t hb[kScanPrefetch];
+#pragma unroll
+        for (int u = 0; u < kScanPrefetch; u++) hb[u] = nb[u];
+#pragma unroll
+        for (int u = 0; u < kScanPrefetch; u++) {   // headers of the next chunk in flight while this one is scanned
+            const int64_t p = base0 + (int64_t)(kScanPrefetch + u) * 64 + lane;
+            nb[u] = p < np ? dense[p] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < kScanPrefetch; u++) {
+            const int64_t base = base0 + (int64_t)u * 64;
+            if (done || base >= np) continue;   // (not break: the loop must unroll to keep hb[] in registers)
+            const int64_t p = base + lane;
+            const bool valid = p < np;
+            const int blk = (int)(hb[u] >> 16), sym = (int)(hb[u] & 0xffffu);
+            if (cur < 0) {   // :88-91, the first packet of the stream -- before its symbol check
+                cur = __shfl(blk, 0);
+                nxt = (cur + 1) & 0xff;
+            }
+            int d = -1;
+            int start = 0;
+            for (;;) {
+                if (++iters > iter_cap) { err = 1; done = true; consumed = base; break; }
+                const bool live = valid && lane >= start;
+                const bool ok = live && sym < n;
+                const bool isC = ok && blk == cur, isN = ok && blk == nxt;
+                const uint64_t bc = __ballot(isC), bn = __ballot(isN);
+                const int c = ccnt + __popcll(bc & le), x = ncnt + __popcll(bn & le);
+                const uint64_t bz = __ballot(live && close_rule(c, x, n, kd, km));
+                const uint64_t upto = bz ? ((bz & (0ull - bz)) << 1) - 1 : ~0ull;   // lanes up to the first close (all if none)
+                const bool mine = live && ((upto >> lane) & 1);
+                if (mine) d = isC ? closes : (isN ? closes + 1 : -1);
+                dropped += __popcll(__ballot(mine && !isC && !isN));
+                ccnt += __popcll(bc & upto);
+                ncnt += __popcll(bn & upto);
+                if (!bz) break;
+                const int L = __ffsll((long long)bz) - 1;
+                if (lane == 0) res[R_WORDS + closes] = cur;   // close_current (:214-243)
+                closes++;
+                cur = nxt;
+                nxt = (nxt + 1) & 0xff;
+                ccnt = ncnt;
+                ncnt = 0;
+                if (closes == max_blocks) { consumed = base + L + 1; done = true; break; }
+                start = L + 1;
+                if (start >= 64) break;
+            }
+            if (valid) dest[p] = d;
+        }
+    }
+    if (lane == 0) {
+        res[R_CUR] = cur; res[R_NEXT] = nxt; res[R_CCNT] = ccnt; res[R_NCNT] = ncnt; res[R_CLOSES] = closes; res[R_ERR] = err;
+        res[R_CONSUMED_LO] = (int32_t)(uint32_t)consumed; res[R_CONSUMED_HI] = (int32_t)(consumed >> 32);
+        res[R_DROPPED_LO] = (int32_t)(uint32_t)dropped; res[R_DROPPED_HI] = (int32_t)(dropped >> 32);
+    }
+}
+
+// ---- (c) last writer wins ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void fec_rx_winners(const uint32_t *__restrict__ dense, const int32_t *__restrict__ dest,
+                                                          int64_t consumed, int n, int32_t *__restrict__ win)
+{
+    for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < consumed; p += (int64_t)gridDim.x * kThreads) {
+        const int s = dest[p];
+        if (s >= 0) atomicMax(&win[(int64_t)s * n + (dense[p] & 0xffffu)], (int32_t)p);   // dest >= 0 only for symbol < n
+    }
+}
+
+// ---- (d) gather into the closed slots, (e) staging planes ------------------------------------------------------------
+struct MoveArgs {
+    const uint8_t *packets;
+    int64_t plen;
+    const int32_t *win;   // [(closes + 2)][n]
+    uint8_t *stage_sym;   // [2][n][S]
+    uint8_t *stage_er;    // [2][n]
+    uint8_t *sym_out;     // gather: [closes][n][S]
+    uint8_t *er_out;      // gather: [closes][n]
+    int n, S, cb, closes;
+};
+
+// Row r of the gather (slot j = r / n, symbol i): the last packet that went there, else -- for a block carried in from an earlier
+// call -- its staging row, else zero and erased (the decoder kernels' assumption 2).
+// Row r of the staging update (serial s = closes + r / n): the last packet, else for a block opened in this call zero and erased;
+// a carried block keeps its staging row.
+template <bool GATHER, bool V16>
+__global__ __launch_bounds__(kThreads) void fec_rx_move(MoveArgs a)
+{
+    const int q = V16 ? a.S / 16 : a.S;   // 16-byte pieces or bytes of a row
+    const int64_t rows = GATHER ? (int64_t)a.closes * a.n : 2 * (int64_t)a.n;
+    const int64_t total = rows * q;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
+        const int64_t r = t / q;
+        const int c = (int)(t - r * q);
+        const int s = (int)(r / a.n) + (GATHER ? 0 : a.closes);   // serial of the block
+        const int i = (int)(r - (int64_t)(r / a.n) * a.n);
+        const int w = a.win[(int64_t)s * a.n + i];
+        const int b = (a.cb + s) & 1;
+        const bool carried = s < 2;
+        const int64_t srow = ((int64_t)b * a.n + i) * a.S;   // the block's staging row
+        uint8_t *dst = GATHER ? a.sym_out + r * a.S : a.stage_sym + srow;
+        if (!GATHER && w < 0 && carried) continue;
+        if (V16) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (w >= 0) {
+                const uint2 *src = reinterpret_cast<const uint2 *>(a.packets + (int64_t)w * a.plen + kHdr + (int64_t)c * 16);
+                const uint2 lo = src[0], hi = src[1];
+                v = make_uint4(lo.x, lo.y, hi.x, hi.y);
+            } else if (carried) {
+                v = *reinterpret_cast<const uint4 *>(a.stage_sym + srow + (int64_t)c * 16);
+            }
+            *reinterpret_cast<uint4 *>(dst + (int64_t)c * 16) = v;
+        } else {
+            uint8_t v = 0;
+            if (w >= 0) v = a.packets[(int64_t)w * a.plen + kHdr + c];
+            else if (carried) v = a.stage_sym[srow + c];
+            dst[c] = v;
+        }
+        if (c == 0) {
+            const uint8_t e = w >= 0 ? 0 : (carried ? a.stage_er[(int64_t)b * a.n + i] : 1);
+            if (GATHER) a.er_out[r] = e;
+            else a.stage_er[(int64_t)b * a.n + i] = e;
+        }
+    }
+}
+
+// A pointer of this context's device (hipMalloc / torch), not host memory.
+bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error, it is not one of ours
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice && at.device == ctx->device;
+}
+
+}  // namespace
+
+struct ldpc_amd_fec_rx_dev {
+    ldpc_amd_ctx *ctx = nullptr;
+    int n = 0, k = 0, S = 0, kd = 0, km = 0;
+    // host mirror of the receiver's state (csrc/wire.cpp's ldpc_amd_fec_rx); cb: staging buffer of the current block
+    int cur = -1, next = -1, ccnt = 0, ncnt = 0, cb = 0;
+    int64_t dropped = 0;
+    uint8_t *stage_sym = nullptr;   // [2][n][S]
+    uint8_t *stage_er = nullptr;    // [2][n]
+    Scratch dense, dest, win, res;  // per-call scratch, grown on demand
+    int32_t *res_host = nullptr;    // pinned copy of res
+    size_t res_host_cap = 0;
+};
+
+extern "C" {
+
+int ldpc_amd_fec_packetize_dev(ldpc_amd_ctx *ctx, const uint8_t *frames, int64_t nframes, int n, int S, unsigned fec_class,
+                               unsigned block0, uint8_t *packets)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (nframes < 0 || n <= 0 || n > 65536 || S <= 0) return set_error(ctx, LDPC_AMD_EINVAL, "fec_packetize_dev: bad nframes/n/S");
+    if (nframes == 0) return LDPC_AMD_OK;
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!frames || !packets || !is_device_ptr(ctx, frames) || !is_device_ptr(ctx, packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_packetize_dev: frames / packets must be device pointers of device %d", ctx->device);
+    const int64_t rows = nframes * n;
+    if (S % 16 == 0 && ((uintptr_t)frames & 15) == 0 && ((uintptr_t)packets & 7) == 0) {
+        hipLaunchKernelGGL(fec_packetize_v16, dim3(grid_for(rows * (S / 16))), dim3(kThreads), 0, ctx->stream,
+                           reinterpret_cast<const uint4 *>(frames), rows, n, S / 16, fec_class, block0, packets);
+    } else {
+        hipLaunchKernelGGL(fec_packetize_bytes, dim3(grid_for(rows * (S + kHdr))), dim3(kThreads), 0, ctx->stream,
+                           frames, rows, n, S, fec_class, block0, packets);
+    }
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+int ldpc_amd_fec_rx_dev_create(ldpc_amd_ctx *ctx, int n, int k, int S, ldpc_amd_fec_rx_dev **out)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!out || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_create: need n <= 65536, 0 < k < n, S >= 1 (n=%d k=%d S=%d)", n, k, S);
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ldpc_amd_fec_rx_dev *rx = new (std::nothrow) ldpc_amd_fec_rx_dev();
+    if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rx_dev_create: out of host memory");
+    rx->ctx = ctx;
+    rx->n = n; rx->k = k; rx->S = S;
+    rx->kd = k + (int)lround((n - k) * 0.8);   // desired_parity_rx, :54
+    rx->km = k + (int)lround((n - k) * 0.2);   // min_parity_rx, :55
+    const size_t plane = (size_t)n * S;
+    hipError_t e = hipMalloc((void **)&rx->stage_sym, 2 * plane);
+    if (e == hipSuccess) e = hipMalloc((void **)&rx->stage_er, 2 * (size_t)n);
+    // :62-71 all symbols erased until a packet produces them, payload zero
+    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_sym, 0, 2 * plane, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_er, 1, 2 * (size_t)n, ctx->stream);
+    if (e != hipSuccess) {
+        ldpc_amd_fec_rx_dev_destroy(rx);
+        return set_error(ctx, e == hipErrorOutOfMemory ? LDPC_AMD_ENOMEM : LDPC_AMD_EHIP, "fec_rx_dev_create: %s", hipGetErrorString(e));
+    }
+    *out = rx;
+    return LDPC_AMD_OK;
+}
+
+void ldpc_amd_fec_rx_dev_destroy(ldpc_amd_fec_rx_dev *rx)
+{
+    if (!rx) return;
+    (void)hipSetDevice(rx->ctx->device);
+    (void)hipStreamSynchronize(rx->ctx->stream);   // pending work of this receiver may still use its buffers
+    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res};
+    for (Scratch *s : sc)
+        if (s->p) (void)hipFree(s->p);
+    if (rx->stage_sym) (void)hipFree(rx->stage_sym);
+    if (rx->stage_er) (void)hipFree(rx->stage_er);
+    if (rx->res_host) (void)hipHostFree(rx->res_host);
+    delete rx;
+}
+
+int64_t ldpc_amd_fec_rx_dev_dropped(const ldpc_amd_fec_rx_dev *rx) { return rx ? rx->dropped : -1; }
+
+int ldpc_amd_fec_rx_dev_push_many(ldpc_amd_fec_rx_dev *rx, const uint8_t *packets, int64_t npackets, uint8_t *sym_batch,
+                                  uint8_t *erased_batch, int *blocks, int max_blocks, int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (npackets < 0 || npackets >= ((int64_t)1 << 31) || max_blocks < 1)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_push_many: need 0 <= npackets < 2^31 and max_blocks >= 1");
+    if (!sym_batch || !erased_batch || (npackets > 0 && !packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_push_many: packets / sym_batch / erased_batch must not be null");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((npackets > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_push_many: packets / sym_batch / erased_batch must be device pointers of device %d",
+                         ctx->device);
+    if (consumed) *consumed = 0;
+    if (npackets == 0) return 0;
+    const int n = rx->n, S = rx->S;
+    const int64_t plen = (int64_t)S + kHdr;
+    const size_t res_bytes = sizeof(int32_t) * ((size_t)R_WORDS + (size_t)max_blocks);
+    int rc;
+    if ((rc = scratch_reserve(ctx, rx->dense, sizeof(uint32_t) * (size_t)npackets)) ||
+        (rc = scratch_reserve(ctx, rx->dest, sizeof(int32_t) * (size_t)npackets)) ||
+        (rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)max_blocks + 2) * (size_t)n)) ||
+        (rc = scratch_reserve(ctx, rx->res, res_bytes)))
+        return rc;
+    if (rx->res_host_cap < res_bytes) {
+        if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every call ends with a synchronisation
+        rx->res_host = nullptr;
+        rx->res_host_cap = 0;
+        LDPC_HIP_TRY(ctx, hipHostMalloc((void **)&rx->res_host, res_bytes, hipHostMallocDefault));
+        rx->res_host_cap = res_bytes;
+    }
+    uint32_t *dense = (uint32_t *)rx->dense.p;
+    int32_t *dest = (int32_t *)rx->dest.p, *win = (int32_t *)rx->win.p, *res = (int32_t *)rx->res.p;
+
+    // (a) + (b): the plan
+    if (plen % 4 == 0 && ((uintptr_t)packets & 3) == 0)
+        hipLaunchKernelGGL(fec_rx_headers<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
+    else
+        hipLaunchKernelGGL(fec_rx_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fec_rx_scan, dim3(1), dim3(64), 0, ctx->stream, dense, npackets, n, rx->kd, rx->km, max_blocks, rx->cur,
+                       rx->next, rx->ccnt, rx->ncnt, dest, res);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->res_host, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = check_device_error(ctx))) return rc;
+    const int32_t *h = rx->res_host;
+    if (h[R_ERR])
+        return set_error(ctx, LDPC_AMD_EHIP, "fec_rx_dev_push_many: the plan scan hit its iteration cap (internal error); the receiver's state is unchanged");
+    const int closes = h[R_CLOSES];
+    const int64_t used = (int64_t)(((uint64_t)(uint32_t)h[R_CONSUMED_HI] << 32) | (uint32_t)h[R_CONSUMED_LO]);
+    const int64_t dd = (int64_t)(((uint64_t)(uint32_t)h[R_DROPPED_HI] << 32) | (uint32_t)h[R_DROPPED_LO]);
+
+    // (c), (d), (e): the data movement, asynchronous
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(win, 0xff, sizeof(int32_t) * ((size_t)closes + 2) * (size_t)n, ctx->stream));   // -1: no packet
+    hipLaunchKernelGGL(fec_rx_winners, dim3(grid_for(used)), dim3(kThreads), 0, ctx->stream, dense, dest, used, n, win);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    MoveArgs a{};
+    a.packets = packets; a.plen = plen; a.win = win; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
+    a.sym_out = sym_batch; a.er_out = erased_batch; a.n = n; a.S = S; a.cb = rx->cb; a.closes = closes;
+    const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0 && ((uintptr_t)sym_batch & 15) == 0;
+    const int64_t q = v16 ? S / 16 : S;
+    if (closes > 0) {
+        if (v16) hipLaunchKernelGGL((fec_rx_move<true, true>), dim3(grid_for((int64_t)closes * n * q)), dim3(kThreads), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((fec_rx_move<true, false>), dim3(grid_for((int64_t)closes * n * q)), dim3(kThreads), 0, ctx->stream, a);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+    }
+    if (v16) hipLaunchKernelGGL((fec_rx_move<false, true>), dim3(grid_for(2 * (int64_t)n * q)), dim3(kThreads), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((fec_rx_move<false, false>), dim3(grid_for(2 * (int64_t)n * q)), dim3(kThreads), 0, ctx->stream, a);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+
+    rx->cur = h[R_CUR]; rx->next = h[R_NEXT]; rx->ccnt = h[R_CCNT]; rx->ncnt = h[R_NCNT];
+    rx->cb ^= closes & 1;   // :241, once per close
+    rx->dropped += dd;
+    if (blocks) memcpy(blocks, h + R_WORDS, sizeof(int) * (size_t)closes);
+    if (consumed) *consumed = used;
+    return closes;
+}
+
+int ldpc_amd_fec_rx_dev_flush(ldpc_amd_fec_rx_dev *rx, uint8_t *sym_out, uint8_t *erased_out, int *block_out)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (rx->cur == -1 || (rx->ccnt == 0 && rx->ncnt == 0)) return 0;
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((sym_out && !is_device_ptr(ctx, sym_out)) || (erased_out && !is_device_ptr(ctx, erased_out)))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_flush: sym_out / erased_out must be device pointers of device %d", ctx->device);
+    const size_t plane = (size_t)rx->n * rx->S;
+    uint8_t *ps = rx->stage_sym + (size_t)rx->cb * plane, *pe = rx->stage_er + (size_t)rx->cb * rx->n;
+    // close_current: hand the current block out, reset its buffer, rotate
+    if (sym_out) LDPC_HIP_TRY(ctx, hipMemcpyAsync(sym_out, ps, plane, hipMemcpyDeviceToDevice, ctx->stream));
+    if (erased_out) LDPC_HIP_TRY(ctx, hipMemcpyAsync(erased_out, pe, rx->n, hipMemcpyDeviceToDevice, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(ps, 0, plane, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(pe, 1, rx->n, ctx->stream));
+    if (block_out) *block_out = rx->cur;
+    rx->cur = rx->next;
+    rx->next = (rx->next + 1) & 0xff;
+    rx->ccnt = rx->ncnt;
+    rx->ncnt = 0;
+    rx->cb ^= 1;
+    return 1;
+}
+
+}  // extern "C"
