@@ -735,6 +735,7 @@ static int host_pipeline(ldpc_amd_ctx *ctx, int64_t nitems, const PipeIn (&ins)[
     (void)hipStreamSynchronize(ctx->aux_in);
     (void)hipStreamSynchronize(ctx->aux_out);
     if (result == LDPC_AMD_OK && failed) result = set_error(ctx, LDPC_AMD_EHIP, "host pipeline (download): %s", helper_err.c_str());
+    if (result == LDPC_AMD_OK) result = check_device_error(ctx);   // every chunk's kernels have finished: what they reported belongs to this call
     return result;
 }
 
@@ -1198,7 +1199,7 @@ int ldpc_amd_rs_decode_batch(ldpc_amd_ctx *ctx, int rs, int S, int64_t nblocks, 
         return rc;
     LDPC_HIP_TRY(ctx, hipMemcpyAsync(msg, ctx->stage_out.p, vb, hipMemcpyDeviceToHost, ctx->stream));
     LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return LDPC_AMD_OK;
+    return check_device_error(ctx);
 }
 
 int ldpc_amd_rs_bad_blocks(ldpc_amd_ctx *ctx, long long *count)
@@ -1348,7 +1349,7 @@ int ldpc_amd_fpga_frame_stats(ldpc_amd_ctx *ctx, long numFrames, int32_t *residu
     if (residual_sys) LDPC_HIP_TRY(ctx, hipMemcpyAsync(residual_sys, res, sizeof(int32_t) * (size_t)numFrames, hipMemcpyDeviceToHost, ctx->stream));
     if (iterations) LDPC_HIP_TRY(ctx, hipMemcpyAsync(iterations, res + numFrames, sizeof(int32_t) * (size_t)numFrames, hipMemcpyDeviceToHost, ctx->stream));
     LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return LDPC_AMD_OK;
+    return check_device_error(ctx);   // the run went through relaxation mode 1: counts of a run that hit a cap are not handed out as good
 }
 
 int ldpc_amd_data_out(ldpc_amd_ctx *ctx, ldpc_amd_symbol_type *data_out, int code_ind, long numFrames,
@@ -1366,6 +1367,8 @@ int ldpc_amd_data_out(ldpc_amd_ctx *ctx, ldpc_amd_symbol_type *data_out, int cod
     if (numFrames > 0) {
         LDPC_HIP_TRY(ctx, hipMemcpyAsync(host, ctx->fpga_stats.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
         LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        int rc = check_device_error(ctx);
+        if (rc) return rc;
     }
     // error_type holds two ints (ldpc_erasure_decoder_top.cl:46-49); N_T = 2e8 frames x 8 RS blocks still fits
     if (stats) { stats->num_LDPC_errors = (int)host[0]; stats->num_RS_errors = (int)host[1]; }
@@ -1401,7 +1404,7 @@ int ldpc_amd_get_profile(ldpc_amd_ctx *ctx, double ms[LDPC_AMD_PROF_KINDS], int6
         if (launches) launches[kd] = (int64_t)ctx->prof_events[kd].size();
         ctx->prof_events[kd].clear();
     }
-    return LDPC_AMD_OK;
+    return check_device_error(ctx);   // (the stream was drained above: times of kernels that gave up are not handed out as good)
 }
 
 const char *ldpc_amd_profile_kernel_name(ldpc_amd_ctx *ctx, int kind)

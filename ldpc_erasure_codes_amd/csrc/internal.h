@@ -114,7 +114,7 @@ struct Knobs {
     int scatter_xl = 1;          // SCATTER_XL: the level phase's lists are translated to accumulator addresses at set-up (0: inside every level)
     int scatter_t2b = 256;       // SCATTER_T2B: bytes of every row per TIER-2 workgroup (256: one workgroup per CU; 128: two)
     int peel_wpb = 0;            // PEEL_WPB: frames per peel workgroup (0 = auto)
-    int peel_gt = -1;            // PEEL_GT: S = 1 kernel reads the code tables from global memory (-1 = auto)
+    int peel_gt = -1;            // PEEL_GT: S = 1 kernel reads the code tables from global memory (-1 = auto; a code whose tables do not fit the LDS takes them from there whatever this says)
     int enc_persist = 1;         // ENC_PERSIST: packet encoder as persistent workgroups (tables and lists set up once per workgroup); 0: one workgroup per (frame, slice)
     int scatter_t2p = 2;         // SCATTER_T2P: tier 2 -- consecutive pieces of a frame per work item (1, 2, 4, 8): the frame's set-up is done once per item
     int scatter_t2p_force = 0;   // SCATTER_T2P_FORCE: 1 = SCATTER_T2P pieces per item whatever the length of the tier-2 list (tests)

@@ -1947,7 +1947,11 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
     int wpb = 1;
     bool gt = false;
     PeelLds L = make_peel_lds(cd, fused, 1);
-    if (L.total > kLdsMax) return set_error(ctx, LDPC_AMD_EUNSUP, "code too large for LDS (%d bytes)", L.total);
+    // (S = 1 keeps id | log(coef) words per edge in LDS: a code whose tables leave no room for a frame -- (8192,4096) -- still runs
+    // with the tables in global memory, whatever PEEL_GT prefers; the relaxation's plan below does the same)
+    const bool lds_tables = L.total <= kLdsMax;
+    if (!lds_tables && (!fused || make_peel_lds(cd, fused, 1, true).total > kLdsMax))
+        return set_error(ctx, LDPC_AMD_EUNSUP, "code too large for LDS (%d bytes)", L.total);
     {
         int best = 0;
         const bool env_w = kn.peel_wpb > 0;   // diagnostic: cap the wavefronts (= frames) per workgroup
@@ -1960,10 +1964,10 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
         }
         // S = 1, long batch: with the code tables left in global memory more frames fit on a CU.  Worth it when the
         // batch is several rounds deep anyway (a single round is latency bound and prefers the LDS tables).
-        if (fused && !env_w && kn.peel_gt != 0) {
+        if (fused && ((!env_w && kn.peel_gt != 0) || !lds_tables)) {
             int bestg = 0, wg = 1;
             PeelLds Lg = L;
-            for (int w = 1; w <= 16; w++) {
+            for (int w = 1; w <= wcap; w++) {
                 const PeelLds t = make_peel_lds(cd, fused, w, true);
                 if (t.total > kLdsMax) break;
                 const int waves = std::min(32, (kLdsMax / t.total) * w);
@@ -1971,7 +1975,7 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
             }
             const bool deep = d.nframes >= (int64_t)3 * best * ctx->sm_count;
             // measured: (4080,3060) 7 -> 11 frames per CU: -18 %, (4000,2000) 5 -> 8: -15 %, (2040,1530) 16 -> 21: +12 % (slower)
-            if (kn.peel_gt == 1 || (deep && bestg * 20 >= best * 29)) { gt = true; wpb = wg; L = Lg; }
+            if (!lds_tables || kn.peel_gt == 1 || (deep && bestg * 20 >= best * 29)) { gt = true; wpb = wg; L = Lg; }
         }
     }
 

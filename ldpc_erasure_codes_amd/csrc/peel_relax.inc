@@ -19,7 +19,10 @@
 //   (independent LDS reads), top-2 of (key << 4 | neighbour slot), candidate = next_visit(i, second key), written to the latest
 //   neighbour if smaller (16-bit keys, no atomics: write, read back, retry while a larger key landed).  Chunks are evaluated round
 //   robin, a chunk again while it still improves something, until every chunk has been evaluated once without any improvement
-//   since: about (sweeps + 1) * chunks evaluations instead of one serial turn per solved symbol.
+//   since: about (sweeps + 1) * chunks evaluations instead of one serial turn per solved symbol on the built-in codes.  A chunk's
+//   checks all read before any of them writes, so a dependency between two checks of ONE chunk costs a round: a staircase parity
+//   part of m checks takes about m rounds, m * m / 64 evaluations (exact, but slower than the serial loop: DESIGN.md 4.1b;
+//   tools/relax_model.py replays the loop on the CPU and counts).
 //   At the fixed point check i records fire[i] = key << 16 | symbol if it is the solver of its latest neighbour.  The solving
 //   checks are counting-sorted by sweep (stable in the check index: that IS time order) and applied 64 at a time; inside a batch a
 //   step waits until all its inputs are valid (the earliest unfinished step of a batch always is ready).
@@ -208,9 +211,14 @@ __global__ __launch_bounds__(1024) void ldpc_peel_relax_kernel(RelaxArgs a)
 #endif
     if (E0 > 0) {
         int clean = 0, ch = 0;
-        // (safety cap, never reached by a correct run: every evaluation that improves something lowers a key, and a key takes at most
-        // m * (itenum + 1) values; an endless loop would hang the GPU for everyone on the host, so it is cut off and REPORTED)
-        long budget = (long)nch * ((long)(a.max_sweeps + 2) * 64 + 64);
+        // (safety cap, never reached by a correct run.  Any nch evaluations in a row visit every chunk once and settle at least the
+        // EARLIEST key that is still above its final value: the other inputs of its solving check are final already, so the check
+        // proposes the final key and writes are min-wins.  A check solves at most one symbol, so at most m keys are ever written:
+        // m such rounds at most, then nch clean evaluations -- nch * (m + 1) in all.  The sweep cap does not enter: a chain through
+        // the checks of one chunk (a staircase parity part) is a single sweep of the reference and one round PER CHECK here, which
+        // is why round 4's nch * ((itenum + 2) * 64 + 64) cut valid frames off from m = 320 on (tools/relax_model.py).
+        // An endless loop would hang the GPU for everyone on the host, so the loop stays cut off and REPORTED)
+        long budget = (long)nch * ((long)m + 2);
         while (clean < nch) {
             if (--budget < 0) { if (lane == 0 && a.err) atomicOr(a.err, kDevErrRelaxCap); break; }
             int row[U];
@@ -446,7 +454,7 @@ __global__ __launch_bounds__(1024) void ldpc_peel_relax_kernel(RelaxArgs a)
             for (int t = 0; t < MAXDEG; t++) off[t] = off16[tix(row) + 64 * t];
             bool done = !active;
             for (int guard = 0; __ballot(!done); guard++) {
-                if (guard > 64) { if (lane == 0 && a.err) atomicOr(a.err, kDevErrRelaxCap); break; }   // (every round finishes at least one step)
+                if (guard > 64) { if (lane == 0 && a.err) atomicOr(a.err, kDevErrRelaxCap); break; }   // (never reached: every round finishes at least the earliest unfinished step, so 64 fully chained steps take 64 rounds, guard 0 .. 63)
                 uint32_t allv = kHas, lv = 0, v[MAXDEG];
 #pragma unroll
                 for (int t = 0; t < MAXDEG; t++) {
@@ -614,7 +622,7 @@ __global__ __launch_bounds__(1024) void ldpc_peel_relax_kernel(RelaxArgs a)
         for (int t = 0; t < MAXDEG; t++) { off[t] = off16[tix(row) + 64 * t]; lc[t] = logc8[tix(row) + 64 * t]; }
         bool done = !active;
         for (int guard = 0; __ballot(!done); guard++) {
-            if (guard > 64) { if (lane == 0 && a.err) atomicOr(a.err, kDevErrRelaxCap); break; }   // (every round finishes at least one step)
+            if (guard > 64) { if (lane == 0 && a.err) atomicOr(a.err, kDevErrRelaxCap); break; }   // (never reached: every round finishes at least the earliest unfinished step, so 64 fully chained steps take 64 rounds, guard 0 .. 63)
             uint32_t v[MAXDEG], lv[MAXDEG];
 #pragma unroll
             for (int t = 0; t < MAXDEG; t++) v[t] = *reinterpret_cast<const uint16_t *>(keyb + off[t]);

@@ -5,30 +5,18 @@
   coefficients.  GF(256) products are associative and distributive, so the codeword must be the row-by-row encoder's
   (Matlab/ErasureCodes_NonBinaryLDPCSim.m:173-182, OpenCL/device/ldpc_erasure_encoder.cl:72-84) byte for byte: every built-in code
   and random triangle codes, every cap, against the oracle and against the level-by-level schedule."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
-from ldpc_erasure_codes_amd import api, codes, synth
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+from relax_model import random_triangle_code as _random_triangle_code  # noqa: E402  (shared with the structured relaxation tests)
+
+from ldpc_erasure_codes_amd import api, codes, synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def _random_triangle_code(rng, n, k, deg):
-    """(n-k) x n, parity part lower triangular with a non-zero diagonal (row i ends in column k+i), random GF(256) coefficients;
-    long dependency chains on purpose: every row takes its previous parity symbol with probability 0.8."""
-    m = n - k
-    row_ptr, cols, coefs = [0], [], []
-    for r in range(m):
-        c = set(rng.choice(k, size=min(deg, k), replace=False).tolist())
-        if r > 0 and rng.random() < 0.8:
-            c.add(k + r - 1)
-        for j in rng.choice(max(r, 1), size=min(2, r), replace=False).tolist() if r > 1 else []:
-            c.add(k + j)
-        c = sorted(c) + [k + r]
-        cols += c
-        coefs += rng.integers(1, 256, size=len(c)).tolist()
-        row_ptr.append(len(cols))
-    return codes.Code(n, k, np.array(row_ptr, dtype=np.uint32), np.array(cols, dtype=np.uint16), np.array(coefs, dtype=np.uint8))
 
 
 @pytest.mark.parametrize("code_ind", [1, 3])
