@@ -82,13 +82,18 @@ def encode(H, source_vec):
     return cw.a.copy()
 
 
-def hybridml_nonbinary_decode(recv_vec_val, H, itenum=10, do_ML_decode=1):
+def prepare(H):
+    """The decoder's inputs that depend on the code alone (H_sparse, Vlist), for several frames of one LARGE code: building them
+    walks all m * n entries in Python."""
+    return M1(H), build_vlist(H)[0]
+
+
+def hybridml_nonbinary_decode(recv_vec_val, H, itenum=10, do_ML_decode=1, prepared=None):
     """Matlab/My_LDPC_HybridML_NonBinary_Erasure_Decoder.m:4-130.
-    Returns (Msg, iterations, dont_do_jordan or None)."""
+    Returns (Msg, iterations, dont_do_jordan or None).  prepared: prepare(H), read only."""
     m, n = H.shape
     k = n - m
-    H_sparse = M1(H)
-    Vlist, _ = build_vlist(H)
+    H_sparse, Vlist = prepared if prepared is not None else prepare(H)
     y_current = M1(recv_vec_val)
     stopsig, itestep = 0, 0
     num_cur_erasures = 0

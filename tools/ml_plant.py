@@ -1,0 +1,554 @@
+#!/usr/bin/env python3
+"""Planted residual systems for the ML stage (csrc/ml_kernel.inc, csrc/ml_pi.inc, the solve kernel): codes whose residual
+system is CHOSEN, the properties the choice was made for in executable form, and the frames that go with them.
+
+The other suites reach the ML stage with whatever the built-in or random codes leave under uniform or bursty erasures: generic
+systems that pivot on or near the diagonal.  Here a T x E block B is written into E source columns of a lower-triangular code
+H = [Hs | Hp] at chosen check rows, every row of B with at least two non-zeros and every other check zero in those columns.
+Erase exactly those E source symbols: no check has a single unknown, the sweeps change nothing
+(Matlab/My_LDPC_HybridML_NonBinary_Erasure_Decoder.m:21-59), and the elimination (:61-128) receives B embedded among m - T
+all-zero rows at the chosen positions.
+
+  plant / plant_many   the codes (one block, or several blocks in disjoint columns: a frame erases any union of them)
+  properties           a plain numpy elimination by the reference's rule (:85-115): where it breaks, how many pivots are
+                       displaced, how many swaps move an all-zero row, the deepest pivot, the status word.  It knows nothing of
+                       the kernels: tests/test_ml_planted_cpu.py pins it on the oracle and asserts the DESIGNED property of every
+                       case, so that an input which stopped hitting its edge fails instead of testing the generic case
+  frame helpers        codewords, a known symbol corrupted inside a touched / inside untouched checks only, extra erased parity
+                       symbols the sweeps solve first, all clear
+
+The library takes rows of up to 24 entries and its fast path (and the packet kernel's scatter plan) columns of up to 16
+(csrc/api.cpp, launch_decode); `plant` keeps inside both unless device=False.  A block with all T * E entries non-zero therefore
+ends at E = 20 on the GPU; `band` (w cyclic diagonals, w - 1 inactivations, fill inside the band) is the dense family beyond.
+Test infrastructure, not product code."""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from pi_model import INV, MUL  # noqa: E402  (GF(256) tables of the project's field)
+
+from ldpc_erasure_codes_amd import codes  # noqa: E402
+
+DEVICE_ROW_DEG = 24     # register_code refuses longer rows
+DEVICE_COL_DEG = 16     # longer columns: no fast path, no scatter plan (still decoded)
+FULL_RANK = ("circulant2", "anti", "dense", "band", "tall", "generic", "generic_tall")
+
+
+def _prod(v):
+    p = 1
+    for x in v:
+        p = int(MUL[p, int(x)])
+    return p
+
+
+# ---- the blocks -------------------------------------------------------------------------------------------------------------------
+def block(rng, kind, E, T=None, c=None, w=None):
+    """The T x E block of a family (uint8, 0 = no entry).
+       circulant2            B[i,i], B[i,(i+1)%E]: one inactivation, then a peel chain of length E; determinant prod(a) + prod(b) != 0
+       circulant2_singular   the same with the last coefficient chosen so that the determinant is 0: the first E - 1 columns are
+                             independent (bidiagonal), the deficiency shows at the LAST column only
+       anti                  B[i,E-1-i], B[i,(E-2-i)%E]: every column's pivot at the far end, long swap cycles
+       dense                 all T * E entries
+       band                  B[i,(i+j)%E], j < w: w - 1 inactivations, the fill stays inside the band
+       dupcol                diagonal + two more per row, then column c+1 = alpha * column c: the break lands at column c + 1
+       wide                  T < E: fewer touched checks than unknowns
+       tall                  T > E, diagonal (i % E) + two more per row: surplus rows, non-zero rows left below E
+       generic               three per row, one of them on a hidden random permutation (every column covered) and none forced
+                             on the diagonal: generic pivoting -- non-zero rows are swapped down and compete again, so the row
+                             with the smallest LOGICAL index is not the one with the smallest original index
+       generic_singular      the same with column E-1 = alpha * column E-2: the pivot order shows in the bytes written back
+       generic_tall          the same with T > E rows (row i on the permutation's column of i % E)"""
+    T = E if T is None else T
+    B = np.zeros((T, E), dtype=np.uint8)
+    nz = lambda size=None: rng.integers(1, 256, size=size)   # noqa: E731
+    if kind in ("circulant2", "circulant2_singular", "anti"):
+        assert T == E and E >= 2
+        a, b = nz(E), nz(E)
+        if kind == "circulant2_singular":
+            b[E - 1] = MUL[_prod(a), INV[_prod(b[:E - 1])]]
+        else:
+            while _prod(a) == _prod(b):
+                b[E - 1] = nz()
+        for i in range(E):
+            if kind == "anti":
+                B[i, E - 1 - i], B[i, (E - 2 - i) % E] = a[i], b[i]
+            else:
+                B[i, i], B[i, (i + 1) % E] = a[i], b[i]
+    elif kind == "dense":
+        B[:] = nz((T, E))
+    elif kind == "band":
+        assert T == E and 2 <= w <= E
+        for i in range(E):
+            B[i, (i + np.arange(w)) % E] = nz(w)
+    elif kind in ("dupcol", "tall"):
+        assert (T == E and 0 <= c <= E - 2 and E >= 4) if kind == "dupcol" else T > E >= 3
+        for i in range(T):
+            others = rng.choice(np.setdiff1d(np.arange(E), [i % E]), size=2, replace=False)
+            B[i, i % E] = nz()
+            B[i, others] = nz(2)
+        if kind == "dupcol":
+            B[:, c + 1] = MUL[int(nz())][B[:, c]]
+    elif kind in ("generic", "generic_singular", "generic_tall"):
+        assert (T > E if kind == "generic_tall" else T == E) and E >= 4
+        pi = rng.permutation(E)
+        for i in range(T):
+            others = rng.choice(np.setdiff1d(np.arange(E), [pi[i % E]]), size=2, replace=False)
+            B[i, pi[i % E]] = nz()
+            B[i, others] = nz(2)
+        if kind == "generic_singular":
+            B[:, E - 1] = MUL[int(nz())][B[:, E - 2]]
+    elif kind == "wide":
+        assert 2 <= T < E
+        for i in range(T):
+            B[i, sorted({i, (i + 1) % E, T + i % (E - T)})] = nz(len({i, (i + 1) % E, T + i % (E - T)}))
+    else:
+        raise ValueError(kind)
+    assert (np.count_nonzero(B, axis=1) >= 2).all(), kind     # no check with a single unknown: the sweeps leave the block alone
+    return B
+
+
+def placement(m, T, where):
+    """Check rows of a block.  top: 0..T-1.  bottom: m-T..m-1 (every pivot search skips m - T zero rows, each of the first E zero
+    rows is swapped down).  third: every third check.  clusters: two runs with a gap, 5 checks off either end."""
+    if where == "top":
+        rows = np.arange(T)
+    elif where == "bottom":
+        rows = np.arange(m - T, m)
+    elif where == "third":
+        rows = 3 * np.arange(T) + (1 if 3 * T < m else 0)
+    elif where == "clusters":
+        h = T // 2
+        rows = np.concatenate([np.arange(5, 5 + h), np.arange(m - 5 - (T - h), m - 5)])
+    else:
+        raise ValueError(where)
+    assert rows.size == T and rows[0] >= 0 and rows[-1] < m and (np.diff(rows) > 0).all(), (m, T, where)
+    return rows
+
+
+# ---- the codes --------------------------------------------------------------------------------------------------------------------
+def plant_many(rng, n, k, blocks, fill=3, device=True):
+    """blocks: dicts kind, E, rows (check indices, ascending) and T / c / w where the family takes them.  Block b takes the source
+    columns col0 .. col0 + E - 1 behind those of block b - 1.  The parity part is triangular: diagonal, parity i - 1 (80 %), one
+    earlier parity symbol (40 %).  Filler entries in the source columns no block uses -- `fill` per check outside the blocks,
+    one per check inside, every filler column in at most 8 checks -- keep the codewords from being trivial.
+    Returns a codes.Code with `.plant`: per block kind, col0, E, T, rows, c, and the expectation of `properties`."""
+    m = n - k
+    used = sum(b["E"] for b in blocks)
+    assert used <= k and m >= 2
+    for tries in range(50):
+        rows = [dict() for _ in range(m)]
+        plant, col0 = [], 0
+        for b in blocks:
+            E, r = b["E"], np.asarray(b["rows"], dtype=np.int64)
+            B = block(rng, b["kind"], E, T=r.size, c=b.get("c"), w=b.get("w"))
+            for i, chk in enumerate(r):
+                for j in np.flatnonzero(B[i]):
+                    rows[chk][col0 + int(j)] = int(B[i, j])
+            plant.append(dict(kind=b["kind"], col0=col0, E=E, T=int(r.size), rows=r, c=b.get("c"), w=b.get("w")))
+            col0 += E
+        planted = np.zeros(m, dtype=bool)
+        for p in plant:
+            planted[p["rows"]] = True
+        pool = np.tile(np.arange(used, k), 8) if k > used else np.zeros(0, dtype=np.int64)
+        pool = list(rng.permutation(pool))
+        for i in range(m):
+            room = (DEVICE_ROW_DEG if device else 1 << 30) - len(rows[i]) - 3
+            for _ in range(max(0, min(1 if planted[i] else fill, room))):
+                while pool and int(pool[-1]) in rows[i]:
+                    pool.pop()
+                if pool:
+                    rows[i][int(pool.pop())] = int(rng.integers(1, 256))
+            if i > 0 and rng.random() < 0.8:
+                rows[i][k + i - 1] = int(rng.integers(1, 256))
+            if i > 1 and rng.random() < 0.4:
+                rows[i][k + int(rng.integers(0, i - 1))] = int(rng.integers(1, 256))
+            rows[i][k + i] = int(rng.integers(1, 256))
+        row_ptr, cols, coefs = [0], [], []
+        for d in rows:
+            cols += sorted(d)
+            coefs += [d[c_] for c_ in sorted(d)]
+            row_ptr.append(len(cols))
+        code = codes.Code(n, k, np.array(row_ptr, dtype=np.uint32), np.array(cols, dtype=np.uint16), np.array(coefs, dtype=np.uint8))
+        code.plant = plant
+        if device:
+            assert int(np.diff(code.row_ptr.astype(np.int64)).max()) <= DEVICE_ROW_DEG, "row longer than the library takes"
+        # the coefficients are random: a full-rank family may come out singular (1 in 256), a deficient one may break early
+        ok = True
+        for b in range(len(plant)):
+            pr = properties(code, erasures(code, [b]))
+            want = expectation(plant[b])
+            plant[b]["expect"] = want
+            if pr["E"] > m:       # more unknowns than checks: the elimination is never started
+                continue
+            ok = ok and pr["E"] == plant[b]["E"] and pr["breaks"] == want["breaks"] and \
+                (want["break_col"] is None or pr["break_col"] == want["break_col"]) and \
+                (not plant[b]["kind"].startswith("generic") or pr["not_min_stored"] > 0)      # generic: the pivot order must matter
+        if ok:
+            return code
+    raise RuntimeError("no draw with the designed rank")
+
+
+def plant(rng, n, k, E, rows, kind, c=None, w=None, fill=3, device=True):
+    """One block of `kind` in the source columns 0..E-1 at the check rows `rows` (see plant_many)."""
+    return plant_many(rng, n, k, [dict(kind=kind, E=E, rows=rows, c=c, w=w)], fill=fill, device=device)
+
+
+def expectation(p):
+    """What the family was chosen for: does the elimination break, and (where the design fixes it) at which column."""
+    if p["kind"] in FULL_RANK and p["T"] >= p["E"]:
+        return dict(breaks=False, break_col=None)
+    if p["kind"] in ("circulant2_singular", "generic_singular"):
+        return dict(breaks=True, break_col=p["E"] - 1)
+    if p["kind"] == "dupcol":
+        return dict(breaks=True, break_col=p["c"] + 1)
+    return dict(breaks=True, break_col=None)      # wide, dense with T < E: deficient somewhere
+
+
+def erasures(code, which=None):
+    """[n] flags: the source columns of the blocks `which` (default: all of them)."""
+    era = np.zeros(code.n, dtype=np.uint8)
+    for b in (range(len(code.plant)) if which is None else which):
+        p = code.plant[b]
+        era[p["col0"]:p["col0"] + p["E"]] = 1
+    return era
+
+
+# ---- what a frame does to the reference ----------------------------------------------------------------------------------------------
+def _rows(code):
+    rp = code.row_ptr.astype(np.int64)
+    return [(code.cols[rp[r]:rp[r + 1]].astype(np.int64), code.coefs[rp[r]:rp[r + 1]]) for r in range(code.m)]
+
+
+def sweeps(code, erased, itenum=10):
+    """The pattern side of the message passing (:21-59): checks in order, a check with ONE unknown neighbour solves it at once.
+    Returns (flags of the symbols still unknown, iterations)."""
+    unk = np.asarray(erased).astype(bool).copy()
+    rows = _rows(code)
+    it = 0
+    left = int(unk.sum())
+    while it < itenum:
+        it += 1
+        solved = 0
+        for c, _ in rows:
+            u = c[unk[c]]
+            if u.size == 1:
+                unk[u[0]] = False
+                solved += 1
+        left -= solved
+        if left == 0:
+            break
+        if solved == 0:       # a sweep that solves nothing repeats itself until the cap
+            it = itenum
+            break
+    return unk, it
+
+
+def properties(code, erased, itenum=10):
+    """One frame's erasure pattern through the reference's rule, in numpy (values play no part: the pivot order depends on the
+    pattern and the coefficients only).  Sweeps, then on find_inv = H(:, unknown) (:65), for col = 1..E (:85-115): the pivot is
+    the FIRST row >= col with a non-zero in column col; none: break.  Swap it to row col, scale, eliminate the rows below.
+      E0, iterations       erased symbols; sweeps performed
+      E, residual_cols     unknowns the sweeps leave, ascending
+      T, touched           checks with an unknown neighbour (the non-zero rows of find_inv)
+      breaks, break_col    the elimination stops at an empty column (0-based) -- rank deficient
+      displaced            columns whose pivot row is not the column index (a real swap)
+      zero_row_swaps       of those, swaps that move an all-zero row of find_inv down
+      max_pivot_row        largest logical row index a pivot is taken from
+      not_min_stored       columns whose pivot -- the candidate with the smallest LOGICAL index -- is not the candidate with the
+                           smallest ORIGINAL index: where a search that minimised the stored row would go wrong
+      status               0 done by the sweeps, 1 ML solved, 2 ML rank deficient, 3 more unknowns than checks: ML cannot run"""
+    m = code.m
+    unk, it = sweeps(code, erased, itenum)
+    cols = np.flatnonzero(unk)
+    E = cols.size
+    res = dict(E0=int(np.asarray(erased).astype(bool).sum()), iterations=it, E=E, residual_cols=cols, T=0,
+               touched=np.zeros(0, dtype=np.int64), breaks=False, break_col=None, displaced=0, zero_row_swaps=0,
+               max_pivot_row=-1, not_min_stored=0, status=0)
+    if E == 0:
+        return res
+    pos = np.full(code.n, -1, dtype=np.int64)
+    pos[cols] = np.arange(E)
+    A = np.zeros((m, E), dtype=np.uint8)
+    for r, (c, h) in enumerate(_rows(code)):
+        sel = unk[c]
+        A[r, pos[c[sel]]] = h[sel]
+    zero = ~A.any(axis=1)
+    orig = np.arange(m)
+    res["touched"] = np.flatnonzero(~zero)
+    res["T"] = int(res["touched"].size)
+    if E > m:
+        res["status"] = 3
+        return res
+    for col in range(E):
+        nzr = np.flatnonzero(A[col:, col]) + col
+        if nzr.size == 0:
+            res["breaks"], res["break_col"] = True, col
+            break
+        p = int(nzr[0])
+        res["max_pivot_row"] = max(res["max_pivot_row"], p)
+        res["not_min_stored"] += int(orig[p] != orig[nzr].min())
+        if p != col:
+            res["displaced"] += 1
+            res["zero_row_swaps"] += int(zero[col])
+            A[[col, p]] = A[[p, col]]
+            zero[[col, p]] = zero[[p, col]]
+            orig[[col, p]] = orig[[p, col]]
+        A[col] = MUL[int(INV[A[col, col]])][A[col]]
+        below = nzr[1:]
+        if below.size:
+            A[below] ^= MUL[A[below, col][:, None], A[col][None, :]]
+    res["status"] = 2 if res["breaks"] else 1
+    return res
+
+
+# ---- frames -------------------------------------------------------------------------------------------------------------------------
+def col_rows(code):
+    """Checks of every symbol (kept with the code)."""
+    if "_col_rows" not in code.__dict__:
+        out = [[] for _ in range(code.n)]
+        for r, (c, _) in enumerate(_rows(code)):
+            for j in c:
+                out[int(j)].append(r)
+        code.__dict__["_col_rows"] = out
+    return code.__dict__["_col_rows"]
+
+
+def erase(cw, era, fill=0x77):
+    """Codeword [n] or [n, S] with the erased symbols overwritten (their bytes must not matter)."""
+    sym = np.array(cw, dtype=np.uint8, copy=True)
+    sym[np.asarray(era).astype(bool)] = fill
+    return sym
+
+
+def _flip(rng, sym, j):
+    sym[j] ^= rng.integers(1, 256, size=sym[j].shape, dtype=np.uint8)     # every byte lane changes
+    return int(j)
+
+
+def corrupt_touched(rng, code, era, sym, pr=None, rows=None):
+    """A received symbol inside a TOUCHED check (one of `rows`, if given) changed in place: the residual system sees it (a
+    fast-path solution is then flagged unless the system stays consistent).  Returns the symbol."""
+    pr = pr or properties(code, era)
+    touched = set(pr["touched"].tolist())
+    if rows is not None:
+        touched &= set(int(r) for r in rows)
+    cr = col_rows(code)
+    cand = [j for j in np.flatnonzero(np.asarray(era) == 0) if touched & set(cr[j])]
+    return _flip(rng, sym, cand[int(rng.integers(len(cand)))])
+
+
+def corrupt_untouched(rng, code, era, sym, pr=None, lo=None, hi=None):
+    """A received symbol ALL of whose checks are untouched changed in place; with lo/hi, one of them in lo <= check < hi.  No
+    equation with an unknown sees it: the frame stays consistent, but the right-hand side of an all-zero row is no longer zero --
+    observable where the reference writes such a row back (logical positions break_col..E-1 of a rank-deficient frame, :127).
+    Returns the symbol, or None when the code has no such symbol."""
+    pr = pr or properties(code, era)
+    touched = set(pr["touched"].tolist())
+    cr = col_rows(code)
+    cand = [j for j in np.flatnonzero(np.asarray(era) == 0) if cr[j] and not (touched & set(cr[j])) and
+            (lo is None or any(lo <= r < hi for r in cr[j]))]
+    if not cand:
+        return None
+    return _flip(rng, sym, cand[int(rng.integers(len(cand)))])
+
+
+def extra_parity(rng, code, era, count=3):
+    """The erasures + up to `count` parity symbols of untouched checks, which the sweeps solve first (the sweeps then run to their
+    cap with something to do, and the ML stage starts from symbols the sweeps wrote).  Checked with `properties`: what is left is
+    still the planted system.  Returns the flags, or None when every check is touched."""
+    pr = properties(code, era)
+    free = np.setdiff1d(np.arange(code.m), pr["touched"])
+    for _ in range(20):
+        if free.size == 0:
+            return None
+        pick = rng.choice(free, size=min(count, free.size), replace=False)
+        era2 = np.array(era, copy=True)
+        era2[code.k + pick] = 1
+        pr2 = properties(code, era2)
+        if np.array_equal(pr2["residual_cols"], pr["residual_cols"]) and np.array_equal(pr2["touched"], pr["touched"]):
+            return era2
+    return None
+
+
+def case_frames(oc, code, pr, S, seed, codewords=False):
+    """Frames of one planted case: two codewords, a symbol corrupted inside a touched check, one corrupted inside untouched checks
+    only (inside the zero rows the reference writes back when the frame is rank deficient), extra parity erased, all clear.
+    oc: the oracle's code (its encoder makes the codewords).  Returns sym [F, n, S], era [F, n], kinds (and, asked for, the
+    codeword of every frame [F, n, S])."""
+    rng = np.random.default_rng(seed)
+    era0 = erasures(code)
+    cws = [oc.encode(rng.integers(0, 256, size=(code.k, S), dtype=np.uint8)).reshape(code.n, S) for _ in range(2)]
+    sym, era, kinds, cw = [], [], [], []
+
+    def add(kind, s, e, w):
+        sym.append(s); era.append(e); kinds.append(kind); cw.append(cws[w])
+    add("codeword", erase(cws[0], era0, 0x77), era0, 0)
+    add("codeword", erase(cws[1], era0, 0x00), era0, 1)
+    s = erase(cws[0], era0)
+    corrupt_touched(rng, code, era0, s, pr)
+    add("touched", s, era0, 0)
+    s = erase(cws[1], era0)
+    lo, hi = (pr["break_col"], pr["E"]) if pr["breaks"] else (None, None)
+    if corrupt_untouched(rng, code, era0, s, pr, lo, hi) is not None or corrupt_untouched(rng, code, era0, s, pr) is not None:
+        add("untouched", s, era0, 1)
+    era2 = extra_parity(rng, code, era0)
+    if era2 is not None:
+        add("extra_parity", erase(cws[0], era2), era2, 0)
+    add("all_clear", cws[1].copy(), np.zeros(code.n, dtype=np.uint8), 1)
+    out = (np.stack(sym), np.stack(era), kinds)
+    return out + (np.stack(cw),) if codewords else out
+
+
+def pi_inactivations(c):
+    """Inactivations of the fast path (tools/pi_model.py, build_schedule) on a codeword frame of case `c`, None where the family does
+    not fix them: the two-diagonal families open their cycle with one, a band of w diagonals needs w - 1, a block with every entry
+    E - 1.  tests/test_ml_planted_cpu.py asserts them on the model; the GPU test sets ML_PI_IMAX on either side."""
+    if c["kind"] in ("circulant2", "anti"):
+        return 1
+    if c["kind"] == "band":
+        return c["w"] - 1 if c["E"] > c["w"] + 1 else None
+    if c["kind"] == "dense" and c["T"] >= c["E"]:
+        return c["E"] - 1
+    return None
+
+
+# ---- the cases the tests run --------------------------------------------------------------------------------------------------------
+E_EDGES = (2, 15, 16, 17, 31, 32, 33, 47, 48, 49, 64, 150, 300)      # either side of the multiples of 16, the extremes
+WHERE = ("top", "bottom", "third", "clusters")
+
+
+def _where(m, T, want):
+    """The placement asked for where the block fits it, else bottom."""
+    if want == "third" and 3 * (T - 1) >= m:
+        return "bottom"
+    if want == "clusters" and T + 12 > m:
+        return "bottom"
+    return want
+
+
+def _case(n, k, kind, E, where, T=None, c=None, w=None):
+    m = n - k
+    T = E if T is None else T
+    where = _where(m, T, where)
+    name = "n%d_%s%s_E%d%s_%s" % (n, kind, "" if c is None else str(c), E, "" if T == E else "_T%d" % T, where)
+    return dict(name=name, n=n, k=k, kind=kind, E=E, T=T, where=where, c=c, w=w)
+
+
+def _cases():
+    cs = []
+    n, k = 600, 300
+    for i, E in enumerate(E_EDGES):
+        cs.append(_case(n, k, "circulant2", E, WHERE[i % 4]))
+        cs.append(_case(n, k, "anti", E, WHERE[(i + 1) % 4]))            # E = 2, 31, 48, 300 at the bottom
+    for E in (16, 33, 64, 150):
+        cs.append(_case(n, k, "anti", E, "bottom"))
+    for i, E in enumerate((2, 16, 17, 33, 64, 300)):
+        cs.append(_case(n, k, "circulant2_singular", E, WHERE[(i + 1) % 4]))
+    for i, E in enumerate((2, 15, 16, 17, 20)):                          # 20 + filler + 3 parity entries: the library's 24
+        cs.append(_case(n, k, "dense", E, WHERE[(i + 1) % 4]))
+    for i, E in enumerate((17, 32, 49, 64, 150, 300)):
+        cs.append(_case(n, k, "band", E, WHERE[(i + 1) % 4], w=16))
+    for E in (16, 33, 48, 64):
+        for c in (0, E // 2, E - 2):
+            cs.append(_case(n, k, "dupcol", E, "bottom", c=c))
+    cs.append(_case(n, k, "dupcol", 150, "top", c=0))
+    cs.append(_case(n, k, "dupcol", 40, "third", c=20))
+    for E, T in ((17, 12), (33, 20), (64, 50), (150, 100)):
+        cs.append(_case(n, k, "wide", E, "bottom" if E != 33 else "clusters", T=T))
+    for i, (E, T) in enumerate(((15, 30), (16, 32), (33, 66), (64, 128), (150, 300))):
+        cs.append(_case(n, k, "tall", E, WHERE[(i + 1) % 4], T=T))
+    # generic pivoting: blocks that reach into the logical positions 0..E-1, so non-zero rows are displaced and compete again
+    for E, where in ((16, "top"), (33, "third"), (64, "top")):
+        cs.append(_case(n, k, "generic", E, where))
+    for E, where in ((17, "top"), (40, "third"), (64, "top"), (48, "clusters")):
+        cs.append(_case(n, k, "generic_singular", E, where))
+    for E, T, where in ((33, 66, "top"), (16, 32, "third")):
+        cs.append(_case(n, k, "generic_tall", E, where, T=T))
+    n, k = 2048, 1024
+    cs += [_case(n, k, "generic_singular", 49, "top"), _case(n, k, "circulant2", 16, "bottom"), _case(n, k, "circulant2", 300, "bottom"), _case(n, k, "anti", 17, "third"),
+           _case(n, k, "anti", 64, "bottom"), _case(n, k, "anti", 300, "bottom"), _case(n, k, "band", 150, "clusters", w=16),
+           _case(n, k, "dupcol", 64, "bottom", c=32), _case(n, k, "dense", 16, "bottom"), _case(n, k, "tall", 48, "third", T=96),
+           _case(n, k, "wide", 49, "top", T=40), _case(n, k, "circulant2_singular", 300, "bottom")]
+    # the ML stage's limit of 4096 checks, planted in rows >= 4000: the 12-bit logical and stored fields of the pivot key near 4095
+    n, k = 8192, 4096
+    cs += [_case(n, k, "anti", 64, "bottom"), _case(n, k, "circulant2_singular", 33, "bottom"),
+           _case(n, k, "dupcol", 48, "bottom", c=24), _case(n, k, "tall", 47, "bottom", T=94),
+           # half of the block at checks 5.., half at checks >= 4000: pivots from rows near 4095 displace NON-ZERO rows, which then
+           # compete from logical positions >= 4000 with small stored indices -- both edges of the key at once
+           _case(n, k, "generic_singular", 48, "clusters")]
+    # E = m and E = m + 1 (more unknowns than checks: status 3) on a small code with k >= m + 1
+    cs += [_case(100, 60, "band", 40, "top", w=3), _case(100, 60, "wide", 41, "top", T=40)]
+    return {c["name"]: c for c in cs}
+
+
+CASES = _cases()
+
+
+def case_code(name, device=True):
+    c = CASES[name]
+    rng = np.random.default_rng(9000 + list(CASES).index(name))
+    return plant(rng, c["n"], c["k"], c["E"], placement(c["n"] - c["k"], c["T"], c["where"]), c["kind"], c=c["c"], w=c["w"], device=device)
+
+
+# several blocks in one code: a frame erases any union of them, so one batch of one code holds every family and residual systems
+# of 2 .. 300 unknowns -- all 16 size classes of the ML stage's work list (class = 16 * unknowns / m)
+MIXED_BLOCKS = (("generic_singular", 40, {}), ("circulant2", 2, {}), ("dense", 16, {}), ("anti", 17, {}), ("dupcol", 20, {"c": 9}), ("circulant2_singular", 31, {}),
+                ("band", 33, {"w": 16}), ("wide", 24, {"T": 20}), ("tall", 20, {"T": 40}), ("circulant2", 64, {}), ("anti", 33, {}))
+
+
+def mixed_code():
+    """(600,300): the blocks of MIXED_BLOCKS one under the other from check 0 on (the tall one overlaps its successor's rows:
+    300 unknowns, 300 checks)."""
+    rng = np.random.default_rng(9900)
+    m, blocks, r0 = 300, [], 0
+    for kind, E, kw in MIXED_BLOCKS:
+        T = kw.get("T", E)
+        r0 = min(r0, m - T)
+        blocks.append(dict(kind=kind, E=E, rows=np.arange(r0, r0 + T), c=kw.get("c"), w=kw.get("w")))
+        r0 += min(T, E)
+    return plant_many(rng, 600, 300, blocks)
+
+
+def mixed_unions(code):
+    """Unions of the mixed code's blocks: each block alone, then for every size class up to three unions of full-rank blocks (those
+    with the tall block first: only surplus checks can make a system inconsistent) and two unions with a deficient block."""
+    nb = len(code.plant)
+    size = [p["E"] for p in code.plant]
+    full = [not p["expect"]["breaks"] for p in code.plant]
+    tall = [b for b in range(nb) if code.plant[b]["kind"] in ("tall", "generic_tall")]
+    out = [[b] for b in range(nb)]
+    masks = sorted(range(1, 1 << nb), key=lambda mk: (not any(mk >> b & 1 for b in tall), mk))
+    per_class = {}
+    for mask in masks:
+        which = [b for b in range(nb) if mask >> b & 1]
+        key = (min(15, 16 * sum(size[b] for b in which) // code.m), all(full[b] for b in which))
+        if len(which) > 1 and per_class.setdefault(key, 0) < (3 if key[1] else 2):
+            per_class[key] += 1
+            out.append(which)
+    if list(range(nb)) not in out:
+        out.append(list(range(nb)))         # every block: as many unknowns as the code has source symbols
+    return out
+
+
+def long_code():
+    """(600,300) for the long batches: a generic block of 12 unknowns in 24 checks at the top (surplus checks, generic pivoting), a
+    band of 258 unknowns (15 inactivations), a 2 x 2 block, and a 16-unknown block whose SECOND column is a multiple of its first."""
+    rng = np.random.default_rng(9901)
+    return plant_many(rng, 600, 300, [dict(kind="generic_tall", E=12, rows=np.arange(24)),
+                                      dict(kind="band", E=258, rows=np.arange(24, 282), w=16),
+                                      dict(kind="circulant2", E=2, rows=np.arange(282, 284)),
+                                      dict(kind="dupcol", E=16, rows=np.arange(284, 300), c=0)])
+
+
+if __name__ == "__main__":
+    for name_ in CASES:
+        code_ = case_code(name_)
+        pr_ = properties(code_, erasures(code_))
+        print("%-44s E %3d T %3d status %d break %-4s displaced %3d zero-row swaps %3d deepest pivot %4d" %
+              (name_, pr_["E"], pr_["T"], pr_["status"], pr_["break_col"], pr_["displaced"], pr_["zero_row_swaps"], pr_["max_pivot_row"]))
