@@ -55,6 +55,10 @@ EXPORTS_WIRE_DEV = [
 # every symbol include/ldpc_erasure_amd_frames.h declares (erasure flags out of the LDPC decoder, RS decode from erased frames)
 EXPORTS_FRAMES = ["ldpc_amd_decode_frames", "ldpc_amd_rs_info", "ldpc_amd_rs_decode_frames"]
 
+# every symbol include/ldpc_erasure_amd_sender.h declares (the fused sender: source symbols straight to wire packets)
+EXPORTS_SENDER = ["ldpc_amd_fec_encode_packets_dev", "ldpc_amd_fec_sender_info"]
+SENDER_PATHS = ("none", "fused", "composed")
+
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
 
@@ -162,6 +166,10 @@ def load_library():
     L.ldpc_amd_fec_rx_dev_flush.argtypes = [vp, vp, vp, C.POINTER(i32)]
     L.ldpc_amd_fec_rx_dev_dropped.argtypes = [vp]
     L.ldpc_amd_fec_rx_dev_dropped.restype = i64
+    # the fused sender (include/ldpc_erasure_amd_sender.h)
+    if hasattr(L, "ldpc_amd_fec_encode_packets_dev"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_encode_packets_dev.argtypes = [vp, i32, i32, i64, vp, C.c_uint, C.c_uint, vp]
+        L.ldpc_amd_fec_sender_info.argtypes = [vp, C.POINTER(i32)]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -549,6 +557,35 @@ class Context:
         """A two-buffer reassembler whose packets and blocks stay on this context's device (FecRxDevice)."""
         return FecRxDevice(self, n, k, S)
 
+    # -- the fused sender (include/ldpc_erasure_amd_sender.h)
+    def fec_encode_packets_device(self, code, source, fec_class=1, block0=0, out=None):
+        """source: torch uint8 [F][k][S] (or [F][k] for S = 1) on this context's device -> packets [F*n][8+S], the bytes of
+        fec_packetize_device(encode(code, source)) without the codeword array in between where the encoder can write the
+        packets itself (fec_sender_info() says which path ran).  Asynchronous on the context's stream."""
+        import torch
+        assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
+        n, k, _ = self.code_info(code)
+        F = source.shape[0]
+        S = 1 if source.ndim == 2 else source.shape[2]
+        assert source.shape[1] == k
+        if out is None:
+            out = torch.empty((F * n, 8 + S), dtype=torch.uint8, device=source.device)
+        assert tuple(out.shape) == (F * n, 8 + S) and out.dtype == torch.uint8
+        self._check(self._L.ldpc_amd_fec_encode_packets_dev(self._h, code, S, F, _ptr(source), fec_class, block0, _ptr(out)),
+                    "fec_encode_packets_dev")
+        return out
+
+    def fec_sender_info(self):
+        """{"path": "none" | "fused" | "composed" of the last fec_encode_packets_device call, "scratch_bytes": codeword scratch the
+        context holds for the composed path}."""
+        info = (C.c_int * 4)()
+        self._check(self._L.ldpc_amd_fec_sender_info(self._h, info), "fec_sender_info")
+        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1])}
+
+    def fec_tx_device(self, code, S, fec_class=1, block0=0):
+        """A sender that numbers its blocks across calls (FecTxDevice)."""
+        return FecTxDevice(self, code, S, fec_class, block0)
+
 
 # ---------------------------------------------------------------------------------------------------------
 # Host-side wire format (include/ldpc_erasure_amd_wire.h): FEC header, packetiser, two-buffer reassembler.
@@ -689,6 +726,24 @@ class FecRxDevice:
             self.close()
         except Exception:
             pass
+
+
+class FecTxDevice:
+    """The sender's side of FecRxDevice.  Its one piece of state is the reference's block counter (blockNum += 1 per frame,
+    OpenCL/device/ldpc_erasure_encoder_VITA_in_UDP_out.cl:134): send(source) returns the packets of F frames numbered from
+    next_block on and advances it by F modulo 256."""
+
+    def __init__(self, ctx, code, S, fec_class=1, block0=0):
+        self._ctx, self.code, self.S, self.fec_class = ctx, code, S, fec_class
+        self.n, self.k, _ = ctx.code_info(code)
+        self.next_block = block0 & 0xFF
+
+    def send(self, source, out=None):
+        """source: torch uint8 [F][k][S] (or [F][k] for S = 1) -> packets [F*n][8+S] in transmission order."""
+        assert (1 if source.ndim == 2 else source.shape[2]) == self.S
+        pk = self._ctx.fec_encode_packets_device(self.code, source, self.fec_class, self.next_block, out=out)
+        self.next_block = (self.next_block + source.shape[0]) & 0xFF
+        return pk
 
 
 def shard_frames(nframes, nranks, rank):

@@ -140,6 +140,8 @@ struct Knobs {
     int enc_b = 128;             // ENC_B: encoder piece size (128: two workgroups per CU; 256: the decoder's plan)
     int enc_list = 0;            // ENC_LIST: encoder streams the source rows in the order of their column degree
     int enc_group = 1;           // ENC_GROUP: encoder runs the grouped (level-collapsed) static schedule when the code has one; 0: level by level
+    int enc_pkt = 1;             // ENC_PKT: ldpc_amd_fec_encode_packets_dev -- the encoder writes the wire packets itself where it has that form (the persistent
+                                 // scatter encoder); 0: always encode into a scratch, then packetise (DESIGN.md section 7 has the two numbers)
     int enc_cap = 8;             // ENC_CAP: read when a code is REGISTERED -- a step of the grouped schedule pulls at most this many accumulators (0: no grouped schedule)
     int rs_generic = 0;          // RS=generic: RS decode always through the generic LDS kernel
     int rs_vw = 0;               // RS_VW: dwords per lane of the packet RS kernel (0 = auto = 1; 2 and 4 where S allows)
@@ -195,6 +197,8 @@ struct ldpc_amd_ctx {
     ldpc_amd::Scratch rsbad;    // int: malformed blocks of the last RS decode (decoded to zeros)
     ldpc_amd::Scratch rssel;    // RS from frames: [nblocks] int32 symbols received, then [nblocks][k] u16 the first k received positions
     ldpc_amd::Scratch frstatus; // decode_frames without a status array: the status words the finalise kernel reads
+    ldpc_amd::Scratch sender_cw;   // fec_encode_packets_dev, composed path: codewords of one chunk of frames (at most 256 MiB)
+    int sender_path = 0;           // ... path of the last call: 0 none yet, 1 fused kernel, 2 composed (ldpc_amd_fec_sender_info)
     // FPGA-harness emulation state (ldpc_amd_data_in / _ldpc_erasure_decoder / _data_out)
     // The run is streamed in chunks like the FPGA's frame loop (ldpc_erasure_decoder_perf_tests.cl:52): fpga_erased holds the
     // flags of ONE chunk, fpga_stats the two running counters (+ per-frame results: of the whole run when it is short
@@ -246,6 +250,11 @@ struct DecodeArgs {
 hipError_t upload_constants(hipStream_t s);
 int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &a);
 int launch_encode(ldpc_amd_ctx *ctx, const DevCode &code, int S, int64_t nframes, const uint8_t *src, uint8_t *cw);
+// The fused sender: source [nframes][k][S] -> packets [nframes * n][8 + S], the encoder storing packets instead of codewords.
+// Returns kEncodeNotFused, with nothing launched, where this call's encoder has no packet-output form (or ENC_PKT = 0).
+constexpr int kEncodeNotFused = 1;
+int launch_encode_packets(ldpc_amd_ctx *ctx, const DevCode &code, int S, int64_t nframes, const uint8_t *src, unsigned fec_class,
+                          unsigned block0, uint8_t *packets);
 int launch_fpga_halves(ldpc_amd_ctx *ctx, const DevCode &code, int64_t nframes, const uint8_t *erased, int num_iter,
                        int32_t *residual_sys, int32_t *iterations);
 int launch_selftest(ldpc_amd_ctx *ctx);

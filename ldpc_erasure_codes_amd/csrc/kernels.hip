@@ -35,6 +35,7 @@
 
 #include "internal.h"
 #include "gf256_dev.h"
+#include "fec_header_dev.h"
 #include "../../include/ldpc_erasure_amd_synth.h"
 
 namespace ldpc_amd {
@@ -640,6 +641,9 @@ struct ScatterArgs {
     int *err;                 // pinned host word (ldpc_amd_ctx::dev_err_host): a kernel whose assumptions do not hold reports here
     int dbg;                  // diagnostic build only (-DLDPC_AMD_MLDBG): 32768 = tier 1 also takes the frames with more than tcap steps,
                               // cut off at tcap steps (WRONG bytes: prices the first pass of a level-split tier 2)
+    uint32_t pkt_hdr;         // packet-output encoder (scatter_frame<..., PKT>): FEC class << 8 | block number of frame 0; out = the packets.
+                              // Nonzero pkt_out asks the launcher for that form (a launch that cannot take it is refused, nothing runs)
+    int pkt_out;
 };
 
 __device__ __forceinline__ MulTab lds_multab(const uint32_t *mt, uint32_t c)
@@ -706,13 +710,19 @@ __device__ __forceinline__ U4 stream_load16(const uint8_t *p)
     return *reinterpret_cast<const U4 *>(p);
 }
 
-template <bool NT>
+// A8: p is only 8-byte aligned (a payload at offset 8 of a packet of stride 8 + S): the plain store goes out as two 8-byte
+// stores, like fec_packetize_v16's; the non-temporal one is four dword stores either way.
+template <bool NT, bool A8 = false>
 __device__ __forceinline__ void stream_store16(uint8_t *p, const U4 &v)
 {
     if (NT) {
         uint32_t *q = reinterpret_cast<uint32_t *>(p);
         __builtin_nontemporal_store(v.x, q); __builtin_nontemporal_store(v.y, q + 1);
         __builtin_nontemporal_store(v.z, q + 2); __builtin_nontemporal_store(v.w, q + 3);
+    } else if (A8) {
+        uint2 *q = reinterpret_cast<uint2 *>(p);
+        q[0] = make_uint2(v.x, v.y);
+        q[1] = make_uint2(v.z, v.w);
     } else {
         *reinterpret_cast<U4 *>(p) = v;
     }
@@ -724,9 +734,14 @@ __device__ __forceinline__ void stream_store16(uint8_t *p, const U4 &v)
 // WARM without PERSIST (decoder, tier 2: ldpc_scatter_big_kernel with several pieces per work item): the item before was another piece of
 // the SAME frame -- everything the set-up builds from the frame's schedule and erasure flags (step tables, check -> slot table, row kinds,
 // translated lists, pull records) is in place; only the accumulators and the row counter start over.
-template <int LPR, int R, bool NT, bool INPLACE, int WPE = 4, bool PERSIST = false, bool WARM = false>
+// PKT (persistent encoder only: ldpc_scatter_static_pkt_kernel): a.out is a packet array [nframes * n][8 + S] instead of a codeword
+// array -- row j of frame f goes to the payload of packet f * n + j, and the lane that stores bytes 0..15 of the row, in the item of
+// slice 0, also stores the packet's 8-byte FEC header (the reference's sender, OpenCL/device/ldpc_erasure_encoder_VITA_in_UDP_out.cl:
+// 84-129,168-211: parity symbol, header and packet in one kernel).  The scatter form never reads `out` back, so nothing else changes.
+template <int LPR, int R, bool NT, bool INPLACE, int WPE = 4, bool PERSIST = false, bool WARM = false, bool PKT = false>
 __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned char *smem, const int64_t f, const int sl)
 {
+    static_assert(!PKT || (PERSIST && !INPLACE), "the packet-output form is the persistent encoder's");
     constexpr bool warm = WARM;
     // (the persistent form is the encoder's: the decoder's paths fold away in its instantiations)
     const bool is_static = PERSIST ? true : (a.static_sched != 0);
@@ -1027,12 +1042,26 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     // Uniform 64-bit bases + 32-bit per-lane offsets (a frame slice spans n * S < 4 GB): the row addresses then cost one
     // 32-bit multiply-add instead of 64-bit multiplies -- the streaming loop is bound by vector ALU issue, not by waits.
     const uint8_t *fin0 = a.sym + f * (int64_t)a.in_rows * S + (int64_t)sl * B;
-    uint8_t *fout0 = a.out + f * (int64_t)n * S + (int64_t)sl * B;
-    const uint32_t lo16 = (uint32_t)gl * 16u, S32 = (uint32_t)S;
+    constexpr int kPktHdr = PKT ? 8 : 0;   // LDPC_AMD_FEC_HEADER_BYTES in front of every output row
+    uint8_t *fout0 = a.out + f * (int64_t)n * (S + kPktHdr) + kPktHdr + (int64_t)sl * B;
+    const uint32_t lo16 = (uint32_t)gl * 16u, S32 = (uint32_t)S, O32 = (uint32_t)(S + kPktHdr);
     // (24-bit multiply: full rate, where the 32-bit one the compiler picked -- v_mad_u64_u32 -- runs at a quarter; j < 2^16 and
-    // S < 2^24 are checked by the host's plan)
+    // S < 2^24 are checked by the host's plan; PKT: 8 + S < 2^24 and n * (8 + S) < 2^32, checked by launch_encode)
     auto in_row = [&](int j) { return fin0 + (__umul24((uint32_t)j, S32) + lo16); };
-    auto out_row = [&](int j) { return fout0 + (__umul24((uint32_t)j, S32) + lo16); };
+    auto out_row = [&](int j) { return fout0 + (__umul24((uint32_t)j, O32) + lo16); };
+    // every output row leaves through here
+    const bool hdr_lane = PKT && sl == 0 && gl == 0;
+    const unsigned pkt_class = PKT ? (a.pkt_hdr >> 8) : 0u, pkt_block = PKT ? (a.pkt_hdr + (unsigned)f) : 0u;
+    auto put_row = [&](int j, const U4 &v) {
+        uint8_t *p = out_row(j);
+        stream_store16<NT, PKT>(p, v);
+        if (PKT && hdr_lane) {
+            const uint64_t hw = fec_header(pkt_class, pkt_block, (unsigned)j);
+            uint32_t *q = reinterpret_cast<uint32_t *>(p - kPktHdr);
+            if (NT) { __builtin_nontemporal_store((uint32_t)hw, q); __builtin_nontemporal_store((uint32_t)(hw >> 32), q + 1); }
+            else *reinterpret_cast<uint2 *>(q) = make_uint2((uint32_t)hw, (uint32_t)(hw >> 32));
+        }
+    };
     // H's static column lists (check | coef << 16); the encoder's are already in (slot | coef << 16) form
     const uint32_t *spad = is_static ? (grouped ? cd.encg_src : cd.enc_src) : cd.cell;
     const bool translate = !is_static;
@@ -1152,7 +1181,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
                 auto process = [&](const RowBatch &b) {
 #pragma unroll
                     for (int r = 0; r < R; r++) {
-                        if (!INPLACE) stream_store16<NT>(out_row(b.row[r]), b.v[r]);
+                        if (!INPLACE) put_row(b.row[r], b.v[r]);
                         uint32_t ew[KQ];
 #pragma unroll
                         for (int q = 0; q < KQ; q++) ew[q] = b.ew[r][q];
@@ -1183,7 +1212,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
 #pragma unroll
                 for (int r = 0; r < R; r++) {
                     const int j = j0 + r * RPW + g;
-                    if (cur.kind[r] == 2 || (cur.kind[r] == 1 && !INPLACE)) stream_store16<NT>(out_row(j), cur.v[r]);
+                    if (cur.kind[r] == 2 || (cur.kind[r] == 1 && !INPLACE)) put_row(j, cur.v[r]);
                     to_slots(cur.ew[r], 0xFFFFu);
                     scatter(cur.v[r], cur.ew[r]);
                 }
@@ -1199,7 +1228,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
 #pragma unroll
                 for (int r = 0; r < R; r++) {
                     const int j = j0 + r * RPW + g;
-                    if (cur.kind[r] == 2 || (cur.kind[r] == 1 && !INPLACE)) stream_store16<NT>(out_row(j), cur.v[r]);
+                    if (cur.kind[r] == 2 || (cur.kind[r] == 1 && !INPLACE)) put_row(j, cur.v[r]);
                     to_slots(cur.ew[r], 0xFFFFu);
                     scatter(cur.v[r], cur.ew[r]);
                 }
@@ -1311,7 +1340,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
                         }
                     }
                     val = gfmul16(lds_multab(mt, invc[s]), a16);
-                    stream_store16<NT>(out_row(t), val);
+                    put_row(t, val);
                 }
                 if (MODE != 1 || !a.xl_setup) to_slots(ew, (s < s1) ? (uint32_t)s : 0xFFFFu);   // (MODE 1: translated at set-up)
                 scatter(val, ew);
@@ -1373,7 +1402,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
                 for (int u = 0; u < U; u++)
                     if (on[u]) {
                         val[u] = gfmul16(lds_multab(mt, invc[su[u]]), a16[u]);
-                        stream_store16<NT>(out_row(tgt[su[u]]), val[u]);
+                        put_row(tgt[su[u]], val[u]);
                     }
                 uint32_t ew[U][KQ];
 #pragma unroll
@@ -1458,10 +1487,11 @@ __global__ __launch_bounds__(1024, WPE) void ldpc_scatter_big_kernel(ScatterArgs
 // Encoder, persistent form: the schedule is the CODE's, so a workgroup sets its tables up once and then encodes (frame, slice) items
 // handed out through a device counter (first come, first served: with a fixed stride the slowest CU's workgroups finish 7 % late).
 // The counter resets itself: the last workgroup to find it exhausted zeroes it for the next launch of this context.
-template <int LPR, int R, bool NT, int WPE>
-__global__ __launch_bounds__(1024, WPE) void ldpc_scatter_static_kernel(ScatterArgs a)
+// PKT: the packet-output form (scatter_frame).  The two forms are two kernels over one body, so that the codeword encoder keeps
+// its name in traces and profiles and the fused sender has one of its own.
+template <int LPR, int R, bool NT, int WPE, bool PKT>
+__device__ __forceinline__ void scatter_static_body(const ScatterArgs &a, unsigned char *smem)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int items = (int)(a.nframes * a.nslices);
     int *slot = reinterpret_cast<int *>(smem + a.lds_rowctr) + 2;   // (ints 0 / 1 of the region are re-initialised by every item)
     auto next_item = [&]() -> int {
@@ -1474,8 +1504,8 @@ __global__ __launch_bounds__(1024, WPE) void ldpc_scatter_static_kernel(ScatterA
     // across the loop -- 108 spilled registers against 12 of the one-item kernel)
     int it = next_item();
     if (it < items) {
-        scatter_frame<LPR, R, NT, false, WPE, true, false>(a, smem, it / a.nslices, it % a.nslices);
-        while ((it = next_item()) < items) scatter_frame<LPR, R, NT, false, WPE, true, true>(a, smem, it / a.nslices, it % a.nslices);
+        scatter_frame<LPR, R, NT, false, WPE, true, false, PKT>(a, smem, it / a.nslices, it % a.nslices);
+        while ((it = next_item()) < items) scatter_frame<LPR, R, NT, false, WPE, true, true, PKT>(a, smem, it / a.nslices, it % a.nslices);
     }
     if (threadIdx.x == 0) {
         __threadfence();
@@ -1484,6 +1514,21 @@ __global__ __launch_bounds__(1024, WPE) void ldpc_scatter_static_kernel(ScatterA
             __threadfence();
         }
     }
+}
+
+template <int LPR, int R, bool NT, int WPE>
+__global__ __launch_bounds__(1024, WPE) void ldpc_scatter_static_kernel(ScatterArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    scatter_static_body<LPR, R, NT, WPE, false>(a, smem);
+}
+
+// The fused sender: source rows in, FEC wire packets out (ldpc_amd_fec_encode_packets_dev).
+template <int LPR, int R, bool NT, int WPE>
+__global__ __launch_bounds__(1024, WPE) void ldpc_scatter_static_pkt_kernel(ScatterArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    scatter_static_body<LPR, R, NT, WPE, true>(a, smem);
 }
 
 #include "ml_kernel.inc"
@@ -1840,21 +1885,26 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
             }
             sa.big_list = (int32_t *)ctx->encctr.p + 16 * (ctx->enc_launches++ % kEncCtrs);
             char nm[96];
-            snprintf(nm, sizeof(nm), "ldpc_scatter_static_kernel<%d, %d, %s, %d>", LPR, R, nt ? "true" : "false", p.two_tier ? 8 : 4);
+            snprintf(nm, sizeof(nm), "ldpc_scatter_static%s_kernel<%d, %d, %s, %d>", sa.pkt_out ? "_pkt" : "", LPR, R, nt ? "true" : "false", p.two_tier ? 8 : 4);
             ctx->prof_names[LDPC_AMD_PROF_APPLY] = nm;
-#define LDPC_SCATTER_PS(NTV, WPE)                                                                            \
+#define LDPC_SCATTER_PS(KERNEL, NTV, WPE)                                                                    \
     {                                                                                                        \
-        auto kfn = ldpc_scatter_static_kernel<LPR, R, NTV, WPE>;                                             \
+        auto kfn = KERNEL<LPR, R, NTV, WPE>;                                                                 \
         LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
         hipLaunchKernelGGL(kfn, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);                         \
     }
-            if (p.two_tier) { if (nt) LDPC_SCATTER_PS(true, 8) else LDPC_SCATTER_PS(false, 8) }
-            else { if (nt) LDPC_SCATTER_PS(true, 4) else LDPC_SCATTER_PS(false, 4) }
+            if (sa.pkt_out) {   // the fused sender: packets out
+                if (p.two_tier) { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, true, 8) else LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, false, 8) }
+                else { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, true, 4) else LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, false, 4) }
+            } else
+            if (p.two_tier) { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_kernel, true, 8) else LDPC_SCATTER_PS(ldpc_scatter_static_kernel, false, 8) }
+            else { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_kernel, true, 4) else LDPC_SCATTER_PS(ldpc_scatter_static_kernel, false, 4) }
 #undef LDPC_SCATTER_PS
             LDPC_HIP_TRY(ctx, hipGetLastError());
             return LDPC_AMD_OK;
         }
     }
+    if (sa.pkt_out) return kEncodeNotFused;   // only the persistent encoder has a packet-output form: nothing was launched
 #define LDPC_SCATTER_T1(NTV, WPE, IPV)                                                                         \
     {                                                                                                        \
         auto kfn = ldpc_scatter_kernel<LPR, R, NTV, WPE, IPV>;                                                    \
@@ -1949,6 +1999,7 @@ static int launch_scatter(ldpc_amd_ctx *ctx, const ScatterPlan &p, const Scatter
         case 2: return launch_scatter_lpr<2, 1>(ctx, p, sa, big_list);
         case 1: return launch_scatter_lpr<1, 1>(ctx, p, sa, big_list);
     }
+    if (sa.pkt_out) return kEncodeNotFused;
     return set_error(ctx, LDPC_AMD_EUNSUP, "scatter: bad plan");
 }
 
@@ -2537,10 +2588,14 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
     return LDPC_AMD_OK;
 }
 
-int launch_encode(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, const uint8_t *src, uint8_t *cw)
+// pkt_out: cw is a packet array [nframes * n][8 + S] and pkt_hdr its header base (ScatterArgs::pkt_hdr) -- the fused sender.  Only
+// the persistent scatter encoder has that form: every other route returns kEncodeNotFused BEFORE anything is launched.
+static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, const uint8_t *src, uint8_t *cw, int pkt_out,
+                              uint32_t pkt_hdr)
 {
     if (nframes <= 0) return LDPC_AMD_OK;
     if (S == 1) {
+        if (pkt_out) return kEncodeNotFused;
         // all parity symbols erased: one in-order sweep of the peeling decoder IS the encoder
         // (row i has exactly one unknown, column k+i, once rows < i are done: triangle form).
         DecodeArgs d{};
@@ -2553,6 +2608,8 @@ int launch_encode(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, 
     if (!kn.apply_gather && cd.maxcoldeg <= 16) {
         // scatter form with the static schedule: source rows read once, all m accumulators in LDS
         ScatterPlan plan = plan_scatter(kn, cd, S);
+        // (packets: a frame's rows are 8 + S bytes apart -- the 32-bit offsets and 24-bit multiplies must hold for that stride)
+        if (pkt_out && ((uint64_t)cd.n * (uint64_t)(S + 8) >= (1ull << 32) || S + 8 >= (1 << 24))) return kEncodeNotFused;
         if (plan.lpr > 0) {
             plan.two_tier = false; plan.tcap = cd.m; plan.lds1 = plan.lds2;
             // The encoder needs all m accumulators (every check is a step), which at 256-byte row pieces fills the LDS with
@@ -2594,7 +2651,7 @@ int launch_encode(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, 
                 // the lists did not fit: the level table of the plan above was sized for the groups, the plain schedule has more levels
                 const int saved = ctx->knobs.enc_group;
                 ctx->knobs.enc_group = 0;
-                const int rc_ = launch_encode(ctx, cd, S, nframes, src, cw);
+                const int rc_ = launch_encode_impl(ctx, cd, S, nframes, src, cw, pkt_out, pkt_hdr);
                 ctx->knobs.enc_group = saved;
                 return rc_;
             }
@@ -2611,15 +2668,29 @@ int launch_encode(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, 
             sa.enc_group = grouped ? 1 : 0;
             ctx->last_enc_grouped = sa.enc_group;
             sa.enc_list = kn.enc_list;   // measured slower (4.62 vs 4.14 ms): off unless asked for
+            sa.pkt_out = pkt_out; sa.pkt_hdr = pkt_hdr;
             return launch_scatter(ctx, plan, sa, nullptr);
         }
     }
+    if (pkt_out) return kEncodeNotFused;
     ApplyArgs aa{};
     aa.code = cd; aa.S = S; aa.nframes = nframes; aa.sym = src; aa.erased = nullptr; aa.in_rows = cd.k; aa.out = cw;
     const size_t lds = (size_t)cd.m * 4 + (size_t)(cd.m + 2) * 2;
     hipLaunchKernelGGL(ldpc_apply_kernel, dim3((unsigned)nframes), dim3(512), lds, ctx->stream, aa);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     return LDPC_AMD_OK;
+}
+
+int launch_encode(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, const uint8_t *src, uint8_t *cw)
+{
+    return launch_encode_impl(ctx, cd, S, nframes, src, cw, 0, 0u);
+}
+
+int launch_encode_packets(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, const uint8_t *src, unsigned fec_class, unsigned block0,
+                          uint8_t *packets)
+{
+    if (ctx->knobs.enc_pkt == 0 || ((uintptr_t)packets & 7) != 0 || ((uintptr_t)src & 15) != 0) return kEncodeNotFused;
+    return launch_encode_impl(ctx, cd, S, nframes, src, packets, 1, ((uint32_t)(fec_class & 0xffu) << 8) | (uint32_t)(block0 & 0xffu));
 }
 
 // FRAMES: val is the frame array [nblocks][n][S], idx / nrecv what rs_select_kernel wrote (launch_rs_decode_frames)

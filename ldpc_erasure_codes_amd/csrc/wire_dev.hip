@@ -30,7 +30,9 @@
 #include <new>
 
 #include "internal.h"
+#include "fec_header_dev.h"
 #include "../../include/ldpc_erasure_amd_wire_dev.h"
+#include "../../include/ldpc_erasure_amd_sender.h"
 
 using namespace ldpc_amd;
 
@@ -43,12 +45,7 @@ constexpr int kScanPrefetch = 16;   // groups of 64 dense headers a scan lane ho
 // Result record of one scan, read back by the host (32-bit words, then the closed blocks' wire numbers).
 enum : int { R_CUR, R_NEXT, R_CCNT, R_NCNT, R_CLOSES, R_ERR, R_CONSUMED_LO, R_CONSUMED_HI, R_DROPPED_LO, R_DROPPED_HI, R_WORDS = 16 };
 
-__device__ __forceinline__ uint64_t fec_header(unsigned fec_class, unsigned block, unsigned symbol)
-{
-    // ldpc_amd_fec_header_pack: {class:8 | block:8 | symbol:16} in both halves of a 64-bit word
-    const uint64_t d = ((uint64_t)(fec_class & 0xffu) << 24) | ((uint64_t)(block & 0xffu) << 16) | (uint64_t)(symbol & 0xffffu);
-    return (d << 32) | d;
-}
+constexpr size_t kSenderScratchMax = (size_t)256 << 20;   // composed sender: codewords of one chunk of frames
 
 inline unsigned grid_for(int64_t items)
 {
@@ -320,6 +317,55 @@ int ldpc_amd_fec_packetize_dev(ldpc_amd_ctx *ctx, const uint8_t *frames, int64_t
                            frames, rows, n, S, fec_class, block0, packets);
     }
     LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// ---- the sender (include/ldpc_erasure_amd_sender.h) ---------------------------------------------------------------------
+// Fused where the encoder has a packet-output form (launch_encode_packets: the persistent scatter encoder stores its rows at their
+// places in the packet array and the headers beside them -- the reference's one-kernel sender, ...VITA_in_UDP_out.cl:84-129,168-211);
+// else composed: encode a chunk of frames into the context's scratch, packetise it, next chunk.  The chunks follow one another on
+// the context's stream, so the scratch is free again when the next encode starts.
+int ldpc_amd_fec_encode_packets_dev(ldpc_amd_ctx *ctx, int code, int S, int64_t nframes, const uint8_t *source, unsigned fec_class,
+                                    unsigned block0, uint8_t *packets)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    const DevCode &cd = ctx->codes[code]->dev;
+    if (nframes < 0 || S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_dev: bad nframes/S");
+    if (nframes == 0) return LDPC_AMD_OK;
+    if (cd.enc_nlevels == 0) return set_error(ctx, LDPC_AMD_EUNSUP, "code is not in triangle form: no systematic encoder");
+    if (S != 1 && S % 16) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 16 (got %d)", S);
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_dev: source / packets must be device pointers of device %d", ctx->device);
+    const size_t src_frame = (size_t)cd.k * S, cw_frame = (size_t)cd.n * S, pk_frame = (size_t)cd.n * ((size_t)S + kHdr);
+    const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)nframes, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)nframes;
+    if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_dev: source and packets overlap");
+    int rc = launch_encode_packets(ctx, cd, S, nframes, source, fec_class, block0, packets);
+    if (rc != kEncodeNotFused) {
+        if (rc == LDPC_AMD_OK) ctx->sender_path = 1;
+        return rc;
+    }
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nframes, (int64_t)(kSenderScratchMax / cw_frame)));
+    if ((rc = scratch_reserve(ctx, ctx->sender_cw, (size_t)chunk * cw_frame))) return rc;
+    uint8_t *cw = (uint8_t *)ctx->sender_cw.p;
+    for (int64_t f0 = 0; f0 < nframes; f0 += chunk) {
+        const int64_t cnt = std::min(chunk, nframes - f0);
+        if ((rc = launch_encode(ctx, cd, S, cnt, source + (size_t)f0 * src_frame, cw))) return rc;
+        if ((rc = ldpc_amd_fec_packetize_dev(ctx, cw, cnt, cd.n, S, fec_class, (block0 + (unsigned)(f0 & 0xff)) & 0xffu, packets + (size_t)f0 * pk_frame)))
+            return rc;
+    }
+    ctx->sender_path = 2;
+    return LDPC_AMD_OK;
+}
+
+int ldpc_amd_fec_sender_info(ldpc_amd_ctx *ctx, int info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_sender_info: info must not be null");
+    info[0] = ctx->sender_path;
+    info[1] = (int)std::min<size_t>(ctx->sender_cw.cap, (size_t)INT32_MAX);
+    info[2] = info[3] = 0;
     return LDPC_AMD_OK;
 }
 
