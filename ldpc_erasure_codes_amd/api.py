@@ -58,6 +58,9 @@ EXPORTS_FRAMES = ["ldpc_amd_decode_frames", "ldpc_amd_rs_info", "ldpc_amd_rs_dec
 # every symbol include/ldpc_erasure_amd_sender.h declares (the fused sender: source symbols straight to wire packets)
 EXPORTS_SENDER = ["ldpc_amd_fec_encode_packets_dev", "ldpc_amd_fec_sender_info"]
 SENDER_PATHS = ("none", "fused", "composed")
+# every symbol include/ldpc_erasure_amd_receiver.h declares (the fused receiver: wire packets straight to decoded frames)
+EXPORTS_RECEIVER = ["ldpc_amd_fec_rx_dev_decode_many", "ldpc_amd_fec_rx_dev_decode_flush", "ldpc_amd_fec_receiver_info"]
+RECEIVER_PATHS = ("none", "fused", "composed")
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
@@ -170,6 +173,11 @@ def load_library():
     if hasattr(L, "ldpc_amd_fec_encode_packets_dev"):   # (absent from the older builds tools/ab_lib.py loads)
         L.ldpc_amd_fec_encode_packets_dev.argtypes = [vp, i32, i32, i64, vp, C.c_uint, C.c_uint, vp]
         L.ldpc_amd_fec_sender_info.argtypes = [vp, C.POINTER(i32)]
+    # the fused receiver (include/ldpc_erasure_amd_receiver.h)
+    if hasattr(L, "ldpc_amd_fec_rx_dev_decode_many"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_rx_dev_decode_many.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i64)]
+        L.ldpc_amd_fec_rx_dev_decode_flush.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]
+        L.ldpc_amd_fec_receiver_info.argtypes = [vp, C.POINTER(i32)]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -586,6 +594,14 @@ class Context:
         """A sender that numbers its blocks across calls (FecTxDevice)."""
         return FecTxDevice(self, code, S, fec_class, block0)
 
+    # -- the fused receiver (include/ldpc_erasure_amd_receiver.h)
+    def fec_receiver_info(self):
+        """{"path": "none" | "fused" | "composed" of the last FecRxDevice.decode_many call, "scratch_bytes": received-symbol scratch
+        the context holds for the composed path, "blocks": blocks that call decoded}."""
+        info = (C.c_int * 4)()
+        self._check(self._L.ldpc_amd_fec_receiver_info(self._h, info), "fec_receiver_info")
+        return {"path": RECEIVER_PATHS[info[0]], "scratch_bytes": int(info[1]), "blocks": int(info[2])}
+
 
 # ---------------------------------------------------------------------------------------------------------
 # Host-side wire format (include/ldpc_erasure_amd_wire.h): FEC header, packetiser, two-buffer reassembler.
@@ -705,6 +721,39 @@ class FecRxDevice:
         blk = C.c_int(-1)
         rc = self._ctx._check(self._L.ldpc_amd_fec_rx_dev_flush(self._h, _ptr(sym), _ptr(er), C.byref(blk)), "fec_rx_dev_flush")
         return (blk.value, sym, er) if rc == 1 else None
+
+    def _frames(self, B):
+        import torch
+        dev = self._device()
+        shape = (B, self.n) if self.S == 1 else (B, self.n, self.S)
+        i32 = [torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(4)]
+        return DecodedFrames(torch.empty(shape, dtype=torch.uint8, device=dev), i32[0], i32[1], i32[2],
+                             torch.empty((B, self.n), dtype=torch.uint8, device=dev), i32[3])
+
+    def decode_many(self, code, packets, max_blocks, max_sweeps=10, do_ml=1):
+        """push_many + Context.decode_frames in one call (include/ldpc_erasure_amd_receiver.h): packets torch uint8 [P][8+S] on the
+        device -> (blocks int32 [B], DecodedFrames of the B closed blocks, consumed).  Where the decoder can fetch its rows from the
+        packets itself no array of received symbols is written (Context.fec_receiver_info() says which path ran).  Keep `packets`
+        alive until the context's stream has passed the call."""
+        import torch
+        assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.shape[1] == 8 + self.S
+        fr = self._frames(max(max_blocks, 1))
+        blocks = np.zeros(max(max_blocks, 1), dtype=np.int32)
+        used = C.c_int64(0)
+        nb = self._ctx._check(self._L.ldpc_amd_fec_rx_dev_decode_many(
+            self._h, code, _ptr(packets) if packets.numel() else None, packets.shape[0], max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps),
+            _ptr(fr.residual), _ptr(fr.status), _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, max_blocks, C.byref(used)),
+            "fec_rx_dev_decode_many")
+        return blocks[:nb], DecodedFrames(*(t[:nb] for t in fr)), used.value
+
+    def decode_flush(self, code, max_sweeps=10, do_ml=1):
+        """None, or (block number, DecodedFrames of that one block) for the block the end of the stream closes."""
+        fr = self._frames(1)
+        blk = C.c_int(-1)
+        rc = self._ctx._check(self._L.ldpc_amd_fec_rx_dev_decode_flush(
+            self._h, code, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status), _ptr(fr.erased_out),
+            _ptr(fr.residual_src), C.byref(blk)), "fec_rx_dev_decode_flush")
+        return (blk.value, fr) if rc == 1 else None
 
     @property
     def dropped(self):

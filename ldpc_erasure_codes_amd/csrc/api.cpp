@@ -117,6 +117,7 @@ static const KnobDesc kKnobs[] = {
     LDPC_KNOB_INT("ENC_GROUP", enc_group, x == 0 || x == 1),
     LDPC_KNOB_INT("ENC_CAP", enc_cap, x >= 0 && x <= 64),
     LDPC_KNOB_INT("ENC_PKT", enc_pkt, x == 0 || x == 1),
+    LDPC_KNOB_INT("RX_PKT", rx_pkt, x == 0 || x == 1),
     {"RS", [](Knobs &k, const char *v) { if (!strcmp(v, "generic")) k.rs_generic = 1; else if (!strcmp(v, "fast")) k.rs_generic = 0; else return false; return true; },
      [](Knobs &k) { k.rs_generic = 0; }, [](const Knobs &k) { return (long long)k.rs_generic; }},
     LDPC_KNOB_INT("RS_VW", rs_vw, x == 0 || x == 1 || x == 2 || x == 4),
@@ -837,7 +838,7 @@ void ldpc_amd_cleanup(ldpc_amd_ctx *ctx)
     }
     Scratch *all[] = {&ctx->sched, &ctx->mlws, &ctx->mlstate, &ctx->mlops, &ctx->mlrec, &ctx->mllist, &ctx->biglist, &ctx->encctr, &ctx->stage_in, &ctx->stage_er,
                       &ctx->stage_out, &ctx->stage_i32, &ctx->schedpull, &ctx->schedlists, &ctx->rsws, &ctx->rsbad, &ctx->fpga_erased, &ctx->fpga_stats,
-                      &ctx->rssel, &ctx->frstatus, &ctx->stage_fr, &ctx->sender_cw};
+                      &ctx->rssel, &ctx->frstatus, &ctx->stage_fr, &ctx->sender_cw, &ctx->rx_sym, &ctx->rx_er, &ctx->rx_src};
     for (Scratch *s : all) scratch_free(*s);
     for (auto &v : ctx->prof_events)
         for (auto &pr : v) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }

@@ -142,6 +142,8 @@ struct Knobs {
     int enc_group = 1;           // ENC_GROUP: encoder runs the grouped (level-collapsed) static schedule when the code has one; 0: level by level
     int enc_pkt = 1;             // ENC_PKT: ldpc_amd_fec_encode_packets_dev -- the encoder writes the wire packets itself where it has that form (the persistent
                                  // scatter encoder); 0: always encode into a scratch, then packetise (DESIGN.md section 7 has the two numbers)
+    int rx_pkt = 1;              // RX_PKT: ldpc_amd_fec_rx_dev_decode_many -- the decoder fetches its rows from the wire packets itself where it has that form (the
+                                 // scatter kernels); 0: always gather the closed blocks into a scratch, then decode (DESIGN.md section 7 has the two numbers)
     int enc_cap = 8;             // ENC_CAP: read when a code is REGISTERED -- a step of the grouped schedule pulls at most this many accumulators (0: no grouped schedule)
     int rs_generic = 0;          // RS=generic: RS decode always through the generic LDS kernel
     int rs_vw = 0;               // RS_VW: dwords per lane of the packet RS kernel (0 = auto = 1; 2 and 4 where S allows)
@@ -199,6 +201,11 @@ struct ldpc_amd_ctx {
     ldpc_amd::Scratch frstatus; // decode_frames without a status array: the status words the finalise kernel reads
     ldpc_amd::Scratch sender_cw;   // fec_encode_packets_dev, composed path: codewords of one chunk of frames (at most 256 MiB)
     int sender_path = 0;           // ... path of the last call: 0 none yet, 1 fused kernel, 2 composed (ldpc_amd_fec_sender_info)
+    ldpc_amd::Scratch rx_sym;      // fec_rx_dev_decode_many, composed path: received symbols of one chunk of closed blocks (at most 256 MiB)
+    ldpc_amd::Scratch rx_er;       // ... both paths: erasure flags of the closed blocks, [closes][n]
+    ldpc_amd::Scratch rx_src;      // ... fused path: row-source words of the closed blocks, [closes][n] u32 (PacketRows)
+    int receiver_path = 0;         // ... path of the last call: 0 none yet, 1 fused, 2 composed (ldpc_amd_fec_receiver_info)
+    int receiver_blocks = 0;       // ... blocks it decoded
     // FPGA-harness emulation state (ldpc_amd_data_in / _ldpc_erasure_decoder / _data_out)
     // The run is streamed in chunks like the FPGA's frame loop (ldpc_erasure_decoder_perf_tests.cl:52): fpga_erased holds the
     // flags of ONE chunk, fpga_stats the two running counters (+ per-frame results: of the whole run when it is short
@@ -226,6 +233,19 @@ struct ldpc_amd_ctx {
 namespace ldpc_amd {
 
 // ---- launchers implemented in the .hip files (all asynchronous on ctx->stream) -----------------
+// Where the rows of a packets-in decode lie (the fused receiver, wire_dev.hip): one word per (frame, symbol) --
+//   p < 2^31        payload of packet p: packets + p * plen + 8
+//   2^31 | i        row i of the staging planes: stage + i * S   (a carried block that got no newer packet for the symbol)
+//   0xFFFFFFFF      erased: nothing is fetched
+// src == nullptr: an ordinary decode, rows from DecodeArgs::sym.
+struct PacketRows {
+    const uint32_t *src = nullptr;      // [nframes][n]
+    const uint8_t *packets = nullptr;   // 8-byte aligned
+    const uint8_t *stage = nullptr;     // [2][n][S], 16-byte aligned
+    int plen = 0;                       // 8 + S
+};
+constexpr uint32_t kRowErased = 0xFFFFFFFFu, kRowStaged = 0x80000000u;
+
 struct DecodeArgs {
     DevCode code;
     int S;
@@ -243,12 +263,14 @@ struct DecodeArgs {
     // frames out (ldpc_amd_decode_frames): the flags of the symbols still unknown after the call, and how many of them are source
     // symbols -- the post-sweep mask, cleared behind the ML stage for the frames it solved.  Both nullptr: nothing is stored or launched
     uint8_t *erased_out = nullptr;        // [nframes][n] 0 / 1
+    PacketRows pin;                       // packets-in decode (sym == nullptr, S % 16 == 0, out of place; only where decode_reads_packets says so)
     int32_t *residual_src = nullptr;      // [nframes]; the kernels' ONE residual_sys outlet: set residual_src or residual_sys, never both
                                           // (launch_decode refuses both; flags_only runs use residual_sys, decode_frames residual_src)
 };
 
 hipError_t upload_constants(hipStream_t s);
 int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &a);
+bool decode_reads_packets(ldpc_amd_ctx *ctx, const DevCode &code, int S);   // launch_decode would take DecodeArgs::pin for this code and S
 int launch_encode(ldpc_amd_ctx *ctx, const DevCode &code, int S, int64_t nframes, const uint8_t *src, uint8_t *cw);
 // The fused sender: source [nframes][k][S] -> packets [nframes * n][8 + S], the encoder storing packets instead of codewords.
 // Returns kEncodeNotFused, with nothing launched, where this call's encoder has no packet-output form (or ENC_PKT = 0).

@@ -644,6 +644,14 @@ struct ScatterArgs {
     uint32_t pkt_hdr;         // packet-output encoder (scatter_frame<..., PKT>): FEC class << 8 | block number of frame 0; out = the packets.
                               // Nonzero pkt_out asks the launcher for that form (a launch that cannot take it is refused, nothing runs)
     int pkt_out;
+    // packets-in decoder (scatter_frame<..., PIN>; DecodeArgs::pin): row j of frame f is fetched where pin_src[f * n + j] says --
+    // payload of packet p (the word is p), row i of the receiver's staging planes (bit 31 | i), or nowhere (erased, 0xFFFFFFFF).
+    // sym is not read.  nullptr: rows come from sym
+    const uint32_t *pin_src;
+    const uint8_t *pin_pkt;   // the packet array; a packet is pin_plen = 8 + S bytes, its payload starts at byte 8
+    const uint8_t *pin_stage; // staging planes [2][n][S]
+    int pin_plen;
+    int lds_pin;              // the list of received rows of the list modes (SCATTER_DYN >= 2), [n] u16: the words keep the row kinds' region
 };
 
 __device__ __forceinline__ MulTab lds_multab(const uint32_t *mt, uint32_t c)
@@ -697,7 +705,9 @@ __device__ __forceinline__ void lds_xor16_at(uint32_t a1, uint32_t a2, const U4 
     __hip_atomic_fetch_xor(reinterpret_cast<lds_u64 *>((uintptr_t)a2), h ? lo : hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <bool NT>
+// A8: p is only 8-byte aligned (a payload at offset 8 of a packet of stride 8 + S): the plain load is two 8-byte loads, like
+// fec_rx_move's; the non-temporal one is four dword loads either way.
+template <bool NT, bool A8 = false>
 __device__ __forceinline__ U4 stream_load16(const uint8_t *p)
 {
     if (NT) {
@@ -706,6 +716,11 @@ __device__ __forceinline__ U4 stream_load16(const uint8_t *p)
         v.x = __builtin_nontemporal_load(q); v.y = __builtin_nontemporal_load(q + 1);
         v.z = __builtin_nontemporal_load(q + 2); v.w = __builtin_nontemporal_load(q + 3);
         return v;
+    }
+    if (A8) {
+        const uint2 *q = reinterpret_cast<const uint2 *>(p);
+        const uint2 lo = q[0], hi = q[1];
+        return U4{lo.x, lo.y, hi.x, hi.y};
     }
     return *reinterpret_cast<const U4 *>(p);
 }
@@ -738,10 +753,17 @@ __device__ __forceinline__ void stream_store16(uint8_t *p, const U4 &v)
 // array -- row j of frame f goes to the payload of packet f * n + j, and the lane that stores bytes 0..15 of the row, in the item of
 // slice 0, also stores the packet's 8-byte FEC header (the reference's sender, OpenCL/device/ldpc_erasure_encoder_VITA_in_UDP_out.cl:
 // 84-129,168-211: parity symbol, header and packet in one kernel).  The scatter form never reads `out` back, so nothing else changes.
-template <int LPR, int R, bool NT, bool INPLACE, int WPE = 4, bool PERSIST = false, bool WARM = false, bool PKT = false>
+// PIN (decoder only: ldpc_scatter_pktin_kernel / ldpc_scatter_pktin_big_kernel): the received rows are not an array [n][S] but lie where
+// the reassembler's plan found them -- in the payloads of wire packets, or in the receiver's staging planes (the reference's receiver,
+// OpenCL/device/ldpc_erasure_decoder_with_reordering_logic.cl:44-141,214-243, reassembles and decodes in one kernel).  The frame's n
+// row-source words are copied to LDS at set-up, IN PLACE OF the row kinds (a word says where a received row lies, or that the row is
+// erased and never solved -- kRowNever -- or erased and solved by a step -- kRowSolved, set by put_step), and the stream reads its word
+// where it read the row kind: no global load sits between a wave and its row loads.  Only the input address changes.
+template <int LPR, int R, bool NT, bool INPLACE, int WPE = 4, bool PERSIST = false, bool WARM = false, bool PKT = false, bool PIN = false>
 __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned char *smem, const int64_t f, const int sl)
 {
     static_assert(!PKT || (PERSIST && !INPLACE), "the packet-output form is the persistent encoder's");
+    static_assert(!PIN || (!PERSIST && !INPLACE && !PKT), "the packets-in form is the out-of-place decoder's");
     constexpr bool warm = WARM;
     // (the persistent form is the encoder's: the decoder's paths fold away in its instantiations)
     const bool is_static = PERSIST ? true : (a.static_sched != 0);
@@ -798,6 +820,11 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     constexpr int SPT = 2, EPT = 4;             // steps / symbols per thread held in registers (m <= 2048, n <= 4096)
     uint32_t stp[SPT];
     uint32_t siv[SPT], erv[EPT];
+    uint32_t srv[EPT];   // PIN: this thread's row-source words
+    uint32_t *psrc = reinterpret_cast<uint32_t *>(smem + a.lds_soc);   // PIN: [n] u32 where the row kinds are otherwise
+    constexpr uint32_t kRowNever = 0xFFFFFFFFu, kRowSolved = 0xFFFFFFFEu;
+    auto row_kind = [](uint32_t w) { return w == kRowNever ? 2 : (w == kRowSolved ? 0 : 1); };
+    const uint32_t *gsrc = PIN ? a.pin_src + f * (int64_t)n : nullptr;
 #pragma unroll
     for (int u = 0; u < SPT; u++) {
         const int s = tid + u * nthr;
@@ -808,6 +835,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     for (int u = 0; u < EPT; u++) {
         const int j = tid + u * nthr;
         erv[u] = (j < n && !warm) ? (erf ? (uint32_t)erf[j] : (j >= a.in_rows ? 1u : 0u)) : 0u;
+        if (PIN) srv[u] = (j < n && !warm) ? gsrc[j] : kRowNever;
     }
     // The column lists of the symbols solved in phase B go to the LDS left over behind the accumulators of this
     // frame (nsteps of nslots used), so that phase B issues no global load: a load behind the phase's row stores
@@ -866,10 +894,13 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
 #pragma unroll
     for (int u = 0; u < EPT; u++) {
         const int j = tid + u * nthr;
-        if (j < n) rk[j] = erv[u] ? (uint8_t)2 : (uint8_t)1;
+        if (!PIN && j < n) rk[j] = erv[u] ? (uint8_t)2 : (uint8_t)1;
+        if (PIN && j < n) psrc[j] = srv[u];   // (erased <=> kRowNever: fec_rx_sources writes the flag and the word together)
     }
-    for (int j = tid + EPT * nthr; j < n; j += nthr)
-        rk[j] = (erf ? (erf[j] != 0) : (j >= a.in_rows)) ? (uint8_t)2 : (uint8_t)1;
+    for (int j = tid + EPT * nthr; j < n; j += nthr) {
+        if (PIN) psrc[j] = gsrc[j];
+        else rk[j] = (erf ? (erf[j] != 0) : (j >= a.in_rows)) ? (uint8_t)2 : (uint8_t)1;
+    }
     }
     __syncthreads();
     auto put_step = [&](int s, uint32_t step, uint32_t iv) {
@@ -877,7 +908,8 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
         tgt[s] = (uint16_t)t;
         if (!is_static) soc[row] = (uint16_t)s;
         invc[s] = (uint8_t)iv;
-        if (!PERSIST) rk[t] = 0;
+        if (PIN) psrc[t] = kRowSolved;
+        else if (!PERSIST) rk[t] = 0;
     };
     auto put_pull = [&](int s, uint32_t lv, uint32_t p0, uint32_t p1) {
         // a pull entry leaves as (LDS address of the pulled accumulator slice | coef << 24), like the scatter entries
@@ -929,7 +961,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     // no conditional memory operation -- every lane group loads (and stores) a row in every pass -- and the compiler
     // can count the outstanding operations instead of waiting for all of them.  The list overwrites the row kinds,
     // which are pulled into registers first.  Rows that were erased and are never solved are zeroed here.
-    uint16_t *rlist = reinterpret_cast<uint16_t *>(rk);
+    uint16_t *rlist = PIN ? reinterpret_cast<uint16_t *>(smem + a.lds_pin) : reinterpret_cast<uint16_t *>(rk);   // (PIN: the words stay, the list has a place of its own)
     int nrecv = 0;
     // Sorted list mode (a.dyn_rows == 3): the list is additionally ordered by the number of accumulators a row feeds
     // (its column-list entries whose check is used by a step of this frame), most first.  The four row pieces a wavefront
@@ -957,7 +989,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
 #pragma unroll
         for (int u = 0; u < EPT; u++) {
             const int j = tid + u * nthr;
-            kd[u] = (j < n) ? (uint32_t)rk[j] : 0u;
+            kd[u] = (j < n) ? (PIN ? (uint32_t)row_kind(psrc[j]) : (uint32_t)rk[j]) : 0u;
             ec[u] = 0;
         }
         if (sorted_mode || win_mode) {
@@ -1047,7 +1079,26 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     const uint32_t lo16 = (uint32_t)gl * 16u, S32 = (uint32_t)S, O32 = (uint32_t)(S + kPktHdr);
     // (24-bit multiply: full rate, where the 32-bit one the compiler picked -- v_mad_u64_u32 -- runs at a quarter; j < 2^16 and
     // S < 2^24 are checked by the host's plan; PKT: 8 + S < 2^24 and n * (8 + S) < 2^32, checked by launch_encode)
-    auto in_row = [&](int j) { return fin0 + (__umul24((uint32_t)j, S32) + lo16); };
+    // PIN: a packet array is not bounded by 2^32 bytes (4096 frames of 2040 packets of 1032 bytes are 8.6 GB), so the address is ONE
+    // 64-bit multiply-add per row and lane -- per-lane base + index * stride, index and stride 32 bits (v_mad_u64_u32: quarter rate,
+    // the cost of the four full-rate instructions a 32-bit offset from a per-call base in 8-byte units would take, and without that
+    // form's 16 GB limit and its fall-back).  A staging row takes the other base and stride (three v_cndmask_b32).
+    const uint8_t *pin_b0 = PIN ? a.pin_pkt + 8 + (int64_t)sl * B + lo16 : nullptr;
+    const uint8_t *pin_b1 = PIN ? a.pin_stage + (int64_t)sl * B + lo16 : nullptr;
+    const uint32_t P32 = PIN ? (uint32_t)a.pin_plen : 0u;
+    auto pin_row = [&](uint32_t e) -> const uint8_t * {
+        const bool st = (e >> 31) != 0u;
+        return (st ? pin_b1 : pin_b0) + (uint64_t)(e & 0x7FFFFFFFu) * (uint64_t)(st ? S32 : P32);
+    };
+    auto in_row = [&](int j) -> const uint8_t * {
+        if constexpr (PIN) {
+            const uint32_t e = psrc[j];
+            const bool st = (e >> 31) != 0u;
+            return (st ? pin_b1 : pin_b0) + (uint64_t)(e & 0x7FFFFFFFu) * (uint64_t)(st ? S32 : P32);
+        } else {
+            return fin0 + (__umul24((uint32_t)j, S32) + lo16);
+        }
+    };
     auto out_row = [&](int j) { return fout0 + (__umul24((uint32_t)j, O32) + lo16); };
     // every output row leaves through here
     const bool hdr_lane = PKT && sl == 0 && gl == 0;
@@ -1133,7 +1184,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
             const int j = (int)rlist[valid ? idx : nrecv - 1];   // past the end: the last row again (same bytes, same place)
             b.kind[r] = valid ? 1 : 0;
             b.row[r] = j;
-            b.v[r] = stream_load16<NT>(in_row(j));
+            b.v[r] = stream_load16<NT, PIN>(in_row(j));
 #pragma unroll
             for (int q = 0; q < KQ; q++) {
                 const int e = gl + q * LPR;
@@ -1149,13 +1200,14 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int j = j0 + r * RPW + g;
-            const int kd = (j < nstream) ? (PERSIST ? 1 : (int)rk[j]) : 0;
+            const uint32_t pw = (PIN && j < nstream) ? psrc[j] : kRowSolved;   // PIN: one LDS read gives the kind and the address
+            const int kd = PIN ? row_kind(pw) : ((j < nstream) ? (PERSIST ? 1 : (int)rk[j]) : 0);
             b.kind[r] = kd;
             b.v[r] = U4{0, 0, 0, 0};
 #pragma unroll
             for (int q = 0; q < KQ; q++) b.ew[r][q] = 0xFFFFFFFFu;
             if (kd == 1) {
-                b.v[r] = stream_load16<NT>(in_row(j));
+                b.v[r] = stream_load16<NT, PIN>(PIN ? pin_row(pw) : in_row(j));
 #pragma unroll
                 for (int q = 0; q < KQ; q++) {
                     const int idx = gl + q * LPR;
@@ -1427,10 +1479,11 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
 
 // Tier 1: one workgroup per (frame, slice); frames with more than tcap steps are left to tier 2.
 // WPE = waves per SIMD the register allocation must allow (8 -> two 1024-thread workgroups per CU).
-template <int LPR, int R, bool NT, int WPE, bool INPLACE>
-__global__ __launch_bounds__(1024, WPE) void ldpc_scatter_kernel(ScatterArgs a)
+// PIN: the packets-in form (scatter_frame).  As with the encoder's packet-output form, the two forms are two kernels over one body:
+// the decoder keeps its names in traces and profiles, the fused receiver has its own.
+template <int LPR, int R, bool NT, int WPE, bool INPLACE, bool PIN>
+__device__ __forceinline__ void scatter_tier1_body(const ScatterArgs &a, unsigned char *smem)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // XCD-aware placement (LDPC_AMD_SCATTER_XCD=0 switches it off): workgroups are dealt round-robin over the 8 XCDs, so
     // block b = 8 i + x handling slice i % nslices of frame (i / nslices) * 8 + x keeps the slices of a frame -- the
     // four 256-byte pieces of every 1 KB row, and the frame's schedule -- on one XCD at about the same time.
@@ -1450,7 +1503,22 @@ __global__ __launch_bounds__(1024, WPE) void ldpc_scatter_kernel(ScatterArgs a)
 #else
     if (!a.static_sched && (int)a.sched_hdr[2 * f] > a.tcap) return;
 #endif
-    scatter_frame<LPR, R, NT, INPLACE, WPE>(a, smem, f, sl);
+    scatter_frame<LPR, R, NT, INPLACE, WPE, false, false, false, PIN>(a, smem, f, sl);
+}
+
+template <int LPR, int R, bool NT, int WPE, bool INPLACE>
+__global__ __launch_bounds__(1024, WPE) void ldpc_scatter_kernel(ScatterArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    scatter_tier1_body<LPR, R, NT, WPE, INPLACE, false>(a, smem);
+}
+
+// The fused receiver's tier 1: rows fetched from FEC wire packets and staging planes (ldpc_amd_fec_rx_dev_decode_many).
+template <int LPR, int R, bool NT, int WPE>
+__global__ __launch_bounds__(1024, WPE) void ldpc_scatter_pktin_kernel(ScatterArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    scatter_tier1_body<LPR, R, NT, WPE, false, true>(a, smem);
 }
 
 // Tier 2: the few frames with many steps (LDS sized for m accumulators), grid-stride over the compacted list.
@@ -1463,6 +1531,7 @@ __global__ __launch_bounds__(1024, WPE) void ldpc_scatter_big_kernel(ScatterArgs
     // A work item is t2_pieces consecutive pieces of ONE frame (1, 2 or all of them): the first sets the frame's tables up, the others find
     // them in place (scatter_frame<..., WARM>) -- the set-up was 9.7 % of a tier-2 workgroup's time on the cfg 3 batch, once per piece.
     // (few frames in the list -- the (4080,3060) batch has four -- keep one piece per item: the kernel then lasts one item, not one frame)
+    // (ldpc_scatter_pktin_big_kernel below is a copy of this loop: a fix here belongs there too)
     int P = a.t2_pieces > 1 ? a.t2_pieces : 1;
     while (P > 1 && !a.t2_force && (int64_t)a.big_list[0] * (a.nslices / P) < (int64_t)8 * gridDim.x) P >>= 1;
     const int G = a.nslices / P;
@@ -1480,6 +1549,34 @@ __global__ __launch_bounds__(1024, WPE) void ldpc_scatter_big_kernel(ScatterArgs
         for (int q = 1; q < P; q++) {
             __syncthreads();   // the last level of the piece before is through with the accumulators
             scatter_frame<LPR, R, NT, INPLACE, WPE, false, true>(a, smem, f, p0 + q);
+        }
+    }
+}
+
+// The fused receiver's tier 2: the same loop over scatter_frame<..., PIN>.  (A copy, not a body shared with ldpc_scatter_big_kernel: with the
+// shared body the existing instantiations came out with a few spilled registers more or less than before.)
+template <int LPR, int R, bool NT, int WPE = 4>
+__global__ __launch_bounds__(1024, WPE) void ldpc_scatter_pktin_big_kernel(ScatterArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // (the loop of ldpc_scatter_big_kernel, comments there)
+    int P = a.t2_pieces > 1 ? a.t2_pieces : 1;
+    while (P > 1 && !a.t2_force && (int64_t)a.big_list[0] * (a.nslices / P) < (int64_t)8 * gridDim.x) P >>= 1;
+    const int G = a.nslices / P;
+    const int items = a.big_list[0] * G;
+    int *slot = reinterpret_cast<int *>(smem + a.lds_rowctr) + 2;   // (ints 0 / 1 of the region are re-initialised by every frame)
+    for (;;) {
+        __syncthreads();
+        if (threadIdx.x == 0) *slot = atomicAdd(&a.big_list[1], 1);
+        __syncthreads();
+        const int it = *slot;
+        if (it >= items) break;
+        const int64_t f = a.big_list[2 + it / G];
+        const int p0 = (it % G) * P;
+        scatter_frame<LPR, R, NT, false, WPE, false, false, false, true>(a, smem, f, p0);
+        for (int q = 1; q < P; q++) {
+            __syncthreads();   // the last level of the piece before is through with the accumulators
+            scatter_frame<LPR, R, NT, false, WPE, false, true, false, true>(a, smem, f, p0 + q);
         }
     }
 }
@@ -1802,10 +1899,11 @@ struct ScatterPlan {
     bool two_tier = false;
     int lds1 = 0, lds2 = 0;                       // dynamic LDS bytes of tier 1 / tier 2
     int o_tgt = 0, o_invc = 0, o_lvl = 0, o_ctr = 0, o_mt = 0, o_soc = 0, o_chk = 0;  // offsets behind the accumulators (relative)
+    int o_pin = 0;      // packets-in decoder: the frame's row-source words
     int soc_bytes = 0;
 };
 
-static int scatter_tail_bytes(const DevCode &cd, ScatterPlan &p)
+static int scatter_tail_bytes(const DevCode &cd, ScatterPlan &p, bool pin = false, bool pin_list = false)
 {
     int off = 0;
     p.o_tgt = off; off += align_up(2 * cd.m, 16);
@@ -1813,19 +1911,24 @@ static int scatter_tail_bytes(const DevCode &cd, ScatterPlan &p)
     p.o_lvl = off; off += align_up(2 * (cd.m + 2), 16);
     p.o_ctr = off; off += 288;  // row-batch counter of the streaming phase, received-row count, bins of the sorted list / window counts
     p.o_mt = off;               // (the multiply tables start the LDS: counted by scatter_lds_bytes, not here)
-    p.o_soc = off; off += align_up(2 * cd.n, 16);  // row kinds (u8), later the list of received rows (u16)
+    p.o_soc = off; off += align_up((pin ? 4 : 2) * cd.n, 16);  // row kinds (u8), later the list of received rows (u16); packets-in decoder: row-source words (u32)
     p.soc_bytes = align_up(2 * cd.n, 16);
     p.o_chk = off; off += align_up(2 * (cd.m + 2), 16);  // check -> slot
+    p.o_pin = off;
+    if (pin && pin_list) off += align_up(2 * cd.n, 16);  // packets-in decoder, list modes: the list of received rows (the words stay for the whole frame)
     return off;
 }
 
-static ScatterPlan plan_scatter(const Knobs &kn, const DevCode &cd, int S)
+// pin: the plan of the packets-in decoder -- its row-source words (4 n bytes) take the place of the row kinds and the row list (2 n),
+// so tier 1 holds a few accumulators fewer ((2040,1530) at S = 1024: 4080 bytes more, tcap 241 instead of 256; with a list mode of the
+// stream, SCATTER_DYN >= 2, another 2 n bytes: 225) and a large code may get narrower pieces than the same decode from an array of rows
+static ScatterPlan plan_scatter(const Knobs &kn, const DevCode &cd, int S, bool pin = false)
 {
     ScatterPlan p;
     if ((uint64_t)cd.n * (uint64_t)S >= (1ull << 32) || S >= (1 << 24) || cd.n >= (1 << 16)) return p;   // the kernel addresses a frame with 32-bit offsets (24-bit multiplies)
     int B = kn.scatter_b;  // A/B knob: bytes of every row per workgroup
     while (B > 16 && (S % B) != 0) B >>= 1;
-    const int tail = scatter_tail_bytes(cd, p) + 8192;   // + the multiply tables in front of the accumulators
+    const int tail = scatter_tail_bytes(cd, p, pin, kn.scatter_dyn >= 2) + 8192;   // + the multiply tables in front of the accumulators
     while (B > 16 && cd.m * B + tail > 156 * 1024) B >>= 1;
     if (cd.m * B + tail > kLdsMax) return p;
     p.lpr = B / 16;
@@ -1854,6 +1957,7 @@ static void scatter_set_lds(ScatterArgs &sa, const ScatterPlan &p, int nacc)
     sa.lds_acc = 8192;
     sa.lds_tgt = base + p.o_tgt; sa.lds_invc = base + p.o_invc; sa.lds_lvlend = base + p.o_lvl;
     sa.lds_rowctr = base + p.o_ctr; sa.lds_mt = 0; sa.lds_soc = base + p.o_soc; sa.lds_chk = base + p.o_chk;
+    sa.lds_pin = base + p.o_pin;
     sa.lds_soc_bytes = p.soc_bytes;
 }
 
@@ -1912,12 +2016,24 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
         hipLaunchKernelGGL(kfn, grid, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);                       \
     }
     const bool ip = sa.inplace != 0;
+    const bool pin = sa.pin_src != nullptr;   // the fused receiver: rows from packets (out of place only: launch_decode checks)
+#define LDPC_SCATTER_T1P(NTV, WPE)                                                                           \
+    {                                                                                                        \
+        auto kfn = ldpc_scatter_pktin_kernel<LPR, R, NTV, WPE>;                                              \
+        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
+        hipLaunchKernelGGL(kfn, grid, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);                       \
+    }
     {
         char nm[96];
-        snprintf(nm, sizeof(nm), "ldpc_scatter_kernel<%d, %d, %s, %d, %s>", LPR, R, nt ? "true" : "false", p.two_tier ? 8 : 4,
+        if (pin) snprintf(nm, sizeof(nm), "ldpc_scatter_pktin_kernel<%d, %d, %s, %d>", LPR, R, nt ? "true" : "false", p.two_tier ? 8 : 4);
+        else snprintf(nm, sizeof(nm), "ldpc_scatter_kernel<%d, %d, %s, %d, %s>", LPR, R, nt ? "true" : "false", p.two_tier ? 8 : 4,
                  ip ? "true" : "false");
         ctx->prof_names[LDPC_AMD_PROF_APPLY] = nm;
     }
+    if (pin) {
+        if (p.two_tier) { if (nt) LDPC_SCATTER_T1P(true, 8) else LDPC_SCATTER_T1P(false, 8) }
+        else { if (nt) LDPC_SCATTER_T1P(true, 4) else LDPC_SCATTER_T1P(false, 4) }
+    } else
     if (p.two_tier) {
         if (ip) { if (nt) LDPC_SCATTER_T1(true, 8, true) else LDPC_SCATTER_T1(false, 8, true) }
         else { if (nt) LDPC_SCATTER_T1(true, 8, false) else LDPC_SCATTER_T1(false, 8, false) }
@@ -1926,6 +2042,7 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
         else { if (nt) LDPC_SCATTER_T1(true, 4, false) else LDPC_SCATTER_T1(false, 4, false) }
     }
 #undef LDPC_SCATTER_T1
+#undef LDPC_SCATTER_T1P
     LDPC_HIP_TRY(ctx, hipGetLastError());
     if (p.two_tier && big_list && !(sa.dbg & 32768)) {
         sa.tcap = sa.code.m; sa.nslots = sa.code.m; sa.big_list = big_list;
@@ -1950,9 +2067,20 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
     if (r2 == 4) LDPC_SCATTER_T2_R((LPR == 16 ? 4 : R), NTV, IPV)                                            \
     else if (r2 == 3) LDPC_SCATTER_T2_R((LPR == 16 ? 3 : R), NTV, IPV)                                       \
     else LDPC_SCATTER_T2_R(R, NTV, IPV)
+#define LDPC_SCATTER_T2P_R(RV, NTV)                                                                          \
+    {                                                                                                        \
+        auto kfn = ldpc_scatter_pktin_big_kernel<LPR, RV, NTV>;                                              \
+        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
+        hipLaunchKernelGGL(kfn, g2, dim3(THREADS), (size_t)p.lds2, ctx->stream, sa);                         \
+    }
+#define LDPC_SCATTER_T2P(NTV)                                                                                \
+    if (r2 == 4) LDPC_SCATTER_T2P_R((LPR == 16 ? 4 : R), NTV)                                                \
+    else if (r2 == 3) LDPC_SCATTER_T2P_R((LPR == 16 ? 3 : R), NTV)                                           \
+    else LDPC_SCATTER_T2P_R(R, NTV)
         {
             char nm[96];
-            snprintf(nm, sizeof(nm), "ldpc_scatter_big_kernel<%d, %d, %s, %s>", LPR, (LPR == 16 && (r2 == 3 || r2 == 4)) ? r2 : R, nt ? "true" : "false",
+            if (pin) snprintf(nm, sizeof(nm), "ldpc_scatter_pktin_big_kernel<%d, %d, %s>", LPR, (LPR == 16 && (r2 == 3 || r2 == 4)) ? r2 : R, nt ? "true" : "false");
+            else snprintf(nm, sizeof(nm), "ldpc_scatter_big_kernel<%d, %d, %s, %s>", LPR, (LPR == 16 && (r2 == 3 || r2 == 4)) ? r2 : R, nt ? "true" : "false",
                      ip ? "true" : "false");
             ctx->prof_names[LDPC_AMD_PROF_APPLY_TIER2] = nm;
         }
@@ -1960,7 +2088,8 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
         // SCATTER_T2B = 128: tier 2 with 128-byte pieces -- all m accumulators then take half a CU's LDS, so TWO tier-2 workgroups
         // share a CU (one streams while the other sets up / runs its levels), at twice the per-byte instruction count of an edge turn
         const int tail_b = p.lds2 - sa.code.m * 16 * p.lpr;   // tables + small arrays of the plan
-        const bool t2_128 = LPR == 16 && kn.scatter_t2b == 128 && (sa.S % 128) == 0 && sa.code.m * 128 + tail_b <= kLdsMax / 2;
+        // (not the packets-in form: with its words in LDS m 128-byte accumulators no longer fit half a CU for the built-in codes; SCATTER_T2B is ignored there)
+        const bool t2_128 = !pin && LPR == 16 && kn.scatter_t2b == 128 && (sa.S % 128) == 0 && sa.code.m * 128 + tail_b <= kLdsMax / 2;
         if (t2_128) {
             ScatterPlan p2 = p;
             p2.lpr = 8; p2.nslices = sa.S / 128; p2.lds2 = sa.code.m * 128 + tail_b;
@@ -1979,10 +2108,13 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
             else { if (nt) LDPC_SCATTER_T2B(true, false) else LDPC_SCATTER_T2B(false, false) }
 #undef LDPC_SCATTER_T2B
         } else
-        if (ip) { if (nt) LDPC_SCATTER_T2(true, true) else LDPC_SCATTER_T2(false, true) }
+        if (pin) { if (nt) LDPC_SCATTER_T2P(true) else LDPC_SCATTER_T2P(false) }
+        else if (ip) { if (nt) LDPC_SCATTER_T2(true, true) else LDPC_SCATTER_T2(false, true) }
         else { if (nt) LDPC_SCATTER_T2(true, false) else LDPC_SCATTER_T2(false, false) }
 #undef LDPC_SCATTER_T2_R
 #undef LDPC_SCATTER_T2
+#undef LDPC_SCATTER_T2P_R
+#undef LDPC_SCATTER_T2P
         prof_end(ctx, LDPC_AMD_PROF_APPLY_TIER2, ev2);
         LDPC_HIP_TRY(ctx, hipGetLastError());
     }
@@ -2018,6 +2150,7 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
             DecodeArgs c = d;
             c.nframes = std::min(kChunk, d.nframes - f0);
             if (d.sym) c.sym = d.sym + f0 * (int64_t)d.in_rows * d.S;
+            if (d.pin.src) c.pin.src = d.pin.src + f0 * cd.n;
             if (d.erased) c.erased = d.erased + f0 * cd.n;
             if (d.out) c.out = d.out + f0 * (int64_t)cd.n * d.S;
             if (d.sweeps) c.sweeps = d.sweeps + f0;
@@ -2050,8 +2183,11 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
     const Knobs &kn = ctx->knobs;
     const bool want_gather = kn.apply_gather != 0;
     ScatterPlan plan{};
-    if (!fused && !d.flags_only && !want_gather && cd.maxcoldeg <= 16) plan = plan_scatter(kn, cd, d.S);
+    const bool pin = d.pin.src != nullptr;   // the fused receiver: the rows are fetched from packets, there is no sym
+    if (!fused && !d.flags_only && !want_gather && cd.maxcoldeg <= 16) plan = plan_scatter(kn, cd, d.S, pin);
     const bool use_scatter = plan.lpr > 0;
+    if (pin && (!use_scatter || d.inplace || d.sym))   // (the caller asks decode_reads_packets first: this is a bug, not an input)
+        return set_error(ctx, LDPC_AMD_EINVAL, "internal: packets-in decode without the scatter kernel, in place, or with a row array");
     if (d.inplace && !use_scatter) return set_error(ctx, LDPC_AMD_EUNSUP, "in-place decode needs the scatter kernel");
 
     // workgroup shape: the peel is latency bound (serial solve chain per frame), so pick the frames-per-workgroup
@@ -2559,6 +2695,7 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
             ScatterArgs sa{};
             sa.code = cd; sa.S = d.S; sa.nslices = plan.nslices; sa.nframes = nf; sa.sym = d.sym; sa.erased = d.erased; sa.out = d.out;
             sa.in_rows = cd.n; sa.static_sched = 0; sa.inplace = d.inplace;
+            sa.pin_src = d.pin.src; sa.pin_pkt = d.pin.packets; sa.pin_stage = d.pin.stage; sa.pin_plen = d.pin.plen;
             sa.dbg = kn.ml_dbg; sa.err = ctx->dev_err_host; sa.xl_setup = kn.scatter_xl;
             sa.sched_pull = pa_pull; sa.pairs = pa_pairs; sa.sched_lists = pa_lists_on ? pa_lists : nullptr;
             sa.sched_hdr = pa.sched_hdr; sa.sched_steps = pa.sched_steps; sa.sched_lvlend = pa.sched_lvlend;
@@ -2586,6 +2723,16 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
         if ((rc = frames_finalize())) return rc;
     }
     return LDPC_AMD_OK;
+}
+
+// The dispatch of ldpc_amd_fec_rx_dev_decode_many: would launch_decode, handed DecodeArgs::pin for this code and S, run the
+// packets-in scatter kernels?  The conditions under which the same decode from an array of rows runs the scatter kernels, with the
+// plan made with the 4 n bytes of LDS the row-source words take in place of the 2 n of the row kinds; the row address wants index and stride in 32 bits.
+bool decode_reads_packets(ldpc_amd_ctx *ctx, const DevCode &cd, int S)
+{
+    const Knobs &kn = ctx->knobs;
+    if (S < 16 || (S % 16) != 0 || kn.apply_gather != 0 || cd.maxcoldeg > 16) return false;
+    return plan_scatter(kn, cd, S, true).lpr > 0;
 }
 
 // pkt_out: cw is a packet array [nframes * n][8 + S] and pkt_hdr its header base (ScatterArgs::pkt_hdr) -- the fused sender.  Only

@@ -33,6 +33,7 @@
 #include "fec_header_dev.h"
 #include "../../include/ldpc_erasure_amd_wire_dev.h"
 #include "../../include/ldpc_erasure_amd_sender.h"
+#include "../../include/ldpc_erasure_amd_receiver.h"
 
 using namespace ldpc_amd;
 
@@ -46,6 +47,7 @@ constexpr int kScanPrefetch = 16;   // groups of 64 dense headers a scan lane ho
 enum : int { R_CUR, R_NEXT, R_CCNT, R_NCNT, R_CLOSES, R_ERR, R_CONSUMED_LO, R_CONSUMED_HI, R_DROPPED_LO, R_DROPPED_HI, R_WORDS = 16 };
 
 constexpr size_t kSenderScratchMax = (size_t)256 << 20;   // composed sender: codewords of one chunk of frames
+constexpr size_t kReceiverScratchMax = (size_t)256 << 20; // composed receiver: received symbols of one chunk of closed blocks
 
 inline unsigned grid_for(int64_t items)
 {
@@ -221,12 +223,13 @@ struct MoveArgs {
     const int32_t *win;   // [(closes + 2)][n]
     uint8_t *stage_sym;   // [2][n][S]
     uint8_t *stage_er;    // [2][n]
-    uint8_t *sym_out;     // gather: [closes][n][S]
-    uint8_t *er_out;      // gather: [closes][n]
+    uint8_t *sym_out;     // gather: [count][n][S], the closed slots first .. first + count - 1
+    uint8_t *er_out;      // gather: [count][n]
     int n, S, cb, closes;
+    int first, count;     // gather: the slots of this launch (the composed receiver gathers chunk by chunk)
 };
 
-// Row r of the gather (slot j = r / n, symbol i): the last packet that went there, else -- for a block carried in from an earlier
+// Row r of the gather (slot j = first + r / n, symbol i): the last packet that went there, else -- for a block carried in from an earlier
 // call -- its staging row, else zero and erased (the decoder kernels' assumption 2).
 // Row r of the staging update (serial s = closes + r / n): the last packet, else for a block opened in this call zero and erased;
 // a carried block keeps its staging row.
@@ -234,12 +237,12 @@ template <bool GATHER, bool V16>
 __global__ __launch_bounds__(kThreads) void fec_rx_move(MoveArgs a)
 {
     const int q = V16 ? a.S / 16 : a.S;   // 16-byte pieces or bytes of a row
-    const int64_t rows = GATHER ? (int64_t)a.closes * a.n : 2 * (int64_t)a.n;
+    const int64_t rows = GATHER ? (int64_t)a.count * a.n : 2 * (int64_t)a.n;
     const int64_t total = rows * q;
     for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
         const int64_t r = t / q;
         const int c = (int)(t - r * q);
-        const int s = (int)(r / a.n) + (GATHER ? 0 : a.closes);   // serial of the block
+        const int s = (int)(r / a.n) + (GATHER ? a.first : a.closes);   // serial of the block
         const int i = (int)(r - (int64_t)(r / a.n) * a.n);
         const int w = a.win[(int64_t)s * a.n + i];
         const int b = (a.cb + s) & 1;
@@ -268,6 +271,27 @@ __global__ __launch_bounds__(kThreads) void fec_rx_move(MoveArgs a)
             if (GATHER) a.er_out[r] = e;
             else a.stage_er[(int64_t)b * a.n + i] = e;
         }
+    }
+}
+
+// ---- (d') the fused receiver: instead of the gather, WHERE every row of the closed slots lies --------------------------------------
+// The rule of the gather's row r, as a word the packets-in decoder follows (internal.h, PacketRows), and the erasure flag the
+// gather would have written.  A carried block's symbol that no packet of this call brought keeps what its staging plane holds: the
+// row if it was received by an earlier call, else erased.  (An erased row's bytes are never read: the decoder zero-fills or solves it.)
+__global__ __launch_bounds__(kThreads) void fec_rx_sources(const int32_t *__restrict__ win, const uint8_t *__restrict__ stage_er, int n,
+                                                          int cb, int closes, uint32_t *__restrict__ src, uint8_t *__restrict__ er)
+{
+    const int64_t total = (int64_t)closes * n;
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < total; r += (int64_t)gridDim.x * kThreads) {
+        const int s = (int)(r / n);
+        const int i = (int)(r - (int64_t)s * n);
+        const int w = win[r];
+        const int row = ((cb + s) & 1) * n + i;   // the block's staging row
+        uint32_t word = kRowErased;
+        if (w >= 0) word = (uint32_t)w;
+        else if (s < 2 && stage_er[row] == 0) word = kRowStaged | (uint32_t)row;
+        src[r] = word;
+        er[r] = word == kRowErased ? 1 : 0;
     }
 }
 
@@ -411,23 +435,20 @@ void ldpc_amd_fec_rx_dev_destroy(ldpc_amd_fec_rx_dev *rx)
 
 int64_t ldpc_amd_fec_rx_dev_dropped(const ldpc_amd_fec_rx_dev *rx) { return rx ? rx->dropped : -1; }
 
-int ldpc_amd_fec_rx_dev_push_many(ldpc_amd_fec_rx_dev *rx, const uint8_t *packets, int64_t npackets, uint8_t *sym_batch,
-                                  uint8_t *erased_batch, int *blocks, int max_blocks, int64_t *consumed)
+}  // extern "C"
+
+// One call's PLAN: (a) + (b) and the read-back.  Nothing of the receiver's state changes before rx_commit.
+struct RxPlan {
+    int closes = 0;
+    int64_t used = 0, dropped = 0;
+    const int32_t *h = nullptr;   // the scan's result record (pinned), the closed blocks' numbers behind R_WORDS
+};
+
+static int rx_plan(ldpc_amd_fec_rx_dev *rx, const char *who, const uint8_t *packets, int64_t npackets, int max_blocks, RxPlan &pl)
 {
-    if (!rx) return LDPC_AMD_EINVAL;
     ldpc_amd_ctx *ctx = rx->ctx;
-    if (npackets < 0 || npackets >= ((int64_t)1 << 31) || max_blocks < 1)
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_push_many: need 0 <= npackets < 2^31 and max_blocks >= 1");
-    if (!sym_batch || !erased_batch || (npackets > 0 && !packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_push_many: packets / sym_batch / erased_batch must not be null");
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((npackets > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_push_many: packets / sym_batch / erased_batch must be device pointers of device %d",
-                         ctx->device);
-    if (consumed) *consumed = 0;
-    if (npackets == 0) return 0;
-    const int n = rx->n, S = rx->S;
-    const int64_t plen = (int64_t)S + kHdr;
+    const int n = rx->n;
+    const int64_t plen = (int64_t)rx->S + kHdr;
     const size_t res_bytes = sizeof(int32_t) * ((size_t)R_WORDS + (size_t)max_blocks);
     int rc;
     if ((rc = scratch_reserve(ctx, rx->dense, sizeof(uint32_t) * (size_t)npackets)) ||
@@ -443,7 +464,7 @@ int ldpc_amd_fec_rx_dev_push_many(ldpc_amd_fec_rx_dev *rx, const uint8_t *packet
         rx->res_host_cap = res_bytes;
     }
     uint32_t *dense = (uint32_t *)rx->dense.p;
-    int32_t *dest = (int32_t *)rx->dest.p, *win = (int32_t *)rx->win.p, *res = (int32_t *)rx->res.p;
+    int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
 
     // (a) + (b): the plan
     if (plen % 4 == 0 && ((uintptr_t)packets & 3) == 0)
@@ -459,35 +480,81 @@ int ldpc_amd_fec_rx_dev_push_many(ldpc_amd_fec_rx_dev *rx, const uint8_t *packet
     if ((rc = check_device_error(ctx))) return rc;
     const int32_t *h = rx->res_host;
     if (h[R_ERR])
-        return set_error(ctx, LDPC_AMD_EHIP, "fec_rx_dev_push_many: the plan scan hit its iteration cap (internal error); the receiver's state is unchanged");
-    const int closes = h[R_CLOSES];
-    const int64_t used = (int64_t)(((uint64_t)(uint32_t)h[R_CONSUMED_HI] << 32) | (uint32_t)h[R_CONSUMED_LO]);
-    const int64_t dd = (int64_t)(((uint64_t)(uint32_t)h[R_DROPPED_HI] << 32) | (uint32_t)h[R_DROPPED_LO]);
+        return set_error(ctx, LDPC_AMD_EHIP, "%s: the plan scan hit its iteration cap (internal error); the receiver's state is unchanged", who);
+    pl.h = h;
+    pl.closes = h[R_CLOSES];
+    pl.used = (int64_t)(((uint64_t)(uint32_t)h[R_CONSUMED_HI] << 32) | (uint32_t)h[R_CONSUMED_LO]);
+    pl.dropped = (int64_t)(((uint64_t)(uint32_t)h[R_DROPPED_HI] << 32) | (uint32_t)h[R_DROPPED_LO]);
+    return LDPC_AMD_OK;
+}
 
-    // (c), (d), (e): the data movement, asynchronous
-    LDPC_HIP_TRY(ctx, hipMemsetAsync(win, 0xff, sizeof(int32_t) * ((size_t)closes + 2) * (size_t)n, ctx->stream));   // -1: no packet
-    hipLaunchKernelGGL(fec_rx_winners, dim3(grid_for(used)), dim3(kThreads), 0, ctx->stream, dense, dest, used, n, win);
+// (c): the winners' table of the call, [(closes + 2)][n]
+static int rx_winners(ldpc_amd_fec_rx_dev *rx, const RxPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    int32_t *win = (int32_t *)rx->win.p;
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(win, 0xff, sizeof(int32_t) * ((size_t)pl.closes + 2) * (size_t)rx->n, ctx->stream));   // -1: no packet
+    hipLaunchKernelGGL(fec_rx_winners, dim3(grid_for(pl.used)), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p,
+                       (const int32_t *)rx->dest.p, pl.used, rx->n, win);
     LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// (d) for the closed slots first .. first + count - 1 (gather) or (e) for the two open blocks
+template <bool GATHER>
+static int rx_move(ldpc_amd_fec_rx_dev *rx, const RxPlan &pl, const uint8_t *packets, int first, int count, uint8_t *sym, uint8_t *er)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, S = rx->S;
     MoveArgs a{};
-    a.packets = packets; a.plen = plen; a.win = win; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
-    a.sym_out = sym_batch; a.er_out = erased_batch; a.n = n; a.S = S; a.cb = rx->cb; a.closes = closes;
-    const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0 && ((uintptr_t)sym_batch & 15) == 0;
+    a.packets = packets; a.plen = (int64_t)S + kHdr; a.win = (const int32_t *)rx->win.p; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
+    a.sym_out = sym; a.er_out = er; a.n = n; a.S = S; a.cb = rx->cb; a.closes = pl.closes; a.first = first; a.count = count;
+    const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0 && ((uintptr_t)sym & 15) == 0;
     const int64_t q = v16 ? S / 16 : S;
-    if (closes > 0) {
-        if (v16) hipLaunchKernelGGL((fec_rx_move<true, true>), dim3(grid_for((int64_t)closes * n * q)), dim3(kThreads), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((fec_rx_move<true, false>), dim3(grid_for((int64_t)closes * n * q)), dim3(kThreads), 0, ctx->stream, a);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-    }
-    if (v16) hipLaunchKernelGGL((fec_rx_move<false, true>), dim3(grid_for(2 * (int64_t)n * q)), dim3(kThreads), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((fec_rx_move<false, false>), dim3(grid_for(2 * (int64_t)n * q)), dim3(kThreads), 0, ctx->stream, a);
+    const int64_t items = (GATHER ? (int64_t)count : 2) * n * q;
+    if (GATHER && count <= 0) return LDPC_AMD_OK;
+    if (v16) hipLaunchKernelGGL((fec_rx_move<GATHER, true>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((fec_rx_move<GATHER, false>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
     LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
 
+static void rx_commit(ldpc_amd_fec_rx_dev *rx, const RxPlan &pl, int *blocks, int64_t *consumed)
+{
+    const int32_t *h = pl.h;
     rx->cur = h[R_CUR]; rx->next = h[R_NEXT]; rx->ccnt = h[R_CCNT]; rx->ncnt = h[R_NCNT];
-    rx->cb ^= closes & 1;   // :241, once per close
-    rx->dropped += dd;
-    if (blocks) memcpy(blocks, h + R_WORDS, sizeof(int) * (size_t)closes);
-    if (consumed) *consumed = used;
-    return closes;
+    rx->cb ^= pl.closes & 1;   // :241, once per close
+    rx->dropped += pl.dropped;
+    if (blocks) memcpy(blocks, h + R_WORDS, sizeof(int) * (size_t)pl.closes);
+    if (consumed) *consumed = pl.used;
+}
+
+extern "C" {
+
+int ldpc_amd_fec_rx_dev_push_many(ldpc_amd_fec_rx_dev *rx, const uint8_t *packets, int64_t npackets, uint8_t *sym_batch,
+                                  uint8_t *erased_batch, int *blocks, int max_blocks, int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (npackets < 0 || npackets >= ((int64_t)1 << 31) || max_blocks < 1)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_push_many: need 0 <= npackets < 2^31 and max_blocks >= 1");
+    if (!sym_batch || !erased_batch || (npackets > 0 && !packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_push_many: packets / sym_batch / erased_batch must not be null");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((npackets > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_push_many: packets / sym_batch / erased_batch must be device pointers of device %d",
+                         ctx->device);
+    if (consumed) *consumed = 0;
+    if (npackets == 0) return 0;
+    int rc;
+    RxPlan pl;
+    if ((rc = rx_plan(rx, "fec_rx_dev_push_many", packets, npackets, max_blocks, pl))) return rc;
+    // (c), (d), (e): the data movement, asynchronous
+    if ((rc = rx_winners(rx, pl)) || (rc = rx_move<true>(rx, pl, packets, 0, pl.closes, sym_batch, erased_batch)) ||
+        (rc = rx_move<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)))
+        return rc;
+    rx_commit(rx, pl, blocks, consumed);
+    return pl.closes;
 }
 
 int ldpc_amd_fec_rx_dev_flush(ldpc_amd_fec_rx_dev *rx, uint8_t *sym_out, uint8_t *erased_out, int *block_out)
@@ -512,6 +579,134 @@ int ldpc_amd_fec_rx_dev_flush(ldpc_amd_fec_rx_dev *rx, uint8_t *sym_out, uint8_t
     rx->ncnt = 0;
     rx->cb ^= 1;
     return 1;
+}
+
+// ---- the receiver (include/ldpc_erasure_amd_receiver.h) -------------------------------------------------------------------
+// push_many + decode_frames in one call.  FUSED where the decoder can fetch its rows from the packets itself (decode_reads_packets:
+// the scatter kernels' packets-in form): (d) shrinks to fec_rx_sources -- n flags and n words per closed block instead of n rows -- and the
+// decode follows the words; the reference's receiver is one kernel that reassembles and decodes (...with_reordering_logic.cl:44-141,
+// 214-243).  Else COMPOSED: (d) gathers a chunk of closed blocks into the context's scratch, the decoder runs on it, next chunk; the
+// chunks follow one another on the context's stream, so the scratch is free again when the next gather starts.
+// (e) is launched BEHIND the decode in both paths: it overwrites the staging planes of the carried blocks, which the fused decode reads.
+static int rx_decode_check(ldpc_amd_ctx *ctx, const ldpc_amd_fec_rx_dev *rx, const char *who, int code, int max_sweeps, uint8_t *out,
+                           int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src)
+{
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    const DevCode &cd = ctx->codes[code]->dev;
+    if (cd.n != rx->n || cd.k != rx->k)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: the code is (%d,%d), the receiver was created for (%d,%d)", who, cd.n, cd.k, rx->n, rx->k);
+    // the decoder's own refusals (launch_decode), before anything is planned
+    if (rx->S != 1 && (rx->S % 16) != 0) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 16 (got %d)", rx->S);
+    if (max_sweeps < 1) return set_error(ctx, LDPC_AMD_EINVAL, "max_sweeps must be >= 1");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const void *opt[] = {sweeps, residual, status, erased_out, residual_src};
+    bool ok = out && is_device_ptr(ctx, out);
+    for (const void *p : opt) ok = ok && (!p || is_device_ptr(ctx, p));
+    if (!ok) return set_error(ctx, LDPC_AMD_EINVAL, "%s: out and the result arrays must be device pointers of device %d", who, ctx->device);
+    return LDPC_AMD_OK;
+}
+
+int ldpc_amd_fec_rx_dev_decode_many(ldpc_amd_fec_rx_dev *rx, int code, const uint8_t *packets, int64_t npackets, int max_sweeps, int do_ml,
+                                    uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
+                                    int32_t *residual_src, int *blocks, int max_blocks, int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    if (npackets < 0 || npackets >= ((int64_t)1 << 31) || max_blocks < 1)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_decode_many: need 0 <= npackets < 2^31 and max_blocks >= 1");
+    if (npackets == 0) {
+        if (consumed) *consumed = 0;
+        return 0;
+    }
+    int rc;
+    if ((rc = rx_decode_check(ctx, rx, "fec_rx_dev_decode_many", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src)))
+        return rc;
+    if (!packets || !is_device_ptr(ctx, packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_decode_many: packets must be a device pointer of device %d", ctx->device);
+    const DevCode &cd = ctx->codes[code]->dev;
+    const int n = rx->n, S = rx->S;
+    const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
+    const size_t frame = (size_t)n * S;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(max_blocks, (int64_t)(kReceiverScratchMax / frame)));
+
+    RxPlan pl;
+    if ((rc = rx_plan(rx, "fec_rx_dev_decode_many", packets, npackets, max_blocks, pl))) return rc;
+    const int closes = pl.closes;
+    // every workspace of the call before anything moves: a refusal leaves the receiver where it was
+    if (closes > 0) {
+        if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)closes * n))) return rc;
+        if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)closes * n);
+        else rc = scratch_reserve(ctx, ctx->rx_sym, (size_t)std::min<int64_t>(chunk, closes) * frame);
+        if (rc) return rc;
+    }
+    if ((rc = rx_winners(rx, pl))) return rc;
+    DecodeArgs d{};
+    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
+    uint8_t *er = (uint8_t *)ctx->rx_er.p;
+    auto slots = [&](int first, int count) {   // the result arrays of closed slots first .. first + count - 1
+        d.nframes = count;
+        d.erased = er + (size_t)first * n;
+        d.out = out + (size_t)first * frame;
+        d.sweeps = sweeps ? sweeps + first : nullptr; d.residual = residual ? residual + first : nullptr;
+        d.status = status ? status + first : nullptr;
+        d.erased_out = erased_out ? erased_out + (size_t)first * n : nullptr;
+        d.residual_src = residual_src ? residual_src + first : nullptr;
+    };
+    if (closes > 0 && fused) {
+        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+        hipLaunchKernelGGL(fec_rx_sources, dim3(grid_for((int64_t)closes * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
+                           rx->stage_er, n, rx->cb, closes, src, er);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        slots(0, closes);
+        d.sym = nullptr;
+        d.pin.src = src; d.pin.packets = packets; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
+        if ((rc = launch_decode(ctx, d))) return rc;
+    } else if (closes > 0) {
+        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
+        for (int first = 0; first < closes; first += (int)chunk) {
+            const int count = (int)std::min<int64_t>(chunk, closes - first);
+            if ((rc = rx_move<true>(rx, pl, packets, first, count, sym, er + (size_t)first * n))) return rc;
+            slots(first, count);
+            d.sym = sym;
+            if ((rc = launch_decode(ctx, d))) return rc;
+        }
+    }
+    if ((rc = rx_move<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
+    rx_commit(rx, pl, blocks, consumed);
+    ctx->receiver_path = fused ? 1 : 2;
+    ctx->receiver_blocks = closes;
+    return closes;
+}
+
+int ldpc_amd_fec_rx_dev_decode_flush(ldpc_amd_fec_rx_dev *rx, int code, int max_sweeps, int do_ml, uint8_t *out, int32_t *sweeps,
+                                     int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src, int *block_out)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    int rc;
+    if ((rc = rx_decode_check(ctx, rx, "fec_rx_dev_decode_flush", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src)))
+        return rc;
+    const size_t frame = (size_t)rx->n * rx->S;
+    if ((rc = scratch_reserve(ctx, ctx->rx_sym, frame)) || (rc = scratch_reserve(ctx, ctx->rx_er, (size_t)rx->n))) return rc;
+    if ((rc = ldpc_amd_fec_rx_dev_flush(rx, (uint8_t *)ctx->rx_sym.p, (uint8_t *)ctx->rx_er.p, block_out)) != 1) return rc;
+    DecodeArgs d{};
+    d.code = ctx->codes[code]->dev; d.S = rx->S; d.in_rows = rx->n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0; d.nframes = 1;
+    d.sym = (const uint8_t *)ctx->rx_sym.p; d.erased = (const uint8_t *)ctx->rx_er.p; d.out = out;
+    d.sweeps = sweeps; d.residual = residual; d.status = status; d.erased_out = erased_out; d.residual_src = residual_src;
+    if ((rc = launch_decode(ctx, d))) return rc;
+    return 1;
+}
+
+int ldpc_amd_fec_receiver_info(ldpc_amd_ctx *ctx, int info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_receiver_info: info must not be null");
+    info[0] = ctx->receiver_path;
+    info[1] = (int)std::min<size_t>(ctx->rx_sym.cap, (size_t)INT32_MAX);
+    info[2] = ctx->receiver_blocks;
+    info[3] = 0;
+    return LDPC_AMD_OK;
 }
 
 }  // extern "C"
