@@ -16,7 +16,8 @@
  *   sym    [nframes][n][S]  uint8   symbol j of frame f is a packet of S bytes; every byte is one GF(256)
  *                                   element.  S = 1 is the Matlab model (one element per symbol,
  *                                   Matlab/My_LDPC_HybridML_NonBinary_Erasure_Decoder.m:4), S = 1024 the FPGA
- *                                   packet of OpenCL/host/src/main.cpp:42-47 (128 x u64).  S is 1 or a multiple of 16.
+ *                                   packet of OpenCL/host/src/main.cpp:42-47 (128 x u64).  S is 1 or a multiple of 16
+ *                                   (or, with symbol unit 4, see ldpc_erasure_amd_words.h).
  *   erased [nframes][n]     uint8   non-zero = erased (Matlab: value -1, ...Decoder.m:9; FPGA: is_erasure,
  *                                   main.cpp:46).  The payload of an erased symbol is ignored.
  *   out    [nframes][n][S]  uint8   the full length-n word, as Matlab returns it (...Decoder.m:129);

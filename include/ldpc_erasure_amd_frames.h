@@ -59,7 +59,8 @@ int ldpc_amd_rs_info(ldpc_amd_ctx *ctx, int rs, int *n, int *k);
  * recv_idx = P[0:k], recv_val = sym[P[0:k]] (nothing received beyond the k-th symbol is read, ReedSolomonErasureCodes.m:81;
  * nor is the payload of an erased symbol), status 0.  Otherwise msg is all zero, status 1.  received[b] = |P|.
  *   sym [nblocks][n][S], erased [nblocks][n], msg [nblocks][k][S]; received, status [nblocks], each may be NULL.
- * S: 1 or a multiple of 16, like ldpc_amd_rs_decode_batch.  The selection cannot produce malformed positions: after this call
+ * S: 1 or a multiple of 16 (or, with symbol unit 4, see ldpc_erasure_amd_words.h), like ldpc_amd_rs_decode_batch.
+ * The selection cannot produce malformed positions: after this call
  * ldpc_amd_rs_bad_blocks reports 0. */
 int ldpc_amd_rs_decode_frames(ldpc_amd_ctx *ctx, int rs, int S, int64_t nblocks, const uint8_t *sym, const uint8_t *erased,
                               uint8_t *msg, int32_t *received, int32_t *status, unsigned flags);

@@ -41,7 +41,8 @@ extern "C" {
  * The caller must keep `packets` alive and unchanged until the context's stream has passed the call: the decoder reads the
  * payloads from it (as ldpc_amd_fec_rx_dev_push_many's gather does).
  * code: a handle of the receiver's context whose (n, k) are the receiver's (else LDPC_AMD_EINVAL; unknown handle:
- * LDPC_AMD_ENOCODE).  The decoder's own refusals pass through: S neither 1 nor a multiple of 16 (LDPC_AMD_EUNSUP),
+ * LDPC_AMD_ENOCODE).  The decoder's own refusals pass through: S neither 1 nor a multiple of 16 (LDPC_AMD_EUNSUP; or,
+ * with symbol unit 4, see ldpc_erasure_amd_words.h),
  * max_sweeps < 1 (LDPC_AMD_EINVAL).  max_blocks < 1: LDPC_AMD_EINVAL.  npackets == 0: returns 0, nothing is touched. */
 int ldpc_amd_fec_rx_dev_decode_many(ldpc_amd_fec_rx_dev *rx, int code, const uint8_t *packets, int64_t npackets,
                                     int max_sweeps, int do_ml,

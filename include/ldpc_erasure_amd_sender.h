@@ -31,7 +31,8 @@ extern "C" {
 /* source [nframes][k][S] -> packets [nframes*n][8+S] in transmission order: byte for byte
  * ldpc_amd_fec_packetize_dev(ldpc_amd_encode_batch(source)).  Device pointers of the context's device only
  * (host pointers: LDPC_AMD_EINVAL, as in the wire_dev header).  Asynchronous on the context's stream.
- * S: 1 or a multiple of 16 (else LDPC_AMD_EUNSUP, the encoder's rule); code not in triangle form: LDPC_AMD_EUNSUP;
+ * S: 1 or a multiple of 16 or, with symbol unit 4, see ldpc_erasure_amd_words.h -- there every word-sized S takes the fused
+ * path, the source pointer 4-byte aligned -- (else LDPC_AMD_EUNSUP, the encoder's rule); code not in triangle form: LDPC_AMD_EUNSUP;
  * unknown handle: LDPC_AMD_ENOCODE; nframes == 0: OK, nothing touched; source and packets must not overlap (EINVAL).
  * Block number of frame f = (block0 + f) & 0xff, symbol number = row, header = ldpc_amd_fec_header_pack. */
 int ldpc_amd_fec_encode_packets_dev(ldpc_amd_ctx *ctx, int code, int S, int64_t nframes, const uint8_t *source,

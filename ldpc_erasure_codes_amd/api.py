@@ -61,6 +61,8 @@ SENDER_PATHS = ("none", "fused", "composed")
 # every symbol include/ldpc_erasure_amd_receiver.h declares (the fused receiver: wire packets straight to decoded frames)
 EXPORTS_RECEIVER = ["ldpc_amd_fec_rx_dev_decode_many", "ldpc_amd_fec_rx_dev_decode_flush", "ldpc_amd_fec_receiver_info"]
 RECEIVER_PATHS = ("none", "fused", "composed")
+# every symbol include/ldpc_erasure_amd_words.h declares (word-sized symbols: any S that is a multiple of 4)
+EXPORTS_WORDS = ["ldpc_amd_set_symbol_unit", "ldpc_amd_get_symbol_unit"]
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
@@ -182,6 +184,10 @@ def load_library():
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.ldpc_amd_rs_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, vp, vp, vp, C.c_uint]
+    # word-sized symbols (include/ldpc_erasure_amd_words.h)
+    if hasattr(L, "ldpc_amd_set_symbol_unit"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_set_symbol_unit.argtypes = [vp, i32]
+        L.ldpc_amd_get_symbol_unit.argtypes = [vp]
     L.ldpc_amd_data_out.argtypes = [vp, vp, i32, C.c_long, C.POINTER(ErrorType)]
     L.ldpc_amd_set_profiling.argtypes = [vp, i32]
     L.ldpc_amd_get_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64)]
@@ -284,6 +290,15 @@ class Context:
         """{key: value or None} -> configure() for each."""
         for k, v in knobs.items():
             self.configure(k, v)
+
+    def set_symbol_unit(self, unit):
+        """16 (default): S is 1 or a multiple of 16.  4: S is 1 or any multiple of 4 that is at least 16, on every entry point of
+        this context that takes a symbol length (include/ldpc_erasure_amd_words.h).  Not a knob: it changes which inputs are
+        accepted, never the bytes of an input both units accept.  Any other unit: LdpcAmdError, the context keeps its unit."""
+        self._check(self._L.ldpc_amd_set_symbol_unit(self._h, int(unit)), "set_symbol_unit")
+
+    def symbol_unit(self):
+        return self._check(self._L.ldpc_amd_get_symbol_unit(self._h), "get_symbol_unit")
 
     def set_profiling(self, enable):
         """False / 0: off; True / 1: one bracket per kind of a call; 2: + the nested tier-2 and solve-kernel brackets."""

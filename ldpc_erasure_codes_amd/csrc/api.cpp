@@ -13,6 +13,7 @@
 
 #include "internal.h"
 #include "../../include/ldpc_erasure_amd_synth.h"
+#include "../../include/ldpc_erasure_amd_words.h"
 
 namespace ldpc_amd {
 
@@ -171,6 +172,12 @@ int set_error(ldpc_amd_ctx *ctx, int code, const char *fmt, ...)
     if (ctx) ctx->err = buf;
     else g_init_error = buf;
     return code;
+}
+
+int refuse_symbol_len(ldpc_amd_ctx *ctx, int S, const char *text16)
+{
+    if (ctx->symbol_unit == 4) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 4 that is at least 16 (got %d)", S);
+    return set_error(ctx, LDPC_AMD_EUNSUP, text16, S);
 }
 
 int check_device_error(ldpc_amd_ctx *ctx)
@@ -902,6 +909,18 @@ int ldpc_amd_knobs(ldpc_amd_ctx *ctx, char *buf, int cap)
     return (int)out.size();
 }
 
+// Word-sized symbols (include/ldpc_erasure_amd_words.h).  Not a knob: it changes which inputs are accepted, so it is kept out of
+// kKnobs, of ldpc_amd_knobs and of the environment.
+int ldpc_amd_set_symbol_unit(ldpc_amd_ctx *ctx, int unit)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (unit != 16 && unit != 4) return set_error(ctx, LDPC_AMD_EINVAL, "ldpc_amd_set_symbol_unit: the unit is 16 or 4 (got %d)", unit);
+    ctx->symbol_unit = unit;
+    return LDPC_AMD_OK;
+}
+
+int ldpc_amd_get_symbol_unit(ldpc_amd_ctx *ctx) { return ctx ? ctx->symbol_unit : LDPC_AMD_EINVAL; }
+
 int ldpc_amd_synchronize(ldpc_amd_ctx *ctx)
 {
     if (!ctx) return LDPC_AMD_EINVAL;
@@ -1196,7 +1215,7 @@ int ldpc_amd_rs_encode_batch(ldpc_amd_ctx *ctx, int rs, int S, int64_t nblocks, 
 {
     HostRs *r = get_rs(ctx, rs);
     if (!r) return ctx ? set_error(ctx, LDPC_AMD_ENOCODE, "unknown RS handle %d", rs) : LDPC_AMD_EINVAL;
-    if (nblocks < 0 || (S != 1 && S % 16)) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 16");
+    if (nblocks < 0 || !symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16");
     if (nblocks == 0) return LDPC_AMD_OK;
     if (!source || !codeword) return set_error(ctx, LDPC_AMD_EINVAL, "null data pointer");
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1223,7 +1242,7 @@ int ldpc_amd_rs_decode_batch(ldpc_amd_ctx *ctx, int rs, int S, int64_t nblocks, 
 {
     HostRs *r = get_rs(ctx, rs);
     if (!r) return ctx ? set_error(ctx, LDPC_AMD_ENOCODE, "unknown RS handle %d", rs) : LDPC_AMD_EINVAL;
-    if (nblocks < 0 || (S != 1 && S % 16)) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 16");
+    if (nblocks < 0 || !symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16");
     if (nblocks == 0) return LDPC_AMD_OK;
     if (!recv_idx || !recv_val || !msg) return set_error(ctx, LDPC_AMD_EINVAL, "null data pointer");
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1273,7 +1292,7 @@ int ldpc_amd_rs_decode_frames(ldpc_amd_ctx *ctx, int rs, int S, int64_t nblocks,
     HostRs *r = get_rs(ctx, rs);
     if (!r) return ctx ? set_error(ctx, LDPC_AMD_ENOCODE, "unknown RS handle %d", rs) : LDPC_AMD_EINVAL;
     if (nblocks < 0) return set_error(ctx, LDPC_AMD_EINVAL, "rs_decode_frames: negative block count");
-    if (S != 1 && S % 16) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 16");
+    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16");
     if (nblocks == 0) return LDPC_AMD_OK;
     if (!sym || !erased || !msg) return set_error(ctx, LDPC_AMD_EINVAL, "sym/erased/msg must not be null");
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));

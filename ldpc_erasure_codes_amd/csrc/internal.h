@@ -228,6 +228,7 @@ struct ldpc_amd_ctx {
     std::string prof_names[LDPC_AMD_PROF_KINDS];   // template instantiation the last launch of each kind used
     int last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launch plan of the last decode (ldpc_amd_last_plan)
     int last_enc_grouped = 0;                      // the last packet-mode encode ran the grouped static schedule (ldpc_amd_encode_info)
+    int symbol_unit = 16;                          // 16, or 4: word-sized symbols (include/ldpc_erasure_amd_words.h; not a knob)
 };
 
 namespace ldpc_amd {
@@ -301,6 +302,14 @@ int scratch_reserve(ldpc_amd_ctx *ctx, Scratch &s, size_t bytes);
 hipEvent_t prof_begin(ldpc_amd_ctx *ctx, int level = 1);
 void prof_end(ldpc_amd_ctx *ctx, int kind, hipEvent_t start);
 int set_error(ldpc_amd_ctx *ctx, int code, const char *fmt, ...);
+// Symbol lengths (include/ldpc_erasure_amd_words.h).  A context accepts S = 1 and the multiples of its unit: of 16, or -- unit 4 --
+// of 4 from 16 bytes up.  The lengths only unit 4 accepts run the WORD FORM of the payload kernels: the same B-byte row pieces,
+// ceil(S / B) of them, piece sl starting at min(sl * B, S - B) -- the last one overlaps its neighbour and ends with the row -- and
+// every global access a 4-byte one (rows start on 4-byte boundaries only).  A multiple of 16 runs what it runs with unit 16.
+inline bool symbol_len_ok(const ldpc_amd_ctx *ctx, int S) { return S == 1 || (ctx->symbol_unit == 4 ? (S >= 16 && (S % 4) == 0) : (S % 16) == 0); }
+inline bool symbol_len_words(int S) { return S != 1 && (S % 16) != 0; }
+// the refusal: LDPC_AMD_EUNSUP with the words header's text under unit 4, else with text16 (the entry point's own, S its one argument)
+int refuse_symbol_len(ldpc_amd_ctx *ctx, int S, const char *text16);
 // After a synchronisation: LDPC_AMD_EHIP (and the word cleared) if a kernel of this context reported a violated assumption.
 int check_device_error(ldpc_amd_ctx *ctx);
 

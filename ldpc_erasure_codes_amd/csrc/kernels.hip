@@ -517,7 +517,33 @@ struct ApplyArgs {
     const uint16_t *sched_lvlend;
 };
 
-__global__ __launch_bounds__(512) void ldpc_apply_kernel(ApplyArgs a)
+// 16 bytes at a 4-byte aligned address (word-sized symbols: the rows of an [n][S] array with S no multiple of 16), or -- W4 false --
+// the 16-byte access the multiples of 16 have always used
+template <bool W4>
+__device__ __forceinline__ U4 row_load16(const uint8_t *p)
+{
+    if (W4) {
+        const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
+        return U4{q[0], q[1], q[2], q[3]};
+    }
+    return *reinterpret_cast<const U4 *>(p);
+}
+template <bool W4>
+__device__ __forceinline__ void row_store16(uint8_t *p, const U4 &v)
+{
+    if (W4) {
+        uint32_t *q = reinterpret_cast<uint32_t *>(p);
+        q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w;
+    } else {
+        *reinterpret_cast<U4 *>(p) = v;
+    }
+}
+
+// W4: the word form (S a multiple of 4, not of 16; ldpc_apply_words_kernel).  The copy phase moves dwords; in the step phase the lane
+// whose 16 bytes would cross the end of the row is moved back to end with it (it then shares bytes with the lane before it: both
+// compute the same values from rows of EARLIER levels -- a step never reads a row of its own level -- and store them twice).
+template <bool W4>
+__device__ __forceinline__ void apply_body(const ApplyArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const DevCode &cd = a.code;
@@ -547,7 +573,14 @@ __global__ __launch_bounds__(512) void ldpc_apply_kernel(ApplyArgs a)
     const uint8_t *fin = a.sym + f * (int64_t)a.in_rows * S;
     uint8_t *fout = a.out + f * (int64_t)n * S;
     const uint8_t *er = a.erased ? a.erased + f * n : nullptr;
-    {
+    if (W4) {
+        const int64_t units = (int64_t)n * S / 4;
+        for (int64_t u = threadIdx.x; u < units; u += blockDim.x) {
+            const int row = (int)((u * 4) / S);
+            const bool e = er ? (er[row] != 0) : (row >= a.in_rows);
+            reinterpret_cast<uint32_t *>(fout)[u] = e ? 0u : reinterpret_cast<const uint32_t *>(fin)[u];
+        }
+    } else {
         const int64_t units = (int64_t)n * S / 16;
         const U4 zero = {0, 0, 0, 0};
         for (int64_t u = threadIdx.x; u < units; u += blockDim.x) {
@@ -569,8 +602,9 @@ __global__ __launch_bounds__(512) void ldpc_apply_kernel(ApplyArgs a)
             const uint32_t row = step & 0xFFFFu, tgt = step >> 16;
             const uint32_t e0 = cd.row_ptr[row], e1 = cd.row_ptr[row + 1];
             for (int p = 0; p < pieces; p++) {
-                const int off = p * 1024 + lane * 16;
-                const bool active = off < S;
+                const int off0 = p * 1024 + lane * 16;
+                const bool active = off0 < S;
+                const int off = W4 ? min(off0, S - 16) : off0;
                 U4 acc = {0, 0, 0, 0};
                 uint32_t ctgt = 1;
                 for (uint32_t e = e0; e < e1; e++) {
@@ -578,19 +612,22 @@ __global__ __launch_bounds__(512) void ldpc_apply_kernel(ApplyArgs a)
                     const uint32_t col = ed & 0xFFFFu, c = (ed >> 16) & 0xFFu;
                     if (col == tgt) { ctgt = c; continue; }
                     if (active) {
-                        const U4 v = *reinterpret_cast<const U4 *>(fout + (int64_t)col * S + off);
+                        const U4 v = row_load16<W4>(fout + (int64_t)col * S + off);
                         gfmac16(acc, load_multab(c), v);
                     }
                 }
                 if (active) {
                     const U4 r = gfmul16(load_multab(uniform(c_inv[ctgt])), acc);
-                    *reinterpret_cast<U4 *>(fout + (int64_t)tgt * S + off) = r;
+                    row_store16<W4>(fout + (int64_t)tgt * S + off, r);
                 }
             }
         }
         __syncthreads();
     }
 }
+
+__global__ __launch_bounds__(512) void ldpc_apply_kernel(ApplyArgs a) { apply_body<false>(a); }
+__global__ __launch_bounds__(512) void ldpc_apply_words_kernel(ApplyArgs a) { apply_body<true>(a); }
 
 // =================================================================================================
 // Kernel B' (packets, the HBM-bound kernel): scatter form of the same arithmetic.
@@ -611,6 +648,8 @@ __global__ __launch_bounds__(512) void ldpc_apply_kernel(ApplyArgs a)
 struct ScatterArgs {
     DevCode code;
     int S, nslices;
+    int piece_last;           // S - B, the start of the last piece of a row: piece sl starts at min(sl * B, piece_last).  B divides S unless
+                              // S is no multiple of 16 (word-sized symbols): then the last piece overlaps its neighbour (scatter_frame)
     int64_t nframes;
     const uint8_t *sym;
     const uint8_t *erased;
@@ -707,6 +746,9 @@ __device__ __forceinline__ void lds_xor16_at(uint32_t a1, uint32_t a2, const U4 
 
 // A8: p is only 8-byte aligned (a payload at offset 8 of a packet of stride 8 + S): the plain load is two 8-byte loads, like
 // fec_rx_move's; the non-temporal one is four dword loads either way.
+// A4 -- p is only 4-byte aligned (word-sized symbols: row j of an [n][S] array starts at j * S, a payload at 8 + p * (8 + S)): that
+// IS the non-temporal form, four dword accesses, and the launcher picks it for every S that is no multiple of 16 (launch_scatter_lpr);
+// the header word of a packet goes out as two dwords there as well (put_row).
 template <bool NT, bool A8 = false>
 __device__ __forceinline__ U4 stream_load16(const uint8_t *p)
 {
@@ -772,6 +814,14 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     constexpr int B = 16 * LPR;                // bytes of every row handled by this workgroup (R pieces in flight per lane)
     const DevCode &cd = a.code;
     const int n = cd.n, S = a.S, cdw = cd.maxcoldeg;
+    // Byte offset of this piece in every row.  Where B divides S (every multiple of 16: the plan sees to it) this is sl * B.  Word-sized
+    // symbols (S a multiple of 4, not of 16): the plan makes ceil(S / B) pieces and the last one starts at S - B, overlapping the one
+    // before it by B - S mod B bytes, so every lane still moves a full 16 bytes inside the row.  The bytes in the overlap are computed by
+    // two workgroups, to the same value (the arithmetic is columnwise), and stored twice.  That is safe because no piece reads back,
+    // from global memory, payload bytes another piece of the launch writes: the rows this function READS are the received rows of the
+    // frame, the rows it WRITES are the erased ones (and, out of place, copies of the received ones into another array) -- disjoint sets
+    // of rows, in place as well; solved rows travel on through the LDS accumulators only.  Tier 1 and tier 2 take disjoint frames.
+    const int64_t poff = (int64_t)min(sl * B, a.piece_last);
     const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
     const int lane = lane_id(), wave = wave_id(), nw = nthr >> 6;
     const int g = lane / LPR, gl = lane % LPR, h = (lane >> 3) & 1;
@@ -1015,7 +1065,7 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
             }
         }
         __syncthreads();
-        uint8_t *fz = a.out + f * (int64_t)n * S + (int64_t)sl * B;
+        uint8_t *fz = a.out + f * (int64_t)n * S + poff;
         if (sorted_mode) {
 #pragma unroll
             for (int u = 0; u < EPT; u++)
@@ -1073,9 +1123,9 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     LDPC_STAMP(12);  // scatter: set-up
     // Uniform 64-bit bases + 32-bit per-lane offsets (a frame slice spans n * S < 4 GB): the row addresses then cost one
     // 32-bit multiply-add instead of 64-bit multiplies -- the streaming loop is bound by vector ALU issue, not by waits.
-    const uint8_t *fin0 = a.sym + f * (int64_t)a.in_rows * S + (int64_t)sl * B;
+    const uint8_t *fin0 = a.sym + f * (int64_t)a.in_rows * S + poff;
     constexpr int kPktHdr = PKT ? 8 : 0;   // LDPC_AMD_FEC_HEADER_BYTES in front of every output row
-    uint8_t *fout0 = a.out + f * (int64_t)n * (S + kPktHdr) + kPktHdr + (int64_t)sl * B;
+    uint8_t *fout0 = a.out + f * (int64_t)n * (S + kPktHdr) + kPktHdr + poff;
     const uint32_t lo16 = (uint32_t)gl * 16u, S32 = (uint32_t)S, O32 = (uint32_t)(S + kPktHdr);
     // (24-bit multiply: full rate, where the 32-bit one the compiler picked -- v_mad_u64_u32 -- runs at a quarter; j < 2^16 and
     // S < 2^24 are checked by the host's plan; PKT: 8 + S < 2^24 and n * (8 + S) < 2^32, checked by launch_encode)
@@ -1083,8 +1133,8 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     // 64-bit multiply-add per row and lane -- per-lane base + index * stride, index and stride 32 bits (v_mad_u64_u32: quarter rate,
     // the cost of the four full-rate instructions a 32-bit offset from a per-call base in 8-byte units would take, and without that
     // form's 16 GB limit and its fall-back).  A staging row takes the other base and stride (three v_cndmask_b32).
-    const uint8_t *pin_b0 = PIN ? a.pin_pkt + 8 + (int64_t)sl * B + lo16 : nullptr;
-    const uint8_t *pin_b1 = PIN ? a.pin_stage + (int64_t)sl * B + lo16 : nullptr;
+    const uint8_t *pin_b0 = PIN ? a.pin_pkt + 8 + poff + lo16 : nullptr;
+    const uint8_t *pin_b1 = PIN ? a.pin_stage + poff + lo16 : nullptr;
     const uint32_t P32 = PIN ? (uint32_t)a.pin_plen : 0u;
     auto pin_row = [&](uint32_t e) -> const uint8_t * {
         const bool st = (e >> 31) != 0u;
@@ -1894,7 +1944,7 @@ static const int kLdsMax = 160 * 1024;
 // ---- scatter kernel launch plan ---------------------------------------------------------------------------
 struct ScatterPlan {
     int lpr = 0;        // 16-byte lanes per row piece (B = 16 * lpr bytes of every row per workgroup), 0 = unusable
-    int nslices = 0;    // S / B
+    int nslices = 0;    // S / B (word form: rounded up)
     int tcap = 0;       // tier 1 handles frames with <= tcap steps
     bool two_tier = false;
     int lds1 = 0, lds2 = 0;                       // dynamic LDS bytes of tier 1 / tier 2
@@ -1927,12 +1977,14 @@ static ScatterPlan plan_scatter(const Knobs &kn, const DevCode &cd, int S, bool 
     ScatterPlan p;
     if ((uint64_t)cd.n * (uint64_t)S >= (1ull << 32) || S >= (1 << 24) || cd.n >= (1 << 16)) return p;   // the kernel addresses a frame with 32-bit offsets (24-bit multiplies)
     int B = kn.scatter_b;  // A/B knob: bytes of every row per workgroup
-    while (B > 16 && (S % B) != 0) B >>= 1;
+    // (word form, S no multiple of 16: the largest piece that is no longer than a row -- B need not divide S, the last piece overlaps)
+    if (symbol_len_words(S)) { while (B > 16 && B > S) B >>= 1; }
+    else while (B > 16 && (S % B) != 0) B >>= 1;
     const int tail = scatter_tail_bytes(cd, p, pin, kn.scatter_dyn >= 2) + 8192;   // + the multiply tables in front of the accumulators
     while (B > 16 && cd.m * B + tail > 156 * 1024) B >>= 1;
     if (cd.m * B + tail > kLdsMax) return p;
     p.lpr = B / 16;
-    p.nslices = S / B;
+    p.nslices = (S + B - 1) / B;
     p.lds2 = cd.m * B + tail;
     // Two workgroups per CU (each half of the 160 KB) hide one workgroup's set-up and level phase behind the
     // other's streaming phase: possible when the accumulators of the typical frame fit in half the LDS.
@@ -1966,16 +2018,24 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
 {
     constexpr int THREADS = (LPR >= 8) ? 1024 : (LPR >= 2 ? 512 : 256);
     const Knobs &kn = ctx->knobs;
-    const bool nt = kn.scatter_nt != 0;
+    // word form (S no multiple of 16): rows are only 4-byte aligned, so the four-dword access form -- the non-temporal instantiations --
+    // runs whatever SCATTER_NT says; the kernels are the ones a multiple of 16 runs, with the last piece moved back (ScatterArgs::piece_last)
+    const bool words = symbol_len_words(sa.S);
+    const bool nt = kn.scatter_nt != 0 || words;
+    sa.piece_last = sa.S - 16 * LPR;
     sa.dyn_rows = kn.scatter_dyn;
     sa.xcd_map = kn.scatter_xcd;  // measured: 3.12 vs 3.22 ms once the set-up was shortened; =0 switches it off
     const dim3 grid((unsigned)(sa.nframes * sa.nslices));
     // tier 1
     sa.tcap = p.tcap; sa.nslots = p.tcap; sa.big_list = nullptr;
     scatter_set_lds(sa, p, p.tcap);
-    if constexpr (LPR >= 8 && R == 2) {   // (the shipped R; the SCATTER_R variants keep the one-item kernel: a third of the instantiations)
+    // (LPR < 8 -- S below 128 -- has a persistent form only for the fused sender's word form: one instantiation each, so that a word-sized
+    // datagram shorter than 128 bytes still goes out in one kernel)
+    constexpr bool kPersistAll = LPR >= 8 && R == 2;
+    if constexpr (kPersistAll || LPR < 8) {   // (the shipped R; the SCATTER_R variants keep the one-item kernel: a third of the instantiations)
         // Encoder: the persistent form (ENC_PERSIST; not with ENC_LIST, whose row list lives where the kept lists do)
-        if (sa.static_sched && kn.enc_persist != 0 && !sa.enc_list && !sa.inplace && (sa.enc_group || sa.enc_clist)) {
+        if (sa.static_sched && kn.enc_persist != 0 && !sa.enc_list && !sa.inplace && (sa.enc_group || sa.enc_clist) &&
+            (kPersistAll || (words && sa.pkt_out))) {
             const int per_cu = std::max(1, std::min(p.two_tier ? 2 : 1, kLdsMax / std::max(1, p.lds1)));
             const dim3 gp((unsigned)std::min<int64_t>((int64_t)grid.x, (int64_t)ctx->sm_count * per_cu));
             // the item counter: self-resetting, so zeroed once (synchronously: whatever stream the context is moved to later sees it);
@@ -1997,6 +2057,9 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
         LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
         hipLaunchKernelGGL(kfn, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);                         \
     }
+            if constexpr (!kPersistAll) {
+                LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, true, 4)
+            } else
             if (sa.pkt_out) {   // the fused sender: packets out
                 if (p.two_tier) { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, true, 8) else LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, false, 8) }
                 else { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, true, 4) else LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, false, 4) }
@@ -2093,7 +2156,7 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
         if (t2_128) {
             ScatterPlan p2 = p;
             p2.lpr = 8; p2.nslices = sa.S / 128; p2.lds2 = sa.code.m * 128 + tail_b;
-            sa.nslices = p2.nslices;
+            sa.nslices = p2.nslices; sa.piece_last = sa.S - 128;
             while (sa.t2_pieces > 1 && (sa.nslices % sa.t2_pieces) != 0) sa.t2_pieces >>= 1;
             scatter_set_lds(sa, p2, sa.code.m);
             const dim3 g3((unsigned)std::min<int64_t>(sa.nframes * sa.nslices, (int64_t)ctx->sm_count * 2));
@@ -2140,7 +2203,10 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
     const DevCode &cd = d.code;
     if (d.nframes <= 0) return LDPC_AMD_OK;
     const bool fused = (d.S == 1) && !d.flags_only;
-    if (!fused && !d.flags_only && (d.S % 16) != 0) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 16 (got %d)", d.S);
+    if (!fused && !d.flags_only && !symbol_len_ok(ctx, d.S)) return refuse_symbol_len(ctx, d.S, "S must be 1 or a multiple of 16 (got %d)");
+    const bool words = !fused && !d.flags_only && symbol_len_words(d.S);   // the kernels' word form (internal.h)
+    if (words && ((((uintptr_t)d.sym | (uintptr_t)d.out | (uintptr_t)d.pin.stage) & 3) != 0 || (d.pin.src && ((uintptr_t)d.pin.packets & 7) != 0)))
+        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", d.S);
     if (d.max_sweeps < 1) return set_error(ctx, LDPC_AMD_EINVAL, "max_sweeps must be >= 1");
 
     // bound the per-call workspaces: long batches are processed in chunks of frames
@@ -2244,13 +2310,14 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
     //      the fast path and the factorisation of what the fast path leaves -- can run beside the packet kernel (second stream)
     MlArgs ma{};
     PiArgs pi{};
+    void (*const ml_kfn)(MlArgs) = words ? ldpc_ml_words_kernel : ldpc_ml_kernel;   // (the word form: a kernel of its own over the same body)
     int pi_nw = 0, pi_total = 0, grid = 0, total = 0, ml_threads = 0, solve_b = 0;
     bool ml_overlap = false, ml_prepared = false, ml_front_done = false;
     hipEvent_t ml_ev = nullptr;
     auto ml_prepare = [&]() -> int {
         int rc;
         ma.code = cd; ma.S = d.S;
-        ma.Spad = fused ? 16 : d.S;
+        ma.Spad = fused ? 16 : align_up(d.S, 16);   // (word form: the scratch rows keep 16-byte chunks, the last one partly unused)
         ma.ml_list = (const int32_t *)ctx->mllist.p; ma.ml_state = (const uint8_t *)ctx->mlstate.p; ma.nframes = nf;
         ma.out = d.out; ma.status = d.status;
         const int maxrow = align_up(cd.m, 16) + 32;
@@ -2282,7 +2349,7 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
         if (total > kLdsMax) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: LDS need %d bytes", total);
         ma.capA = (total - off) & ~15;
         grid = (int)std::min<int64_t>(nf, (int64_t)ctx->sm_count * pack);
-        const size_t perA = (size_t)cd.m * maxrow, perR = fused ? 0 : (size_t)cd.m * d.S;
+        const size_t perA = (size_t)cd.m * maxrow, perR = fused ? 0 : (size_t)cd.m * ma.Spad;
         if ((rc = scratch_reserve(ctx, ctx->mlws, (perA + perR) * grid + 256))) return rc;
         // work counters: [0] frame hand-out counter, [2..3] arena bump pointer (u64), [4] task counter of the solve kernel.  They
         // sit in the free tail of the residual list's header (ints 18..23), which launch_decode zeroes with that header: one
@@ -2304,7 +2371,8 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
         ma.dbg = kn.ml_dbg;
         if (ma.use_solve) {
             solve_b = kn.ml_solve_b;   // A/B knob
-            while (solve_b > 16 && (d.S % solve_b) != 0) solve_b >>= 1;
+            if (words) { while (solve_b > 16 && solve_b > d.S) solve_b >>= 1; }   // (the last piece overlaps: MlSolveArgs::piece_last)
+            else while (solve_b > 16 && (d.S % solve_b) != 0) solve_b >>= 1;
             const int tail_sv = align_up(4 * (2 * cd.m + 6), 16) + 8192 + 16 + 4 * kMlClasses;
             while (solve_b > 16 && cd.m * solve_b + tail_sv > 79 * 1024) solve_b >>= 1;
             if (cd.m * solve_b + tail_sv > kLdsMax || cd.n > 65535) ma.use_solve = 0;
@@ -2332,8 +2400,8 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
             ma.rec = (uint32_t *)ctx->mlrec.p;   // the fall-back flag is written in either case
         }
         ml_threads = kn.ml_threads > 0 ? kn.ml_threads : std::max(256, (1024 / pack) & ~63);
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(ldpc_ml_kernel)));
-        ctx->prof_names[LDPC_AMD_PROF_ML] = "ldpc_ml_kernel";
+        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(ml_kfn)));
+        ctx->prof_names[LDPC_AMD_PROF_ML] = words ? "ldpc_ml_words_kernel" : "ldpc_ml_kernel";
         // Packets: the fast path first (ml_pi.inc: peel on, inactivate, small dense system; a wavefront per frame).  It emits
         // the schedules of the full-rank frames; ldpc_ml_kernel then factors what it left (rank-deficient frames, rec[6] = 0).
         // (A context whose LAST packet batch had no residual frame at all -- its arena demand, back through the pinned host word, was
@@ -2432,7 +2500,7 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
         }
         if (ml_overlap && kn.ml_overlap != 2 && (rc = fork())) return rc;
         ma.mode = ml_overlap ? 1 : 0;
-        hipLaunchKernelGGL(ldpc_ml_kernel, dim3(grid), dim3(ml_threads), (size_t)total, st, ma);
+        hipLaunchKernelGGL(ml_kfn, dim3(grid), dim3(ml_threads), (size_t)total, st, ma);
         LDPC_HIP_TRY(ctx, hipGetLastError());
         if (ml_overlap) LDPC_HIP_TRY(ctx, hipEventRecord(ctx->ml_events[1], ctx->aux_ml));
         return LDPC_AMD_OK;
@@ -2443,12 +2511,12 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
             ml_ev = prof_begin(ctx);
             LDPC_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ml_events[1], 0));
             ma.mode = 2;   // the deferred frames only (none, normally: the kernel leaves after one load)
-            hipLaunchKernelGGL(ldpc_ml_kernel, dim3(grid), dim3(ml_threads), (size_t)total, ctx->stream, ma);
+            hipLaunchKernelGGL(ml_kfn, dim3(grid), dim3(ml_threads), (size_t)total, ctx->stream, ma);
             LDPC_HIP_TRY(ctx, hipGetLastError());
         }
         if (ma.use_solve && kn.ml_solve != 2) {   // =2: diagnostic, schedules emitted but not run (timing of the factor part)
             MlSolveArgs sv{};
-            sv.code = cd; sv.S = d.S; sv.nslices = d.S / solve_b; sv.nframes = nf; sv.ml_list = ma.ml_list; sv.rec = ma.rec; sv.ops = ma.ops;
+            sv.code = cd; sv.S = d.S; sv.nslices = (d.S + solve_b - 1) / solve_b; sv.piece_last = d.S - solve_b; sv.nframes = nf; sv.ml_list = ma.ml_list; sv.rec = ma.rec; sv.ops = ma.ops;
             sv.out = d.out; sv.work = ma.work + 4;
             sv.dbg = ma.dbg; sv.err = ctx->dev_err_host;
             sv.nfail = ma.nfail; sv.round = 1;
@@ -2460,13 +2528,14 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
             const dim3 sg((unsigned)std::min<int64_t>(nf * sv.nslices, (int64_t)ctx->sm_count * per_cu));
 #define LDPC_ML_SOLVE(LPRV)                                                                                   \
     {                                                                                                        \
-        auto sfn = ldpc_ml_solve_kernel<LPRV>;                                                               \
+        void (*sfn)(MlSolveArgs) = ldpc_ml_solve_kernel<LPRV>;                                               \
+        if (words) sfn = ldpc_ml_solve_words_kernel<LPRV>;                                                   \
         LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(sfn)));                               \
         hipLaunchKernelGGL(sfn, sg, dim3(512), (size_t)o, ctx->stream, sv);                                  \
     }
             {
                 char nm[64];
-                snprintf(nm, sizeof(nm), "ldpc_ml_solve_kernel<%d>", solve_b / 16);
+                snprintf(nm, sizeof(nm), "ldpc_ml_solve%s_kernel<%d>", words ? "_words" : "", solve_b / 16);
                 ctx->prof_names[LDPC_AMD_PROF_ML_SOLVE] = nm;
             }
             hipEvent_t evs = prof_begin(ctx, 2);
@@ -2484,7 +2553,7 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
                 // equations they did not use; the solve kernel flags a frame with a non-zero one (rec[7], nfail), and these two
                 // launches -- which leave after one load when nothing was flagged -- redo such frames in the reference's order.
                 ma.mode = 3;
-                hipLaunchKernelGGL(ldpc_ml_kernel, dim3(grid), dim3(ml_threads), (size_t)total, ctx->stream, ma);
+                hipLaunchKernelGGL(ml_kfn, dim3(grid), dim3(ml_threads), (size_t)total, ctx->stream, ma);
                 LDPC_HIP_TRY(ctx, hipGetLastError());
                 sv.round = 2; sv.work = (int32_t *)ctx->mllist.p + 26;
                 switch (solve_b) {
@@ -2708,8 +2777,10 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
         aa.code = cd; aa.S = d.S; aa.nframes = nf; aa.sym = d.sym; aa.erased = d.erased; aa.in_rows = d.in_rows; aa.out = d.out;
         aa.sched_hdr = pa.sched_hdr; aa.sched_steps = pa.sched_steps; aa.sched_lvlend = pa.sched_lvlend;
         const size_t lds = (size_t)cd.m * 4 + (size_t)(cd.m + 2) * 2;
-        ctx->prof_names[LDPC_AMD_PROF_APPLY] = "ldpc_apply_kernel";
+        ctx->prof_names[LDPC_AMD_PROF_APPLY] = words ? "ldpc_apply_words_kernel" : "ldpc_apply_kernel";
         ev = prof_begin(ctx);
+        if (words) hipLaunchKernelGGL(ldpc_apply_words_kernel, dim3((unsigned)nf), dim3(512), lds, ctx->stream, aa);
+        else
         hipLaunchKernelGGL(ldpc_apply_kernel, dim3((unsigned)nf), dim3(512), lds, ctx->stream, aa);
         LDPC_HIP_TRY(ctx, hipGetLastError());
         prof_end(ctx, LDPC_AMD_PROF_APPLY, ev);
@@ -2731,7 +2802,7 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
 bool decode_reads_packets(ldpc_amd_ctx *ctx, const DevCode &cd, int S)
 {
     const Knobs &kn = ctx->knobs;
-    if (S < 16 || (S % 16) != 0 || kn.apply_gather != 0 || cd.maxcoldeg > 16) return false;
+    if (S < 16 || !symbol_len_ok(ctx, S) || kn.apply_gather != 0 || cd.maxcoldeg > 16) return false;
     return plan_scatter(kn, cd, S, true).lpr > 0;
 }
 
@@ -2750,7 +2821,10 @@ static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64
         d.max_sweeps = 1; d.do_ml = 0; d.out = cw;
         return launch_decode(ctx, d);
     }
-    if (S % 16) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 16 (got %d)", S);
+    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
+    const bool words = symbol_len_words(S);   // the kernels' word form (internal.h)
+    if (words && (((uintptr_t)src | (uintptr_t)cw) & 3) != 0)
+        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
     const Knobs &kn = ctx->knobs;
     if (!kn.apply_gather && cd.maxcoldeg <= 16) {
         // scatter form with the static schedule: source rows read once, all m accumulators in LDS
@@ -2768,7 +2842,7 @@ static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64
             const int nlev_plan = grouped ? cd.encg_nlevels : cd.enc_nlevels;
             const int gent2 = (cd.encg_ent_n + 7) & ~7;
             const int need_g = 3 * gent2 + 2 * ((cd.m + 8) & ~7) + ((cd.m + 15) & ~15);
-            if (plan.lpr == 16 && eb == 128 && (S % 128) == 0) {
+            if (plan.lpr == 16 && eb == 128 && ((S % 128) == 0 || words)) {   // (word form: the last 128-byte piece overlaps)
                 ScatterPlan q = plan;
                 int off = 0;
                 q.o_tgt = off; off += align_up(2 * cd.m, 16);
@@ -2780,7 +2854,7 @@ static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64
                 q.soc_bytes = align_up(2 * cd.k, 16) >= cd.n ? align_up(2 * cd.k, 16) : align_up(cd.n, 16);
                 q.o_chk = off;                               // unused in static mode
                 if (8192 + cd.m * 128 + off <= kLdsMax / 2) {
-                    q.lpr = 8; q.nslices = S / 128; q.lds1 = q.lds2 = 8192 + cd.m * 128 + off;
+                    q.lpr = 8; q.nslices = (S + 127) / 128; q.lds1 = q.lds2 = 8192 + cd.m * 128 + off;
                     q.two_tier = true;    // (only selects the 8-waves-per-SIMD instantiation; tcap = m: no frame goes to tier 2)
                     plan = q;
                 }
@@ -2823,6 +2897,8 @@ static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64
     ApplyArgs aa{};
     aa.code = cd; aa.S = S; aa.nframes = nframes; aa.sym = src; aa.erased = nullptr; aa.in_rows = cd.k; aa.out = cw;
     const size_t lds = (size_t)cd.m * 4 + (size_t)(cd.m + 2) * 2;
+    if (words) hipLaunchKernelGGL(ldpc_apply_words_kernel, dim3((unsigned)nframes), dim3(512), lds, ctx->stream, aa);
+    else
     hipLaunchKernelGGL(ldpc_apply_kernel, dim3((unsigned)nframes), dim3(512), lds, ctx->stream, aa);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     return LDPC_AMD_OK;
@@ -2836,7 +2912,8 @@ int launch_encode(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, 
 int launch_encode_packets(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, const uint8_t *src, unsigned fec_class, unsigned block0,
                           uint8_t *packets)
 {
-    if (ctx->knobs.enc_pkt == 0 || ((uintptr_t)packets & 7) != 0 || ((uintptr_t)src & 15) != 0) return kEncodeNotFused;
+    // (word form: the source rows are 4-byte aligned whatever the array's alignment, and a packet of 8 + S bytes only every other one)
+    if (ctx->knobs.enc_pkt == 0 || ((uintptr_t)packets & 7) != 0 || ((uintptr_t)src & (symbol_len_words(S) ? 3 : 15)) != 0) return kEncodeNotFused;
     return launch_encode_impl(ctx, cd, S, nframes, src, packets, 1, ((uint32_t)(fec_class & 0xffu) << 8) | (uint32_t)(block0 & 0xffu));
 }
 
@@ -2867,7 +2944,11 @@ static int launch_rs_decode_t(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_
     a.bad = (int *)ctx->rsbad.p;
     LDPC_HIP_TRY(ctx, hipMemsetAsync(a.bad, 0, sizeof(int), ctx->stream));
     // (frames: the packet kernel's row address is a 24-bit multiply; a larger S -- 8 MB per symbol -- takes the generic kernel)
-    if (S >= 256 && (S % 256) == 0 && R <= 32 && rs.k <= 256 && !rs_generic && (!FRAMES || S < (1 << 23))) {
+    // (word form, S a multiple of 4 and not of 16: one dword per lane and ceil(S / 256) slices, the last one overlapping -- rs_decode_packets_kernel)
+    const bool words = symbol_len_words(S);
+    if (words && ((((uintptr_t)val | (uintptr_t)msg) & 3) != 0))
+        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
+    if (S >= 256 && ((S % 256) == 0 || words) && R <= 32 && rs.k <= 256 && !rs_generic && (!FRAMES || S < (1 << 23))) {
         // packets: one wavefront per (block, slice), M^-1 in registers, rows streamed once, accumulators in registers
         // dwords per lane: 1 (a wavefront per 256-byte slice of the block, 32 accumulator registers, four wavefronts per SIMD) is
         // the fastest -- 21.5 ms per 60 k blocks of 1 KB packets against 22.2 (2 dwords) and 24.9 (4 dwords: 256 registers, two
@@ -2876,7 +2957,7 @@ static int launch_rs_decode_t(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_
         if (FRAMES) vw = 1;   // (the A/B widths are not instantiated for frames)
         else if (ctx->knobs.rs_vw == 4 && (S % 1024) == 0) vw = 4;
         else if (ctx->knobs.rs_vw == 2 && (S % 512) == 0) vw = 2;
-        const int nslices = S / (256 * vw);
+        const int nslices = (S + 256 * vw - 1) / (256 * vw);
         RsPkLds L{};
         int o = 0;
         L.pt = o; o += align_up(R * rs.k, 16);
@@ -2958,6 +3039,8 @@ int launch_rs_decode_frames(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t 
 int launch_rs_encode(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks, const uint8_t *src, uint8_t *cw)
 {
     if (nblocks <= 0) return LDPC_AMD_OK;
+    if (symbol_len_words(S) && ((((uintptr_t)src | (uintptr_t)cw) & 3) != 0))
+        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
     const int grid = (int)std::min<int64_t>(nblocks, (int64_t)ctx->sm_count * 8);
     hipLaunchKernelGGL(rs_encode_kernel, dim3(grid), dim3(256), 0, ctx->stream, rs.n, rs.k, S, nblocks,
                        (const uint8_t *)rs.d_pt, src, cw);

@@ -96,7 +96,13 @@ __device__ __forceinline__ uint32_t ml_rhs_byte(const DevCode &cd, const uint16_
     return acc;
 }
 
-template <bool IN_LDS, bool PK>   // PK: packets (S != 1) -- LU in place, forward levels, solve-schedule emission
+// W4 (packets only; ldpc_ml_words_kernel): S is a multiple of 4, not of 16 -- the rows of `out` start on 4-byte boundaries and the
+// last 16-byte chunk of a row would cross its end.  A lane's chunk i then lies at min(16 i, S - 16): the last chunk is moved back to
+// end with the row and shares bytes with the one before it.  The scratch rows R keep the chunk index (stride Spad = S rounded up to
+// 16, 16-byte accesses), so chunk i of a scratch row always belongs to the same bytes of the symbols.  Both lanes of an overlap compute
+// the same values (the arithmetic is columnwise) and store them twice; every row of `out` that is read here was either received (the
+// packet kernel wrote it, an earlier launch) or written by a wavefront of an EARLIER level, with a workgroup barrier in between.
+template <bool IN_LDS, bool PK, bool W4 = false>   // PK: packets (S != 1) -- LU in place, forward levels, solve-schedule emission
 __device__ __forceinline__ void ml_frame(const MlArgs &a, const int64_t f, const int slot, const uint8_t *state, const int E,
                                          const int nzr, const int nch, const int ach)
 {
@@ -108,6 +114,7 @@ __device__ __forceinline__ void ml_frame(const MlArgs &a, const int64_t f, const
     const int W = nch << 4;
     const int ro = ach << 4;                                   // S == 1: byte offset of the rhs inside a row
     const int rch = a.Spad >> 4;
+    auto fo = [&](int i) { return W4 ? min(i * 16, S - 16) : i * 16; };   // byte offset of chunk i in a row of `out`
 
     uint16_t *colmap = reinterpret_cast<uint16_t *>(smem + a.lds_colmap);   // build phase only (aliases rlist[1..2])
     uint16_t *elist = reinterpret_cast<uint16_t *>(smem + a.lds_elist);
@@ -199,7 +206,7 @@ __device__ __forceinline__ void ml_frame(const MlArgs &a, const int64_t f, const
                             km &= km - 1;
                             const uint32_t col = (uint32_t)__builtin_amdgcn_readlane((int)colL, e);
                             cf[u] = (uint32_t)__builtin_amdgcn_readlane((int)cfL, e);
-                            if (act) v[u] = *reinterpret_cast<const U4 *>(fout + (int64_t)col * S + i * 16);
+                            if (act) v[u] = row_load16<W4>(fout + (int64_t)col * S + fo(i));
                         }
                     }
 #pragma unroll
@@ -814,7 +821,7 @@ __device__ __forceinline__ void ml_frame(const MlArgs &a, const int64_t f, const
                                         km &= km - 1;
                                         cf[u] = (uint32_t)__builtin_amdgcn_readlane((int)bU, e);
                                         const uint32_t sc = elist[base + e];
-                                        if (act) v[u] = *reinterpret_cast<const U4 *>(fout + (int64_t)sc * S + i * 16);
+                                        if (act) v[u] = row_load16<W4>(fout + (int64_t)sc * S + fo(i));
                                     }
                                 }
 #pragma unroll
@@ -822,7 +829,7 @@ __device__ __forceinline__ void ml_frame(const MlArgs &a, const int64_t f, const
                                     if (cf[u]) gfmac16(acc, load_multab(cf[u]), v[u]);
                             }
                         }
-                        if (act) *reinterpret_cast<U4 *>(dst + i * 16) = gfmul16(ts, acc);
+                        if (act) row_store16<W4>(dst + fo(i), gfmul16(ts, acc));
                     }
                 }
                 __syncthreads();
@@ -854,16 +861,16 @@ __device__ __forceinline__ void ml_frame(const MlArgs &a, const int64_t f, const
                         const uint32_t col = cd.ell_col[(size_t)tt * mp + r];
                         if (col == 0xFFFFu) break;
                         if (state[col]) continue;
-                        const U4 v = *reinterpret_cast<const U4 *>(fout + (int64_t)col * S + i * 16);
+                        const U4 v = row_load16<W4>(fout + (int64_t)col * S + fo(i));
                         gfmac16(acc, load_multab(uniform(cd.ell_coef[(size_t)tt * mp + r])), v);
                     }
-                    *reinterpret_cast<U4 *>(dst + i * 16) = acc;
+                    row_store16<W4>(dst + fo(i), acc);
                 }
             } else {
                 const uint8_t *src = R + (size_t)w * a.Spad;
                 const MulTab ts = load_multab(uniform(t < npiv ? ex[plog[t]] : 1u));
                 for (int i = lane; i < rch; i += kWave)
-                    *reinterpret_cast<U4 *>(dst + i * 16) = gfmul16(ts, *reinterpret_cast<const U4 *>(src + i * 16));
+                    row_store16<W4>(dst + fo(i), gfmul16(ts, *reinterpret_cast<const U4 *>(src + i * 16)));
             }
         }
     }
@@ -871,7 +878,8 @@ __device__ __forceinline__ void ml_frame(const MlArgs &a, const int64_t f, const
     if (tid == 0 && a.status) a.status[f] = dont_do_jordan ? LDPC_AMD_ST_ML_RANKDEF : LDPC_AMD_ST_ML_SOLVED;
 }
 
-__global__ __launch_bounds__(1024) void ldpc_ml_kernel(MlArgs a)
+template <bool W4>
+__device__ __forceinline__ void ml_kernel_body(const MlArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const DevCode &cd = a.code;
@@ -977,11 +985,15 @@ __global__ __launch_bounds__(1024) void ldpc_ml_kernel(MlArgs a)
             if (in_lds) ml_frame<true, false>(a, f, slot, state, E, nzr, nch, ach);
             else ml_frame<false, false>(a, f, slot, state, E, nzr, nch, ach);
         } else {
-            if (in_lds) ml_frame<true, true>(a, f, slot, state, E, nzr, nch, ach);
-            else ml_frame<false, true>(a, f, slot, state, E, nzr, nch, ach);
+            if (in_lds) ml_frame<true, true, W4>(a, f, slot, state, E, nzr, nch, ach);
+            else ml_frame<false, true, W4>(a, f, slot, state, E, nzr, nch, ach);
         }
     }
 }
+
+__global__ __launch_bounds__(1024) void ldpc_ml_kernel(MlArgs a) { ml_kernel_body<false>(a); }
+// the word form (S a multiple of 4, not of 16: ml_frame<..., W4>); never launched for S = 1
+__global__ __launch_bounds__(1024) void ldpc_ml_words_kernel(MlArgs a) { ml_kernel_body<true>(a); }
 
 // =================================================================================================
 // Packets: executes the solve schedules the ML kernel emitted.  One workgroup per (ML frame, B-byte slice of its rows);
@@ -993,6 +1005,7 @@ __global__ __launch_bounds__(1024) void ldpc_ml_kernel(MlArgs a)
 struct MlSolveArgs {
     DevCode code;
     int S, nslices;
+    int piece_last;           // S - B: piece sl of a row starts at min(sl * B, piece_last) (the word form's last piece overlaps its neighbour)
     int64_t nframes;          // frames of the batch (stride of the size-class lists)
     const int32_t *ml_list;
     uint32_t *rec;           // [7]: set to 1 by the first workgroup that finds a non-zero check of a fast-path schedule
@@ -1006,8 +1019,12 @@ struct MlSolveArgs {
     int dbg;                         // diagnostic build only (-DLDPC_AMD_MLDBG, tools/sens_ml.py)
 };
 
-template <int LPR>
-__global__ __launch_bounds__(512, 4) void ldpc_ml_solve_kernel(MlSolveArgs a)
+// W4 (ldpc_ml_solve_words_kernel): S is a multiple of 4, not of 16 -- ceil(S / B) pieces, the last one moved back to end with the
+// row, 4-byte accesses.  The overlap is safe: level 0 READS known rows (received, or solved by the packet kernel: an earlier launch),
+// the last level WRITES unknown rows -- disjoint sets -- and everything in between lives in this workgroup's LDS slots; the two pieces
+// that share bytes write the same values there.
+template <int LPR, bool W4>
+__device__ __forceinline__ void ml_solve_body(const MlSolveArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int B = 16 * LPR;
@@ -1067,7 +1084,7 @@ __global__ __launch_bounds__(512, 4) void ldpc_ml_solve_kernel(MlSolveArgs a)
         const uint32_t *tab = reinterpret_cast<const uint32_t *>(a.ops + off);
         const unsigned long long *ops = a.ops + off + (unsigned long long)((NL + 2) / 2);
         const int64_t f = a.ml_list[kMlHdr + slot];
-        uint8_t *fout = a.out + f * (int64_t)n * S + (int64_t)sl * B + gl * 16;
+        uint8_t *fout = a.out + f * (int64_t)n * S + (int64_t)(W4 ? min(sl * B, a.piece_last) : sl * B) + gl * 16;
         for (int i = tid; i < NL; i += nthr) ltab[i] = tab[i];
         for (int i = tid; i < nslots * LPR; i += nthr) reinterpret_cast<U4 *>(slots)[i] = U4{0, 0, 0, 0};
         // Ops of a level are dealt round-robin to the lane groups, restarting at every level: group g takes ops o0 + g,
@@ -1107,7 +1124,7 @@ __global__ __launch_bounds__(512, 4) void ldpc_ml_solve_kernel(MlSolveArgs a)
 #endif
             for (uint32_t base = (uint32_t)g; base < e0x; base += (uint32_t)(C * NG)) {
 #pragma unroll
-                for (int i = 0; i < C; i++) vr[i] = *reinterpret_cast<const U4 *>(row_of((uint32_t)(oq[i] >> 32)));
+                for (int i = 0; i < C; i++) vr[i] = row_load16<W4>(row_of((uint32_t)(oq[i] >> 32)));
 #pragma unroll
                 for (int i = 0; i < C; i++) on[i] = opat(base + (uint32_t)((C + i) * NG));
 #pragma unroll
@@ -1188,10 +1205,15 @@ __global__ __launch_bounds__(512, 4) void ldpc_ml_solve_kernel(MlSolveArgs a)
                         if (((uint32_t)oq[i] & 0xFFFFu) == 0xFFFFu) {   // a check op of the fast path: an equation it did not use must hold
                             if ((val.x | val.y | val.z | val.w) != 0u && atomicExch(&rec[7], 1u) == 0u) atomicAdd(a.nfail, 1);
                         } else {
-                            *reinterpret_cast<U4 *>(row_of((uint32_t)oq[i])) = gfmul16(lds_multab_at((uint32_t)oq[i] >> 19), val);
+                            row_store16<W4>(row_of((uint32_t)oq[i]), gfmul16(lds_multab_at((uint32_t)oq[i] >> 19), val));
                         }
                     }
             }
         }
     }
 }
+
+template <int LPR>
+__global__ __launch_bounds__(512, 4) void ldpc_ml_solve_kernel(MlSolveArgs a) { ml_solve_body<LPR, false>(a); }
+template <int LPR>
+__global__ __launch_bounds__(512, 4) void ldpc_ml_solve_words_kernel(MlSolveArgs a) { ml_solve_body<LPR, true>(a); }

@@ -57,6 +57,14 @@ __global__ __launch_bounds__(256) void rs_select_kernel(int n, int k, int64_t nb
     }
 }
 
+// 16 bytes of a row; w4 (wave-uniform): the row is only 4-byte aligned (S a multiple of 4, not of 16) -- four dword accesses
+__device__ __forceinline__ U4 rs_ld16(const uint8_t *p, bool w4) { return w4 ? row_load16<true>(p) : row_load16<false>(p); }
+__device__ __forceinline__ void rs_st16(uint8_t *p, const U4 &v, bool w4)
+{
+    if (w4) row_store16<true>(p, v);
+    else row_store16<false>(p, v);
+}
+
 template <bool FRAMES>
 __global__ __launch_bounds__(256) void rs_decode_kernel(RsArgs a)
 {
@@ -190,17 +198,23 @@ __global__ __launch_bounds__(256) void rs_decode_kernel(RsArgs a)
             for (int t = tid; t < nsys; t += nthr) out[sidx[t]] = val[rw(t)];
         } else {
             uint8_t *ws = a.ws + (size_t)blockIdx.x * R * S;
-            const int chunks = S >> 4;
+            // Word form (S a multiple of 4, not of 16; off the hot path, so a run-time switch): ceil(S / 16) chunks, the last one moved
+            // back to end with the row, 4-byte accesses (rs_ld16 / rs_st16).  The chunk that overlaps its neighbour is computed by two lanes
+            // of one wavefront from the same bytes: the rows of val are only read, the rows of ws and out are each written by ONE
+            // wavefront, and ws is read back only behind the barrier.
+            const bool w4 = (S & 15) != 0;
+            const int chunks = (S + 15) >> 4;
+            auto co = [&](int i) { return w4 ? min(i * 16, S - 16) : i * 16; };
             for (int q = wave; q < r; q += nw) {
                 const int j = (int)sidx[nsys + q] - k;
                 for (int i = lane; i < chunks; i += kWave) {
-                    U4 acc = *reinterpret_cast<const U4 *>(val + rw(nsys + q) * S + i * 16);
+                    U4 acc = rs_ld16(val + rw(nsys + q) * S + co(i), w4);
                     for (int t = 0; t < nsys; t++) {
                         const uint32_t c = uniform(a.pt[(size_t)j * k + sidx[t]]);
-                        const U4 v = *reinterpret_cast<const U4 *>(val + rw(t) * S + i * 16);
+                        const U4 v = rs_ld16(val + rw(t) * S + co(i), w4);
                         gfmac16(acc, load_multab(c), v);
                     }
-                    *reinterpret_cast<U4 *>(ws + (size_t)q * S + i * 16) = acc;
+                    rs_st16(ws + (size_t)q * S + co(i), acc, w4);
                 }
             }
             __syncthreads();
@@ -209,16 +223,15 @@ __global__ __launch_bounds__(256) void rs_decode_kernel(RsArgs a)
                     U4 acc = {0, 0, 0, 0};
                     for (int q = 0; q < r; q++) {
                         const uint32_t c = uniform(M[t * W2 + r + q]);
-                        const U4 v = *reinterpret_cast<const U4 *>(ws + (size_t)q * S + i * 16);
+                        const U4 v = rs_ld16(ws + (size_t)q * S + co(i), w4);
                         gfmac16(acc, load_multab(c), v);
                     }
-                    *reinterpret_cast<U4 *>(out + (size_t)ulist[t] * S + i * 16) = acc;
+                    rs_st16(out + (size_t)ulist[t] * S + co(i), acc, w4);
                 }
             }
             for (int t = wave; t < nsys; t += nw)
                 for (int i = lane; i < chunks; i += kWave)
-                    *reinterpret_cast<U4 *>(out + (size_t)sidx[t] * S + i * 16) =
-                        *reinterpret_cast<const U4 *>(val + rw(t) * S + i * 16);
+                    rs_st16(out + (size_t)sidx[t] * S + co(i), rs_ld16(val + rw(t) * S + co(i), w4), w4);
         }
     }
 }
@@ -487,7 +500,10 @@ __global__ __launch_bounds__(256, WPS) void rs_decode_packets_kernel(RsArgs a, R
         const int64_t blk = item / nslices;
         const int sl = (int)(item - blk * nslices);
         const uint16_t *idx = a.recv_idx + blk * k;
-        const uint32_t loff = (uint32_t)sl * (uint32_t)(256 * VW) + (uint32_t)lane * (uint32_t)(4 * VW);
+        // (word form, S a multiple of 4 and not of 16, VW = 1: ceil(S / 256) slices, the last one moved back to end with the row -- where 256 VW
+        // divides S the min changes nothing.  Every access of this kernel is a dword one already; a slice reads received rows and writes
+        // its own bytes of msg, so the bytes two slices share are written twice with the same values and never read back)
+        const uint32_t loff = min((uint32_t)sl * (uint32_t)(256 * VW), (uint32_t)(S - 256 * VW)) + (uint32_t)lane * (uint32_t)(4 * VW);
         const uint8_t *val = a.recv_val + blk * (int64_t)(FRAMES ? a.n : k) * S + loff;
         uint8_t *out = a.msg + blk * (int64_t)k * S + loff;
         uint32_t id[4];
@@ -735,17 +751,24 @@ __global__ __launch_bounds__(256) void rs_encode_kernel(int n, int k, int S, int
                 if (lane == 0) c[k + j] = (uint8_t)acc;
             }
         } else {
-            const int chunks = S >> 4;
-            for (int64_t u = threadIdx.x; u < (int64_t)k * chunks; u += blockDim.x)
-                reinterpret_cast<U4 *>(c)[u] = reinterpret_cast<const U4 *>(s)[u];
+            const bool w4 = (S & 15) != 0;   // word form: dword copy, ceil(S / 16) chunks with the last one moved back (rs_decode_kernel)
+            const int chunks = (S + 15) >> 4;
+            if (w4) {
+                for (int64_t u = threadIdx.x; u < (int64_t)k * (S >> 2); u += blockDim.x)
+                    reinterpret_cast<uint32_t *>(c)[u] = reinterpret_cast<const uint32_t *>(s)[u];
+            } else {
+                for (int64_t u = threadIdx.x; u < (int64_t)k * chunks; u += blockDim.x)
+                    reinterpret_cast<U4 *>(c)[u] = reinterpret_cast<const U4 *>(s)[u];
+            }
             for (int j = wave; j < R; j += nw)
                 for (int i = lane; i < chunks; i += kWave) {
+                    const int off = w4 ? min(i * 16, S - 16) : i * 16;
                     U4 acc = {0, 0, 0, 0};
                     for (int t = 0; t < k; t++) {
-                        const U4 v = *reinterpret_cast<const U4 *>(s + (size_t)t * S + i * 16);
+                        const U4 v = rs_ld16(s + (size_t)t * S + off, w4);
                         gfmac16(acc, load_multab(uniform(pt[(size_t)j * k + t])), v);
                     }
-                    *reinterpret_cast<U4 *>(c + (size_t)(k + j) * S + i * 16) = acc;
+                    rs_st16(c + (size_t)(k + j) * S + off, acc, w4);
                 }
         }
     }

@@ -358,7 +358,7 @@ int ldpc_amd_fec_encode_packets_dev(ldpc_amd_ctx *ctx, int code, int S, int64_t 
     if (nframes < 0 || S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_dev: bad nframes/S");
     if (nframes == 0) return LDPC_AMD_OK;
     if (cd.enc_nlevels == 0) return set_error(ctx, LDPC_AMD_EUNSUP, "code is not in triangle form: no systematic encoder");
-    if (S != 1 && S % 16) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 16 (got %d)", S);
+    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets))
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_dev: source / packets must be device pointers of device %d", ctx->device);
@@ -596,7 +596,7 @@ static int rx_decode_check(ldpc_amd_ctx *ctx, const ldpc_amd_fec_rx_dev *rx, con
     if (cd.n != rx->n || cd.k != rx->k)
         return set_error(ctx, LDPC_AMD_EINVAL, "%s: the code is (%d,%d), the receiver was created for (%d,%d)", who, cd.n, cd.k, rx->n, rx->k);
     // the decoder's own refusals (launch_decode), before anything is planned
-    if (rx->S != 1 && (rx->S % 16) != 0) return set_error(ctx, LDPC_AMD_EUNSUP, "S must be 1 or a multiple of 16 (got %d)", rx->S);
+    if (!symbol_len_ok(ctx, rx->S)) return refuse_symbol_len(ctx, rx->S, "S must be 1 or a multiple of 16 (got %d)");
     if (max_sweeps < 1) return set_error(ctx, LDPC_AMD_EINVAL, "max_sweeps must be >= 1");
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const void *opt[] = {sweeps, residual, status, erased_out, residual_src};
