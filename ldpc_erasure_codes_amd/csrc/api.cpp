@@ -1550,10 +1550,10 @@ int ldpc_amd_ml_stats(ldpc_amd_ctx *ctx, long long stats[4])
     stats[0] = stats[1] = stats[2] = stats[3] = 0;
     if (!ctx->mllist.p) return LDPC_AMD_OK;   // no decode yet
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int32_t hdr[32];
+    int32_t hdr[kMlHdrWords];
     LDPC_HIP_TRY(ctx, hipMemcpyAsync(hdr, ctx->mllist.p, sizeof(hdr), hipMemcpyDeviceToHost, ctx->stream));
     LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    stats[0] = hdr[0]; stats[1] = hdr[27]; stats[2] = hdr[24]; stats[3] = hdr[19];   // layout: launch_decode (kernels.hip)
+    stats[0] = hdr[kMlHdrCount]; stats[1] = hdr[kMlHdrPiDone]; stats[2] = hdr[kMlHdrNfail]; stats[3] = hdr[kMlHdrDeferred];
     return LDPC_AMD_OK;
 }
 

@@ -270,6 +270,22 @@ struct DecodeArgs {
 };
 
 hipError_t upload_constants(hipStream_t s);
+// Words of the residual list's header (the first 32 ints of the ML list: [0] the residual frames, [1..16] the size-class counts)
+// that hold the ML stage's work counters and statistics.  Every decode zeroes them with the header; ldpc_amd_ml_stats reads them back.
+enum MlHdrWord {
+    kMlHdrCount = 0,        // residual frames
+    kMlHdrWork2 = 17,       // hand-out counter of the launch that solves the deferred frames (mode 2)
+    kMlHdrWork = 18,        // MlArgs::work: [0] frame hand-out counter of the factorisation, and the five words behind it:
+    kMlHdrDeferred = 19,    //   [1] frames deferred by the launch beside the packet kernel
+    kMlHdrOpsHead = 20,     //   [2..3] arena bump pointer (u64)
+    kMlHdrSolveWork = 22,   //   [4] task counter of the solve kernel
+    kMlHdrPiWork = 23,      //   [5] frame hand-out counter of the fast path (ldpc_ml_pi_kernel)
+    kMlHdrNfail = 24,       // frames whose fast-path solution failed the consistency check (not codewords)
+    kMlHdrWork3 = 25,       // hand-out counter of the launch that factors them again, exactly (mode 3)
+    kMlHdrSolveWork2 = 26,  // task counter of the solve kernel's second round, which redoes them
+    kMlHdrPiDone = 27,      // frames the fast path emitted
+    kMlHdrWords = 32,
+};
 int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &a);
 bool decode_reads_packets(ldpc_amd_ctx *ctx, const DevCode &code, int S);   // launch_decode would take DecodeArgs::pin for this code and S
 int launch_encode(ldpc_amd_ctx *ctx, const DevCode &code, int S, int64_t nframes, const uint8_t *src, uint8_t *cw);

@@ -1860,6 +1860,8 @@ __global__ __launch_bounds__(1024) void copy_probe_kernel(const uint8_t *src, ui
 // =================================================================================================
 // Host side: constants, LDS layouts, launches
 // =================================================================================================
+static const int kLdsMax = 160 * 1024;
+
 // Every kernel instantiation that uses dynamic LDS is allowed the full 160 KB ONCE per device (process-wide kernel
 // attribute): a per-launch attribute sized for one code / S could be shrunk by another context between set and launch.
 static hipError_t allow_max_lds(const void *fn)
@@ -1871,9 +1873,47 @@ static hipError_t allow_max_lds(const void *fn)
     if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lk(mu);
     if (done.count({dev, fn})) return hipSuccess;
-    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
     if (e == hipSuccess) done.insert({dev, fn});
     return e;
+}
+
+// The one way a kernel with dynamic LDS is launched.
+template <class... KA, class... A>
+static int launch_lds(ldpc_amd_ctx *ctx, void (*kfn)(KA...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const A &...args)
+{
+    LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));
+    hipLaunchKernelGGL(kfn, grid, block, lds_bytes, stream, args...);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// A run-time choice as a template argument: f is a generic lambda that gets std::true_type / std::false_type (with_bool) or the
+// std::integral_constant of the value that matched (with_int: false when none did, f not called) and instantiates its kernel from
+// decltype(x)::value.  Plain inlined calls: no std::function, nothing on the heap.
+template <class F>
+static int with_bool(bool v, F &&f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <int... Vs, class F>
+static bool with_int(int v, F &&f) { return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
+
+// "base<16, 2, true, 8>": the name of an instantiation as the profile tools print it (ldpc_amd_profile_kernel_name), written in
+// the scope that holds the template arguments as compile-time values -- the same ones the launch next to it uses.
+struct KernelName {
+    char s[96];
+    int len = 0;
+    void put(const char *t) { len += snprintf(s + len, sizeof(s) - (size_t)len, "%s", t); }
+    void arg(bool v) { put(v ? "true" : "false"); }
+    void arg(int v) { len += snprintf(s + len, sizeof(s) - (size_t)len, "%d", v); }
+};
+template <class... A>
+static void prof_name(ldpc_amd_ctx *ctx, int kind, const char *base, A... a)
+{
+    KernelName k;
+    k.put(base); k.put("<");
+    int i = 0;
+    ((k.put(i++ ? ", " : ""), k.arg(a)), ...);
+    k.put(">");
+    ctx->prof_names[kind] = k.s;
 }
 
 hipError_t upload_constants(hipStream_t s)
@@ -1915,31 +1955,184 @@ static PeelLds make_peel_lds(const DevCode &cd, bool fused, int wpb, bool gt = f
     return L;
 }
 
-template <bool FUSED, bool GT = false>
-static hipError_t launch_peel_t(const PeelArgs &a, int wpb, hipStream_t s)
+// ---- peel shape ---------------------------------------------------------------------------------------------
+// The peel is latency bound (serial solve chain per frame), so the frames per workgroup are the ones that put the most
+// wavefronts on a CU within its 160 KB of LDS (the code tables are shared by a workgroup).
+struct PeelShape {
+    int wpb = 1;         // wavefronts (= frames) per workgroup
+    bool gt = false;     // the code tables stay in global memory
+    PeelLds lds{};
+    int per_cu = 0;      // frames on a CU
+    int lds_need = 0;    // != 0: the code is too large -- what one frame would need
+};
+
+static PeelShape plan_peel(const Knobs &kn, const DevCode &cd, bool fused, int64_t nframes, int sm_count)
 {
-    const int grid = (int)((a.nframes + wpb - 1) / wpb);
-    const dim3 g(grid), b(wpb * 64);
-    const size_t lds = (size_t)a.lds.total;
-#define LDPC_PEEL_CASE(D)                                                                                  \
-    case D: {                                                                                              \
-        auto kfn = ldpc_peel_kernel<D, FUSED, GT>;                                                         \
-        hipError_t e = allow_max_lds(reinterpret_cast<const void *>(kfn));                                 \
-        if (e != hipSuccess) return e;                                                                     \
-        hipLaunchKernelGGL(kfn, g, b, lds, s, a);                                                          \
-        return hipGetLastError();                                                                          \
+    PeelShape s;
+    s.lds = make_peel_lds(cd, fused, 1);
+    // (S = 1 keeps id | log(coef) words per edge in LDS: a code whose tables leave no room for a frame -- (8192,4096) -- still runs
+    // with the tables in global memory, whatever PEEL_GT prefers; the relaxation's plan below does the same)
+    const bool lds_tables = s.lds.total <= kLdsMax;
+    if (!lds_tables && (!fused || make_peel_lds(cd, fused, 1, true).total > kLdsMax)) { s.lds_need = s.lds.total; return s; }
+    int best = 0;
+    const bool env_w = kn.peel_wpb > 0;   // diagnostic: cap the wavefronts (= frames) per workgroup
+    const int wcap = env_w ? std::max(1, std::min(16, kn.peel_wpb)) : 16;
+    for (int w = 1; w <= wcap; w++) {
+        const PeelLds t = make_peel_lds(cd, fused, w);
+        if (t.total > kLdsMax) break;
+        const int waves = env_w ? w : std::min(32, (kLdsMax / t.total) * w);
+        if (waves > best) { best = waves; s.wpb = w; s.lds = t; }
     }
-    switch (a.code.degpad) {
-        LDPC_PEEL_CASE(8)
-        LDPC_PEEL_CASE(14)
-        LDPC_PEEL_CASE(16)
-        LDPC_PEEL_CASE(24)
+    // S = 1, long batch: with the code tables left in global memory more frames fit on a CU.  Worth it when the
+    // batch is several rounds deep anyway (a single round is latency bound and prefers the LDS tables).
+    if (fused && ((!env_w && kn.peel_gt != 0) || !lds_tables)) {
+        int bestg = 0, wg = 1;
+        PeelLds Lg = s.lds;
+        for (int w = 1; w <= wcap; w++) {
+            const PeelLds t = make_peel_lds(cd, fused, w, true);
+            if (t.total > kLdsMax) break;
+            const int waves = std::min(32, (kLdsMax / t.total) * w);
+            if (waves > bestg) { bestg = waves; wg = w; Lg = t; }
+        }
+        const bool deep = nframes >= (int64_t)3 * best * sm_count;
+        // measured: (4080,3060) 7 -> 11 frames per CU: -18 %, (4000,2000) 5 -> 8: -15 %, (2040,1530) 16 -> 21: +12 % (slower)
+        if (!lds_tables || kn.peel_gt == 1 || (deep && bestg * 20 >= best * 29)) { s.gt = true; s.wpb = wg; s.lds = Lg; }
     }
-#undef LDPC_PEEL_CASE
-    return hipErrorInvalidValue;
+    s.per_cu = std::min(32, (kLdsMax / s.lds.total) * s.wpb);
+    return s;
 }
 
-static const int kLdsMax = 160 * 1024;
+// `profiled`: name the instantiation and bracket the launch for the profile (the pattern-only run does neither)
+template <bool FUSED, bool GT = false>
+static int launch_peel_t(ldpc_amd_ctx *ctx, const PeelArgs &a, int wpb, bool profiled)
+{
+    const dim3 g((unsigned)((a.nframes + wpb - 1) / wpb)), b((unsigned)(wpb * 64));
+    int rc = LDPC_AMD_OK;
+    const bool found = with_int<8, 14, 16, 24>(a.code.degpad, [&](auto D) {
+        constexpr int kD = decltype(D)::value;
+        if (profiled) prof_name(ctx, LDPC_AMD_PROF_PEEL, "ldpc_peel_kernel", kD, FUSED, GT);
+        hipEvent_t ev = profiled ? prof_begin(ctx) : nullptr;
+        rc = launch_lds(ctx, ldpc_peel_kernel<kD, FUSED, GT>, g, b, (size_t)a.lds.total, ctx->stream, a);
+        if (!rc) prof_end(ctx, LDPC_AMD_PROF_PEEL, ev);
+    });
+    if (!found) LDPC_HIP_TRY(ctx, hipErrorInvalidValue);
+    return rc;
+}
+
+// ---- relaxation plan ----------------------------------------------------------------------------------------
+// Exact time-stamp relaxation instead of the serial per-solve loop (peel_relax.inc) when the keys fit 16 bits: S = 1 decode
+// (mode 0), the pattern-only runs (mode 1), the packet path's schedules (mode 2).  The encoder's one-sweep chain and
+// everything else keep ldpc_peel_kernel.
+struct RelaxPlan {
+    bool keys_fit = false;   // the relaxation applies to this call ...
+    bool ok = false;         // ... and a frame fits the LDS: it runs
+    int logM = 0;
+    int wpb = 1, per_cu = 0;
+    bool gt = false;
+    RelaxLds lds{};
+};
+
+// LDS plan: per frame its keys / values, solver and order lists (packets: + the level histogram); the code tables once per
+// workgroup (or from global memory).
+static RelaxLds make_relax_lds(const DevCode &cd, int mode, bool gt, int wpb)
+{
+    RelaxLds Lr{};
+    int off = 0;
+    Lr.off16 = off; if (!gt) off += align_up(2 * cd.degpad * cd.mpad, 16);
+    Lr.logc8 = off; if (!gt && mode == 0) off += align_up(cd.degpad * cd.mpad, 16);
+    Lr.lg = off; off += 256;
+    Lr.ex = off; off += 512;
+    Lr.wave0 = off;
+    int w = 0;
+    Lr.key = w; w += align_up(2 * (cd.n + 1), 16);
+    Lr.fire = w; w += align_up(2 * cd.mpad, 16);
+    Lr.order = w; w += align_up(2 * cd.mpad, 16);
+    // (mode 2: the per-sweep counts of the time sort live at the start of the level histogram, which is not in use yet then --
+    // with them apart the (2040,1530) frame state is 9472 bytes and only 15 frames fit a CU: a 4096-frame batch needs 16)
+    Lr.cnt = w; if (mode != 2) w += 256;
+    Lr.hist = w; if (mode == 2) w += align_up(std::max(4 * (cd.m + 2), 256), 16);
+    Lr.dep = w; if (mode == 2) w += align_up(cd.mpad, 16);
+    Lr.sinv = w; if (mode == 2) w += align_up(cd.mpad, 16);
+    Lr.wave_stride = w;
+    Lr.total = off + wpb * w;
+    return Lr;
+}
+
+// the frames per workgroup that put the most frames on a CU -> frames per CU (0: not even one frame fits)
+static int best_relax_lds(const Knobs &kn, const DevCode &cd, int mode, bool gt, int &w_best, RelaxLds &L_best)
+{
+    int best_f = 0, best_score = 0;
+    const int wcap = kn.peel_wpb > 0 ? std::min(16, kn.peel_wpb) : 16;
+    for (int w = 1; w <= wcap; w++) {
+        const RelaxLds t = make_relax_lds(cd, mode, gt, w);
+        if (t.total > kLdsMax) break;
+        const int wgs = kLdsMax / t.total;
+        const int frames = kn.peel_wpb > 0 ? w : std::min(32, wgs * w);
+        // without tables to stage, two (or more) smaller workgroups per CU beat one large one holding a frame more
+        // ((4080,3060), 65536 frames: 6 x 2 frames 2.20 ms, 13 x 1 2.30 ms): a tenth of a bonus
+        const int score = frames * ((gt && wgs >= 2 && kn.peel_wpb <= 0) ? 11 : 10);
+        if (score >= best_score) { best_score = score; best_f = frames; w_best = w; L_best = t; }
+    }
+    return best_f;
+}
+
+// Frames per CU = workgroups per CU x wavefronts per workgroup; the tables in LDS for short batches (a single round is latency
+// bound), in global memory when the batch is deep and that puts >= 1.3x more frames on a CU (measured: (2040,1530) 59 -> 70 M
+// frames/s, (4080,3060) 23 -> 27 M on 65536 frames; 4096 frames: 53 M with the LDS copy, 34 M without).
+static RelaxPlan plan_relax(const Knobs &kn, const DevCode &cd, int mode, bool have_flags, int in_rows, int max_sweeps, int64_t nframes,
+                            int sm_count)
+{
+    RelaxPlan r;
+    while ((1 << r.logM) < cd.mpad) r.logM++;
+    r.keys_fit = kn.peel_relax != 0 && have_flags && in_rows == cd.n && cd.degpad <= 16 && cd.n <= 32767 && max_sweeps <= 62 &&
+                 ((long)(max_sweeps + 1) << r.logM) <= 65535;
+    if (!r.keys_fit) return r;
+    int w_l = 1, w_g = 1;
+    RelaxLds L_l{}, L_g{};
+    const int f_l = best_relax_lds(kn, cd, mode, false, w_l, L_l), f_g = best_relax_lds(kn, cd, mode, true, w_g, L_g);
+    if (f_l <= 0 && f_g <= 0) return r;
+    const bool deep = nframes >= (int64_t)3 * std::max(f_l, 1) * sm_count;
+    r.gt = kn.peel_gt == 1 || f_l == 0 || (kn.peel_gt != 0 && deep && f_g * 10 >= f_l * 13);
+    r.wpb = r.gt ? w_g : w_l;
+    r.per_cu = r.gt ? f_g : f_l;
+    r.lds = r.gt ? L_g : L_l;
+    r.ok = true;
+    return r;
+}
+
+// pa: the call's PeelArgs (outputs, residual list, and in mode 2 the schedule arrays); pull / lists (mode 2): the per-step records
+// of the paired-level schedules and the steps' column lists in schedule order, both read by the packet kernel's set-up
+template <int MODE>
+static int launch_relax(ldpc_amd_ctx *ctx, const RelaxPlan &rp, const DecodeArgs &d, const PeelArgs &pa, uint32_t *pull, uint32_t *lists)
+{
+    const DevCode &cd = d.code;
+    RelaxArgs ra{};
+    ra.n = cd.n; ra.k = cd.k; ra.m = cd.m; ra.mpad = cd.mpad; ra.logM = rp.logM;
+    ra.rx_off = cd.rx_off; ra.ell_logc = cd.rx_logc; ra.ell_coef = cd.ell_coef;
+    ra.nframes = d.nframes; ra.sym = d.sym; ra.erased = d.erased; ra.max_sweeps = d.max_sweeps; ra.do_ml = MODE == 1 ? 0 : d.do_ml;
+    ra.out = d.out; ra.sweeps = d.sweeps; ra.residual = d.residual; ra.status = d.status; ra.residual_sys = pa.residual_sys; ra.erased_out = d.erased_out;
+    ra.ml_list = pa.ml_list; ra.ml_state = pa.ml_state; ra.err = ctx->dev_err_host;
+    ra.sched_hdr = pa.sched_hdr; ra.sched_steps = pa.sched_steps; ra.sched_lvlend = pa.sched_lvlend; ra.sched_invc = pa.sched_invc;
+    ra.big_list = pa.big_list; ra.tcap = pa.tcap;
+    ra.sched_pull = pull; ra.pairs = (MODE == 2 && pull) ? 1 : 0;
+    ra.sched_lists = MODE == 2 ? lists : nullptr; ra.cell = cd.cell; ra.cdw = cd.maxcoldeg; ra.cdw_shift = cd.cdw_shift;
+    ra.lds = rp.lds;
+    const dim3 g((unsigned)((d.nframes + rp.wpb - 1) / rp.wpb)), b((unsigned)(rp.wpb * 64));
+    int rc = LDPC_AMD_OK;
+    const bool found = with_int<8, 14, 16>(cd.degpad, [&](auto D) {
+        rc = with_bool(rp.gt, [&](auto G) {
+            constexpr int kD = decltype(D)::value;
+            constexpr bool kG = decltype(G)::value;
+            prof_name(ctx, LDPC_AMD_PROF_PEEL, "ldpc_peel_relax_kernel", kD, kG, MODE);
+            hipEvent_t ev = prof_begin(ctx);
+            const int rcl = launch_lds(ctx, ldpc_peel_relax_kernel<kD, kG, MODE>, g, b, (size_t)ra.lds.total, ctx->stream, ra);
+            if (!rcl) prof_end(ctx, LDPC_AMD_PROF_PEEL, ev);
+            return rcl;
+        });
+    });
+    if (!found) LDPC_HIP_TRY(ctx, hipErrorInvalidValue);   // (plan_relax: the pad is at most 16)
+    return rc;
+}
 
 // ---- scatter kernel launch plan ---------------------------------------------------------------------------
 struct ScatterPlan {
@@ -1953,14 +2146,23 @@ struct ScatterPlan {
     int soc_bytes = 0;
 };
 
-static int scatter_tail_bytes(const DevCode &cd, ScatterPlan &p, bool pin = false, bool pin_list = false)
+// enc_levels > 0: the encoder's static schedule of that many levels (or groups) -- as many level offsets as it has, the row kinds
+// (u8 [n]) and then the source-row list (u16 [k]) in one array, and neither the check -> slot table nor the packets-in words
+// (their offsets are left as they are: unused in static mode)
+static int scatter_tail_bytes(const DevCode &cd, ScatterPlan &p, bool pin = false, bool pin_list = false, int enc_levels = 0)
 {
     int off = 0;
     p.o_tgt = off; off += align_up(2 * cd.m, 16);
     p.o_invc = off; off += align_up(cd.m, 16);
-    p.o_lvl = off; off += align_up(2 * (cd.m + 2), 16);
+    p.o_lvl = off; off += align_up(2 * ((enc_levels > 0 ? enc_levels : cd.m) + 2), 16);
     p.o_ctr = off; off += 288;  // row-batch counter of the streaming phase, received-row count, bins of the sorted list / window counts
     p.o_mt = off;               // (the multiply tables start the LDS: counted by scatter_lds_bytes, not here)
+    if (enc_levels > 0) {
+        p.soc_bytes = align_up(2 * cd.k, 16) >= cd.n ? align_up(2 * cd.k, 16) : align_up(cd.n, 16);
+        p.o_soc = off; off += p.soc_bytes;
+        p.o_chk = off;
+        return off;
+    }
     p.o_soc = off; off += align_up((pin ? 4 : 2) * cd.n, 16);  // row kinds (u8), later the list of received rows (u16); packets-in decoder: row-source words (u32)
     p.soc_bytes = align_up(2 * cd.n, 16);
     p.o_chk = off; off += align_up(2 * (cd.m + 2), 16);  // check -> slot
@@ -2002,6 +2204,58 @@ static ScatterPlan plan_scatter(const Knobs &kn, const DevCode &cd, int S, bool 
     return p;
 }
 
+// ---- the encoder's scatter plan -----------------------------------------------------------------------------
+struct EncodePlan {
+    ScatterPlan plan;      // lpr == 0: no scatter form, the gather kernel encodes
+    bool grouped = false;  // the grouped static schedule (levels collapsed offline)
+    int clist = 0;         // the compact lists of the parity symbols for the level phase
+};
+
+// allow_group = false: the plain schedule even where the code has a grouped one (ENC_GROUP = 0, and the re-plan below)
+static EncodePlan plan_encode(const Knobs &kn, const DevCode &cd, int S, bool allow_group)
+{
+    EncodePlan e;
+    ScatterPlan &plan = e.plan;
+    plan = plan_scatter(kn, cd, S);
+    if (plan.lpr <= 0) return e;
+    plan.two_tier = false; plan.tcap = cd.m; plan.lds1 = plan.lds2;
+    // grouped static schedule: used when the code has one and its lists fit the LDS plan below
+    e.grouped = allow_group && cd.encg_nlevels > 0;
+    const int nlev_plan = e.grouped ? cd.encg_nlevels : cd.enc_nlevels;
+    const int gent2 = (cd.encg_ent_n + 7) & ~7;
+    const int need_g = 3 * gent2 + 2 * ((cd.m + 8) & ~7) + ((cd.m + 15) & ~15);
+    // The encoder needs all m accumulators (every check is a step), which at 256-byte row pieces fills the LDS with
+    // ONE workgroup per CU.  With 128-byte pieces and the tables the static schedule does not need left out (check ->
+    // slot table, received-row list) two workgroups fit, and one streams while the other runs its 27 levels.
+    if (plan.lpr == 16 && kn.enc_b == 128 && ((S % 128) == 0 || symbol_len_words(S))) {   // (word form: the last 128-byte piece overlaps)
+        ScatterPlan q = plan;
+        const int tail = scatter_tail_bytes(cd, q, false, false, nlev_plan);   // (the tables sit in front of the accumulators: added below)
+        if (8192 + cd.m * 128 + tail <= kLdsMax / 2) {
+            q.lpr = 8; q.nslices = (S + 127) / 128; q.lds1 = q.lds2 = 8192 + cd.m * 128 + tail;
+            q.two_tier = true;    // (only selects the 8-waves-per-SIMD instantiation; tcap = m: no frame goes to tier 2)
+            plan = q;
+        }
+    }
+    // the compact lists of the parity symbols for the level phase: over the row tables (dead by then), which end the layout --
+    // the allocation grows by what they need beyond those tables when that still fits
+    const int soc_off = 8192 + align_up(cd.m * 16 * plan.lpr, 16) + plan.o_soc;
+    const int limit = (plan.two_tier && plan.lpr == 8) ? kLdsMax / 2 : kLdsMax;
+    if (e.grouped) {
+        if (soc_off + need_g <= limit) plan.lds1 = plan.lds2 = std::max(plan.lds1, soc_off + need_g);
+        // the lists did not fit: the level table of the plan above was sized for the groups, the plain schedule has more levels
+        else if (nlev_plan != cd.enc_nlevels) return plan_encode(kn, cd, S, false);
+        else e.grouped = false;
+    }
+    if (!e.grouped && kn.enc_clist && cd.enc_lst_n > 0) {
+        const int need = 4 * cd.enc_lst_n + align_up(2 * (cd.m + 1), 16);
+        if (soc_off + need <= limit) {
+            e.clist = 1;
+            plan.lds1 = plan.lds2 = std::max(plan.lds1, soc_off + need);
+        }
+    }
+    return e;
+}
+
 static void scatter_set_lds(ScatterArgs &sa, const ScatterPlan &p, int nacc)
 {
     // [0, 8192) multiply tables | [8192, ...) accumulators | small tables   (kMtOff / kAccOff of scatter_frame)
@@ -2013,10 +2267,124 @@ static void scatter_set_lds(ScatterArgs &sa, const ScatterPlan &p, int nacc)
     sa.lds_soc_bytes = p.soc_bytes;
 }
 
+template <int LPR>
+constexpr int kScatterThreads = (LPR >= 8) ? 1024 : (LPR >= 2 ? 512 : 256);
+
+// NT and the waves per SIMD the kernel is compiled for (8 where two workgroups share a CU) as template arguments
+template <class F>
+static int with_nt_wpe(bool nt, bool two_tier, F &&f)
+{
+    return with_bool(nt, [&](auto NT) {
+        return with_bool(two_tier, [&](auto T2) { return f(NT, std::integral_constant<int, decltype(T2)::value ? 8 : 4>{}); });
+    });
+}
+
+// Encoder: the persistent form (ENC_PERSIST; not with ENC_LIST, whose row list lives where the kept lists do).
+// Instantiated for the shipped R at LPR >= 8 only (the SCATTER_R variants keep the one-item kernel: a third of the instantiations);
+// LPR < 8 -- S below 128 -- has it only for the fused sender's word form: one instantiation each, so that a word-sized datagram
+// shorter than 128 bytes still goes out in one kernel.
+template <int LPR, int R>
+static int launch_scatter_persistent(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterArgs sa, unsigned items, bool nt)
+{
+    constexpr bool kPersistAll = LPR >= 8 && R == 2;
+    constexpr int THREADS = kScatterThreads<LPR>;
+    const int per_cu = std::max(1, std::min(p.two_tier ? 2 : 1, kLdsMax / std::max(1, p.lds1)));
+    const dim3 gp((unsigned)std::min<int64_t>((int64_t)items, (int64_t)ctx->sm_count * per_cu));
+    // the item counter: self-resetting, so zeroed once (synchronously: whatever stream the context is moved to later sees it);
+    // consecutive launches take consecutive counters of a ring, so two encodes in flight (a caller that changed the context's
+    // stream without waiting) do not share one
+    constexpr int kEncCtrs = 64;
+    if (!ctx->encctr.p) {
+        int rc_e;
+        if ((rc_e = scratch_reserve(ctx, ctx->encctr, (size_t)kEncCtrs * 64))) return rc_e;
+        LDPC_HIP_TRY(ctx, hipMemset(ctx->encctr.p, 0, (size_t)kEncCtrs * 64));
+    }
+    sa.big_list = (int32_t *)ctx->encctr.p + 16 * (ctx->enc_launches++ % kEncCtrs);
+    if constexpr (!kPersistAll) {   // (the word form: NT, and one workgroup per CU)
+        prof_name(ctx, LDPC_AMD_PROF_APPLY, "ldpc_scatter_static_pkt_kernel", LPR, R, true, 4);
+        return launch_lds(ctx, ldpc_scatter_static_pkt_kernel<LPR, R, true, 4>, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);
+    } else {
+        return with_nt_wpe(nt, p.two_tier, [&](auto NT, auto WPE) {
+            constexpr bool kNT = decltype(NT)::value;
+            constexpr int kWPE = decltype(WPE)::value;
+            if (sa.pkt_out) {   // the fused sender: packets out
+                prof_name(ctx, LDPC_AMD_PROF_APPLY, "ldpc_scatter_static_pkt_kernel", LPR, R, kNT, kWPE);
+                return launch_lds(ctx, ldpc_scatter_static_pkt_kernel<LPR, R, kNT, kWPE>, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);
+            }
+            prof_name(ctx, LDPC_AMD_PROF_APPLY, "ldpc_scatter_static_kernel", LPR, R, kNT, kWPE);
+            return launch_lds(ctx, ldpc_scatter_static_kernel<LPR, R, kNT, kWPE>, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);
+        });
+    }
+}
+
+// Tier 2: the frames tier 1 listed (more than tcap steps), all m accumulators, one workgroup per CU
+template <int LPR, int R>
+static int launch_scatter_tier2(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterArgs sa, int32_t *big_list, bool nt, bool ip, bool pin)
+{
+    constexpr int THREADS = kScatterThreads<LPR>;
+    const Knobs &kn = ctx->knobs;
+    sa.tcap = sa.code.m; sa.nslots = sa.code.m; sa.big_list = big_list;
+    scatter_set_lds(sa, p, sa.code.m);
+    {   // pieces of a frame per work item (SCATTER_T2P; the list modes of the stream rebuild their row list per piece: one piece)
+        int tp = kn.scatter_dyn <= 1 ? std::max(1, kn.scatter_t2p) : 1;
+        while (tp > 1 && (sa.nslices % tp) != 0) tp >>= 1;
+        sa.t2_pieces = tp; sa.t2_force = kn.scatter_t2p_force;
+    }
+    const dim3 g2((unsigned)std::min<int64_t>(sa.nframes * sa.nslices, ctx->sm_count));
+    hipEvent_t ev2 = prof_begin(ctx, 2);
+    // SCATTER_T2B = 128: tier 2 with 128-byte pieces -- all m accumulators then take half a CU's LDS, so TWO tier-2 workgroups
+    // share a CU (one streams while the other sets up / runs its levels), at twice the per-byte instruction count of an edge turn
+    const int tail_b = p.lds2 - sa.code.m * 16 * p.lpr;   // tables + small arrays of the plan
+    // (not the packets-in form: with its words in LDS m 128-byte accumulators no longer fit half a CU for the built-in codes; SCATTER_T2B is ignored there)
+    const bool t2_128 = !pin && LPR == 16 && kn.scatter_t2b == 128 && (sa.S % 128) == 0 && sa.code.m * 128 + tail_b <= kLdsMax / 2;
+    int rc;
+    if (t2_128) {
+        ScatterPlan p2 = p;
+        p2.lpr = 8; p2.nslices = sa.S / 128; p2.lds2 = sa.code.m * 128 + tail_b;
+        sa.nslices = p2.nslices; sa.piece_last = sa.S - 128;
+        while (sa.t2_pieces > 1 && (sa.nslices % sa.t2_pieces) != 0) sa.t2_pieces >>= 1;
+        scatter_set_lds(sa, p2, sa.code.m);
+        const dim3 g3((unsigned)std::min<int64_t>(sa.nframes * sa.nslices, (int64_t)ctx->sm_count * 2));
+        rc = with_bool(nt, [&](auto NT) { return with_bool(ip, [&](auto IP) {
+            constexpr bool kNT = decltype(NT)::value, kIP = decltype(IP)::value;
+            prof_name(ctx, LDPC_AMD_PROF_APPLY_TIER2, "ldpc_scatter_big_kernel", 8, 2, kNT, kIP, 8);
+            return launch_lds(ctx, ldpc_scatter_big_kernel<8, 2, kNT, kIP, 8>, g3, dim3(1024), (size_t)p2.lds2, ctx->stream, sa);
+        }); });
+    } else {
+        // tier 2 runs one workgroup per CU (4 waves per SIMD, 128 VGPRs each): more row pieces in flight per lane group make up
+        // for part of the missing occupancy.  Round 2: two / three / four pieces 4.50 / 4.28 / 4.24 ms on cfg 3 (four shipped, 160 B
+        // of spills per lane); round 3, with six vector instructions fewer per edge turn: 4.01 / 3.95 / 4.08 -- three ship (no spills).
+        // (SCATTER_R2 = 3 / 4 exist at 256-byte pieces only; elsewhere tier 2 keeps tier 1's R)
+        auto with_rows = [&](auto &&f) {
+            if constexpr (LPR == 16) {
+                if (kn.scatter_r2 == 4) return f(std::integral_constant<int, 4>{});
+                if (kn.scatter_r2 == 3) return f(std::integral_constant<int, 3>{});
+            }
+            return f(std::integral_constant<int, R>{});
+        };
+        rc = with_rows([&](auto RV) { return with_bool(nt, [&](auto NT) {
+            constexpr int kR = decltype(RV)::value;
+            constexpr bool kNT = decltype(NT)::value;
+            if (pin) {
+                prof_name(ctx, LDPC_AMD_PROF_APPLY_TIER2, "ldpc_scatter_pktin_big_kernel", LPR, kR, kNT);
+                return launch_lds(ctx, ldpc_scatter_pktin_big_kernel<LPR, kR, kNT>, g2, dim3(THREADS), (size_t)p.lds2, ctx->stream, sa);
+            }
+            return with_bool(ip, [&](auto IP) {
+                constexpr bool kIP = decltype(IP)::value;
+                prof_name(ctx, LDPC_AMD_PROF_APPLY_TIER2, "ldpc_scatter_big_kernel", LPR, kR, kNT, kIP);
+                return launch_lds(ctx, ldpc_scatter_big_kernel<LPR, kR, kNT, kIP>, g2, dim3(THREADS), (size_t)p.lds2, ctx->stream, sa);
+            });
+        }); });
+    }
+    if (rc) return rc;
+    prof_end(ctx, LDPC_AMD_PROF_APPLY_TIER2, ev2);
+    return LDPC_AMD_OK;
+}
+
 template <int LPR, int R>
 static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterArgs sa, int32_t *big_list)
 {
-    constexpr int THREADS = (LPR >= 8) ? 1024 : (LPR >= 2 ? 512 : 256);
+    constexpr int THREADS = kScatterThreads<LPR>;
     const Knobs &kn = ctx->knobs;
     // word form (S no multiple of 16): rows are only 4-byte aligned, so the four-dword access form -- the non-temporal instantiations --
     // runs whatever SCATTER_NT says; the kernels are the ones a multiple of 16 runs, with the last piece moved back (ScatterArgs::piece_last)
@@ -2029,158 +2397,30 @@ static int launch_scatter_lpr(ldpc_amd_ctx *ctx, const ScatterPlan &p, ScatterAr
     // tier 1
     sa.tcap = p.tcap; sa.nslots = p.tcap; sa.big_list = nullptr;
     scatter_set_lds(sa, p, p.tcap);
-    // (LPR < 8 -- S below 128 -- has a persistent form only for the fused sender's word form: one instantiation each, so that a word-sized
-    // datagram shorter than 128 bytes still goes out in one kernel)
     constexpr bool kPersistAll = LPR >= 8 && R == 2;
-    if constexpr (kPersistAll || LPR < 8) {   // (the shipped R; the SCATTER_R variants keep the one-item kernel: a third of the instantiations)
-        // Encoder: the persistent form (ENC_PERSIST; not with ENC_LIST, whose row list lives where the kept lists do)
+    if constexpr (kPersistAll || LPR < 8) {
         if (sa.static_sched && kn.enc_persist != 0 && !sa.enc_list && !sa.inplace && (sa.enc_group || sa.enc_clist) &&
-            (kPersistAll || (words && sa.pkt_out))) {
-            const int per_cu = std::max(1, std::min(p.two_tier ? 2 : 1, kLdsMax / std::max(1, p.lds1)));
-            const dim3 gp((unsigned)std::min<int64_t>((int64_t)grid.x, (int64_t)ctx->sm_count * per_cu));
-            // the item counter: self-resetting, so zeroed once (synchronously: whatever stream the context is moved to later sees it);
-            // consecutive launches take consecutive counters of a ring, so two encodes in flight (a caller that changed the context's
-            // stream without waiting) do not share one
-            constexpr int kEncCtrs = 64;
-            if (!ctx->encctr.p) {
-                int rc_e;
-                if ((rc_e = scratch_reserve(ctx, ctx->encctr, (size_t)kEncCtrs * 64))) return rc_e;
-                LDPC_HIP_TRY(ctx, hipMemset(ctx->encctr.p, 0, (size_t)kEncCtrs * 64));
-            }
-            sa.big_list = (int32_t *)ctx->encctr.p + 16 * (ctx->enc_launches++ % kEncCtrs);
-            char nm[96];
-            snprintf(nm, sizeof(nm), "ldpc_scatter_static%s_kernel<%d, %d, %s, %d>", sa.pkt_out ? "_pkt" : "", LPR, R, nt ? "true" : "false", p.two_tier ? 8 : 4);
-            ctx->prof_names[LDPC_AMD_PROF_APPLY] = nm;
-#define LDPC_SCATTER_PS(KERNEL, NTV, WPE)                                                                    \
-    {                                                                                                        \
-        auto kfn = KERNEL<LPR, R, NTV, WPE>;                                                                 \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
-        hipLaunchKernelGGL(kfn, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);                         \
-    }
-            if constexpr (!kPersistAll) {
-                LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, true, 4)
-            } else
-            if (sa.pkt_out) {   // the fused sender: packets out
-                if (p.two_tier) { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, true, 8) else LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, false, 8) }
-                else { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, true, 4) else LDPC_SCATTER_PS(ldpc_scatter_static_pkt_kernel, false, 4) }
-            } else
-            if (p.two_tier) { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_kernel, true, 8) else LDPC_SCATTER_PS(ldpc_scatter_static_kernel, false, 8) }
-            else { if (nt) LDPC_SCATTER_PS(ldpc_scatter_static_kernel, true, 4) else LDPC_SCATTER_PS(ldpc_scatter_static_kernel, false, 4) }
-#undef LDPC_SCATTER_PS
-            LDPC_HIP_TRY(ctx, hipGetLastError());
-            return LDPC_AMD_OK;
-        }
+            (kPersistAll || (words && sa.pkt_out)))
+            return launch_scatter_persistent<LPR, R>(ctx, p, sa, grid.x, nt);
     }
     if (sa.pkt_out) return kEncodeNotFused;   // only the persistent encoder has a packet-output form: nothing was launched
-#define LDPC_SCATTER_T1(NTV, WPE, IPV)                                                                         \
-    {                                                                                                        \
-        auto kfn = ldpc_scatter_kernel<LPR, R, NTV, WPE, IPV>;                                                    \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
-        hipLaunchKernelGGL(kfn, grid, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);                       \
-    }
     const bool ip = sa.inplace != 0;
     const bool pin = sa.pin_src != nullptr;   // the fused receiver: rows from packets (out of place only: launch_decode checks)
-#define LDPC_SCATTER_T1P(NTV, WPE)                                                                           \
-    {                                                                                                        \
-        auto kfn = ldpc_scatter_pktin_kernel<LPR, R, NTV, WPE>;                                              \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
-        hipLaunchKernelGGL(kfn, grid, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);                       \
-    }
-    {
-        char nm[96];
-        if (pin) snprintf(nm, sizeof(nm), "ldpc_scatter_pktin_kernel<%d, %d, %s, %d>", LPR, R, nt ? "true" : "false", p.two_tier ? 8 : 4);
-        else snprintf(nm, sizeof(nm), "ldpc_scatter_kernel<%d, %d, %s, %d, %s>", LPR, R, nt ? "true" : "false", p.two_tier ? 8 : 4,
-                 ip ? "true" : "false");
-        ctx->prof_names[LDPC_AMD_PROF_APPLY] = nm;
-    }
-    if (pin) {
-        if (p.two_tier) { if (nt) LDPC_SCATTER_T1P(true, 8) else LDPC_SCATTER_T1P(false, 8) }
-        else { if (nt) LDPC_SCATTER_T1P(true, 4) else LDPC_SCATTER_T1P(false, 4) }
-    } else
-    if (p.two_tier) {
-        if (ip) { if (nt) LDPC_SCATTER_T1(true, 8, true) else LDPC_SCATTER_T1(false, 8, true) }
-        else { if (nt) LDPC_SCATTER_T1(true, 8, false) else LDPC_SCATTER_T1(false, 8, false) }
-    } else {
-        if (ip) { if (nt) LDPC_SCATTER_T1(true, 4, true) else LDPC_SCATTER_T1(false, 4, true) }
-        else { if (nt) LDPC_SCATTER_T1(true, 4, false) else LDPC_SCATTER_T1(false, 4, false) }
-    }
-#undef LDPC_SCATTER_T1
-#undef LDPC_SCATTER_T1P
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    if (p.two_tier && big_list && !(sa.dbg & 32768)) {
-        sa.tcap = sa.code.m; sa.nslots = sa.code.m; sa.big_list = big_list;
-        scatter_set_lds(sa, p, sa.code.m);
-        {   // pieces of a frame per work item (SCATTER_T2P; the list modes of the stream rebuild their row list per piece: one piece)
-            int tp = kn.scatter_dyn <= 1 ? std::max(1, kn.scatter_t2p) : 1;
-            while (tp > 1 && (sa.nslices % tp) != 0) tp >>= 1;
-            sa.t2_pieces = tp; sa.t2_force = kn.scatter_t2p_force;
+    int rc = with_nt_wpe(nt, p.two_tier, [&](auto NT, auto WPE) {
+        constexpr bool kNT = decltype(NT)::value;
+        constexpr int kWPE = decltype(WPE)::value;
+        if (pin) {
+            prof_name(ctx, LDPC_AMD_PROF_APPLY, "ldpc_scatter_pktin_kernel", LPR, R, kNT, kWPE);
+            return launch_lds(ctx, ldpc_scatter_pktin_kernel<LPR, R, kNT, kWPE>, grid, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);
         }
-        const dim3 g2((unsigned)std::min<int64_t>(sa.nframes * sa.nslices, ctx->sm_count));
-        // tier 2 runs one workgroup per CU (4 waves per SIMD, 128 VGPRs each): more row pieces in flight per lane group make up
-        // for part of the missing occupancy.  Round 2: two / three / four pieces 4.50 / 4.28 / 4.24 ms on cfg 3 (four shipped, 160 B
-        // of spills per lane); round 3, with six vector instructions fewer per edge turn: 4.01 / 3.95 / 4.08 -- three ship (no spills)
-        const int r2 = LPR == 16 ? kn.scatter_r2 : 0;
-#define LDPC_SCATTER_T2_R(RV, NTV, IPV)                                                                      \
-    {                                                                                                        \
-        auto kfn = ldpc_scatter_big_kernel<LPR, RV, NTV, IPV>;                                               \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
-        hipLaunchKernelGGL(kfn, g2, dim3(THREADS), (size_t)p.lds2, ctx->stream, sa);                         \
-    }
-#define LDPC_SCATTER_T2(NTV, IPV)                                                                            \
-    if (r2 == 4) LDPC_SCATTER_T2_R((LPR == 16 ? 4 : R), NTV, IPV)                                            \
-    else if (r2 == 3) LDPC_SCATTER_T2_R((LPR == 16 ? 3 : R), NTV, IPV)                                       \
-    else LDPC_SCATTER_T2_R(R, NTV, IPV)
-#define LDPC_SCATTER_T2P_R(RV, NTV)                                                                          \
-    {                                                                                                        \
-        auto kfn = ldpc_scatter_pktin_big_kernel<LPR, RV, NTV>;                                              \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
-        hipLaunchKernelGGL(kfn, g2, dim3(THREADS), (size_t)p.lds2, ctx->stream, sa);                         \
-    }
-#define LDPC_SCATTER_T2P(NTV)                                                                                \
-    if (r2 == 4) LDPC_SCATTER_T2P_R((LPR == 16 ? 4 : R), NTV)                                                \
-    else if (r2 == 3) LDPC_SCATTER_T2P_R((LPR == 16 ? 3 : R), NTV)                                           \
-    else LDPC_SCATTER_T2P_R(R, NTV)
-        {
-            char nm[96];
-            if (pin) snprintf(nm, sizeof(nm), "ldpc_scatter_pktin_big_kernel<%d, %d, %s>", LPR, (LPR == 16 && (r2 == 3 || r2 == 4)) ? r2 : R, nt ? "true" : "false");
-            else snprintf(nm, sizeof(nm), "ldpc_scatter_big_kernel<%d, %d, %s, %s>", LPR, (LPR == 16 && (r2 == 3 || r2 == 4)) ? r2 : R, nt ? "true" : "false",
-                     ip ? "true" : "false");
-            ctx->prof_names[LDPC_AMD_PROF_APPLY_TIER2] = nm;
-        }
-        hipEvent_t ev2 = prof_begin(ctx, 2);
-        // SCATTER_T2B = 128: tier 2 with 128-byte pieces -- all m accumulators then take half a CU's LDS, so TWO tier-2 workgroups
-        // share a CU (one streams while the other sets up / runs its levels), at twice the per-byte instruction count of an edge turn
-        const int tail_b = p.lds2 - sa.code.m * 16 * p.lpr;   // tables + small arrays of the plan
-        // (not the packets-in form: with its words in LDS m 128-byte accumulators no longer fit half a CU for the built-in codes; SCATTER_T2B is ignored there)
-        const bool t2_128 = !pin && LPR == 16 && kn.scatter_t2b == 128 && (sa.S % 128) == 0 && sa.code.m * 128 + tail_b <= kLdsMax / 2;
-        if (t2_128) {
-            ScatterPlan p2 = p;
-            p2.lpr = 8; p2.nslices = sa.S / 128; p2.lds2 = sa.code.m * 128 + tail_b;
-            sa.nslices = p2.nslices; sa.piece_last = sa.S - 128;
-            while (sa.t2_pieces > 1 && (sa.nslices % sa.t2_pieces) != 0) sa.t2_pieces >>= 1;
-            scatter_set_lds(sa, p2, sa.code.m);
-            const dim3 g3((unsigned)std::min<int64_t>(sa.nframes * sa.nslices, (int64_t)ctx->sm_count * 2));
-            ctx->prof_names[LDPC_AMD_PROF_APPLY_TIER2] = std::string("ldpc_scatter_big_kernel<8, 2, ") + (nt ? "true" : "false") + ", " + (ip ? "true" : "false") + ", 8>";
-#define LDPC_SCATTER_T2B(NTV, IPV)                                                                           \
-    {                                                                                                        \
-        auto kfn = ldpc_scatter_big_kernel<8, 2, NTV, IPV, 8>;                                               \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
-        hipLaunchKernelGGL(kfn, g3, dim3(1024), (size_t)p2.lds2, ctx->stream, sa);                           \
-    }
-            if (ip) { if (nt) LDPC_SCATTER_T2B(true, true) else LDPC_SCATTER_T2B(false, true) }
-            else { if (nt) LDPC_SCATTER_T2B(true, false) else LDPC_SCATTER_T2B(false, false) }
-#undef LDPC_SCATTER_T2B
-        } else
-        if (pin) { if (nt) LDPC_SCATTER_T2P(true) else LDPC_SCATTER_T2P(false) }
-        else if (ip) { if (nt) LDPC_SCATTER_T2(true, true) else LDPC_SCATTER_T2(false, true) }
-        else { if (nt) LDPC_SCATTER_T2(true, false) else LDPC_SCATTER_T2(false, false) }
-#undef LDPC_SCATTER_T2_R
-#undef LDPC_SCATTER_T2
-#undef LDPC_SCATTER_T2P_R
-#undef LDPC_SCATTER_T2P
-        prof_end(ctx, LDPC_AMD_PROF_APPLY_TIER2, ev2);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-    }
+        return with_bool(ip, [&](auto IP) {
+            constexpr bool kIP = decltype(IP)::value;
+            prof_name(ctx, LDPC_AMD_PROF_APPLY, "ldpc_scatter_kernel", LPR, R, kNT, kWPE, kIP);
+            return launch_lds(ctx, ldpc_scatter_kernel<LPR, R, kNT, kWPE, kIP>, grid, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);
+        });
+    });
+    if (rc) return rc;
+    if (p.two_tier && big_list && !(sa.dbg & 32768)) return launch_scatter_tier2<LPR, R>(ctx, p, sa, big_list, nt, ip, pin);
     return LDPC_AMD_OK;
 }
 
@@ -2198,6 +2438,491 @@ static int launch_scatter(ldpc_amd_ctx *ctx, const ScatterPlan &p, const Scatter
     return set_error(ctx, LDPC_AMD_EUNSUP, "scatter: bad plan");
 }
 
+// The gather kernel (LDPC_AMD_APPLY=gather, or a code whose columns are too heavy for the scatter kernel's lists), decode and encode.
+// `profiled`: the decoder's launch, named and bracketed for the profile
+static int launch_apply(ldpc_amd_ctx *ctx, const ApplyArgs &aa, bool words, bool profiled)
+{
+    const size_t lds = (size_t)aa.code.m * 4 + (size_t)(aa.code.m + 2) * 2;
+    if (profiled) ctx->prof_names[LDPC_AMD_PROF_APPLY] = words ? "ldpc_apply_words_kernel" : "ldpc_apply_kernel";
+    hipEvent_t ev = profiled ? prof_begin(ctx) : nullptr;
+    hipLaunchKernelGGL(words ? ldpc_apply_words_kernel : ldpc_apply_kernel, dim3((unsigned)aa.nframes), dim3(512), lds, ctx->stream, aa);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    prof_end(ctx, LDPC_AMD_PROF_APPLY, ev);
+    return LDPC_AMD_OK;
+}
+
+// ---- the ML stage (a2-a4) -------------------------------------------------------------------------------------
+static_assert(kMlHdr == kMlHdrWords && 1 + kMlClasses <= kMlHdrWork2 && kMlHdrPiDone < kMlHdr, "ml_list header: no room for the work counters");
+static_assert(kMlHdrDeferred == kMlHdrWork + 1 && kMlHdrOpsHead == kMlHdrWork + 2 && (kMlHdrOpsHead & 1) == 0 && kMlHdrSolveWork == kMlHdrWork + 4 &&
+              kMlHdrPiWork == kMlHdrWork + 5, "ml_list header: the kernels index MlArgs::work");
+// Its plan: LDS layouts and launch shapes.  `ma` and `pi` hold the offsets and scalars only; MlStage::prepare adds the pointers.
+struct MlPlan {
+    MlArgs ma{};
+    PiArgs pi{};
+    int lds_need = 0;            // != 0: refused, the LDS bytes it would take
+    bool too_many_checks = false;
+    int total = 0;               // dynamic LDS of ldpc_ml_kernel
+    int grid = 0, threads = 0;
+    size_t perA = 0, perR = 0;   // global scratch per workgroup: the matrix, the right-hand sides
+    int solve_b = 0;             // bytes of every row per workgroup of the solve kernel
+    int pi_nw = 0, pi_total = 0; // fast path: wavefronts per workgroup (0: not run), dynamic LDS
+    bool overlap = false;        // fast path and factorisation beside the packet kernel, on the second stream
+};
+
+// fast_path: the context did not just see a batch without residual frames (MlStage::prepare)
+static MlPlan plan_ml(const Knobs &kn, const DevCode &cd, int S, bool fused, bool words, bool use_scatter, bool fast_path, int64_t nf,
+                      int sm_count)
+{
+    MlPlan p;
+    MlArgs &ma = p.ma;
+    ma.S = S;
+    ma.Spad = fused ? 16 : align_up(S, 16);   // (word form: the scratch rows keep 16-byte chunks, the last one partly unused)
+    const int maxrow = align_up(cd.m, 16) + 32;
+    ma.maxrow = maxrow;
+    int off = 0;
+    // rlist[3][m] u32; colmap[n] u16 is only alive while rlist[1..2] are not, and shares their bytes
+    ma.lds_rlist = off; ma.lds_colmap = off + 4 * cd.m;
+    // (packets: the same bytes later hold the per-level histogram, 2 m + 4 words, and the slot map, m halfwords)
+    off += align_up(std::max(std::max(12 * cd.m, 4 * cd.m + 2 * cd.n), 4 * (2 * cd.m + 4) + 2 * cd.m + 16), 16);
+    ma.lds_elist = off; off += align_up(2 * cd.m, 16);
+    ma.lds_colv = off; off += align_up(3 * cd.mpad, 16);
+    ma.lds_perm = off; off += align_up(2 * cd.m + 2, 16);
+    ma.lds_iperm = off; off += align_up(2 * cd.m, 16);
+    ma.lds_orow = off; off += align_up(2 * cd.m, 16);
+    ma.lds_plog = off; off += align_up(cd.m, 16);
+    ma.lds_mt = off; off += 8192;
+    ma.lds_lg = off; off += 256;
+    ma.lds_ex = off; off += 1024;
+    ma.lds_misc = off; off += 128 + 4 * kMlClasses;
+    ma.lds_lvl = off; off += align_up(4 * (cd.m + 2), 16);
+    ma.lds_A = off;
+    if (off > kLdsMax) { p.lds_need = off; return p; }
+    if (cd.m > 4096) { p.too_many_checks = true; return p; }   // 12-bit row fields of the pivot key
+    // ML_PACK = P workgroups per CU (1024 / P threads, 160 KB / P of LDS each): the factorisation is bound by the instructions
+    // all wavefronts of a workgroup issue per column, not by the work in a column, so P small workgroups -- P systems per CU,
+    // their matrices in the global scratch (L2) when they do not fit the LDS share -- issue P times fewer of them per system
+    const int pack = std::max(1, std::min(4, kn.ml_pack));
+    p.total = std::max(off + 256, (kLdsMax / pack) & ~255);
+    if (p.total > kLdsMax) { p.lds_need = p.total; return p; }
+    ma.capA = (p.total - off) & ~15;
+    p.grid = (int)std::min<int64_t>(nf, (int64_t)sm_count * pack);
+    p.threads = kn.ml_threads > 0 ? kn.ml_threads : std::max(256, (1024 / pack) & ~63);
+    p.perA = (size_t)cd.m * maxrow;
+    p.perR = fused ? 0 : (size_t)cd.m * ma.Spad;
+    // packets: the ML kernel factors every residual system on bytes and emits a solve schedule (64-bit ops grouped by
+    // dependency level) into an arena; ldpc_ml_solve_kernel then runs the schedules on LDS-resident row slices.
+    // Frames whose schedule does not fit the arena are solved inside the ML kernel (same bytes, slower).
+    ma.use_solve = (!fused && kn.ml_solve != 0) ? 1 : 0;
+    ma.dbg = kn.ml_dbg;
+    if (ma.use_solve) {
+        int b = kn.ml_solve_b;   // A/B knob
+        if (words) { while (b > 16 && b > S) b >>= 1; }   // (the last piece overlaps: MlSolveArgs::piece_last)
+        else while (b > 16 && (S % b) != 0) b >>= 1;
+        const int tail_sv = align_up(4 * (2 * cd.m + 6), 16) + 8192 + 16 + 4 * kMlClasses;
+        while (b > 16 && cd.m * b + tail_sv > 79 * 1024) b >>= 1;
+        if (cd.m * b + tail_sv > kLdsMax || cd.n > 65535) ma.use_solve = 0;
+        p.solve_b = b;
+    }
+    ma.solve_b = p.solve_b;
+    // Packets: the fast path first (ml_pi.inc: peel on, inactivate, small dense system; a wavefront per frame).  It emits
+    // the schedules of the full-rank frames; ldpc_ml_kernel then factors what it left (rank-deficient frames, rec[6] = 0).
+    if (ma.use_solve && kn.ml_pi != 0 && fast_path) {
+        PiArgs &pi = p.pi;
+        int shared = 8192 + 256 + 1024 + 64;   // multiply tables, log, antilog, size-class counts
+        pi.lds_mt = 0; pi.lds_lg = 8192; pi.lds_ex = 8192 + 256;
+        pi.lds_edges = pi.lds_rowptr = -1;
+        const int rows_bytes = align_up(4 * cd.nnz, 16) + align_up(4 * (cd.m + 1), 16);
+        if (rows_bytes <= 40 * 1024) {   // the code's rows in LDS (every frame walks them a few times); else from global memory
+            pi.lds_edges = shared; pi.lds_rowptr = shared + align_up(4 * cd.nnz, 16);
+            shared += rows_bytes;
+        }
+        int o = 0;
+        pi.o_vinfo = o; o += align_up(2 * cd.n, 16);
+        pi.o_cnt = o; o += align_up(4 * (cd.m + 264), 16);
+        pi.o_lvl = o; o += align_up(4 * cd.m, 16);
+        pi.o_ustate = o; o += align_up(2 * cd.m, 16);
+        pi.o_uvar = o; o += align_up(2 * cd.m, 16);
+        pi.o_stepc = o; o += align_up(2 * cd.m, 16);
+        pi.o_stepi = o; o += align_up(2 * cd.m, 16);
+        pi.o_slvl = o; o += align_up(2 * cd.m, 16);
+        pi.o_sginv = o; o += align_up(cd.m, 16);
+        pi.o_queue = o; o += align_up(2 * cd.m, 16);
+        pi.o_candpiv = o; o += align_up(2 * cd.m, 16);
+        pi.o_inact = o; o += 512;
+        pi.o_sel = o; o += 512;
+        pi.o_sellvl = o; o += 512;
+        pi.o_dlog = o; o += 256;
+        pi.o_misc = o; o += 16 + 512;   // queue tail; the winners of a batch
+        pi.o_av = o;
+        const int budget = std::max(32, std::min(160, kn.ml_pi_lds)) * 1024 - shared;
+        const int av_want = std::min(cd.m * 32, 16 * 1024);
+        p.pi_nw = std::max(1, std::min(std::max(1, std::min(4, kn.ml_pi_waves)), budget / (o + av_want)));
+        const int per_wave = (budget / p.pi_nw) & ~15;
+        if (per_wave >= o + 1024 && cd.maxdeg <= kWave && cd.maxcoldeg <= 16 && cd.m < 0x8000 && cd.n < 0xFFFF) {
+            pi.av_bytes = per_wave - o;
+            pi.lds_wave0 = shared; pi.lds_wave_stride = per_wave;
+            p.pi_total = shared + p.pi_nw * per_wave;
+        } else {
+            p.pi_nw = 0;
+        }
+    }
+    ma.use_pi = p.pi_nw > 0 ? 1 : 0;
+    // The factorisation needs the erasure pattern only: in packet mode (schedules, not payload) it runs on a second stream
+    // beside the packet kernel.  A frame whose schedule does not fit the arena is DEFERRED there (rec[5] = 2, ma.work[1] counts
+    // them) and solved by a second launch behind the packet kernel -- its in-kernel solve reads the payload.
+    // (Only with the fast path: beside the packet kernel the factorisation of EVERY residual frame takes as much from the packet
+    // kernel as it saves -- 6.87 against 6.94 ms on cfg 3 -- while the few frames the fast path leaves disappear behind it.)
+    p.overlap = ma.use_solve && use_scatter && p.pi_nw > 0 && kn.ml_overlap != 0;
+    return p;
+}
+
+// One call's ML stage.  prepare() comes before the packet kernel is launched, because in packet mode the stage's pattern-only part --
+// the fast path and the factorisation of what the fast path leaves, front() -- can run beside the packet kernel (second stream);
+// finish() runs what is left of it behind the packet kernel.
+struct MlStage {
+    ldpc_amd_ctx *ctx;
+    const DecodeArgs &d;
+    bool fused, words;
+    MlPlan p{};
+    MlArgs ma{};
+    PiArgs pi{};
+    void (*kfn)(MlArgs) = nullptr;
+    hipEvent_t ev = nullptr;    // the open LDPC_AMD_PROF_ML bracket
+    bool front_done = false;
+
+    int prepare(bool use_scatter);
+    int fork(hipStream_t &st);
+    int front();
+    int launch_solve(const MlSolveArgs &sv, dim3 grid, size_t lds, bool profiled);
+    int back();
+    int finalize();
+    int finish()
+    {
+        int rc;
+        if (!front_done && (rc = front())) return rc;
+        if ((rc = back())) return rc;
+        return finalize();
+    }
+};
+
+int MlStage::prepare(bool use_scatter)
+{
+    const DevCode &cd = d.code;
+    const Knobs &kn = ctx->knobs;
+    const int64_t nf = d.nframes;
+    int rc;
+    // (A context whose LAST packet batch had no residual frame at all -- its arena demand, back through the pinned host word, was
+    // zero -- skips the fast path's four extra launches for this batch: 23 -> 8.5 us of empty launches per step on a workload
+    // message passing completes.  Whatever does reach the ML stage then is factored exactly; the next batch has the fast path again.)
+    const bool ml_quiet = kn.ml_pi_adaptive && ctx->ml_head_host && ctx->ml_head_valid && *ctx->ml_head_host == 0;
+    p = plan_ml(kn, cd, d.S, fused, words, use_scatter, !ml_quiet, nf, ctx->sm_count);
+    if (p.lds_need) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: LDS need %d bytes", p.lds_need);
+    if (p.too_many_checks) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: more than 4096 checks (%d)", cd.m);
+    ma = p.ma;
+    ma.code = cd;
+    ma.ml_list = (const int32_t *)ctx->mllist.p; ma.ml_state = (const uint8_t *)ctx->mlstate.p; ma.nframes = nf;
+    ma.out = d.out; ma.status = d.status;
+    if ((rc = scratch_reserve(ctx, ctx->mlws, (p.perA + p.perR) * p.grid + 256))) return rc;
+    // The work counters sit in the free tail of the residual list's header (MlHdrWord, internal.h), which decode_chunk zeroes with
+    // that header: one memset per call less (a call is launch-bound at S = 1)
+    int32_t *const hdr = (int32_t *)ctx->mllist.p;
+    ma.work = hdr + kMlHdrWork;
+    ma.work2 = hdr + kMlHdrWork2;
+    ma.nfail = hdr + kMlHdrNfail;
+    ma.work3 = hdr + kMlHdrWork3;
+    ma.wsA = (uint8_t *)ctx->mlws.p + 256;
+    ma.wsR = ma.wsA + p.perA * p.grid;
+    if (ma.use_solve) {
+        // The arena follows DEMAND, not the batch size: 16 MB to start with (2 M words); the words the previous call asked for
+        // come back through a pinned host word (copied behind every call, never waited for), and when they exceeded three quarters of
+        // the arena it grows to twice that demand, at most 1 GB.  A call that overflows is still correct -- the frames
+        // that do not fit are solved inside the ML kernel -- so a steady workload is at full speed from its second or third
+        // batch, and a batch message passing completes pins 16 MB instead of 64 KB per frame.
+        size_t words = std::max<size_t>(ctx->ml_arena_words, (size_t)1 << 21);
+        if (ctx->ml_head_host) {
+            const unsigned long long need = *ctx->ml_head_host;   // demand of an earlier call (whatever has landed)
+            if (need > words / 4 * 3) words = std::min<size_t>(std::max<size_t>(words, (size_t)need * 2), (size_t)1 << 27);
+        }
+        if (kn.ml_arena_words >= 1024) words = (size_t)kn.ml_arena_words;   // test knob: a small arena makes some frames fall back
+        ctx->ml_arena_words = kn.ml_arena_words >= 1024 ? ctx->ml_arena_words : words;
+        if ((rc = scratch_reserve(ctx, ctx->mlops, words * 8)) || (rc = scratch_reserve(ctx, ctx->mlrec, (size_t)nf * 32))) return rc;
+        ma.ops = (unsigned long long *)ctx->mlops.p; ma.ops_cap = words;
+        ma.ops_head = (unsigned long long *)(hdr + kMlHdrOpsHead);
+        ma.rec = (uint32_t *)ctx->mlrec.p;
+    } else if (!fused) {
+        if ((rc = scratch_reserve(ctx, ctx->mlrec, (size_t)nf * 32))) return rc;
+        ma.rec = (uint32_t *)ctx->mlrec.p;   // the fall-back flag is written in either case
+    }
+    kfn = words ? ldpc_ml_words_kernel : ldpc_ml_kernel;   // (the word form: a kernel of its own over the same body)
+    ctx->prof_names[LDPC_AMD_PROF_ML] = words ? "ldpc_ml_words_kernel" : "ldpc_ml_kernel";
+    if (p.pi_nw > 0) {
+        pi = p.pi;
+        pi.code = cd; pi.ml_list = ma.ml_list; pi.nframes = nf; pi.ml_state = ma.ml_state; pi.work = hdr + kMlHdrPiWork;
+        pi.status = d.status; pi.ops = ma.ops; pi.ops_cap = ma.ops_cap; pi.ops_head = ma.ops_head; pi.rec = ma.rec;
+        pi.solve_b = p.solve_b;
+        pi.verify = kn.ml_pi == 1 ? 1 : 0;
+        pi.ndone = hdr + kMlHdrPiDone;
+        pi.imax = kn.ml_pi_imax;
+    }
+    if (p.overlap) {
+        if (!ctx->aux_ml) {   // lowest priority: its kernels fill the gaps the packet kernel leaves, not the other way round
+            int lo = 0, hi = 0;
+            LDPC_HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
+            LDPC_HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->aux_ml, hipStreamNonBlocking, kn.ml_overlap_prio ? lo : 0));
+        }
+        for (hipEvent_t &e : ctx->ml_events)
+            if (!e) LDPC_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    return LDPC_AMD_OK;
+}
+
+// the rest of the stage's front half goes to the second stream
+int MlStage::fork(hipStream_t &st)
+{
+    prof_end(ctx, LDPC_AMD_PROF_ML, ev);
+    ev = nullptr;
+    LDPC_HIP_TRY(ctx, hipEventRecord(ctx->ml_events[0], ctx->stream));
+    LDPC_HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_ml, ctx->ml_events[0], 0));
+    st = ctx->aux_ml;
+    return LDPC_AMD_OK;
+}
+
+// fast path + factorisation (pattern only in packet mode)
+int MlStage::front()
+{
+    const Knobs &kn = ctx->knobs;
+    int rc;
+    front_done = true;
+    // (profiling: LDPC_AMD_PROF_ML is the stage's share of the MAIN stream.  With the fast path and the factorisation both beside
+    // the packet kernel that is back() alone; with ML_OVERLAP=1 it comes in two pieces, i.e. two launches of the kind per call)
+    ev = (p.overlap && kn.ml_overlap == 2) ? nullptr : prof_begin(ctx);
+    hipStream_t st = ctx->stream;
+    if (p.overlap && kn.ml_overlap == 2 && (rc = fork(st))) return rc;   // =2: the fast path beside the packet kernel too
+    if (p.pi_nw > 0) {
+        const int wgs_per_cu = std::max(1, kLdsMax / p.pi_total);
+        int pgrid = (int)std::min<int64_t>((d.nframes + p.pi_nw - 1) / p.pi_nw, (int64_t)ctx->sm_count * wgs_per_cu);
+        if (kn.ml_pi_wgs > 0) pgrid = std::min(pgrid, kn.ml_pi_wgs);
+        if ((rc = launch_lds(ctx, ldpc_ml_pi_kernel, dim3(pgrid), dim3(64 * p.pi_nw), (size_t)p.pi_total, st, pi))) return rc;
+    }
+    if (p.overlap && kn.ml_overlap != 2 && (rc = fork(st))) return rc;
+    ma.mode = p.overlap ? 1 : 0;
+    if ((rc = launch_lds(ctx, kfn, dim3(p.grid), dim3(p.threads), (size_t)p.total, st, ma))) return rc;
+    if (p.overlap) LDPC_HIP_TRY(ctx, hipEventRecord(ctx->ml_events[1], ctx->aux_ml));
+    return LDPC_AMD_OK;
+}
+
+// `profiled`: the first round, named and bracketed (level 2) for the profile
+int MlStage::launch_solve(const MlSolveArgs &sv, dim3 grid, size_t lds, bool profiled)
+{
+    int rc = LDPC_AMD_OK;
+    const bool found = with_int<8, 4, 2, 1>(p.solve_b / 16, [&](auto L) {
+        rc = with_bool(words, [&](auto W) {
+            constexpr int kL = decltype(L)::value;
+            constexpr bool kW = decltype(W)::value;
+            if (profiled) prof_name(ctx, LDPC_AMD_PROF_ML_SOLVE, kW ? "ldpc_ml_solve_words_kernel" : "ldpc_ml_solve_kernel", kL);
+            hipEvent_t evs = profiled ? prof_begin(ctx, 2) : nullptr;
+            void (*sfn)(MlSolveArgs);
+            if constexpr (kW) sfn = ldpc_ml_solve_words_kernel<kL>; else sfn = ldpc_ml_solve_kernel<kL>;
+            const int rcl = launch_lds(ctx, sfn, grid, dim3(512), lds, ctx->stream, sv);
+            if (!rcl) prof_end(ctx, LDPC_AMD_PROF_ML_SOLVE, evs);
+            return rcl;
+        });
+    });
+    if (!found) LDPC_HIP_TRY(ctx, hipErrorInvalidValue);   // (plan_ml: 16, 32, 64 or 128 bytes)
+    return rc;
+}
+
+// what needs the payload: deferred frames, the solve kernel
+int MlStage::back()
+{
+    const DevCode &cd = d.code;
+    const Knobs &kn = ctx->knobs;
+    int rc;
+    if (p.overlap) {
+        ev = prof_begin(ctx);
+        LDPC_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ml_events[1], 0));
+        ma.mode = 2;   // the deferred frames only (none, normally: the kernel leaves after one load)
+        if ((rc = launch_lds(ctx, kfn, dim3(p.grid), dim3(p.threads), (size_t)p.total, ctx->stream, ma))) return rc;
+    }
+    if (ma.use_solve && kn.ml_solve != 2) {   // =2: diagnostic, schedules emitted but not run (timing of the factor part)
+        int32_t *const hdr = (int32_t *)ctx->mllist.p;
+        MlSolveArgs sv{};
+        sv.code = cd; sv.S = d.S; sv.nslices = (d.S + p.solve_b - 1) / p.solve_b; sv.piece_last = d.S - p.solve_b; sv.nframes = d.nframes;
+        sv.ml_list = ma.ml_list; sv.rec = ma.rec; sv.ops = ma.ops;
+        sv.out = d.out; sv.work = hdr + kMlHdrSolveWork;
+        sv.dbg = ma.dbg; sv.err = ctx->dev_err_host;
+        sv.nfail = ma.nfail; sv.round = 1;
+        int o = 8192 + cd.m * p.solve_b;   // multiply tables first (kMlSlot0), then the slots
+        sv.lds_tab = o; o += align_up(4 * (2 * cd.m + 6), 16);
+        sv.lds_mt = 0;
+        sv.lds_misc = o; o += 16 + 4 * kMlClasses;
+        const int per_cu = std::max(1, std::min(4, kLdsMax / o));
+        const dim3 sg((unsigned)std::min<int64_t>(d.nframes * sv.nslices, (int64_t)ctx->sm_count * per_cu));
+        if ((rc = launch_solve(sv, sg, (size_t)o, true))) return rc;
+        if (p.pi_nw > 0 && pi.verify) {
+            // Verified fast path: a frame whose received symbols are not a codeword makes the residual system INCONSISTENT, and
+            // then the bytes depend on which equations a solver uses.  The fast-path schedules therefore also evaluate the
+            // equations they did not use; the solve kernel flags a frame with a non-zero one (rec[7], nfail), and these two
+            // launches -- which leave after one load when nothing was flagged -- redo such frames in the reference's order.
+            ma.mode = 3;
+            if ((rc = launch_lds(ctx, kfn, dim3(p.grid), dim3(p.threads), (size_t)p.total, ctx->stream, ma))) return rc;
+            sv.round = 2; sv.work = hdr + kMlHdrSolveWork2;
+            if ((rc = launch_solve(sv, sg, (size_t)o, false))) return rc;
+        }
+    }
+    prof_end(ctx, LDPC_AMD_PROF_ML, ev);
+    if (ma.use_solve) {   // this call's arena demand -> pinned host word, read by a later call (no wait here)
+        if (!ctx->ml_head_host) {
+            if (hipHostMalloc((void **)&ctx->ml_head_host, 64, hipHostMallocDefault) != hipSuccess) ctx->ml_head_host = nullptr;
+            else *ctx->ml_head_host = 0;
+        }
+        if (ctx->ml_head_host) {
+            LDPC_HIP_TRY(ctx, hipMemcpyAsync(ctx->ml_head_host, ma.ops_head, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+            ctx->ml_head_valid = true;
+        }
+    }
+    return LDPC_AMD_OK;
+}
+
+// frames out: behind the LAST launch of the ML stage (the redo launches of the fast path included), on the main stream: the
+// frames it solved have no unknown symbol left.  One wavefront per slot of the residual list.
+int MlStage::finalize()
+{
+    if (!d.erased_out && !d.residual_src) return LDPC_AMD_OK;
+    const int nw = 4;
+    const unsigned fgrid = (unsigned)std::min<int64_t>((d.nframes + nw - 1) / nw, (int64_t)ctx->sm_count * 8);
+    hipLaunchKernelGGL(ldpc_frames_finalize_kernel, dim3(fgrid), dim3(64 * nw), 0, ctx->stream, d.code.n, (const int32_t *)ctx->mllist.p,
+                       (const int32_t *)d.status, d.erased_out, d.residual_src);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// ---- decode ---------------------------------------------------------------------------------------------------
+// What ldpc_amd_last_plan reports: the peel shape (the relaxation's, where it runs in the peel kernel's place) and the packet plan
+static void record_plan(ldpc_amd_ctx *ctx, const PeelShape &shape, const RelaxPlan &relax, const ScatterPlan &plan)
+{
+    int *lp = ctx->last_plan;
+    lp[0] = shape.wpb; lp[1] = shape.per_cu; lp[2] = shape.gt ? 1 : 0; lp[3] = shape.lds.total; lp[4] = shape.lds.wave_stride;
+    if (relax.ok) { lp[0] = relax.wpb; lp[1] = relax.per_cu; lp[2] = relax.gt ? 1 : 0; lp[3] = relax.lds.total; lp[4] = relax.lds.wave_stride; }
+    const bool use_scatter = plan.lpr > 0;
+    lp[5] = use_scatter ? plan.lpr * 16 : 0; lp[6] = use_scatter ? plan.tcap : 0; lp[7] = use_scatter && plan.two_tier ? 1 : 0;
+}
+
+// S = 1: one kernel peels and applies (the relaxation when its keys fit, else the serial loop), then the ML stage
+static int decode_s1(ldpc_amd_ctx *ctx, const DecodeArgs &d, const PeelShape &shape, const RelaxPlan &relax, const PeelArgs &pa)
+{
+    int rc;
+    if (relax.ok) rc = launch_relax<0>(ctx, relax, d, pa, nullptr, nullptr);
+    else rc = shape.gt ? launch_peel_t<true, true>(ctx, pa, shape.wpb, true) : launch_peel_t<true>(ctx, pa, shape.wpb, true);
+    if (rc || !d.do_ml) return rc;
+    MlStage ml{ctx, d, true, false};
+    if ((rc = ml.prepare(false))) return rc;
+    return ml.finish();
+}
+
+// Packets: the schedules (relaxation or serial peel), the packet kernel -- scatter form (rows read once, accumulators in LDS) or
+// gather form -- with the pattern-only part of the ML stage beside it, then the rest of the ML stage
+static int decode_packets(ldpc_amd_ctx *ctx, const DecodeArgs &d, const ScatterPlan &plan, const PeelShape &shape, const RelaxPlan &relax,
+                          PeelArgs pa, bool words)
+{
+    const DevCode &cd = d.code;
+    const Knobs &kn = ctx->knobs;
+    const int64_t nf = d.nframes;
+    const bool use_scatter = plan.lpr > 0;
+    int rc;
+    const size_t hdr = (size_t)nf * 2 * 4, st = (size_t)nf * cd.m * 4, le = (size_t)nf * (cd.m + 1) * 2, iv = (size_t)nf * cd.m;
+    const size_t o1 = (hdr + 255) & ~(size_t)255, o2 = (o1 + st + 255) & ~(size_t)255, o3 = (o2 + le + 255) & ~(size_t)255;
+    if ((rc = scratch_reserve(ctx, ctx->sched, o3 + iv))) return rc;
+    unsigned char *base = (unsigned char *)ctx->sched.p;
+    pa.sched_hdr = (uint32_t *)base; pa.sched_steps = (uint32_t *)(base + o1); pa.sched_lvlend = (uint16_t *)(base + o2);
+    pa.sched_invc = base + o3;
+    if (use_scatter) {
+        pa.tcap = plan.tcap;
+        pa.big_list = plan.two_tier ? (int32_t *)ctx->biglist.p : nullptr;
+    }
+    uint32_t *pull = nullptr;    // per-step records of the paired-level schedules (peel_relax.inc mode 2 -> packet kernel)
+    uint32_t *lists = nullptr;   // the steps' column lists in schedule order (peel_relax.inc mode 2 -> packet kernel set-up)
+    if (use_scatter && relax.keys_fit && kn.scatter_pairs != 0) {   // paired levels: 16 bytes per step for the records the packet kernel reads at set-up
+        if ((rc = scratch_reserve(ctx, ctx->schedpull, (size_t)nf * cd.m * 16))) return rc;
+        pull = (uint32_t *)ctx->schedpull.p;
+    }
+    if (use_scatter && relax.keys_fit && kn.scatter_lists != 0) {
+        if ((rc = scratch_reserve(ctx, ctx->schedlists, (size_t)nf * cd.m * cd.maxcoldeg * 4))) return rc;
+        lists = (uint32_t *)ctx->schedlists.p;
+    }
+    // the schedules by relaxation when its keys fit (else, and with PEEL_RELAX=0: the serial loop)
+    if ((rc = relax.ok ? launch_relax<2>(ctx, relax, d, pa, pull, lists) : launch_peel_t<false>(ctx, pa, shape.wpb, true))) return rc;
+
+    MlStage ml{ctx, d, false, words};
+    if (d.do_ml) {
+        if ((rc = ml.prepare(use_scatter))) return rc;
+        if (ml.p.overlap && (rc = ml.front())) return rc;
+    }
+    if (use_scatter) {
+        ScatterArgs sa{};
+        sa.code = cd; sa.S = d.S; sa.nslices = plan.nslices; sa.nframes = nf; sa.sym = d.sym; sa.erased = d.erased; sa.out = d.out;
+        sa.in_rows = cd.n; sa.static_sched = 0; sa.inplace = d.inplace;
+        sa.pin_src = d.pin.src; sa.pin_pkt = d.pin.packets; sa.pin_stage = d.pin.stage; sa.pin_plen = d.pin.plen;
+        sa.dbg = kn.ml_dbg; sa.err = ctx->dev_err_host; sa.xl_setup = kn.scatter_xl;
+        sa.sched_pull = pull; sa.pairs = (relax.ok && pull) ? 1 : 0; sa.sched_lists = relax.ok ? lists : nullptr;
+        sa.sched_hdr = pa.sched_hdr; sa.sched_steps = pa.sched_steps; sa.sched_lvlend = pa.sched_lvlend;
+        sa.sched_invc = pa.sched_invc;
+        hipEvent_t ev = prof_begin(ctx);
+        if ((rc = launch_scatter(ctx, plan, sa, (int32_t *)ctx->biglist.p))) return rc;
+        prof_end(ctx, LDPC_AMD_PROF_APPLY, ev);
+    } else {
+        ApplyArgs aa{};
+        aa.code = cd; aa.S = d.S; aa.nframes = nf; aa.sym = d.sym; aa.erased = d.erased; aa.in_rows = d.in_rows; aa.out = d.out;
+        aa.sched_hdr = pa.sched_hdr; aa.sched_steps = pa.sched_steps; aa.sched_lvlend = pa.sched_lvlend;
+        if ((rc = launch_apply(ctx, aa, words, true))) return rc;
+    }
+    return d.do_ml ? ml.finish() : LDPC_AMD_OK;
+}
+
+// One chunk of frames: the plans, the workspaces every path shares, then the path -- flags only, S = 1, packets
+static int decode_chunk(ldpc_amd_ctx *ctx, const DecodeArgs &d, bool fused, bool words)
+{
+    const DevCode &cd = d.code;
+    const Knobs &kn = ctx->knobs;
+    const int64_t nf = d.nframes;
+    if (d.residual_src && d.residual_sys) return set_error(ctx, LDPC_AMD_EINVAL, "internal: residual_src and residual_sys are one outlet, set one");
+
+    // packet path: scatter kernel (rows read once, accumulators in LDS) unless the code's columns are too
+    // heavy for the padded per-source lists, or LDPC_AMD_APPLY=gather asks for the gather kernel (A/B runs)
+    ScatterPlan plan{};
+    const bool pin = d.pin.src != nullptr;   // the fused receiver: the rows are fetched from packets, there is no sym
+    if (!fused && !d.flags_only && kn.apply_gather == 0 && cd.maxcoldeg <= 16) plan = plan_scatter(kn, cd, d.S, pin);
+    const bool use_scatter = plan.lpr > 0;
+    if (pin && (!use_scatter || d.inplace || d.sym))   // (the caller asks decode_reads_packets first: this is a bug, not an input)
+        return set_error(ctx, LDPC_AMD_EINVAL, "internal: packets-in decode without the scatter kernel, in place, or with a row array");
+    if (d.inplace && !use_scatter) return set_error(ctx, LDPC_AMD_EUNSUP, "in-place decode needs the scatter kernel");
+    const PeelShape shape = plan_peel(kn, cd, fused, nf, ctx->sm_count);
+    if (shape.lds_need) return set_error(ctx, LDPC_AMD_EUNSUP, "code too large for LDS (%d bytes)", shape.lds_need);
+    const RelaxPlan relax = plan_relax(kn, cd, fused ? 0 : (d.flags_only ? 1 : 2), d.erased != nullptr, d.in_rows, d.max_sweeps, nf, ctx->sm_count);
+    record_plan(ctx, shape, relax, plan);
+
+    int rc;
+    if ((rc = scratch_reserve(ctx, ctx->mllist, sizeof(int32_t) * ((size_t)(1 + kMlClasses) * nf + kMlHdr)))) return rc;
+    if (d.do_ml && (rc = scratch_reserve(ctx, ctx->mlstate, (size_t)nf * cd.n))) return rc;
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(ctx->mllist.p, 0, kMlHdr * sizeof(int32_t), ctx->stream));   // (the ML stage's work counters with it)
+    if (use_scatter && plan.two_tier) {
+        if ((rc = scratch_reserve(ctx, ctx->biglist, sizeof(int32_t) * (size_t)(nf + 2)))) return rc;
+        LDPC_HIP_TRY(ctx, hipMemsetAsync(ctx->biglist.p, 0, 2 * sizeof(int32_t), ctx->stream));   // [0] count, [1] tier 2's work counter
+    }
+
+    PeelArgs pa{};
+    pa.code = cd; pa.lds = shape.lds; pa.nframes = nf; pa.sym = d.sym; pa.erased = d.erased; pa.in_rows = d.in_rows;
+    pa.max_sweeps = d.max_sweeps; pa.do_ml = d.do_ml; pa.out = d.out;
+    pa.sweeps = d.sweeps; pa.residual = d.residual; pa.status = d.status; pa.erased_out = d.erased_out;
+    pa.residual_sys = d.residual_src ? d.residual_src : d.residual_sys;   // residual_src is the public outlet of the kernels' residual_sys
+    pa.ml_list = (int32_t *)ctx->mllist.p; pa.ml_state = (uint8_t *)ctx->mlstate.p;
+
+    if (d.flags_only)   // the pattern-only run: flags in, flags and counts out, no ML stage, not profiled
+        return relax.ok ? launch_relax<1>(ctx, relax, d, pa, nullptr, nullptr) : launch_peel_t<false>(ctx, pa, shape.wpb, false);
+    if (fused) return decode_s1(ctx, d, shape, relax, pa);
+    return decode_packets(ctx, d, plan, shape, relax, pa, words);
+}
+
 int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
 {
     const DevCode &cd = d.code;
@@ -2211,587 +2936,28 @@ int launch_decode(ldpc_amd_ctx *ctx, const DecodeArgs &d)
 
     // bound the per-call workspaces: long batches are processed in chunks of frames
     const int64_t kChunk = fused ? (int64_t)ctx->knobs.chunk_s1 : 16384;
-    if (d.nframes > kChunk) {
-        for (int64_t f0 = 0; f0 < d.nframes; f0 += kChunk) {
-            DecodeArgs c = d;
-            c.nframes = std::min(kChunk, d.nframes - f0);
-            if (d.sym) c.sym = d.sym + f0 * (int64_t)d.in_rows * d.S;
-            if (d.pin.src) c.pin.src = d.pin.src + f0 * cd.n;
-            if (d.erased) c.erased = d.erased + f0 * cd.n;
-            if (d.out) c.out = d.out + f0 * (int64_t)cd.n * d.S;
-            if (d.sweeps) c.sweeps = d.sweeps + f0;
-            if (d.residual) c.residual = d.residual + f0;
-            if (d.status) c.status = d.status + f0;
-            if (d.residual_sys) c.residual_sys = d.residual_sys + f0;
-            if (d.erased_out) c.erased_out = d.erased_out + f0 * cd.n;
-            if (d.residual_src) c.residual_src = d.residual_src + f0;
-            int rcc = launch_decode(ctx, c);
-            if (rcc) return rcc;
-        }
-        return LDPC_AMD_OK;
-    }
-
-    // frames out: the kernel that finalises the flags behind the ML stage reads the status words; a caller that did not ask for
-    // them gets them from a scratch array
-    const bool frames_out = d.erased_out || d.residual_src;
-    if (frames_out && d.do_ml && !d.status) {
-        int rcs = scratch_reserve(ctx, ctx->frstatus, sizeof(int32_t) * (size_t)d.nframes);
-        if (rcs) return rcs;
+    for (int64_t f0 = 0; f0 < d.nframes; f0 += kChunk) {
         DecodeArgs c = d;
-        c.status = (int32_t *)ctx->frstatus.p;
-        return launch_decode(ctx, c);
-    }
-    if (d.residual_src && d.residual_sys) return set_error(ctx, LDPC_AMD_EINVAL, "internal: residual_src and residual_sys are one outlet, set one");
-    int32_t *const rsys_out = d.residual_src ? d.residual_src : d.residual_sys;   // residual_src is the public outlet of the kernels' residual_sys
-
-    // packet path: scatter kernel (rows read once, accumulators in LDS) unless the code's columns are too
-    // heavy for the padded per-source lists, or LDPC_AMD_APPLY=gather asks for the gather kernel (A/B runs)
-    const Knobs &kn = ctx->knobs;
-    const bool want_gather = kn.apply_gather != 0;
-    ScatterPlan plan{};
-    const bool pin = d.pin.src != nullptr;   // the fused receiver: the rows are fetched from packets, there is no sym
-    if (!fused && !d.flags_only && !want_gather && cd.maxcoldeg <= 16) plan = plan_scatter(kn, cd, d.S, pin);
-    const bool use_scatter = plan.lpr > 0;
-    if (pin && (!use_scatter || d.inplace || d.sym))   // (the caller asks decode_reads_packets first: this is a bug, not an input)
-        return set_error(ctx, LDPC_AMD_EINVAL, "internal: packets-in decode without the scatter kernel, in place, or with a row array");
-    if (d.inplace && !use_scatter) return set_error(ctx, LDPC_AMD_EUNSUP, "in-place decode needs the scatter kernel");
-
-    // workgroup shape: the peel is latency bound (serial solve chain per frame), so pick the frames-per-workgroup
-    // that puts the most wavefronts on a CU within its 160 KB of LDS (the code tables are shared by a workgroup)
-    int wpb = 1;
-    bool gt = false;
-    PeelLds L = make_peel_lds(cd, fused, 1);
-    // (S = 1 keeps id | log(coef) words per edge in LDS: a code whose tables leave no room for a frame -- (8192,4096) -- still runs
-    // with the tables in global memory, whatever PEEL_GT prefers; the relaxation's plan below does the same)
-    const bool lds_tables = L.total <= kLdsMax;
-    if (!lds_tables && (!fused || make_peel_lds(cd, fused, 1, true).total > kLdsMax))
-        return set_error(ctx, LDPC_AMD_EUNSUP, "code too large for LDS (%d bytes)", L.total);
-    {
-        int best = 0;
-        const bool env_w = kn.peel_wpb > 0;   // diagnostic: cap the wavefronts (= frames) per workgroup
-        const int wcap = env_w ? std::max(1, std::min(16, kn.peel_wpb)) : 16;
-        for (int w = 1; w <= wcap; w++) {
-            const PeelLds t = make_peel_lds(cd, fused, w);
-            if (t.total > kLdsMax) break;
-            const int waves = env_w ? w : std::min(32, (kLdsMax / t.total) * w);
-            if (waves > best) { best = waves; wpb = w; L = t; }
+        c.nframes = std::min(kChunk, d.nframes - f0);
+        if (d.sym) c.sym = d.sym + f0 * (int64_t)d.in_rows * d.S;
+        if (d.pin.src) c.pin.src = d.pin.src + f0 * cd.n;
+        if (d.erased) c.erased = d.erased + f0 * cd.n;
+        if (d.out) c.out = d.out + f0 * (int64_t)cd.n * d.S;
+        if (d.sweeps) c.sweeps = d.sweeps + f0;
+        if (d.residual) c.residual = d.residual + f0;
+        if (d.status) c.status = d.status + f0;
+        if (d.residual_sys) c.residual_sys = d.residual_sys + f0;
+        if (d.erased_out) c.erased_out = d.erased_out + f0 * cd.n;
+        if (d.residual_src) c.residual_src = d.residual_src + f0;
+        // frames out: the kernel that finalises the flags behind the ML stage reads the status words; a caller that did not ask for
+        // them gets them from a scratch array
+        if ((d.erased_out || d.residual_src) && d.do_ml && !d.status) {
+            int rcs = scratch_reserve(ctx, ctx->frstatus, sizeof(int32_t) * (size_t)c.nframes);
+            if (rcs) return rcs;
+            c.status = (int32_t *)ctx->frstatus.p;
         }
-        // S = 1, long batch: with the code tables left in global memory more frames fit on a CU.  Worth it when the
-        // batch is several rounds deep anyway (a single round is latency bound and prefers the LDS tables).
-        if (fused && ((!env_w && kn.peel_gt != 0) || !lds_tables)) {
-            int bestg = 0, wg = 1;
-            PeelLds Lg = L;
-            for (int w = 1; w <= wcap; w++) {
-                const PeelLds t = make_peel_lds(cd, fused, w, true);
-                if (t.total > kLdsMax) break;
-                const int waves = std::min(32, (kLdsMax / t.total) * w);
-                if (waves > bestg) { bestg = waves; wg = w; Lg = t; }
-            }
-            const bool deep = d.nframes >= (int64_t)3 * best * ctx->sm_count;
-            // measured: (4080,3060) 7 -> 11 frames per CU: -18 %, (4000,2000) 5 -> 8: -15 %, (2040,1530) 16 -> 21: +12 % (slower)
-            if (!lds_tables || kn.peel_gt == 1 || (deep && bestg * 20 >= best * 29)) { gt = true; wpb = wg; L = Lg; }
-        }
-    }
-
-    ctx->last_plan[0] = wpb; ctx->last_plan[1] = std::min(32, (kLdsMax / L.total) * wpb); ctx->last_plan[2] = gt ? 1 : 0;
-    ctx->last_plan[3] = L.total; ctx->last_plan[4] = L.wave_stride; ctx->last_plan[5] = use_scatter ? plan.lpr * 16 : 0;
-    ctx->last_plan[6] = use_scatter ? plan.tcap : 0; ctx->last_plan[7] = use_scatter && plan.two_tier ? 1 : 0;
-    const int64_t nf = d.nframes;
-    int rc;
-    if ((rc = scratch_reserve(ctx, ctx->mllist, sizeof(int32_t) * ((size_t)(1 + kMlClasses) * nf + kMlHdr)))) return rc;
-    if (d.do_ml && (rc = scratch_reserve(ctx, ctx->mlstate, (size_t)nf * cd.n))) return rc;
-    LDPC_HIP_TRY(ctx, hipMemsetAsync(ctx->mllist.p, 0, kMlHdr * sizeof(int32_t), ctx->stream));
-    if (use_scatter && plan.two_tier) {
-        if ((rc = scratch_reserve(ctx, ctx->biglist, sizeof(int32_t) * (size_t)(nf + 2)))) return rc;
-        LDPC_HIP_TRY(ctx, hipMemsetAsync(ctx->biglist.p, 0, 2 * sizeof(int32_t), ctx->stream));   // [0] count, [1] tier 2's work counter
-    }
-
-    // ---- the ML stage (a2-a4): prepared before the packet kernel is launched, because in packet mode its pattern-only part --
-    //      the fast path and the factorisation of what the fast path leaves -- can run beside the packet kernel (second stream)
-    MlArgs ma{};
-    PiArgs pi{};
-    void (*const ml_kfn)(MlArgs) = words ? ldpc_ml_words_kernel : ldpc_ml_kernel;   // (the word form: a kernel of its own over the same body)
-    int pi_nw = 0, pi_total = 0, grid = 0, total = 0, ml_threads = 0, solve_b = 0;
-    bool ml_overlap = false, ml_prepared = false, ml_front_done = false;
-    hipEvent_t ml_ev = nullptr;
-    auto ml_prepare = [&]() -> int {
-        int rc;
-        ma.code = cd; ma.S = d.S;
-        ma.Spad = fused ? 16 : align_up(d.S, 16);   // (word form: the scratch rows keep 16-byte chunks, the last one partly unused)
-        ma.ml_list = (const int32_t *)ctx->mllist.p; ma.ml_state = (const uint8_t *)ctx->mlstate.p; ma.nframes = nf;
-        ma.out = d.out; ma.status = d.status;
-        const int maxrow = align_up(cd.m, 16) + 32;
-        ma.maxrow = maxrow;
-        int off = 0;
-        // rlist[3][m] u32; colmap[n] u16 is only alive while rlist[1..2] are not, and shares their bytes
-        ma.lds_rlist = off; ma.lds_colmap = off + 4 * cd.m;
-        // (packets: the same bytes later hold the per-level histogram, 2 m + 4 words, and the slot map, m halfwords)
-        off += align_up(std::max(std::max(12 * cd.m, 4 * cd.m + 2 * cd.n), 4 * (2 * cd.m + 4) + 2 * cd.m + 16), 16);
-        ma.lds_elist = off; off += align_up(2 * cd.m, 16);
-        ma.lds_colv = off; off += align_up(3 * cd.mpad, 16);
-        ma.lds_perm = off; off += align_up(2 * cd.m + 2, 16);
-        ma.lds_iperm = off; off += align_up(2 * cd.m, 16);
-        ma.lds_orow = off; off += align_up(2 * cd.m, 16);
-        ma.lds_plog = off; off += align_up(cd.m, 16);
-        ma.lds_mt = off; off += 8192;
-        ma.lds_lg = off; off += 256;
-        ma.lds_ex = off; off += 1024;
-        ma.lds_misc = off; off += 128 + 4 * kMlClasses;
-        ma.lds_lvl = off; off += align_up(4 * (cd.m + 2), 16);
-        ma.lds_A = off;
-        if (off > kLdsMax) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: LDS need %d bytes", off);
-        if (cd.m > 4096) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: more than 4096 checks (%d)", cd.m);   // 12-bit row fields of the pivot key
-        // ML_PACK = P workgroups per CU (1024 / P threads, 160 KB / P of LDS each): the factorisation is bound by the instructions
-        // all wavefronts of a workgroup issue per column, not by the work in a column, so P small workgroups -- P systems per CU,
-        // their matrices in the global scratch (L2) when they do not fit the LDS share -- issue P times fewer of them per system
-        const int pack = std::max(1, std::min(4, kn.ml_pack));
-        total = std::max(off + 256, (kLdsMax / pack) & ~255);
-        if (total > kLdsMax) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: LDS need %d bytes", total);
-        ma.capA = (total - off) & ~15;
-        grid = (int)std::min<int64_t>(nf, (int64_t)ctx->sm_count * pack);
-        const size_t perA = (size_t)cd.m * maxrow, perR = fused ? 0 : (size_t)cd.m * ma.Spad;
-        if ((rc = scratch_reserve(ctx, ctx->mlws, (perA + perR) * grid + 256))) return rc;
-        // work counters: [0] frame hand-out counter, [2..3] arena bump pointer (u64), [4] task counter of the solve kernel.  They
-        // sit in the free tail of the residual list's header (ints 18..23), which launch_decode zeroes with that header: one
-        // memset per call less (a call is launch-bound at S = 1)
-        // [1] frames deferred by the launch beside the packet kernel, [5] frame hand-out counter of the fast path (ldpc_ml_pi_kernel)
-        // header ints 24..27: verification failures of the fast path, hand-out counters of the two launches that redo those frames,
-        // frames the fast path emitted (read back by ldpc_amd_ml_stats with [0] and [19] = ma.work[1], the deferred frames)
-        static_assert(kMlHdr == 32 && 1 + kMlClasses <= 17, "ml_list header: no room for the work counters");
-        ma.work = (int32_t *)ctx->mllist.p + 18;
-        ma.work2 = (int32_t *)ctx->mllist.p + 17;   // hand-out counter of the launch that solves the deferred frames (mode 2)
-        ma.nfail = (int32_t *)ctx->mllist.p + 24;   // frames whose fast-path solution failed the consistency check (not codewords)
-        ma.work3 = (int32_t *)ctx->mllist.p + 25;   // hand-out counter of the launch that factors them again, exactly (mode 3)
-        ma.wsA = (uint8_t *)ctx->mlws.p + 256;
-        ma.wsR = ma.wsA + perA * grid;
-        // packets: the ML kernel factors every residual system on bytes and emits a solve schedule (64-bit ops grouped by
-        // dependency level) into an arena; ldpc_ml_solve_kernel then runs the schedules on LDS-resident row slices.
-        // Frames whose schedule does not fit the arena are solved inside the ML kernel (same bytes, slower).
-        ma.use_solve = (!fused && kn.ml_solve != 0) ? 1 : 0;
-        ma.dbg = kn.ml_dbg;
-        if (ma.use_solve) {
-            solve_b = kn.ml_solve_b;   // A/B knob
-            if (words) { while (solve_b > 16 && solve_b > d.S) solve_b >>= 1; }   // (the last piece overlaps: MlSolveArgs::piece_last)
-            else while (solve_b > 16 && (d.S % solve_b) != 0) solve_b >>= 1;
-            const int tail_sv = align_up(4 * (2 * cd.m + 6), 16) + 8192 + 16 + 4 * kMlClasses;
-            while (solve_b > 16 && cd.m * solve_b + tail_sv > 79 * 1024) solve_b >>= 1;
-            if (cd.m * solve_b + tail_sv > kLdsMax || cd.n > 65535) ma.use_solve = 0;
-        }
-        ma.solve_b = solve_b;
-        if (ma.use_solve) {
-            // The arena follows DEMAND, not the batch size: 16 MB to start with (2 M words); the words the previous call asked for
-            // come back through a pinned host word (copied behind every call, never waited for), and when they exceeded three quarters of
-            // the arena it grows to twice that demand, at most 1 GB.  A call that overflows is still correct -- the frames
-            // that do not fit are solved inside the ML kernel -- so a steady workload is at full speed from its second or third
-            // batch, and a batch message passing completes pins 16 MB instead of 64 KB per frame.
-            size_t words = std::max<size_t>(ctx->ml_arena_words, (size_t)1 << 21);
-            if (ctx->ml_head_host) {
-                const unsigned long long need = *ctx->ml_head_host;   // demand of an earlier call (whatever has landed)
-                if (need > words / 4 * 3) words = std::min<size_t>(std::max<size_t>(words, (size_t)need * 2), (size_t)1 << 27);
-            }
-            if (kn.ml_arena_words >= 1024) words = (size_t)kn.ml_arena_words;   // test knob: a small arena makes some frames fall back
-            ctx->ml_arena_words = kn.ml_arena_words >= 1024 ? ctx->ml_arena_words : words;
-            if ((rc = scratch_reserve(ctx, ctx->mlops, words * 8)) || (rc = scratch_reserve(ctx, ctx->mlrec, (size_t)nf * 32))) return rc;
-            ma.ops = (unsigned long long *)ctx->mlops.p; ma.ops_cap = words;
-            ma.ops_head = (unsigned long long *)(ma.work + 2);
-            ma.rec = (uint32_t *)ctx->mlrec.p;
-        } else if (!fused) {
-            if ((rc = scratch_reserve(ctx, ctx->mlrec, (size_t)nf * 32))) return rc;
-            ma.rec = (uint32_t *)ctx->mlrec.p;   // the fall-back flag is written in either case
-        }
-        ml_threads = kn.ml_threads > 0 ? kn.ml_threads : std::max(256, (1024 / pack) & ~63);
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(ml_kfn)));
-        ctx->prof_names[LDPC_AMD_PROF_ML] = words ? "ldpc_ml_words_kernel" : "ldpc_ml_kernel";
-        // Packets: the fast path first (ml_pi.inc: peel on, inactivate, small dense system; a wavefront per frame).  It emits
-        // the schedules of the full-rank frames; ldpc_ml_kernel then factors what it left (rank-deficient frames, rec[6] = 0).
-        // (A context whose LAST packet batch had no residual frame at all -- its arena demand, back through the pinned host word, was
-        // zero -- skips the fast path's four extra launches for this batch: 23 -> 8.5 us of empty launches per step on a workload
-        // message passing completes.  Whatever does reach the ML stage then is factored exactly; the next batch has the fast path again.)
-        const bool ml_quiet = kn.ml_pi_adaptive && ctx->ml_head_host && ctx->ml_head_valid && *ctx->ml_head_host == 0;
-        if (ma.use_solve && kn.ml_pi != 0 && !ml_quiet) {
-            int shared = 8192 + 256 + 1024 + 64;   // multiply tables, log, antilog, size-class counts
-            pi.lds_mt = 0; pi.lds_lg = 8192; pi.lds_ex = 8192 + 256;
-            pi.lds_edges = pi.lds_rowptr = -1;
-            const int rows_bytes = align_up(4 * cd.nnz, 16) + align_up(4 * (cd.m + 1), 16);
-            if (rows_bytes <= 40 * 1024) {   // the code's rows in LDS (every frame walks them a few times); else from global memory
-                pi.lds_edges = shared; pi.lds_rowptr = shared + align_up(4 * cd.nnz, 16);
-                shared += rows_bytes;
-            }
-            int o = 0;
-            pi.o_vinfo = o; o += align_up(2 * cd.n, 16);
-            pi.o_cnt = o; o += align_up(4 * (cd.m + 264), 16);
-            pi.o_lvl = o; o += align_up(4 * cd.m, 16);
-            pi.o_ustate = o; o += align_up(2 * cd.m, 16);
-            pi.o_uvar = o; o += align_up(2 * cd.m, 16);
-            pi.o_stepc = o; o += align_up(2 * cd.m, 16);
-            pi.o_stepi = o; o += align_up(2 * cd.m, 16);
-            pi.o_slvl = o; o += align_up(2 * cd.m, 16);
-            pi.o_sginv = o; o += align_up(cd.m, 16);
-            pi.o_queue = o; o += align_up(2 * cd.m, 16);
-            pi.o_candpiv = o; o += align_up(2 * cd.m, 16);
-            pi.o_inact = o; o += 512;
-            pi.o_sel = o; o += 512;
-            pi.o_sellvl = o; o += 512;
-            pi.o_dlog = o; o += 256;
-            pi.o_misc = o; o += 16 + 512;   // queue tail; the winners of a batch
-            pi.o_av = o;
-            const int budget = std::max(32, std::min(160, kn.ml_pi_lds)) * 1024 - shared;
-            const int av_want = std::min(cd.m * 32, 16 * 1024);
-            pi_nw = std::max(1, std::min(std::max(1, std::min(4, kn.ml_pi_waves)), budget / (o + av_want)));
-            const int per_wave = (budget / pi_nw) & ~15;
-            if (per_wave >= o + 1024 && cd.maxdeg <= kWave && cd.maxcoldeg <= 16 && cd.m < 0x8000 && cd.n < 0xFFFF) {
-                pi.av_bytes = per_wave - o;
-                pi.lds_wave0 = shared; pi.lds_wave_stride = per_wave;
-                pi_total = shared + pi_nw * per_wave;
-            } else {
-                pi_nw = 0;
-            }
-        }
-        ma.use_pi = pi_nw > 0 ? 1 : 0;
-        if (pi_nw > 0) {
-            pi.code = cd; pi.ml_list = ma.ml_list; pi.nframes = nf; pi.ml_state = ma.ml_state; pi.work = ma.work + 5;
-            pi.status = d.status; pi.ops = ma.ops; pi.ops_cap = ma.ops_cap; pi.ops_head = ma.ops_head; pi.rec = ma.rec;
-            pi.solve_b = solve_b;
-            pi.verify = kn.ml_pi == 1 ? 1 : 0;
-            pi.ndone = (int32_t *)ctx->mllist.p + 27;   // frames the fast path emitted (ldpc_amd_ml_stats)
-            pi.imax = kn.ml_pi_imax;
-            LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(ldpc_ml_pi_kernel)));
-        }
-        // The factorisation needs the erasure pattern only: in packet mode (schedules, not payload) it runs on a second stream
-        // beside the packet kernel.  A frame whose schedule does not fit the arena is DEFERRED there (rec[5] = 2, ma.work[1] counts
-        // them) and solved by a second launch behind the packet kernel -- its in-kernel solve reads the payload.
-        // (Only with the fast path: beside the packet kernel the factorisation of EVERY residual frame takes as much from the packet
-        // kernel as it saves -- 6.87 against 6.94 ms on cfg 3 -- while the few frames the fast path leaves disappear behind it.)
-        ml_overlap = ma.use_solve && use_scatter && pi_nw > 0 && kn.ml_overlap != 0;
-        if (ml_overlap) {
-            if (!ctx->aux_ml) {   // lowest priority: its kernels fill the gaps the packet kernel leaves, not the other way round
-                int lo = 0, hi = 0;
-                LDPC_HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
-                LDPC_HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->aux_ml, hipStreamNonBlocking, kn.ml_overlap_prio ? lo : 0));
-            }
-            for (hipEvent_t &e : ctx->ml_events)
-                if (!e) LDPC_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        return LDPC_AMD_OK;
-    };
-    // fast path + factorisation (pattern only in packet mode)
-    auto ml_front = [&]() -> int {
-        int rc;
-        (void)rc;
-        // (profiling: LDPC_AMD_PROF_ML is the stage's share of the MAIN stream.  With the fast path and the factorisation both beside
-        // the packet kernel that is ml_back alone; with ML_OVERLAP=1 it comes in two pieces, i.e. two launches of the kind per call)
-        ml_ev = (ml_overlap && kn.ml_overlap == 2) ? nullptr : prof_begin(ctx);
-        hipStream_t st = ctx->stream;
-        auto fork = [&]() -> int {
-            prof_end(ctx, LDPC_AMD_PROF_ML, ml_ev);
-            ml_ev = nullptr;
-            LDPC_HIP_TRY(ctx, hipEventRecord(ctx->ml_events[0], ctx->stream));
-            LDPC_HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_ml, ctx->ml_events[0], 0));
-            st = ctx->aux_ml;
-            return LDPC_AMD_OK;
-        };
-        if (ml_overlap && kn.ml_overlap == 2 && (rc = fork())) return rc;   // =2: the fast path beside the packet kernel too
-        if (pi_nw > 0) {
-            const int wgs_per_cu = std::max(1, kLdsMax / pi_total);
-            int pgrid = (int)std::min<int64_t>((nf + pi_nw - 1) / pi_nw, (int64_t)ctx->sm_count * wgs_per_cu);
-            if (kn.ml_pi_wgs > 0) pgrid = std::min(pgrid, kn.ml_pi_wgs);
-            hipLaunchKernelGGL(ldpc_ml_pi_kernel, dim3(pgrid), dim3(64 * pi_nw), (size_t)pi_total, st, pi);
-            LDPC_HIP_TRY(ctx, hipGetLastError());
-        }
-        if (ml_overlap && kn.ml_overlap != 2 && (rc = fork())) return rc;
-        ma.mode = ml_overlap ? 1 : 0;
-        hipLaunchKernelGGL(ml_kfn, dim3(grid), dim3(ml_threads), (size_t)total, st, ma);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-        if (ml_overlap) LDPC_HIP_TRY(ctx, hipEventRecord(ctx->ml_events[1], ctx->aux_ml));
-        return LDPC_AMD_OK;
-    };
-    // what needs the payload: deferred frames, the solve kernel
-    auto ml_back = [&]() -> int {
-        if (ml_overlap) {
-            ml_ev = prof_begin(ctx);
-            LDPC_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ml_events[1], 0));
-            ma.mode = 2;   // the deferred frames only (none, normally: the kernel leaves after one load)
-            hipLaunchKernelGGL(ml_kfn, dim3(grid), dim3(ml_threads), (size_t)total, ctx->stream, ma);
-            LDPC_HIP_TRY(ctx, hipGetLastError());
-        }
-        if (ma.use_solve && kn.ml_solve != 2) {   // =2: diagnostic, schedules emitted but not run (timing of the factor part)
-            MlSolveArgs sv{};
-            sv.code = cd; sv.S = d.S; sv.nslices = (d.S + solve_b - 1) / solve_b; sv.piece_last = d.S - solve_b; sv.nframes = nf; sv.ml_list = ma.ml_list; sv.rec = ma.rec; sv.ops = ma.ops;
-            sv.out = d.out; sv.work = ma.work + 4;
-            sv.dbg = ma.dbg; sv.err = ctx->dev_err_host;
-            sv.nfail = ma.nfail; sv.round = 1;
-            int o = 8192 + cd.m * solve_b;   // multiply tables first (kMlSlot0), then the slots
-            sv.lds_tab = o; o += align_up(4 * (2 * cd.m + 6), 16);
-            sv.lds_mt = 0;
-            sv.lds_misc = o; o += 16 + 4 * kMlClasses;
-            const int per_cu = std::max(1, std::min(4, kLdsMax / o));
-            const dim3 sg((unsigned)std::min<int64_t>(nf * sv.nslices, (int64_t)ctx->sm_count * per_cu));
-#define LDPC_ML_SOLVE(LPRV)                                                                                   \
-    {                                                                                                        \
-        void (*sfn)(MlSolveArgs) = ldpc_ml_solve_kernel<LPRV>;                                               \
-        if (words) sfn = ldpc_ml_solve_words_kernel<LPRV>;                                                   \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(sfn)));                               \
-        hipLaunchKernelGGL(sfn, sg, dim3(512), (size_t)o, ctx->stream, sv);                                  \
-    }
-            {
-                char nm[64];
-                snprintf(nm, sizeof(nm), "ldpc_ml_solve%s_kernel<%d>", words ? "_words" : "", solve_b / 16);
-                ctx->prof_names[LDPC_AMD_PROF_ML_SOLVE] = nm;
-            }
-            hipEvent_t evs = prof_begin(ctx, 2);
-            switch (solve_b) {
-                case 128: LDPC_ML_SOLVE(8) break;
-                case 64: LDPC_ML_SOLVE(4) break;
-                case 32: LDPC_ML_SOLVE(2) break;
-                default: LDPC_ML_SOLVE(1) break;
-            }
-            prof_end(ctx, LDPC_AMD_PROF_ML_SOLVE, evs);
-            LDPC_HIP_TRY(ctx, hipGetLastError());
-            if (pi_nw > 0 && pi.verify) {
-                // Verified fast path: a frame whose received symbols are not a codeword makes the residual system INCONSISTENT, and
-                // then the bytes depend on which equations a solver uses.  The fast-path schedules therefore also evaluate the
-                // equations they did not use; the solve kernel flags a frame with a non-zero one (rec[7], nfail), and these two
-                // launches -- which leave after one load when nothing was flagged -- redo such frames in the reference's order.
-                ma.mode = 3;
-                hipLaunchKernelGGL(ml_kfn, dim3(grid), dim3(ml_threads), (size_t)total, ctx->stream, ma);
-                LDPC_HIP_TRY(ctx, hipGetLastError());
-                sv.round = 2; sv.work = (int32_t *)ctx->mllist.p + 26;
-                switch (solve_b) {
-                    case 128: LDPC_ML_SOLVE(8) break;
-                    case 64: LDPC_ML_SOLVE(4) break;
-                    case 32: LDPC_ML_SOLVE(2) break;
-                    default: LDPC_ML_SOLVE(1) break;
-                }
-                LDPC_HIP_TRY(ctx, hipGetLastError());
-            }
-#undef LDPC_ML_SOLVE
-        }
-        prof_end(ctx, LDPC_AMD_PROF_ML, ml_ev);
-        if (ma.use_solve) {   // this call's arena demand -> pinned host word, read by a later call (no wait here)
-            if (!ctx->ml_head_host) {
-                if (hipHostMalloc((void **)&ctx->ml_head_host, 64, hipHostMallocDefault) != hipSuccess) ctx->ml_head_host = nullptr;
-                else *ctx->ml_head_host = 0;
-            }
-            if (ctx->ml_head_host) {
-                LDPC_HIP_TRY(ctx, hipMemcpyAsync(ctx->ml_head_host, ma.ops_head, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-                ctx->ml_head_valid = true;
-            }
-        }
-        return LDPC_AMD_OK;
-    };
-
-    // frames out: behind the LAST launch of the ML stage (the redo launches of the fast path included), on the main stream: the
-    // frames it solved have no unknown symbol left.  One wavefront per slot of the residual list.
-    auto frames_finalize = [&]() -> int {
-        if (!frames_out) return LDPC_AMD_OK;
-        const int nw = 4;
-        const unsigned fgrid = (unsigned)std::min<int64_t>((nf + nw - 1) / nw, (int64_t)ctx->sm_count * 8);
-        hipLaunchKernelGGL(ldpc_frames_finalize_kernel, dim3(fgrid), dim3(64 * nw), 0, ctx->stream, cd.n, (const int32_t *)ctx->mllist.p,
-                           (const int32_t *)d.status, d.erased_out, d.residual_src);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-        return LDPC_AMD_OK;
-    };
-
-    PeelArgs pa{};
-    pa.code = cd; pa.lds = L; pa.nframes = nf; pa.sym = d.sym; pa.erased = d.erased; pa.in_rows = d.in_rows;
-    pa.max_sweeps = d.max_sweeps; pa.do_ml = d.do_ml; pa.out = d.out;
-    pa.sweeps = d.sweeps; pa.residual = d.residual; pa.status = d.status; pa.residual_sys = rsys_out; pa.erased_out = d.erased_out;
-    pa.ml_list = (int32_t *)ctx->mllist.p; pa.ml_state = (uint8_t *)ctx->mlstate.p;
-
-    // ---- exact time-stamp relaxation instead of the serial per-solve loop (peel_relax.inc) when the keys fit 16 bits: S = 1 decode
-    //      (mode 0), the pattern-only runs (mode 1), the packet path's schedules (mode 2).  The encoder's one-sweep chain and
-    //      everything else keep ldpc_peel_kernel.  Returns 1: launched, 0: not applicable, < 0: error.
-    uint32_t *pa_lists = nullptr;  // packets: the steps' column lists in schedule order (peel_relax.inc mode 2 -> packet kernel set-up)
-    bool pa_lists_on = false;
-    uint32_t *pa_pull = nullptr;   // packets: per-step records of the paired-level schedules (peel_relax.inc mode 2 -> packet kernel)
-    int pa_pairs = 0;
-    int logM = 0;
-    while ((1 << logM) < cd.mpad) logM++;
-    const bool relax_ok = kn.peel_relax != 0 && d.erased != nullptr && d.in_rows == cd.n && cd.degpad <= 16 && cd.n <= 32767 &&
-                          d.max_sweeps <= 62 && ((long)(d.max_sweeps + 1) << logM) <= 65535;
-    auto relax_launch = [&](int mode) -> int {
-        if (!relax_ok) return 0;
-        RelaxArgs ra{};
-        ra.n = cd.n; ra.k = cd.k; ra.m = cd.m; ra.mpad = cd.mpad; ra.logM = logM;
-        ra.rx_off = cd.rx_off; ra.ell_logc = cd.rx_logc; ra.ell_coef = cd.ell_coef;
-        ra.nframes = nf; ra.sym = d.sym; ra.erased = d.erased; ra.max_sweeps = d.max_sweeps; ra.do_ml = mode == 1 ? 0 : d.do_ml;
-        ra.out = d.out; ra.sweeps = d.sweeps; ra.residual = d.residual; ra.status = d.status; ra.residual_sys = rsys_out; ra.erased_out = d.erased_out;
-        ra.ml_list = (int32_t *)ctx->mllist.p; ra.ml_state = (uint8_t *)ctx->mlstate.p; ra.err = ctx->dev_err_host;
-        ra.sched_hdr = pa.sched_hdr; ra.sched_steps = pa.sched_steps; ra.sched_lvlend = pa.sched_lvlend; ra.sched_invc = pa.sched_invc;
-        ra.big_list = pa.big_list; ra.tcap = pa.tcap;
-        ra.sched_pull = pa_pull; ra.pairs = (mode == 2 && pa_pull) ? 1 : 0;
-        ra.sched_lists = mode == 2 ? pa_lists : nullptr; ra.cell = cd.cell; ra.cdw = cd.maxcoldeg; ra.cdw_shift = cd.cdw_shift;
-        // LDS plan: per frame its keys / values, solver and order lists (packets: + the level histogram); the code tables once per
-        // workgroup (or from global memory).  Frames per CU = workgroups per CU x wavefronts per workgroup; the tables in LDS for short
-        // batches (a single round is latency bound), in global memory when the batch is deep and that puts >= 1.3x more frames on a CU
-        // (measured: (2040,1530) 59 -> 70 M frames/s, (4080,3060) 23 -> 27 M on 65536 frames; 4096 frames: 53 M with the LDS copy, 34 M without).
-        auto plan = [&](bool gt_, int w_, RelaxLds &Lr) {
-            int off = 0;
-            Lr.off16 = off; if (!gt_) off += align_up(2 * cd.degpad * cd.mpad, 16);
-            Lr.logc8 = off; if (!gt_ && mode == 0) off += align_up(cd.degpad * cd.mpad, 16);
-            Lr.lg = off; off += 256;
-            Lr.ex = off; off += 512;
-            Lr.wave0 = off;
-            int w = 0;
-            Lr.key = w; w += align_up(2 * (cd.n + 1), 16);
-            Lr.fire = w; w += align_up(2 * cd.mpad, 16);
-            Lr.order = w; w += align_up(2 * cd.mpad, 16);
-            // (mode 2: the per-sweep counts of the time sort live at the start of the level histogram, which is not in use yet then --
-            // with them apart the (2040,1530) frame state is 9472 bytes and only 15 frames fit a CU: a 4096-frame batch needs 16)
-            Lr.cnt = w; if (mode != 2) w += 256;
-            Lr.hist = w; if (mode == 2) w += align_up(std::max(4 * (cd.m + 2), 256), 16);
-            Lr.dep = w; if (mode == 2) w += align_up(cd.mpad, 16);
-            Lr.sinv = w; if (mode == 2) w += align_up(cd.mpad, 16);
-            Lr.wave_stride = w;
-            Lr.total = off + w_ * w;
-        };
-        auto best_plan = [&](bool gt_, int &w_best, RelaxLds &L_best) -> int {
-            int best_f = 0, best_score = 0;
-            const int wcap = kn.peel_wpb > 0 ? std::min(16, kn.peel_wpb) : 16;
-            for (int w_ = 1; w_ <= wcap; w_++) {
-                RelaxLds t;
-                plan(gt_, w_, t);
-                if (t.total > kLdsMax) break;
-                const int wgs = kLdsMax / t.total;
-                const int frames = kn.peel_wpb > 0 ? w_ : std::min(32, wgs * w_);
-                // without tables to stage, two (or more) smaller workgroups per CU beat one large one holding a frame more
-                // ((4080,3060), 65536 frames: 6 x 2 frames 2.20 ms, 13 x 1 2.30 ms): a tenth of a bonus
-                const int score = frames * ((gt_ && wgs >= 2 && kn.peel_wpb <= 0) ? 11 : 10);
-                if (score >= best_score) { best_score = score; best_f = frames; w_best = w_; L_best = t; }
-            }
-            return best_f;
-        };
-        int w_l = 1, w_g = 1;
-        RelaxLds L_l{}, L_g{};
-        const int f_l = best_plan(false, w_l, L_l), f_g = best_plan(true, w_g, L_g);
-        if (f_l <= 0 && f_g <= 0) return 0;
-        const bool deep = nf >= (int64_t)3 * std::max(f_l, 1) * ctx->sm_count;
-        const bool use_gt = kn.peel_gt == 1 || f_l == 0 || (kn.peel_gt != 0 && deep && f_g * 10 >= f_l * 13);
-        const int wr = use_gt ? w_g : w_l;
-        ra.lds = use_gt ? L_g : L_l;
-        ctx->last_plan[0] = wr; ctx->last_plan[1] = use_gt ? f_g : f_l; ctx->last_plan[2] = use_gt ? 1 : 0;
-        ctx->last_plan[3] = ra.lds.total; ctx->last_plan[4] = ra.lds.wave_stride;
-        const dim3 g((unsigned)((nf + wr - 1) / wr)), b((unsigned)(wr * 64));
-        char nm[96];
-        snprintf(nm, sizeof(nm), "ldpc_peel_relax_kernel<%d, %s, %d>", cd.degpad, use_gt ? "true" : "false", mode);
-        ctx->prof_names[LDPC_AMD_PROF_PEEL] = nm;
-        hipEvent_t ev = prof_begin(ctx);
-        bool launched = false;
-#define LDPC_RELAX_CASE(D, G, MD)                                                                                        \
-    if (!launched && cd.degpad == D && use_gt == G && mode == MD) {                                                      \
-        auto kfn = ldpc_peel_relax_kernel<D, G, MD>;                                                                     \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                                           \
-        hipLaunchKernelGGL(kfn, g, b, (size_t)ra.lds.total, ctx->stream, ra);                                            \
-        launched = true;                                                                                                 \
-    }
-#define LDPC_RELAX_DEG(D)                                                                                                \
-    LDPC_RELAX_CASE(D, false, 0) LDPC_RELAX_CASE(D, true, 0) LDPC_RELAX_CASE(D, false, 1) LDPC_RELAX_CASE(D, true, 1)    \
-    LDPC_RELAX_CASE(D, false, 2) LDPC_RELAX_CASE(D, true, 2)
-        LDPC_RELAX_DEG(8) LDPC_RELAX_DEG(14) LDPC_RELAX_DEG(16)
-#undef LDPC_RELAX_DEG
-#undef LDPC_RELAX_CASE
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-        prof_end(ctx, LDPC_AMD_PROF_PEEL, ev);
-        return launched ? 1 : 0;
-    };
-    if (fused || d.flags_only) {
-        const int rl = relax_launch(d.flags_only ? 1 : 0);
-        if (rl < 0) return rl;
-        if (rl > 0) {
-            if (d.flags_only) return LDPC_AMD_OK;
-            if (d.do_ml) {
-                if ((rc = ml_prepare())) return rc;
-                if ((rc = ml_front())) return rc;
-                if ((rc = ml_back())) return rc;
-                if ((rc = frames_finalize())) return rc;
-            }
-            return LDPC_AMD_OK;
-        }
-    }
-    if (d.flags_only) {
-        LDPC_HIP_TRY(ctx, launch_peel_t<false>(pa, wpb, ctx->stream));
-        return LDPC_AMD_OK;
-    }
-    {
-        char nm[96];
-        snprintf(nm, sizeof(nm), "ldpc_peel_kernel<%d, %s, %s>", cd.degpad, fused ? "true" : "false", gt ? "true" : "false");
-        ctx->prof_names[LDPC_AMD_PROF_PEEL] = nm;
-    }
-    if (fused) {
-        hipEvent_t ev = prof_begin(ctx);
-        if (gt) { LDPC_HIP_TRY(ctx, (launch_peel_t<true, true>(pa, wpb, ctx->stream))); }
-        else { LDPC_HIP_TRY(ctx, launch_peel_t<true>(pa, wpb, ctx->stream)); }
-        prof_end(ctx, LDPC_AMD_PROF_PEEL, ev);
-    } else {
-        const size_t hdr = (size_t)nf * 2 * 4, st = (size_t)nf * cd.m * 4, le = (size_t)nf * (cd.m + 1) * 2, iv = (size_t)nf * cd.m;
-        const size_t o1 = (hdr + 255) & ~(size_t)255, o2 = (o1 + st + 255) & ~(size_t)255, o3 = (o2 + le + 255) & ~(size_t)255;
-        if ((rc = scratch_reserve(ctx, ctx->sched, o3 + iv))) return rc;
-        unsigned char *base = (unsigned char *)ctx->sched.p;
-        pa.sched_hdr = (uint32_t *)base; pa.sched_steps = (uint32_t *)(base + o1); pa.sched_lvlend = (uint16_t *)(base + o2);
-        pa.sched_invc = base + o3;
-        if (use_scatter) {
-            pa.tcap = plan.tcap;
-            pa.big_list = plan.two_tier ? (int32_t *)ctx->biglist.p : nullptr;
-        }
-        hipEvent_t ev = nullptr;
-        if (use_scatter && relax_ok && kn.scatter_pairs != 0) {   // paired levels: 16 bytes per step for the records the packet kernel reads at set-up
-            if ((rc = scratch_reserve(ctx, ctx->schedpull, (size_t)nf * cd.m * 16))) return rc;
-            pa_pull = (uint32_t *)ctx->schedpull.p;
-        }
-        if (use_scatter && relax_ok && kn.scatter_lists != 0) {
-            if ((rc = scratch_reserve(ctx, ctx->schedlists, (size_t)nf * cd.m * cd.maxcoldeg * 4))) return rc;
-            pa_lists = (uint32_t *)ctx->schedlists.p;
-        }
-        const int rl = relax_launch(2);   // the schedules by relaxation when its keys fit (else, and with PEEL_RELAX=0: the serial loop)
-        if (rl < 0) return rl;
-        pa_pairs = (rl > 0 && pa_pull) ? 1 : 0;
-        pa_lists_on = rl > 0 && pa_lists;
-        if (rl == 0) {
-            ev = prof_begin(ctx);
-            LDPC_HIP_TRY(ctx, launch_peel_t<false>(pa, wpb, ctx->stream));
-            prof_end(ctx, LDPC_AMD_PROF_PEEL, ev);
-        }
-
-        if (d.do_ml) {
-            if ((rc = ml_prepare())) return rc;
-            ml_prepared = true;
-            if (ml_overlap) {
-                if ((rc = ml_front())) return rc;
-                ml_front_done = true;
-            }
-        }
-        if (use_scatter) {
-            ScatterArgs sa{};
-            sa.code = cd; sa.S = d.S; sa.nslices = plan.nslices; sa.nframes = nf; sa.sym = d.sym; sa.erased = d.erased; sa.out = d.out;
-            sa.in_rows = cd.n; sa.static_sched = 0; sa.inplace = d.inplace;
-            sa.pin_src = d.pin.src; sa.pin_pkt = d.pin.packets; sa.pin_stage = d.pin.stage; sa.pin_plen = d.pin.plen;
-            sa.dbg = kn.ml_dbg; sa.err = ctx->dev_err_host; sa.xl_setup = kn.scatter_xl;
-            sa.sched_pull = pa_pull; sa.pairs = pa_pairs; sa.sched_lists = pa_lists_on ? pa_lists : nullptr;
-            sa.sched_hdr = pa.sched_hdr; sa.sched_steps = pa.sched_steps; sa.sched_lvlend = pa.sched_lvlend;
-            sa.sched_invc = pa.sched_invc;
-            ev = prof_begin(ctx);
-            if ((rc = launch_scatter(ctx, plan, sa, (int32_t *)ctx->biglist.p))) return rc;
-            prof_end(ctx, LDPC_AMD_PROF_APPLY, ev);
-        } else {
-        ApplyArgs aa{};
-        aa.code = cd; aa.S = d.S; aa.nframes = nf; aa.sym = d.sym; aa.erased = d.erased; aa.in_rows = d.in_rows; aa.out = d.out;
-        aa.sched_hdr = pa.sched_hdr; aa.sched_steps = pa.sched_steps; aa.sched_lvlend = pa.sched_lvlend;
-        const size_t lds = (size_t)cd.m * 4 + (size_t)(cd.m + 2) * 2;
-        ctx->prof_names[LDPC_AMD_PROF_APPLY] = words ? "ldpc_apply_words_kernel" : "ldpc_apply_kernel";
-        ev = prof_begin(ctx);
-        if (words) hipLaunchKernelGGL(ldpc_apply_words_kernel, dim3((unsigned)nf), dim3(512), lds, ctx->stream, aa);
-        else
-        hipLaunchKernelGGL(ldpc_apply_kernel, dim3((unsigned)nf), dim3(512), lds, ctx->stream, aa);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-        prof_end(ctx, LDPC_AMD_PROF_APPLY, ev);
-        }
-    }
-
-    if (d.do_ml) {
-        if (!ml_prepared && (rc = ml_prepare())) return rc;
-        if (!ml_front_done && (rc = ml_front())) return rc;
-        if ((rc = ml_back())) return rc;
-        if ((rc = frames_finalize())) return rc;
+        int rcc = decode_chunk(ctx, c, fused, words);
+        if (rcc) return rcc;
     }
     return LDPC_AMD_OK;
 }
@@ -2827,81 +2993,25 @@ static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64
         return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
     const Knobs &kn = ctx->knobs;
     if (!kn.apply_gather && cd.maxcoldeg <= 16) {
-        // scatter form with the static schedule: source rows read once, all m accumulators in LDS
-        ScatterPlan plan = plan_scatter(kn, cd, S);
         // (packets: a frame's rows are 8 + S bytes apart -- the 32-bit offsets and 24-bit multiplies must hold for that stride)
         if (pkt_out && ((uint64_t)cd.n * (uint64_t)(S + 8) >= (1ull << 32) || S + 8 >= (1 << 24))) return kEncodeNotFused;
-        if (plan.lpr > 0) {
-            plan.two_tier = false; plan.tcap = cd.m; plan.lds1 = plan.lds2;
-            // The encoder needs all m accumulators (every check is a step), which at 256-byte row pieces fills the LDS with
-            // ONE workgroup per CU.  With 128-byte pieces and the tables the static schedule does not need left out (check ->
-            // slot table, received-row list) two workgroups fit, and one streams while the other runs its 27 levels.
-            const int eb = kn.enc_b;
-            // grouped static schedule (levels collapsed offline): used when the code has one and its lists fit the LDS plan below
-            bool grouped = kn.enc_group != 0 && cd.encg_nlevels > 0;
-            const int nlev_plan = grouped ? cd.encg_nlevels : cd.enc_nlevels;
-            const int gent2 = (cd.encg_ent_n + 7) & ~7;
-            const int need_g = 3 * gent2 + 2 * ((cd.m + 8) & ~7) + ((cd.m + 15) & ~15);
-            if (plan.lpr == 16 && eb == 128 && ((S % 128) == 0 || words)) {   // (word form: the last 128-byte piece overlaps)
-                ScatterPlan q = plan;
-                int off = 0;
-                q.o_tgt = off; off += align_up(2 * cd.m, 16);
-                q.o_invc = off; off += align_up(cd.m, 16);
-                q.o_lvl = off; off += align_up(2 * (nlev_plan + 2), 16);   // (level / group offsets: as many as this schedule has)
-                q.o_ctr = off; off += 288;
-                q.o_mt = off;                // (the tables sit in front of the accumulators: added to the total below)
-                q.o_soc = off; off += align_up(2 * cd.k, 16) >= cd.n ? align_up(2 * cd.k, 16) : align_up(cd.n, 16);   // row kinds (u8), then the source-row list (u16 [k])
-                q.soc_bytes = align_up(2 * cd.k, 16) >= cd.n ? align_up(2 * cd.k, 16) : align_up(cd.n, 16);
-                q.o_chk = off;                               // unused in static mode
-                if (8192 + cd.m * 128 + off <= kLdsMax / 2) {
-                    q.lpr = 8; q.nslices = (S + 127) / 128; q.lds1 = q.lds2 = 8192 + cd.m * 128 + off;
-                    q.two_tier = true;    // (only selects the 8-waves-per-SIMD instantiation; tcap = m: no frame goes to tier 2)
-                    plan = q;
-                }
-            }
-            // the compact lists of the parity symbols for the level phase: over the row tables (dead by then), which end the layout --
-            // the allocation grows by what they need beyond those tables when that still fits
-            int enc_clist = 0;
-            const int soc_off = 8192 + align_up(cd.m * 16 * plan.lpr, 16) + plan.o_soc;
-            const int limit = (plan.two_tier && plan.lpr == 8) ? kLdsMax / 2 : kLdsMax;
-            if (grouped) {
-                if (soc_off + need_g <= limit) plan.lds1 = plan.lds2 = std::max(plan.lds1, soc_off + need_g);
-                else grouped = false;   // (the plan's level table was sized for the groups: still enough? no -- re-plan below)
-            }
-            if (!grouped && kn.enc_group != 0 && cd.encg_nlevels > 0 && nlev_plan != cd.enc_nlevels) {
-                // the lists did not fit: the level table of the plan above was sized for the groups, the plain schedule has more levels
-                const int saved = ctx->knobs.enc_group;
-                ctx->knobs.enc_group = 0;
-                const int rc_ = launch_encode_impl(ctx, cd, S, nframes, src, cw, pkt_out, pkt_hdr);
-                ctx->knobs.enc_group = saved;
-                return rc_;
-            }
-            if (!grouped && kn.enc_clist && cd.enc_lst_n > 0) {
-                const int need = 4 * cd.enc_lst_n + align_up(2 * (cd.m + 1), 16);
-                if (soc_off + need <= limit) {
-                    enc_clist = 1;
-                    plan.lds1 = plan.lds2 = std::max(plan.lds1, soc_off + need);
-                }
-            }
+        // scatter form with the static schedule: source rows read once, all m accumulators in LDS
+        const EncodePlan e = plan_encode(kn, cd, S, kn.enc_group != 0);
+        if (e.plan.lpr > 0) {
             ScatterArgs sa{};
-            sa.code = cd; sa.S = S; sa.nslices = plan.nslices; sa.nframes = nframes; sa.sym = src; sa.erased = nullptr; sa.out = cw;
-            sa.in_rows = cd.k; sa.static_sched = 1; sa.enc_clist = enc_clist; sa.err = ctx->dev_err_host;
-            sa.enc_group = grouped ? 1 : 0;
+            sa.code = cd; sa.S = S; sa.nslices = e.plan.nslices; sa.nframes = nframes; sa.sym = src; sa.erased = nullptr; sa.out = cw;
+            sa.in_rows = cd.k; sa.static_sched = 1; sa.enc_clist = e.clist; sa.err = ctx->dev_err_host;
+            sa.enc_group = e.grouped ? 1 : 0;
             ctx->last_enc_grouped = sa.enc_group;
             sa.enc_list = kn.enc_list;   // measured slower (4.62 vs 4.14 ms): off unless asked for
             sa.pkt_out = pkt_out; sa.pkt_hdr = pkt_hdr;
-            return launch_scatter(ctx, plan, sa, nullptr);
+            return launch_scatter(ctx, e.plan, sa, nullptr);
         }
     }
     if (pkt_out) return kEncodeNotFused;
     ApplyArgs aa{};
     aa.code = cd; aa.S = S; aa.nframes = nframes; aa.sym = src; aa.erased = nullptr; aa.in_rows = cd.k; aa.out = cw;
-    const size_t lds = (size_t)cd.m * 4 + (size_t)(cd.m + 2) * 2;
-    if (words) hipLaunchKernelGGL(ldpc_apply_words_kernel, dim3((unsigned)nframes), dim3(512), lds, ctx->stream, aa);
-    else
-    hipLaunchKernelGGL(ldpc_apply_kernel, dim3((unsigned)nframes), dim3(512), lds, ctx->stream, aa);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    return LDPC_AMD_OK;
+    return launch_apply(ctx, aa, words, false);
 }
 
 int launch_encode(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, const uint8_t *src, uint8_t *cw)
@@ -2968,18 +3078,12 @@ static int launch_rs_decode_t(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_
         o += nw * L.wstride;
         const int64_t items = nblocks * nslices;
         const int grid = (int)std::min<int64_t>((items + nw - 1) / nw, (int64_t)ctx->sm_count * 96);
-#define LDPC_RS_PK(VWV, WPSV)                                                                                \
-    {                                                                                                        \
-        auto kfn = rs_decode_packets_kernel<VWV, WPSV, FRAMES && VWV == 1>;                                  \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));                               \
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * nw), (size_t)o, ctx->stream, a, L, nslices);          \
-    }
         // (one dword per lane compiled for four wavefronts per SIMD: 19.9 ms; for six / eight -- 80 / 64 registers, the Gauss-Jordan
         // part spills -- 31.0 / 26.6 ms)
-        if (vw == 4) LDPC_RS_PK(4, 2) else if (vw == 2) LDPC_RS_PK(2, 4) else LDPC_RS_PK(1, 4)
-#undef LDPC_RS_PK
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-        return LDPC_AMD_OK;
+        const dim3 g(grid), b(64 * nw);
+        if (vw == 4) return launch_lds(ctx, rs_decode_packets_kernel<4, 2, false>, g, b, (size_t)o, ctx->stream, a, L, nslices);
+        if (vw == 2) return launch_lds(ctx, rs_decode_packets_kernel<2, 4, false>, g, b, (size_t)o, ctx->stream, a, L, nslices);
+        return launch_lds(ctx, rs_decode_packets_kernel<1, 4, FRAMES>, g, b, (size_t)o, ctx->stream, a, L, nslices);
     }
     if (S == 1 && R <= 32 && rs.k <= 256 && !rs_generic) {
         // one wavefront per block, system in registers
@@ -3005,11 +3109,7 @@ static int launch_rs_decode_t(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_
         if (rc) return rc;
         a.ws = (uint8_t *)ctx->rsws.p;
     }
-    auto kfn = rs_decode_kernel<FRAMES>;
-    LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn)));
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(threads), (size_t)off, ctx->stream, a);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    return LDPC_AMD_OK;
+    return launch_lds(ctx, rs_decode_kernel<FRAMES>, dim3(grid), dim3(threads), (size_t)off, ctx->stream, a);
 }
 
 int launch_rs_decode(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks, const uint16_t *idx,
@@ -3069,19 +3169,13 @@ int launch_fpga_halves(ldpc_amd_ctx *ctx, const DevCode &code, int64_t nframes, 
     const size_t lds = (size_t)wave0 + (size_t)wpb * wstride;
     if (lds > (size_t)kLdsMax) return set_error(ctx, LDPC_AMD_EUNSUP, "FPGA perf decoder: LDS need %zu bytes", lds);
     const dim3 grid((unsigned)((nframes + wpb - 1) / wpb));
-#define LDPC_FPGA_HALVES(D)                                                                                     \
-    {                                                                                                          \
-        auto kfn = fpga_halves_kernel<D>;                                                                      \
-        LDPC_HIP_TRY(ctx, allow_max_lds(reinterpret_cast<const void *>(kfn))); \
-        hipLaunchKernelGGL(kfn, grid, dim3(64 * wpb), lds, ctx->stream, code, nframes, erased, num_iter, residual_sys, iterations, wave0, wstride); \
-    }
-    if (code.degpad <= 8) LDPC_FPGA_HALVES(8)
-    else if (code.degpad <= 14) LDPC_FPGA_HALVES(14)
-    else if (code.degpad <= 16) LDPC_FPGA_HALVES(16)
-    else LDPC_FPGA_HALVES(24)
-#undef LDPC_FPGA_HALVES
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    return LDPC_AMD_OK;
+    int rc = LDPC_AMD_OK;
+    const bool found = with_int<8, 14, 16, 24>(code.degpad, [&](auto D) {   // (the pads a code can have: api.cpp)
+        rc = launch_lds(ctx, fpga_halves_kernel<decltype(D)::value>, grid, dim3(64 * wpb), lds, ctx->stream, code, nframes, erased, num_iter, residual_sys,
+                        iterations, wave0, wstride);
+    });
+    if (!found) LDPC_HIP_TRY(ctx, hipErrorInvalidValue);
+    return rc;
 }
 
 #ifdef LDPC_AMD_STAMPS

@@ -5,7 +5,7 @@ is chosen (tools/ml_plant.py; tests/test_ml_planted_cpu.py asserts that every ca
 hundreds of rows below the diagonal in every column, all-zero rows in the first E logical positions of rank-deficient frames
 that are not codewords, E on either side of every multiple of 16 up to 64 and at 150 and 300, E = m and E = m + 1, breaks at the
 second, a middle and the last column, fewer and twice as many touched checks as unknowns, blocks no peeling gets through.
-Codes (600,300), (2048,1024), and (8192,4096) planted in rows >= 4000: 4096 checks is the ML stage's limit (launch_decode
+Codes (600,300), (2048,1024), and (8192,4096) planted in rows >= 4000: 4096 checks is the ML stage's limit (plan_ml; launch_decode
 answers LDPC_AMD_EUNSUP above it: the pivot key has 12-bit row fields), and registration and decode accept it.
 
 The library registers rows of up to 24 entries, so a block with ALL entries non-zero ends at E = 20 here (E = 64 is on the CPU

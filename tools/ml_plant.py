@@ -18,7 +18,7 @@ all-zero rows at the chosen positions.
                        symbols the sweeps solve first, all clear
 
 The library takes rows of up to 24 entries and its fast path (and the packet kernel's scatter plan) columns of up to 16
-(csrc/api.cpp, launch_decode); `plant` keeps inside both unless device=False.  A block with all T * E entries non-zero therefore
+(csrc/api.cpp; plan_ml and decode_chunk of csrc/kernels.hip); `plant` keeps inside both unless device=False.  A block with all T * E entries non-zero therefore
 ends at E = 20 on the GPU; `band` (w cyclic diagonals, w - 1 inactivations, fill inside the band) is the dense family beyond.
 Test infrastructure, not product code."""
 import os

@@ -37,7 +37,7 @@ MAX_DEG = 16        # 4-bit neighbour slot of the top-2 key
 
 # ---- the kernel's limits ----------------------------------------------------------------------------------------------------------
 def log_m(m):
-    """logM of launch_decode (kernels.hip: `while ((1 << logM) < cd.mpad) logM++`)."""
+    """logM of plan_relax (kernels.hip: `while ((1 << r.logM) < cd.mpad) r.logM++`)."""
     mpad = -(-m // CHUNK) * CHUNK
     lg = 0
     while (1 << lg) < mpad:
@@ -46,7 +46,7 @@ def log_m(m):
 
 
 def fits(m, max_sweeps):
-    """The sweep-cap half of launch_decode's `relax_ok`: the keys fit 16 bits and the sweeps fit the time sort's counters."""
+    """The sweep-cap half of plan_relax's `keys_fit` (kernels.hip): the keys fit 16 bits and the sweeps fit the time sort's counters."""
     return max_sweeps <= MAX_SWEEPS and ((max_sweeps + 1) << log_m(m)) <= 65535
 
 

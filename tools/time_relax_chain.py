@@ -4,7 +4,7 @@ default) against the serial per-solve loop (PEEL_RELAX = 0), PEEL kind of the li
 
 The relaxation settles one check of a chunk per round on a chain, about m * m / 64 evaluations against m serial solves
 (DESIGN.md section 4.1b); this prints what that costs, one JSON line per erasure pattern, so that a later change can decide
-whether launch_decode's `relax_ok` should look at the code's chain depth.
+whether plan_relax's `keys_fit` (kernels.hip) should look at the code's chain depth.
 
     python tools/time_relax_chain.py [--m 1024] [--frames 4096] [--reps 5] [--out FILE]"""
 import argparse
