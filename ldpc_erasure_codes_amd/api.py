@@ -63,6 +63,11 @@ EXPORTS_RECEIVER = ["ldpc_amd_fec_rx_dev_decode_many", "ldpc_amd_fec_rx_dev_deco
 RECEIVER_PATHS = ("none", "fused", "composed")
 # every symbol include/ldpc_erasure_amd_words.h declares (word-sized symbols: any S that is a multiple of 4)
 EXPORTS_WORDS = ["ldpc_amd_set_symbol_unit", "ldpc_amd_get_symbol_unit"]
+# every symbol include/ldpc_erasure_amd_flows.h declares (the multi-flow device receiver: many FEC streams per call)
+EXPORTS_FLOWS = [
+    "ldpc_amd_fec_rx_flows_create", "ldpc_amd_fec_rx_flows_destroy", "ldpc_amd_fec_rx_flows_push_many", "ldpc_amd_fec_rx_flows_decode_many",
+    "ldpc_amd_fec_rx_flows_flush", "ldpc_amd_fec_rx_flows_decode_flush", "ldpc_amd_fec_rx_flows_dropped",
+]
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
@@ -180,6 +185,17 @@ def load_library():
         L.ldpc_amd_fec_rx_dev_decode_many.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i64)]
         L.ldpc_amd_fec_rx_dev_decode_flush.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]
         L.ldpc_amd_fec_receiver_info.argtypes = [vp, C.POINTER(i32)]
+    # the multi-flow receiver (include/ldpc_erasure_amd_flows.h)
+    if hasattr(L, "ldpc_amd_fec_rx_flows_create"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_rx_flows_create.argtypes = [vp, i32, i32, i32, i32, C.POINTER(vp)]
+        L.ldpc_amd_fec_rx_flows_destroy.argtypes = [vp]
+        L.ldpc_amd_fec_rx_flows_destroy.restype = None
+        L.ldpc_amd_fec_rx_flows_push_many.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
+        L.ldpc_amd_fec_rx_flows_decode_many.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+        L.ldpc_amd_fec_rx_flows_flush.argtypes = [vp, i32, vp, vp, C.POINTER(i32)]
+        L.ldpc_amd_fec_rx_flows_decode_flush.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]
+        L.ldpc_amd_fec_rx_flows_dropped.argtypes = [vp, i32]
+        L.ldpc_amd_fec_rx_flows_dropped.restype = i64
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -617,6 +633,11 @@ class Context:
         self._check(self._L.ldpc_amd_fec_receiver_info(self._h, info), "fec_receiver_info")
         return {"path": RECEIVER_PATHS[info[0]], "scratch_bytes": int(info[1]), "blocks": int(info[2])}
 
+    # -- the multi-flow receiver (include/ldpc_erasure_amd_flows.h)
+    def fec_rx_flows(self, nflows, n, k, S):
+        """nflows device receivers that are fed, planned and decoded together, one call for all of them (FecRxFlows)."""
+        return FecRxFlows(self, nflows, n, k, S)
+
 
 # ---------------------------------------------------------------------------------------------------------
 # Host-side wire format (include/ldpc_erasure_amd_wire.h): FEC header, packetiser, two-buffer reassembler.
@@ -777,6 +798,96 @@ class FecRxDevice:
     def close(self):
         if getattr(self, "_h", None):
             self._L.ldpc_amd_fec_rx_dev_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FecRxFlows:
+    """nflows FecRxDevice in one object (include/ldpc_erasure_amd_flows.h): one packet array segmented by flow -- flow f owns the
+    packets flow_begin[f] .. flow_begin[f+1]-1 -- is planned for all flows at once and read back once, and every block that closed, of
+    every flow, is decoded in one launch.  Flow f behaves exactly like a FecRxDevice fed its segment with max_blocks =
+    max_blocks_per_flow.  The closed blocks come out dense in flow order: flow 0's in closing order, then flow 1's, ...; flow f's
+    start at closes[:f].sum().  Close it before its Context."""
+
+    def __init__(self, ctx, nflows, n, k, S):
+        self._ctx, self._L = ctx, ctx._L
+        h = C.c_void_p()
+        ctx._check(self._L.ldpc_amd_fec_rx_flows_create(ctx._h, nflows, n, k, S, C.byref(h)), "fec_rx_flows_create")
+        self._h, self.nflows, self.n, self.k, self.S = h, nflows, n, k, S
+
+    _device = FecRxDevice._device
+    _frames = FecRxDevice._frames
+
+    def _segments(self, packets, flow_begin, max_blocks_per_flow):
+        import torch
+        assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.shape[1] == 8 + self.S
+        fb = np.ascontiguousarray(flow_begin, dtype=np.int64)
+        assert fb.shape == (self.nflows + 1,) and int(fb[-1]) == packets.shape[0]
+        slots = max(self.nflows * max(max_blocks_per_flow, 1), 1)
+        return (fb, slots, np.zeros(slots, dtype=np.int32), np.zeros(self.nflows, dtype=np.int32), np.zeros(self.nflows, dtype=np.int64),
+                _ptr(packets) if packets.numel() else None)
+
+    def push_many(self, packets, flow_begin, max_blocks_per_flow):
+        """packets: torch uint8 [P][8+S] on the device, flow_begin: nflows + 1 packet indices.  Returns (closes int32 [nflows],
+        blocks int32 [T], sym torch uint8 [T][n][S], erased torch uint8 [T][n], consumed int64 [nflows])."""
+        import torch
+        fb, slots, blocks, closes, consumed, pp = self._segments(packets, flow_begin, max_blocks_per_flow)
+        sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=packets.device)
+        er = torch.empty((slots, self.n), dtype=torch.uint8, device=packets.device)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_push_many(self._h, pp, fb.ctypes.data, _ptr(sym), _ptr(er), blocks.ctypes.data,
+                                                                     closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
+                             "fec_rx_flows_push_many")
+        return closes, blocks[:T], sym[:T], er[:T], consumed
+
+    def decode_many(self, code, packets, flow_begin, max_blocks_per_flow, max_sweeps=10, do_ml=1):
+        """push_many + Context.decode_frames of all flows in one call -> (closes int32 [nflows], blocks int32 [T], DecodedFrames of
+        the T closed blocks, consumed int64 [nflows]).  Fused or composed as FecRxDevice.decode_many would be
+        (Context.fec_receiver_info() says which path ran).  Keep `packets` alive until the context's stream has passed the call."""
+        fb, slots, blocks, closes, consumed, pp = self._segments(packets, flow_begin, max_blocks_per_flow)
+        fr = self._frames(slots)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_decode_many(
+            self._h, code, pp, fb.ctypes.data, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status),
+            _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
+            "fec_rx_flows_decode_many")
+        return closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed
+
+    def flush(self, flow):
+        """None, or (block number, sym torch [n][S], erased torch [n]) of the block the end of flow `flow`'s stream closes."""
+        import torch
+        sym = torch.empty((self.n, self.S), dtype=torch.uint8, device=self._device())
+        er = torch.empty(self.n, dtype=torch.uint8, device=self._device())
+        blk = C.c_int(-1)
+        rc = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_flush(self._h, flow, _ptr(sym), _ptr(er), C.byref(blk)), "fec_rx_flows_flush")
+        return (blk.value, sym, er) if rc == 1 else None
+
+    def decode_flush(self, flow, code, max_sweeps=10, do_ml=1):
+        """None, or (block number, DecodedFrames of that one block) for the block the end of flow `flow`'s stream closes."""
+        fr = self._frames(1)
+        blk = C.c_int(-1)
+        rc = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_decode_flush(
+            self._h, flow, code, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status), _ptr(fr.erased_out),
+            _ptr(fr.residual_src), C.byref(blk)), "fec_rx_flows_decode_flush")
+        return (blk.value, fr) if rc == 1 else None
+
+    @property
+    def dropped(self):
+        """int64 [nflows]: packets of each flow that went to no block so far"""
+        return np.array([self._L.ldpc_amd_fec_rx_flows_dropped(self._h, f) for f in range(self.nflows)], dtype=np.int64)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ldpc_amd_fec_rx_flows_destroy(self._h)
             self._h = None
 
     def __enter__(self):

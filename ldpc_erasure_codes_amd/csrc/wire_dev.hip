@@ -34,6 +34,7 @@
 #include "../../include/ldpc_erasure_amd_wire_dev.h"
 #include "../../include/ldpc_erasure_amd_sender.h"
 #include "../../include/ldpc_erasure_amd_receiver.h"
+#include "../../include/ldpc_erasure_amd_flows.h"
 
 using namespace ldpc_amd;
 
@@ -132,7 +133,8 @@ __device__ __forceinline__ bool close_rule(int c, int x, int n, int kd, int km)
 // host (a block whose count reached n through the next block's packets closes at the packet after the rotation).
 // The loop is bounded: every iteration assigns at least one packet or ends its group, so a call takes at most
 // npackets + closes + groups iterations; a cap on that reports R_ERR instead of spinning on a bad stream.
-__global__ __launch_bounds__(64) void fec_rx_scan(const uint32_t *__restrict__ dense, int64_t np, int n, int kd, int km,
+// The body is one function: fec_rx_scan runs it on a call's packets, fec_rx_scan_flows on the segment of one flow per workgroup.
+__device__ __forceinline__ void fec_rx_scan_body(const uint32_t *__restrict__ dense, int64_t np, int n, int kd, int km,
                                                  int max_blocks, int cur, int nxt, int ccnt, int ncnt,
                                                  int32_t *__restrict__ dest, int32_t *__restrict__ res)
 {
@@ -204,6 +206,13 @@ __global__ __launch_bounds__(64) void fec_rx_scan(const uint32_t *__restrict__ d
         res[R_CONSUMED_LO] = (int32_t)(uint32_t)consumed; res[R_CONSUMED_HI] = (int32_t)(consumed >> 32);
         res[R_DROPPED_LO] = (int32_t)(uint32_t)dropped; res[R_DROPPED_HI] = (int32_t)(dropped >> 32);
     }
+}
+
+__global__ __launch_bounds__(64) void fec_rx_scan(const uint32_t *__restrict__ dense, int64_t np, int n, int kd, int km,
+                                                 int max_blocks, int cur, int nxt, int ccnt, int ncnt,
+                                                 int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    fec_rx_scan_body(dense, np, n, kd, km, max_blocks, cur, nxt, ccnt, ncnt, dest, res);
 }
 
 // ---- (c) last writer wins ---------------------------------------------------------------------------------------------
@@ -287,6 +296,143 @@ __global__ __launch_bounds__(kThreads) void fec_rx_sources(const int32_t *__rest
         const int i = (int)(r - (int64_t)s * n);
         const int w = win[r];
         const int row = ((cb + s) & 1) * n + i;   // the block's staging row
+        uint32_t word = kRowErased;
+        if (w >= 0) word = (uint32_t)w;
+        else if (s < 2 && stage_er[row] == 0) word = kRowStaged | (uint32_t)row;
+        src[r] = word;
+        er[r] = word == kRowErased ? 1 : 0;
+    }
+}
+
+// ---- the multi-flow receiver (include/ldpc_erasure_amd_flows.h) ---------------------------------------------------------
+// The same five steps for nflows streams whose packets lie in one array, flow f's in begin .. begin + len - 1.  (a) is flow-agnostic.
+// (b) runs fec_rx_scan's body once per flow, one wavefront each: serials, and with them `dest`, are LOCAL to the flow.  The host
+// reads every flow's result record back in one copy, takes the prefix sum of the closes -- flow f's closed blocks are the GLOBAL
+// slots base[f] .. base[f] + closes[f] - 1, T slots in all -- and hands the kernels behind it one record per flow (FlowTab).
+// The winners' table is [(T + 2 nflows)][n]: the closed slots first, then the two open blocks of flow 0, of flow 1, ...
+// The staging planes are [nflows][2][n][S] / [nflows][2][n]: serial s of flow f lives in plane f * 2 + ((cb[f] + s) & 1), so row i
+// of it is staging row (f * 2 + b) * n + i of ONE base -- the row-source word of the packets-in decoder (PacketRows) needs no more.
+struct FlowIn {    // written by the host before the plan
+    int64_t begin, len;   // the flow's segment of the packet array
+    int cur, nxt, ccnt, ncnt;
+};
+struct FlowTab {   // written by the host behind the plan
+    int64_t begin, used;   // the packets the flow consumed: begin .. begin + used - 1
+    int base, closes, cb, pad;
+};
+
+// (b) grid: nflows workgroups of one wavefront; res: [nflows][R_WORDS + max_blocks]
+__global__ __launch_bounds__(64) void fec_rx_scan_flows(const uint32_t *__restrict__ dense, const FlowIn *__restrict__ in, int n, int kd,
+                                                       int km, int max_blocks, int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    const FlowIn f = in[blockIdx.x];
+    fec_rx_scan_body(dense + f.begin, f.len, n, kd, km, max_blocks, f.cur, f.nxt, f.ccnt, f.ncnt, dest + f.begin,
+                     res + (int64_t)blockIdx.x * (R_WORDS + max_blocks));
+}
+
+// slot -> flow, [T]: one workgroup per flow
+__global__ __launch_bounds__(64) void fec_rx_flow_slots(const FlowTab *__restrict__ tab, int32_t *__restrict__ slot_flow)
+{
+    const FlowTab f = tab[blockIdx.x];
+    for (int s = threadIdx.x; s < f.closes; s += 64) slot_flow[f.base + s] = (int)blockIdx.x;
+}
+
+// (c) grid: (x, nflows); over each flow's consumed prefix only.  The packet index is the global one: the last copy wins, as on the host.
+__global__ __launch_bounds__(kThreads) void fec_rx_winners_flows(const uint32_t *__restrict__ dense, const int32_t *__restrict__ dest,
+                                                                const FlowTab *__restrict__ tab, int n, int T, int32_t *__restrict__ win)
+{
+    const FlowTab f = tab[blockIdx.y];
+    for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < f.used; q += (int64_t)gridDim.x * kThreads) {
+        const int64_t p = f.begin + q;
+        const int s = dest[p];
+        if (s < 0) continue;
+        const int64_t row = s < f.closes ? (int64_t)f.base + s : (int64_t)T + 2 * (int64_t)blockIdx.y + (s - f.closes);
+        atomicMax(&win[row * n + (dense[p] & 0xffffu)], (int32_t)p);
+    }
+}
+
+struct FlowMoveArgs {
+    const uint8_t *packets;
+    int64_t plen;
+    const int32_t *win;         // [(T + 2 nflows)][n]
+    const FlowTab *tab;         // [nflows]
+    const int32_t *slot_flow;   // [T]
+    uint8_t *stage_sym;         // [nflows][2][n][S]
+    uint8_t *stage_er;          // [nflows][2][n]
+    uint8_t *sym_out;           // gather: [count][n][S], the closed slots first .. first + count - 1
+    uint8_t *er_out;            // gather: [count][n]
+    int n, S, T, nflows;
+    int first, count;
+};
+
+// fec_rx_move for all flows.  Gather: row r is symbol i of global slot j = first + r / n, which is serial j - base[f] of flow f =
+// slot_flow[j].  Staging update: row r is symbol i of open block o = 0, 1 of flow f = r / (2 n), its serial closes[f] + o.
+template <bool GATHER, bool V16>
+__global__ __launch_bounds__(kThreads) void fec_rx_move_flows(FlowMoveArgs a)
+{
+    const int q = V16 ? a.S / 16 : a.S;
+    const int64_t rows = GATHER ? (int64_t)a.count * a.n : 2 * (int64_t)a.nflows * a.n;
+    const int64_t total = rows * q;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
+        const int64_t r = t / q;
+        const int c = (int)(t - r * q);
+        const int64_t blk = r / a.n;
+        const int i = (int)(r - blk * a.n);
+        int f, s;
+        int64_t wrow;
+        if (GATHER) {
+            wrow = a.first + blk;
+            f = a.slot_flow[wrow];
+            s = (int)wrow - a.tab[f].base;
+        } else {
+            f = (int)(blk >> 1);
+            s = a.tab[f].closes + (int)(blk & 1);
+            wrow = (int64_t)a.T + blk;
+        }
+        const int w = a.win[wrow * a.n + i];
+        const int b = (a.tab[f].cb + s) & 1;
+        const bool carried = s < 2;
+        const int64_t erow = ((int64_t)f * 2 + b) * a.n + i;   // the block's staging row
+        const int64_t srow = erow * a.S;
+        uint8_t *dst = GATHER ? a.sym_out + r * a.S : a.stage_sym + srow;
+        if (!GATHER && w < 0 && carried) continue;
+        if (V16) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (w >= 0) {
+                const uint2 *src = reinterpret_cast<const uint2 *>(a.packets + (int64_t)w * a.plen + kHdr + (int64_t)c * 16);
+                const uint2 lo = src[0], hi = src[1];
+                v = make_uint4(lo.x, lo.y, hi.x, hi.y);
+            } else if (carried) {
+                v = *reinterpret_cast<const uint4 *>(a.stage_sym + srow + (int64_t)c * 16);
+            }
+            *reinterpret_cast<uint4 *>(dst + (int64_t)c * 16) = v;
+        } else {
+            uint8_t v = 0;
+            if (w >= 0) v = a.packets[(int64_t)w * a.plen + kHdr + c];
+            else if (carried) v = a.stage_sym[srow + c];
+            dst[c] = v;
+        }
+        if (c == 0) {
+            const uint8_t e = w >= 0 ? 0 : (carried ? a.stage_er[erow] : 1);
+            if (GATHER) a.er_out[r] = e;
+            else a.stage_er[erow] = e;
+        }
+    }
+}
+
+// fec_rx_sources for all flows: the row-source words and flags of the T closed slots
+__global__ __launch_bounds__(kThreads) void fec_rx_sources_flows(const int32_t *__restrict__ win, const uint8_t *__restrict__ stage_er,
+                                                                const FlowTab *__restrict__ tab, const int32_t *__restrict__ slot_flow, int n,
+                                                                int T, uint32_t *__restrict__ src, uint8_t *__restrict__ er)
+{
+    const int64_t total = (int64_t)T * n;
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < total; r += (int64_t)gridDim.x * kThreads) {
+        const int j = (int)(r / n);
+        const int i = (int)(r - (int64_t)j * n);
+        const int f = slot_flow[j];
+        const int s = j - tab[f].base;
+        const int w = win[r];
+        const int64_t row = ((int64_t)f * 2 + ((tab[f].cb + s) & 1)) * n + i;   // the block's staging row, < 2^31 - 2 (create)
         uint32_t word = kRowErased;
         if (w >= 0) word = (uint32_t)w;
         else if (s < 2 && stage_er[row] == 0) word = kRowStaged | (uint32_t)row;
@@ -588,7 +734,8 @@ int ldpc_amd_fec_rx_dev_flush(ldpc_amd_fec_rx_dev *rx, uint8_t *sym_out, uint8_t
 // 214-243).  Else COMPOSED: (d) gathers a chunk of closed blocks into the context's scratch, the decoder runs on it, next chunk; the
 // chunks follow one another on the context's stream, so the scratch is free again when the next gather starts.
 // (e) is launched BEHIND the decode in both paths: it overwrites the staging planes of the carried blocks, which the fused decode reads.
-static int rx_decode_check(ldpc_amd_ctx *ctx, const ldpc_amd_fec_rx_dev *rx, const char *who, int code, int max_sweeps, uint8_t *out,
+extern "C++" template <class Rx>   // ldpc_amd_fec_rx_dev or ldpc_amd_fec_rx_flows: n, k, S
+static int rx_decode_check(ldpc_amd_ctx *ctx, const Rx *rx, const char *who, int code, int max_sweeps, uint8_t *out,
                            int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src)
 {
     if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
@@ -707,6 +854,372 @@ int ldpc_amd_fec_receiver_info(ldpc_amd_ctx *ctx, int info[4])
     info[2] = ctx->receiver_blocks;
     info[3] = 0;
     return LDPC_AMD_OK;
+}
+
+}  // extern "C"
+
+// ---- the multi-flow receiver (include/ldpc_erasure_amd_flows.h) ---------------------------------------------------------
+struct ldpc_amd_fec_rx_flows {
+    ldpc_amd_ctx *ctx = nullptr;
+    int nflows = 0, n = 0, k = 0, S = 0, kd = 0, km = 0;
+    // host mirror of every flow's state, as in ldpc_amd_fec_rx_dev
+    std::vector<int> cur, next, ccnt, ncnt, cb;
+    std::vector<int64_t> dropped;
+    uint8_t *stage_sym = nullptr;   // [nflows][2][n][S]
+    uint8_t *stage_er = nullptr;    // [nflows][2][n]
+    Scratch dense, dest, win, res, slots;   // per-call scratch, grown on demand
+    FlowIn *in_dev = nullptr, *in_host = nullptr;      // [nflows]; the host copies are pinned
+    FlowTab *tab_dev = nullptr, *tab_host = nullptr;   // [nflows]
+    int32_t *res_host = nullptr;    // pinned copy of res
+    size_t res_host_cap = 0;
+};
+
+// One call's PLAN for all flows: (a) + (b), ONE read-back, the slot bases.  Nothing of any flow's state changes before flows_commit.
+struct FlowsPlan {
+    int T = 0;             // closed blocks of all flows
+    int64_t max_used = 0;  // the longest consumed prefix
+    size_t rec = 0;        // words of one flow's result record
+};
+
+static int flows_check_call(ldpc_amd_fec_rx_flows *rx, const char *who, const int64_t *flow_begin, int max_blocks, int64_t &P)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (!flow_begin || flow_begin[0] != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin must not be null and must start at 0", who);
+    for (int f = 0; f < rx->nflows; f++)
+        if (flow_begin[f + 1] < flow_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin decreases at flow %d", who, f);
+    P = flow_begin[rx->nflows];
+    if (P >= ((int64_t)1 << 31)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need fewer than 2^31 packets in all", who);
+    if (max_blocks < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need max_blocks_per_flow >= 1", who);
+    if ((int64_t)rx->nflows * max_blocks * rx->n >= ((int64_t)1 << 31) - 2)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows * max_blocks_per_flow * n must be below 2^31 - 2", who);
+    return LDPC_AMD_OK;
+}
+
+static void flows_nothing(const ldpc_amd_fec_rx_flows *rx, int *closes, int64_t *consumed)
+{
+    if (closes) std::fill(closes, closes + rx->nflows, 0);
+    if (consumed) std::fill(consumed, consumed + rx->nflows, (int64_t)0);
+}
+
+static int flows_plan(ldpc_amd_fec_rx_flows *rx, const char *who, const uint8_t *packets, const int64_t *flow_begin, int64_t npackets,
+                      int max_blocks, FlowsPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, nf = rx->nflows;
+    const int64_t plen = (int64_t)rx->S + kHdr;
+    pl.rec = (size_t)R_WORDS + (size_t)max_blocks;
+    const size_t res_bytes = sizeof(int32_t) * pl.rec * (size_t)nf;
+    int rc;
+    if ((rc = scratch_reserve(ctx, rx->dense, sizeof(uint32_t) * (size_t)npackets)) ||
+        (rc = scratch_reserve(ctx, rx->dest, sizeof(int32_t) * (size_t)npackets)) || (rc = scratch_reserve(ctx, rx->res, res_bytes)))
+        return rc;
+    if (rx->res_host_cap < res_bytes) {
+        if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every plan ends with a synchronisation
+        rx->res_host = nullptr;
+        rx->res_host_cap = 0;
+        LDPC_HIP_TRY(ctx, hipHostMalloc((void **)&rx->res_host, res_bytes, hipHostMallocDefault));
+        rx->res_host_cap = res_bytes;
+    }
+    uint32_t *dense = (uint32_t *)rx->dense.p;
+    int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
+    for (int f = 0; f < nf; f++)   // (the copy of the previous call's records is behind that call's synchronisation)
+        rx->in_host[f] = FlowIn{flow_begin[f], flow_begin[f + 1] - flow_begin[f], rx->cur[f], rx->next[f], rx->ccnt[f], rx->ncnt[f]};
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->in_dev, rx->in_host, sizeof(FlowIn) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
+
+    // (a) + (b): the plan
+    if (plen % 4 == 0 && ((uintptr_t)packets & 3) == 0)
+        hipLaunchKernelGGL(fec_rx_headers<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
+    else
+        hipLaunchKernelGGL(fec_rx_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fec_rx_scan_flows, dim3(nf), dim3(64), 0, ctx->stream, dense, rx->in_dev, n, rx->kd, rx->km, max_blocks, dest, res);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->res_host, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = check_device_error(ctx))) return rc;
+    int64_t base = 0;
+    for (int f = 0; f < nf; f++) {   // the tables of the kernels behind the plan (their copy of the previous call is behind this synchronisation)
+        const int32_t *h = rx->res_host + (size_t)f * pl.rec;
+        if (h[R_ERR])
+            return set_error(ctx, LDPC_AMD_EHIP, "%s: the plan scan of flow %d hit its iteration cap (internal error); every flow's state is unchanged",
+                             who, f);
+        const int64_t used = (int64_t)(((uint64_t)(uint32_t)h[R_CONSUMED_HI] << 32) | (uint32_t)h[R_CONSUMED_LO]);
+        rx->tab_host[f] = FlowTab{flow_begin[f], used, (int)base, h[R_CLOSES], rx->cb[f], 0};
+        base += h[R_CLOSES];
+        pl.max_used = std::max(pl.max_used, used);
+    }
+    pl.T = (int)base;   // <= nflows * max_blocks < 2^31
+    if ((rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)pl.T + 2 * (size_t)nf) * (size_t)n)) ||
+        (rc = scratch_reserve(ctx, rx->slots, sizeof(int32_t) * (size_t)std::max(pl.T, 1))))
+        return rc;
+    return LDPC_AMD_OK;
+}
+
+// the flow table, the slot map and (c): the winners' table of the call, [(T + 2 nflows)][n]
+static int flows_winners(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int nf = rx->nflows;
+    int32_t *win = (int32_t *)rx->win.p;
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->tab_dev, rx->tab_host, sizeof(FlowTab) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
+    if (pl.T > 0) {
+        hipLaunchKernelGGL(fec_rx_flow_slots, dim3(nf), dim3(64), 0, ctx->stream, rx->tab_dev, (int32_t *)rx->slots.p);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+    }
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(win, 0xff, sizeof(int32_t) * ((size_t)pl.T + 2 * (size_t)nf) * (size_t)rx->n, ctx->stream));   // -1: no packet
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pl.max_used + kThreads - 1) / kThreads, std::max(1, 32768 / nf)));
+    hipLaunchKernelGGL(fec_rx_winners_flows, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p,
+                       (const int32_t *)rx->dest.p, rx->tab_dev, rx->n, pl.T, win);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// (d) for the closed slots first .. first + count - 1 (gather) or (e) for the two open blocks of every flow
+template <bool GATHER>
+static int flows_move(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl, const uint8_t *packets, int first, int count, uint8_t *sym, uint8_t *er)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, S = rx->S;
+    FlowMoveArgs a{};
+    a.packets = packets; a.plen = (int64_t)S + kHdr; a.win = (const int32_t *)rx->win.p; a.tab = rx->tab_dev;
+    a.slot_flow = (const int32_t *)rx->slots.p; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
+    a.sym_out = sym; a.er_out = er; a.n = n; a.S = S; a.T = pl.T; a.nflows = rx->nflows; a.first = first; a.count = count;
+    const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0 && ((uintptr_t)sym & 15) == 0;
+    const int64_t q = v16 ? S / 16 : S;
+    const int64_t items = (GATHER ? (int64_t)count : 2 * (int64_t)rx->nflows) * n * q;
+    if (GATHER && count <= 0) return LDPC_AMD_OK;
+    if (v16) hipLaunchKernelGGL((fec_rx_move_flows<GATHER, true>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((fec_rx_move_flows<GATHER, false>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+static void flows_commit(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl, int *blocks, int *closes, int64_t *consumed)
+{
+    for (int f = 0; f < rx->nflows; f++) {
+        const int32_t *h = rx->res_host + (size_t)f * pl.rec;
+        const FlowTab &t = rx->tab_host[f];
+        rx->cur[f] = h[R_CUR]; rx->next[f] = h[R_NEXT]; rx->ccnt[f] = h[R_CCNT]; rx->ncnt[f] = h[R_NCNT];
+        rx->cb[f] ^= t.closes & 1;   // :241, once per close
+        rx->dropped[f] += (int64_t)(((uint64_t)(uint32_t)h[R_DROPPED_HI] << 32) | (uint32_t)h[R_DROPPED_LO]);
+        if (blocks) memcpy(blocks + t.base, h + R_WORDS, sizeof(int) * (size_t)t.closes);
+        if (closes) closes[f] = t.closes;
+        if (consumed) consumed[f] = t.used;
+    }
+}
+
+extern "C" {
+
+int ldpc_amd_fec_rx_flows_create(ldpc_amd_ctx *ctx, int nflows, int n, int k, int S, ldpc_amd_fec_rx_flows **out)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!out || nflows < 1 || nflows > 4096 || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_create: need 1 <= nflows <= 4096, n <= 65536, 0 < k < n, S >= 1 (nflows=%d n=%d k=%d S=%d)",
+                         nflows, n, k, S);
+    if ((int64_t)nflows * 2 * n >= ((int64_t)1 << 31) - 2)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_create: nflows * 2 * n must be below 2^31 - 2");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ldpc_amd_fec_rx_flows *rx = new (std::nothrow) ldpc_amd_fec_rx_flows();
+    if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rx_flows_create: out of host memory");
+    rx->ctx = ctx;
+    rx->nflows = nflows; rx->n = n; rx->k = k; rx->S = S;
+    rx->kd = k + (int)lround((n - k) * 0.8);   // desired_parity_rx, :54
+    rx->km = k + (int)lround((n - k) * 0.2);   // min_parity_rx, :55
+    rx->cur.assign(nflows, -1); rx->next.assign(nflows, -1);
+    rx->ccnt.assign(nflows, 0); rx->ncnt.assign(nflows, 0); rx->cb.assign(nflows, 0);
+    rx->dropped.assign(nflows, 0);
+    const size_t planes = 2 * (size_t)nflows, plane = (size_t)n * S;
+    // (a request beyond the device's memory is not always answered with hipErrorOutOfMemory: a staging plane that cannot be had is ENOMEM)
+    hipError_t e = hipMalloc((void **)&rx->stage_sym, planes * plane);
+    if (e == hipSuccess) e = hipMalloc((void **)&rx->stage_er, planes * (size_t)n);
+    const bool no_planes = e != hipSuccess;
+    if (e == hipSuccess) e = hipMalloc((void **)&rx->in_dev, sizeof(FlowIn) * (size_t)nflows);
+    if (e == hipSuccess) e = hipMalloc((void **)&rx->tab_dev, sizeof(FlowTab) * (size_t)nflows);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&rx->in_host, sizeof(FlowIn) * (size_t)nflows, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&rx->tab_host, sizeof(FlowTab) * (size_t)nflows, hipHostMallocDefault);
+    // :62-71 all symbols erased until a packet produces them, payload zero
+    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_sym, 0, planes * plane, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_er, 1, planes * (size_t)n, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ldpc_amd_fec_rx_flows_destroy(rx);
+        return set_error(ctx, no_planes || e == hipErrorOutOfMemory ? LDPC_AMD_ENOMEM : LDPC_AMD_EHIP, "fec_rx_flows_create: %s%s",
+                         no_planes ? "the staging planes do not fit: " : "", hipGetErrorString(e));
+    }
+    *out = rx;
+    return LDPC_AMD_OK;
+}
+
+void ldpc_amd_fec_rx_flows_destroy(ldpc_amd_fec_rx_flows *rx)
+{
+    if (!rx) return;
+    (void)hipSetDevice(rx->ctx->device);
+    (void)hipStreamSynchronize(rx->ctx->stream);   // pending work of this object may still use its buffers
+    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots};
+    for (Scratch *s : sc)
+        if (s->p) (void)hipFree(s->p);
+    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    void *host[] = {rx->in_host, rx->tab_host, rx->res_host};
+    for (void *p : host)
+        if (p) (void)hipHostFree(p);
+    delete rx;
+}
+
+int64_t ldpc_amd_fec_rx_flows_dropped(const ldpc_amd_fec_rx_flows *rx, int flow)
+{
+    return rx && flow >= 0 && flow < rx->nflows ? rx->dropped[flow] : -1;
+}
+
+int ldpc_amd_fec_rx_flows_push_many(ldpc_amd_fec_rx_flows *rx, const uint8_t *packets, const int64_t *flow_begin, uint8_t *sym_batch,
+                                    uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    int rc;
+    int64_t P = 0;
+    if ((rc = flows_check_call(rx, "fec_rx_flows_push_many", flow_begin, max_blocks_per_flow, P))) return rc;
+    if (!sym_batch || !erased_batch || (P > 0 && !packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_push_many: packets / sym_batch / erased_batch must not be null");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((P > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_push_many: packets / sym_batch / erased_batch must be device pointers of device %d",
+                         ctx->device);
+    if (P == 0) {
+        flows_nothing(rx, closes, consumed);
+        return 0;
+    }
+    FlowsPlan pl;
+    if ((rc = flows_plan(rx, "fec_rx_flows_push_many", packets, flow_begin, P, max_blocks_per_flow, pl))) return rc;
+    // (c), (d), (e): the data movement, asynchronous
+    if ((rc = flows_winners(rx, pl)) || (rc = flows_move<true>(rx, pl, packets, 0, pl.T, sym_batch, erased_batch)) ||
+        (rc = flows_move<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)))
+        return rc;
+    flows_commit(rx, pl, blocks, closes, consumed);
+    return pl.T;
+}
+
+int ldpc_amd_fec_rx_flows_flush(ldpc_amd_fec_rx_flows *rx, int flow, uint8_t *sym_out, uint8_t *erased_out, int *block_out)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (flow < 0 || flow >= rx->nflows) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_flush: no flow %d (nflows = %d)", flow, rx->nflows);
+    const int f = flow;
+    if (rx->cur[f] == -1 || (rx->ccnt[f] == 0 && rx->ncnt[f] == 0)) return 0;
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((sym_out && !is_device_ptr(ctx, sym_out)) || (erased_out && !is_device_ptr(ctx, erased_out)))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_flush: sym_out / erased_out must be device pointers of device %d", ctx->device);
+    const size_t plane = (size_t)rx->n * rx->S, pi = (size_t)f * 2 + (size_t)rx->cb[f];
+    uint8_t *ps = rx->stage_sym + pi * plane, *pe = rx->stage_er + pi * rx->n;
+    // close_current: hand the current block out, reset its buffer, rotate
+    if (sym_out) LDPC_HIP_TRY(ctx, hipMemcpyAsync(sym_out, ps, plane, hipMemcpyDeviceToDevice, ctx->stream));
+    if (erased_out) LDPC_HIP_TRY(ctx, hipMemcpyAsync(erased_out, pe, rx->n, hipMemcpyDeviceToDevice, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(ps, 0, plane, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(pe, 1, rx->n, ctx->stream));
+    if (block_out) *block_out = rx->cur[f];
+    rx->cur[f] = rx->next[f];
+    rx->next[f] = (rx->next[f] + 1) & 0xff;
+    rx->ccnt[f] = rx->ncnt[f];
+    rx->ncnt[f] = 0;
+    rx->cb[f] ^= 1;
+    return 1;
+}
+
+// ldpc_amd_fec_rx_dev_decode_many for all flows: ONE launch_decode over the T closed slots (composed: one per chunk of slots).  The
+// staging update of all flows is one launch BEHIND the decode, for the reason given there.
+int ldpc_amd_fec_rx_flows_decode_many(ldpc_amd_fec_rx_flows *rx, int code, const uint8_t *packets, const int64_t *flow_begin, int max_sweeps,
+                                      int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
+                                      int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    int rc;
+    int64_t P = 0;
+    if ((rc = flows_check_call(rx, "fec_rx_flows_decode_many", flow_begin, max_blocks_per_flow, P))) return rc;
+    if (P == 0) {
+        flows_nothing(rx, closes, consumed);
+        return 0;
+    }
+    if ((rc = rx_decode_check(ctx, rx, "fec_rx_flows_decode_many", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src)))
+        return rc;
+    if (!packets || !is_device_ptr(ctx, packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_decode_many: packets must be a device pointer of device %d", ctx->device);
+    const DevCode &cd = ctx->codes[code]->dev;
+    const int n = rx->n, S = rx->S;
+    const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
+    const size_t frame = (size_t)n * S;
+
+    FlowsPlan pl;
+    if ((rc = flows_plan(rx, "fec_rx_flows_decode_many", packets, flow_begin, P, max_blocks_per_flow, pl))) return rc;
+    const int T = pl.T;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kReceiverScratchMax / frame)));
+    // every workspace of the call before anything moves: a refusal leaves every flow where it was
+    if (T > 0) {
+        if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)T * n))) return rc;
+        if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)T * n);
+        else rc = scratch_reserve(ctx, ctx->rx_sym, (size_t)chunk * frame);
+        if (rc) return rc;
+    }
+    if ((rc = flows_winners(rx, pl))) return rc;
+    DecodeArgs d{};
+    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
+    uint8_t *er = (uint8_t *)ctx->rx_er.p;
+    auto slots = [&](int first, int count) {   // the result arrays of closed slots first .. first + count - 1
+        d.nframes = count;
+        d.erased = er + (size_t)first * n;
+        d.out = out + (size_t)first * frame;
+        d.sweeps = sweeps ? sweeps + first : nullptr; d.residual = residual ? residual + first : nullptr;
+        d.status = status ? status + first : nullptr;
+        d.erased_out = erased_out ? erased_out + (size_t)first * n : nullptr;
+        d.residual_src = residual_src ? residual_src + first : nullptr;
+    };
+    if (T > 0 && fused) {
+        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+        hipLaunchKernelGGL(fec_rx_sources_flows, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
+                           rx->stage_er, rx->tab_dev, (const int32_t *)rx->slots.p, n, T, src, er);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        slots(0, T);
+        d.sym = nullptr;
+        d.pin.src = src; d.pin.packets = packets; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
+        if ((rc = launch_decode(ctx, d))) return rc;
+    } else if (T > 0) {
+        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
+        for (int first = 0; first < T; first += (int)chunk) {
+            const int count = (int)std::min<int64_t>(chunk, T - first);
+            if ((rc = flows_move<true>(rx, pl, packets, first, count, sym, er + (size_t)first * n))) return rc;
+            slots(first, count);
+            d.sym = sym;
+            if ((rc = launch_decode(ctx, d))) return rc;
+        }
+    }
+    if ((rc = flows_move<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
+    flows_commit(rx, pl, blocks, closes, consumed);
+    ctx->receiver_path = fused ? 1 : 2;
+    ctx->receiver_blocks = T;
+    return T;
+}
+
+int ldpc_amd_fec_rx_flows_decode_flush(ldpc_amd_fec_rx_flows *rx, int flow, int code, int max_sweeps, int do_ml, uint8_t *out, int32_t *sweeps,
+                                       int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src, int *block_out)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (flow < 0 || flow >= rx->nflows)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_decode_flush: no flow %d (nflows = %d)", flow, rx->nflows);
+    int rc;
+    if ((rc = rx_decode_check(ctx, rx, "fec_rx_flows_decode_flush", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src)))
+        return rc;
+    const size_t frame = (size_t)rx->n * rx->S;
+    if ((rc = scratch_reserve(ctx, ctx->rx_sym, frame)) || (rc = scratch_reserve(ctx, ctx->rx_er, (size_t)rx->n))) return rc;
+    if ((rc = ldpc_amd_fec_rx_flows_flush(rx, flow, (uint8_t *)ctx->rx_sym.p, (uint8_t *)ctx->rx_er.p, block_out)) != 1) return rc;
+    DecodeArgs d{};
+    d.code = ctx->codes[code]->dev; d.S = rx->S; d.in_rows = rx->n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0; d.nframes = 1;
+    d.sym = (const uint8_t *)ctx->rx_sym.p; d.erased = (const uint8_t *)ctx->rx_er.p; d.out = out;
+    d.sweeps = sweeps; d.residual = residual; d.status = status; d.erased_out = erased_out; d.residual_src = residual_src;
+    if ((rc = launch_decode(ctx, d))) return rc;
+    return 1;
 }
 
 }  // extern "C"
