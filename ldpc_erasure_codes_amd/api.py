@@ -68,6 +68,11 @@ EXPORTS_FLOWS = [
     "ldpc_amd_fec_rx_flows_create", "ldpc_amd_fec_rx_flows_destroy", "ldpc_amd_fec_rx_flows_push_many", "ldpc_amd_fec_rx_flows_decode_many",
     "ldpc_amd_fec_rx_flows_flush", "ldpc_amd_fec_rx_flows_decode_flush", "ldpc_amd_fec_rx_flows_dropped",
 ]
+# every symbol include/ldpc_erasure_amd_flows_mixed.h declares (the multi-flow receiver fed with interleaved packets and a flow id each)
+EXPORTS_FLOWS_MIXED = [
+    "ldpc_amd_fec_rx_flows_push_mixed", "ldpc_amd_fec_rx_flows_decode_mixed", "ldpc_amd_fec_rx_flows_unrouted", "ldpc_amd_fec_flows_demux_dev",
+    "ldpc_amd_fec_flows_demux_info",
+]
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
@@ -196,6 +201,15 @@ def load_library():
         L.ldpc_amd_fec_rx_flows_decode_flush.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]
         L.ldpc_amd_fec_rx_flows_dropped.argtypes = [vp, i32]
         L.ldpc_amd_fec_rx_flows_dropped.restype = i64
+    # ... fed with interleaved packets (include/ldpc_erasure_amd_flows_mixed.h)
+    if hasattr(L, "ldpc_amd_fec_rx_flows_push_mixed"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_rx_flows_push_mixed.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]
+        L.ldpc_amd_fec_rx_flows_decode_mixed.argtypes = [vp, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+        L.ldpc_amd_fec_rx_flows_unrouted.argtypes = [vp]
+        L.ldpc_amd_fec_rx_flows_unrouted.restype = i64
+        L.ldpc_amd_fec_flows_demux_dev.argtypes = [vp, vp, i64, i32, vp, vp]
+        L.ldpc_amd_fec_flows_demux_dev.restype = i64
+        L.ldpc_amd_fec_flows_demux_info.argtypes = [vp, C.POINTER(i64)]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -638,6 +652,26 @@ class Context:
         """nflows device receivers that are fed, planned and decoded together, one call for all of them (FecRxFlows)."""
         return FecRxFlows(self, nflows, n, k, S)
 
+    # -- ... fed with interleaved packets (include/ldpc_erasure_amd_flows_mixed.h)
+    def fec_flows_demux(self, flow_of, nflows):
+        """The stable partition of packet indices by flow, on its own: flow_of torch int32 [P] on this context's device (any value
+        outside 0 .. nflows-1: a packet of no flow) -> (order torch int64 [R] on the device: the routed packets' indices flow by flow,
+        each flow in arrival order; counts int64 [nflows]).  Synchronous."""
+        import torch
+        assert _is_torch(flow_of) and flow_of.dtype == torch.int32 and flow_of.ndim == 1
+        P = flow_of.shape[0]
+        order = torch.empty(max(P, 1), dtype=torch.int32, device=flow_of.device)   # (the library's uint32; an index is below 2^31)
+        counts = np.zeros(nflows, dtype=np.int64)
+        R = self._check(self._L.ldpc_amd_fec_flows_demux_dev(self._h, _ptr(flow_of) if P else None, P, nflows, _ptr(order), counts.ctypes.data),
+                        "fec_flows_demux_dev")
+        return order[:R].to(torch.int64), counts
+
+    def fec_flows_demux_info(self):
+        """{"tile": tile length in packets of the last partition, "tiles": its tiles, "scratch_bytes": table bytes the context holds}."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_flows_demux_info(self._h, info), "fec_flows_demux_info")
+        return {"tile": int(info[0]), "tiles": int(info[1]), "scratch_bytes": int(info[2])}
+
 
 # ---------------------------------------------------------------------------------------------------------
 # Host-side wire format (include/ldpc_erasure_amd_wire.h): FEC header, packetiser, two-buffer reassembler.
@@ -818,7 +852,8 @@ class FecRxFlows:
     packets flow_begin[f] .. flow_begin[f+1]-1 -- is planned for all flows at once and read back once, and every block that closed, of
     every flow, is decoded in one launch.  Flow f behaves exactly like a FecRxDevice fed its segment with max_blocks =
     max_blocks_per_flow.  The closed blocks come out dense in flow order: flow 0's in closing order, then flow 1's, ...; flow f's
-    start at closes[:f].sum().  Close it before its Context."""
+    start at closes[:f].sum().  push_mixed / decode_mixed take the packets in arrival order with a flow number each instead
+    (include/ldpc_erasure_amd_flows_mixed.h) and return the same; all four calls mix freely.  Close it before its Context."""
 
     def __init__(self, ctx, nflows, n, k, S):
         self._ctx, self._L = ctx, ctx._L
@@ -861,6 +896,48 @@ class FecRxFlows:
             _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
             "fec_rx_flows_decode_many")
         return closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed
+
+    def _mixed(self, packets, flow_of, max_blocks_per_flow, want_left):
+        import torch
+        assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.shape[1] == 8 + self.S
+        assert _is_torch(flow_of) and flow_of.dtype == torch.int32 and flow_of.shape == (packets.shape[0],)
+        P = packets.shape[0]
+        slots = max(self.nflows * max(max_blocks_per_flow, 1), 1)
+        left = torch.empty(max(P, 1), dtype=torch.uint8, device=packets.device) if want_left else None
+        return (P, slots, np.zeros(slots, dtype=np.int32), np.zeros(self.nflows, dtype=np.int32), np.zeros(self.nflows, dtype=np.int64),
+                np.zeros(self.nflows, dtype=np.int64), _ptr(packets) if P else None, _ptr(flow_of) if P else None, left)
+
+    def push_mixed(self, packets, flow_of, max_blocks_per_flow, want_left=False):
+        """push_many for packets in arrival order (include/ldpc_erasure_amd_flows_mixed.h): packets torch uint8 [P][8+S], flow_of torch
+        int32 [P] on the device, flow_of[p] = the flow of packet p (outside 0 .. nflows-1: no flow, ignored and counted in
+        `unrouted`).  Returns push_many's tuple for the per-flow segments, then offered int64 [nflows] (packets of each flow), then --
+        want_left -- left torch uint8 [P]: 1 for the packets behind their flow's consumed prefix, to be submitted again."""
+        import torch
+        P, slots, blocks, closes, consumed, offered, pp, fp, left = self._mixed(packets, flow_of, max_blocks_per_flow, want_left)
+        sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=packets.device)
+        er = torch.empty((slots, self.n), dtype=torch.uint8, device=packets.device)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_push_mixed(
+            self._h, pp, fp, P, _ptr(sym), _ptr(er), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data,
+            offered.ctypes.data, _ptr(left) if want_left else None), "fec_rx_flows_push_mixed")
+        r = (closes, blocks[:T], sym[:T], er[:T], consumed, offered)
+        return r + (left[:P],) if want_left else r
+
+    def decode_mixed(self, code, packets, flow_of, max_blocks_per_flow, max_sweeps=10, do_ml=1, want_left=False):
+        """decode_many for packets in arrival order with a flow number each (push_mixed): decode_many's tuple, then offered (and left
+        when asked).  No payload byte is copied to sort the packets: only their indices are partitioned by flow."""
+        P, slots, blocks, closes, consumed, offered, pp, fp, left = self._mixed(packets, flow_of, max_blocks_per_flow, want_left)
+        fr = self._frames(slots)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_decode_mixed(
+            self._h, code, pp, fp, P, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status),
+            _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data,
+            offered.ctypes.data, _ptr(left) if want_left else None), "fec_rx_flows_decode_mixed")
+        r = (closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed, offered)
+        return r + (left[:P],) if want_left else r
+
+    @property
+    def unrouted(self):
+        """packets of no flow the mixed calls were given so far"""
+        return int(self._L.ldpc_amd_fec_rx_flows_unrouted(self._h))
 
     def flush(self, flow):
         """None, or (block number, sym torch [n][S], erased torch [n]) of the block the end of flow `flow`'s stream closes."""

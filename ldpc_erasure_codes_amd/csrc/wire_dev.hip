@@ -35,6 +35,7 @@
 #include "../../include/ldpc_erasure_amd_sender.h"
 #include "../../include/ldpc_erasure_amd_receiver.h"
 #include "../../include/ldpc_erasure_amd_flows.h"
+#include "../../include/ldpc_erasure_amd_flows_mixed.h"
 
 using namespace ldpc_amd;
 
@@ -439,6 +440,173 @@ __global__ __launch_bounds__(kThreads) void fec_rx_sources_flows(const int32_t *
         src[r] = word;
         er[r] = word == kRowErased ? 1 : 0;
     }
+}
+
+// ---- interleaved packets (include/ldpc_erasure_amd_flows_mixed.h) ----------------------------------------------------------
+// The packets of a call lie in arrival order and flow_of[p] names the flow of packet p.  Nothing behind the plan needs a flow's
+// packets side by side -- the plan reads the dense header words, the gather and the decoder address a payload by packet index -- so
+// only the packet INDICES are partitioned by flow: order[q] = the q-th packet when the routed packets are listed flow by flow, each
+// flow in arrival order.  The plan then runs on positions q (dense[q] = header of packets[order[q]], flow f's segment is
+// base[f] .. base[f+1]-1), and one pass over the winners' table turns the winning positions back into packet indices.
+//
+// The partition is a stable counting sort in three steps over TILES of consecutive packets (tile length a multiple of 64):
+//   (i)   fec_demux_count   one workgroup per tile: histogram of the tile's flows in LDS -> row `tile` of table[tiles][nflows]
+//   (ii)  fec_demux_tiles   per flow an exclusive scan down the tiles, in place; the flow's total -> base[f]
+//         fec_demux_bases   one wavefront: exclusive scan of the totals across flows, in place; base[nflows] = routed packets
+//   (iii) fec_demux_place   ONE WAVEFRONT per tile walks it in index order, 64 packets at a time, with a running position per flow in
+//                           LDS (base[f] + table[tile][f] at the start).  Within a group a lane finds the lanes of its own flow with
+//                           one ballot per bit of the flow number (at most 12) and takes its rank among them from a prefix popcount;
+//                           the packet goes to position[flow] + rank, and the first lane of each flow advances the position by the
+//                           flow's lanes.
+// Stability and determinism: packets of flow f in an earlier tile come first (ii), inside a tile those of an earlier group come first
+// (one wavefront executes its groups in order, so a group reads the positions the group before it wrote), inside a group the lower
+// lane comes first (the prefix popcount).  No atomic decides a position; those of (i) only count.
+// A flow number outside 0 .. nflows-1 (compared unsigned, so negative ones too) is no flow: the packet is counted nowhere and gets no position.
+constexpr int kMaxFlows = 4096;
+constexpr int64_t kDemuxMaxTiles = 1024, kDemuxMinTile = 1024;   // the table is at most kDemuxMaxTiles * kMaxFlows words: the tile grows instead
+
+__global__ __launch_bounds__(kThreads) void fec_demux_count(const int32_t *__restrict__ flow_of, int64_t np, int64_t tile, int nflows,
+                                                           uint32_t *__restrict__ table)
+{
+    __shared__ uint32_t cnt[kMaxFlows];
+    for (int f = threadIdx.x; f < nflows; f += kThreads) cnt[f] = 0;
+    __syncthreads();
+    const int64_t p0 = (int64_t)blockIdx.x * tile, p1 = p0 + tile < np ? p0 + tile : np;
+    for (int64_t p = p0 + threadIdx.x; p < p1; p += kThreads) {
+        const uint32_t f = (uint32_t)flow_of[p];
+        if (f < (uint32_t)nflows) atomicAdd(&cnt[f], 1u);
+    }
+    __syncthreads();
+    uint32_t *row = table + (int64_t)blockIdx.x * nflows;
+    for (int f = threadIdx.x; f < nflows; f += kThreads) row[f] = cnt[f];
+}
+
+// Workgroup: 64 flows x kDemuxChunks runs of consecutive tiles.  A thread sums its run of its flow's column (loads only, so they
+// overlap), the runs' sums are scanned through LDS, and the thread walks its run again, eight tiles at a time, writing the exclusive
+// prefix over each count.  A column read one tile after the other would cost a memory latency per tile.
+constexpr int kDemuxChunks = 16;
+__global__ __launch_bounds__(64 * kDemuxChunks) void fec_demux_tiles(uint32_t *__restrict__ table, int tiles, int nflows,
+                                                                    uint32_t *__restrict__ base)
+{
+    __shared__ uint32_t part[kDemuxChunks][64];
+    const int f = blockIdx.x * 64 + threadIdx.x, c = threadIdx.y;
+    const int per = (tiles + kDemuxChunks - 1) / kDemuxChunks;
+    const int t0 = c * per < tiles ? c * per : tiles, t1 = t0 + per < tiles ? t0 + per : tiles;
+    const bool live = f < nflows;
+    uint32_t sum = 0;
+    if (live)
+        for (int t = t0; t < t1; t++) sum += table[(int64_t)t * nflows + f];
+    part[c][threadIdx.x] = sum;
+    __syncthreads();
+    if (!live) return;
+    uint32_t run = 0;
+    for (int j = 0; j < c; j++) run += part[j][threadIdx.x];
+    if (c == kDemuxChunks - 1) base[f] = run + sum;
+    for (int t = t0; t < t1; t += 8) {
+        uint32_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = t + u < t1 ? table[(int64_t)(t + u) * nflows + f] : 0u;
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            if (t + u < t1) table[(int64_t)(t + u) * nflows + f] = run;
+            run += v[u];
+        }
+    }
+}
+
+// Lane l owns the flows l * chunk .. (l + 1) * chunk - 1.  With `in` it also writes every flow's segment of the q-space, where the
+// plan scan looks for it (the host has uploaded the rest of the record).
+__global__ __launch_bounds__(64) void fec_demux_bases(uint32_t *__restrict__ base, int nflows, FlowIn *__restrict__ in)
+{
+    const int lane = threadIdx.x, chunk = (nflows + 63) / 64;
+    const int f0 = lane * chunk, f1 = f0 + chunk < nflows ? f0 + chunk : nflows;
+    uint32_t sum = 0;
+    for (int f = f0; f < f1; f++) sum += base[f];
+    uint32_t incl = sum;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
+    }
+    const uint32_t total = __shfl(incl, 63);
+    uint32_t run = incl - sum;
+    for (int f = f0; f < f1; f++) {
+        const uint32_t v = base[f];
+        base[f] = run;
+        if (in) {
+            in[f].begin = run;
+            in[f].len = v;
+        }
+        run += v;
+    }
+    if (lane == 0) base[nflows] = total;
+}
+
+__global__ __launch_bounds__(64) void fec_demux_place(const int32_t *__restrict__ flow_of, int64_t np, int64_t tile, int nflows,
+                                                     int bits, const uint32_t *__restrict__ table, const uint32_t *__restrict__ base,
+                                                     uint32_t *__restrict__ order)
+{
+    __shared__ uint32_t pos[kMaxFlows];
+    const int lane = threadIdx.x;
+    const uint32_t *row = table + (int64_t)blockIdx.x * nflows;
+    for (int f = lane; f < nflows; f += 64) pos[f] = base[f] + row[f];
+    __syncthreads();
+    const uint64_t lt = (1ull << lane) - 1;   // lanes below this one
+    const int64_t p0 = (int64_t)blockIdx.x * tile, p1 = p0 + tile < np ? p0 + tile : np;
+    uint32_t fn = p0 + lane < p1 ? (uint32_t)flow_of[p0 + lane] : ~0u;
+    for (int64_t g = p0; g < p1; g += 64) {
+        const int64_t p = g + lane;
+        const uint32_t f = fn;
+        fn = p + 64 < p1 ? (uint32_t)flow_of[p + 64] : ~0u;   // the next group's flows in flight while this one is ranked
+        const bool routed = f < (uint32_t)nflows;              // (a lane past the end holds ~0u: no flow)
+        // the lanes of this lane's flow: those that agree with it in every bit of the flow number.  `bits` ballots (nflows <= 2^bits)
+        // that do not depend on one another, instead of a pass per distinct flow of the group, each waiting for the one before
+        uint64_t same = __ballot(routed);
+        for (int b = 0; b < bits; b++) {
+            const uint64_t one = __ballot((f >> b) & 1u);
+            same &= ((f >> b) & 1u) ? one : ~one;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & lt), lanes = (uint32_t)__popcll(same);
+        uint32_t start = 0;
+        if (routed) {
+            start = pos[f];
+            if ((int64_t)start + rank < np) order[start + rank] = (uint32_t)p;   // (always, unless flow_of changed under the call)
+        }
+        if (routed && rank == 0) pos[f] = start + lanes;   // behind the read above: a wavefront's LDS accesses keep their order
+    }
+}
+
+// (a) on the permutation: dense[q] = the header word of packet order[q], for the *routed positions q
+template <bool ALIGNED4>
+__global__ __launch_bounds__(kThreads) void fec_rx_headers_idx(const uint8_t *__restrict__ packets, const uint32_t *__restrict__ order,
+                                                              const uint32_t *__restrict__ routed, int plen, uint32_t *__restrict__ dense)
+{
+    const int64_t nq = *routed;
+    for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < nq; q += (int64_t)gridDim.x * kThreads) {
+        const uint8_t *h = packets + (int64_t)order[q] * plen;
+        uint32_t w;
+        if (ALIGNED4) w = *reinterpret_cast<const uint32_t *>(h) & 0x00ffffffu;
+        else w = (uint32_t)h[0] | (uint32_t)h[1] << 8 | (uint32_t)h[2] << 16;
+        dense[q] = w;
+    }
+}
+
+// (c) left the winning POSITION in every cell of the winners' table: the packet index instead, which is what everything behind reads
+__global__ __launch_bounds__(kThreads) void fec_rx_win_order(int32_t *__restrict__ win, int64_t cells, const uint32_t *__restrict__ order)
+{
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < cells; r += (int64_t)gridDim.x * kThreads) {
+        const int32_t q = win[r];
+        if (q >= 0) win[r] = (int32_t)order[q];   // a packet index is below 2^31
+    }
+}
+
+// left[p] = 1 for the packets behind a flow's consumed prefix (the caller has zeroed left); grid: (x, nflows)
+__global__ __launch_bounds__(kThreads) void fec_rx_left_flows(const FlowTab *__restrict__ tab, const FlowIn *__restrict__ in,
+                                                             const uint32_t *__restrict__ order, uint8_t *__restrict__ left)
+{
+    const FlowTab f = tab[blockIdx.y];
+    const int64_t len = in[blockIdx.y].len;
+    for (int64_t q = f.used + (int64_t)blockIdx.x * kThreads + threadIdx.x; q < len; q += (int64_t)gridDim.x * kThreads)
+        left[order[f.begin + q]] = 1;
 }
 
 // A pointer of this context's device (hipMalloc / torch), not host memory.
@@ -865,9 +1033,10 @@ struct ldpc_amd_fec_rx_flows {
     // host mirror of every flow's state, as in ldpc_amd_fec_rx_dev
     std::vector<int> cur, next, ccnt, ncnt, cb;
     std::vector<int64_t> dropped;
+    int64_t unrouted = 0;           // packets of no flow the mixed calls were given
     uint8_t *stage_sym = nullptr;   // [nflows][2][n][S]
     uint8_t *stage_er = nullptr;    // [nflows][2][n]
-    Scratch dense, dest, win, res, slots;   // per-call scratch, grown on demand
+    Scratch dense, dest, win, res, slots, order;   // per-call scratch, grown on demand (order: the mixed calls' partition, u32 [P])
     FlowIn *in_dev = nullptr, *in_host = nullptr;      // [nflows]; the host copies are pinned
     FlowTab *tab_dev = nullptr, *tab_host = nullptr;   // [nflows]
     int32_t *res_host = nullptr;    // pinned copy of res
@@ -879,7 +1048,64 @@ struct FlowsPlan {
     int T = 0;             // closed blocks of all flows
     int64_t max_used = 0;  // the longest consumed prefix
     size_t rec = 0;        // words of one flow's result record
+    // a mixed call (else null / 0): the partition, the flow bases as read back behind the scan records ([nflows + 1], the last one =
+    // the routed packets), the longest remainder behind a consumed prefix
+    const uint32_t *order = nullptr, *base = nullptr;
+    int64_t max_left = 0;
 };
+
+// Where the packets of a call are: segmented by the caller (flow_begin, host) or interleaved with a flow number each (flow_of, device)
+struct FlowsSrc {
+    bool mixed = false;
+    const int64_t *flow_begin = nullptr;
+    const int32_t *flow_of = nullptr;
+};
+
+// the partition's tiling for P packets: at most kDemuxMaxTiles tiles of a multiple of 64 packets
+static void demux_tiling(int64_t P, int64_t &tile, int64_t &tiles)
+{
+    tile = std::max<int64_t>(kDemuxMinTile, ((P + kDemuxMaxTiles - 1) / kDemuxMaxTiles + 63) / 64 * 64);
+    tiles = (P + tile - 1) / tile;
+}
+
+static int demux_reserve(ldpc_amd_ctx *ctx, int64_t P, int nflows)
+{
+    int64_t tile, tiles;
+    demux_tiling(P, tile, tiles);
+    return scratch_reserve(ctx, ctx->demux_tab, sizeof(uint32_t) * ((size_t)tiles * (size_t)nflows + (size_t)nflows + 1));
+}
+
+// (i) - (iii) on the context's stream, P > 0; base: [nflows + 1] device words; in: the flows' records or null.  demux_reserve came first.
+static int demux_launch(ldpc_amd_ctx *ctx, const int32_t *flow_of, int64_t P, int nflows, uint32_t *base, FlowIn *in, uint32_t *order)
+{
+    int64_t tile, tiles;
+    demux_tiling(P, tile, tiles);
+    uint32_t *table = (uint32_t *)ctx->demux_tab.p;
+    hipLaunchKernelGGL(fec_demux_count, dim3((unsigned)tiles), dim3(kThreads), 0, ctx->stream, flow_of, P, tile, nflows, table);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fec_demux_tiles, dim3((unsigned)((nflows + 63) / 64)), dim3(64, kDemuxChunks), 0, ctx->stream, table, (int)tiles, nflows, base);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fec_demux_bases, dim3(1), dim3(64), 0, ctx->stream, base, nflows, in);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    int bits = 0;
+    while ((1 << bits) < nflows) bits++;
+    hipLaunchKernelGGL(fec_demux_place, dim3((unsigned)tiles), dim3(64), 0, ctx->stream, flow_of, P, tile, nflows, bits, (const uint32_t *)table,
+                       (const uint32_t *)base, order);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    ctx->demux_tile = tile;
+    ctx->demux_tiles = tiles;
+    return LDPC_AMD_OK;
+}
+
+static int flows_check_limits(ldpc_amd_fec_rx_flows *rx, const char *who, int64_t P, int max_blocks)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (P < 0 || P >= ((int64_t)1 << 31)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need fewer than 2^31 packets in all", who);
+    if (max_blocks < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need max_blocks_per_flow >= 1", who);
+    if ((int64_t)rx->nflows * max_blocks * rx->n >= ((int64_t)1 << 31) - 2)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows * max_blocks_per_flow * n must be below 2^31 - 2", who);
+    return LDPC_AMD_OK;
+}
 
 static int flows_check_call(ldpc_amd_fec_rx_flows *rx, const char *who, const int64_t *flow_begin, int max_blocks, int64_t &P)
 {
@@ -888,31 +1114,42 @@ static int flows_check_call(ldpc_amd_fec_rx_flows *rx, const char *who, const in
     for (int f = 0; f < rx->nflows; f++)
         if (flow_begin[f + 1] < flow_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin decreases at flow %d", who, f);
     P = flow_begin[rx->nflows];
-    if (P >= ((int64_t)1 << 31)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need fewer than 2^31 packets in all", who);
-    if (max_blocks < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need max_blocks_per_flow >= 1", who);
-    if ((int64_t)rx->nflows * max_blocks * rx->n >= ((int64_t)1 << 31) - 2)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows * max_blocks_per_flow * n must be below 2^31 - 2", who);
-    return LDPC_AMD_OK;
+    return flows_check_limits(rx, who, P, max_blocks);
 }
 
-static void flows_nothing(const ldpc_amd_fec_rx_flows *rx, int *closes, int64_t *consumed)
+static void flows_nothing(const ldpc_amd_fec_rx_flows *rx, int *closes, int64_t *consumed, int64_t *offered)
 {
     if (closes) std::fill(closes, closes + rx->nflows, 0);
     if (consumed) std::fill(consumed, consumed + rx->nflows, (int64_t)0);
+    if (offered) std::fill(offered, offered + rx->nflows, (int64_t)0);
 }
 
-static int flows_plan(ldpc_amd_fec_rx_flows *rx, const char *who, const uint8_t *packets, const int64_t *flow_begin, int64_t npackets,
+// the mixed calls' own arguments, P > 0 (the device is set)
+static int flows_check_mixed(ldpc_amd_fec_rx_flows *rx, const char *who, const int32_t *flow_of, const uint8_t *left)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (!flow_of || !is_device_ptr(ctx, flow_of))
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be a device pointer of device %d", who, ctx->device);
+    if ((uintptr_t)flow_of & 3) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be 4-byte aligned", who);
+    if (left && !is_device_ptr(ctx, left)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: left must be a device pointer of device %d", who, ctx->device);
+    return LDPC_AMD_OK;
+}
+
+static int flows_plan(ldpc_amd_fec_rx_flows *rx, const char *who, const uint8_t *packets, const FlowsSrc &src, int64_t npackets,
                       int max_blocks, FlowsPlan &pl)
 {
     ldpc_amd_ctx *ctx = rx->ctx;
     const int n = rx->n, nf = rx->nflows;
     const int64_t plen = (int64_t)rx->S + kHdr;
+    const int64_t *flow_begin = src.flow_begin;
+    const bool mixed = src.mixed;
     pl.rec = (size_t)R_WORDS + (size_t)max_blocks;
-    const size_t res_bytes = sizeof(int32_t) * pl.rec * (size_t)nf;
+    const size_t res_bytes = sizeof(int32_t) * (pl.rec * (size_t)nf + (mixed ? (size_t)nf + 1 : 0));   // mixed: the flow bases behind the records
     int rc;
     if ((rc = scratch_reserve(ctx, rx->dense, sizeof(uint32_t) * (size_t)npackets)) ||
         (rc = scratch_reserve(ctx, rx->dest, sizeof(int32_t) * (size_t)npackets)) || (rc = scratch_reserve(ctx, rx->res, res_bytes)))
         return rc;
+    if (mixed && ((rc = scratch_reserve(ctx, rx->order, sizeof(uint32_t) * (size_t)npackets)) || (rc = demux_reserve(ctx, npackets, nf)))) return rc;
     if (rx->res_host_cap < res_bytes) {
         if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every plan ends with a synchronisation
         rx->res_host = nullptr;
@@ -923,11 +1160,24 @@ static int flows_plan(ldpc_amd_fec_rx_flows *rx, const char *who, const uint8_t 
     uint32_t *dense = (uint32_t *)rx->dense.p;
     int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
     for (int f = 0; f < nf; f++)   // (the copy of the previous call's records is behind that call's synchronisation)
-        rx->in_host[f] = FlowIn{flow_begin[f], flow_begin[f + 1] - flow_begin[f], rx->cur[f], rx->next[f], rx->ccnt[f], rx->ncnt[f]};
+        rx->in_host[f] = FlowIn{mixed ? 0 : flow_begin[f], mixed ? 0 : flow_begin[f + 1] - flow_begin[f], rx->cur[f], rx->next[f], rx->ccnt[f],
+                                rx->ncnt[f]};
     LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->in_dev, rx->in_host, sizeof(FlowIn) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
 
-    // (a) + (b): the plan
-    if (plen % 4 == 0 && ((uintptr_t)packets & 3) == 0)
+    // (a) + (b): the plan; a mixed call's on the partition, which also fills in every flow's segment (begin, len) on the device
+    const bool aligned4 = plen % 4 == 0 && ((uintptr_t)packets & 3) == 0;
+    if (mixed) {
+        uint32_t *base = (uint32_t *)res + pl.rec * (size_t)nf, *order = (uint32_t *)rx->order.p;
+        if ((rc = demux_launch(ctx, src.flow_of, npackets, nf, base, rx->in_dev, order))) return rc;
+        if (aligned4)
+            hipLaunchKernelGGL(fec_rx_headers_idx<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, (const uint32_t *)order,
+                               (const uint32_t *)base + nf, (int)plen, dense);
+        else
+            hipLaunchKernelGGL(fec_rx_headers_idx<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, (const uint32_t *)order,
+                               (const uint32_t *)base + nf, (int)plen, dense);
+        pl.order = order;
+        pl.base = (const uint32_t *)rx->res_host + pl.rec * (size_t)nf;
+    } else if (aligned4)
         hipLaunchKernelGGL(fec_rx_headers<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
     else
         hipLaunchKernelGGL(fec_rx_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
@@ -944,9 +1194,10 @@ static int flows_plan(ldpc_amd_fec_rx_flows *rx, const char *who, const uint8_t 
             return set_error(ctx, LDPC_AMD_EHIP, "%s: the plan scan of flow %d hit its iteration cap (internal error); every flow's state is unchanged",
                              who, f);
         const int64_t used = (int64_t)(((uint64_t)(uint32_t)h[R_CONSUMED_HI] << 32) | (uint32_t)h[R_CONSUMED_LO]);
-        rx->tab_host[f] = FlowTab{flow_begin[f], used, (int)base, h[R_CLOSES], rx->cb[f], 0};
+        rx->tab_host[f] = FlowTab{mixed ? (int64_t)pl.base[f] : flow_begin[f], used, (int)base, h[R_CLOSES], rx->cb[f], 0};
         base += h[R_CLOSES];
         pl.max_used = std::max(pl.max_used, used);
+        if (mixed) pl.max_left = std::max(pl.max_left, (int64_t)(pl.base[f + 1] - pl.base[f]) - used);
     }
     pl.T = (int)base;   // <= nflows * max_blocks < 2^31
     if ((rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)pl.T + 2 * (size_t)nf) * (size_t)n)) ||
@@ -971,6 +1222,11 @@ static int flows_winners(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl)
     hipLaunchKernelGGL(fec_rx_winners_flows, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p,
                        (const int32_t *)rx->dest.p, rx->tab_dev, rx->n, pl.T, win);
     LDPC_HIP_TRY(ctx, hipGetLastError());
+    if (pl.order) {   // a mixed call planned on positions: every winner back to its packet index
+        const int64_t cells = ((int64_t)pl.T + 2 * (int64_t)nf) * rx->n;
+        hipLaunchKernelGGL(fec_rx_win_order, dim3(grid_for(cells)), dim3(kThreads), 0, ctx->stream, win, cells, pl.order);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+    }
     return LDPC_AMD_OK;
 }
 
@@ -994,8 +1250,28 @@ static int flows_move(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl, const uint
     return LDPC_AMD_OK;
 }
 
-static void flows_commit(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl, int *blocks, int *closes, int64_t *consumed)
+// a mixed call's `left` (may be null): zero, then 1 behind every flow's consumed prefix
+static int flows_left(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl, int64_t npackets, uint8_t *left)
 {
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (!left) return LDPC_AMD_OK;
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(left, 0, (size_t)npackets, ctx->stream));
+    if (pl.max_left <= 0) return LDPC_AMD_OK;
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pl.max_left + kThreads - 1) / kThreads, std::max(1, 32768 / rx->nflows)));
+    hipLaunchKernelGGL(fec_rx_left_flows, dim3(gx, rx->nflows), dim3(kThreads), 0, ctx->stream, (const FlowTab *)rx->tab_dev,
+                       (const FlowIn *)rx->in_dev, pl.order, left);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// (a mixed call: offered and the unrouted count too)
+static void flows_commit(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl, int *blocks, int *closes, int64_t *consumed, int64_t npackets,
+                         int64_t *offered)
+{
+    if (pl.base) {
+        rx->unrouted += npackets - (int64_t)pl.base[rx->nflows];
+        for (int f = 0; offered && f < rx->nflows; f++) offered[f] = (int64_t)(pl.base[f + 1] - pl.base[f]);
+    }
     for (int f = 0; f < rx->nflows; f++) {
         const int32_t *h = rx->res_host + (size_t)f * pl.rec;
         const FlowTab &t = rx->tab_host[f];
@@ -1055,7 +1331,7 @@ void ldpc_amd_fec_rx_flows_destroy(ldpc_amd_fec_rx_flows *rx)
     if (!rx) return;
     (void)hipSetDevice(rx->ctx->device);
     (void)hipStreamSynchronize(rx->ctx->stream);   // pending work of this object may still use its buffers
-    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots};
+    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots, &rx->order};
     for (Scratch *s : sc)
         if (s->p) (void)hipFree(s->p);
     void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev};
@@ -1072,33 +1348,61 @@ int64_t ldpc_amd_fec_rx_flows_dropped(const ldpc_amd_fec_rx_flows *rx, int flow)
     return rx && flow >= 0 && flow < rx->nflows ? rx->dropped[flow] : -1;
 }
 
-int ldpc_amd_fec_rx_flows_push_many(ldpc_amd_fec_rx_flows *rx, const uint8_t *packets, const int64_t *flow_begin, uint8_t *sym_batch,
-                                    uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+}  // extern "C"
+
+// push_many and push_mixed: P is the segmented call's flow_begin[nflows], or the mixed call's argument
+static int flows_push(ldpc_amd_fec_rx_flows *rx, const char *who, const uint8_t *packets, const FlowsSrc &src, int64_t P, uint8_t *sym_batch,
+                      uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed, int64_t *offered, uint8_t *left)
 {
     if (!rx) return LDPC_AMD_EINVAL;
     ldpc_amd_ctx *ctx = rx->ctx;
+    const bool mixed = src.mixed;
     int rc;
-    int64_t P = 0;
-    if ((rc = flows_check_call(rx, "fec_rx_flows_push_many", flow_begin, max_blocks_per_flow, P))) return rc;
+    if ((rc = mixed ? flows_check_limits(rx, who, P, max_blocks_per_flow) : flows_check_call(rx, who, src.flow_begin, max_blocks_per_flow, P)))
+        return rc;
     if (!sym_batch || !erased_batch || (P > 0 && !packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_push_many: packets / sym_batch / erased_batch must not be null");
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must not be null", who);
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((P > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_push_many: packets / sym_batch / erased_batch must be device pointers of device %d",
-                         ctx->device);
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must be device pointers of device %d", who, ctx->device);
     if (P == 0) {
-        flows_nothing(rx, closes, consumed);
+        flows_nothing(rx, closes, consumed, offered);
         return 0;
     }
+    if (mixed && (rc = flows_check_mixed(rx, who, src.flow_of, left))) return rc;
     FlowsPlan pl;
-    if ((rc = flows_plan(rx, "fec_rx_flows_push_many", packets, flow_begin, P, max_blocks_per_flow, pl))) return rc;
+    if ((rc = flows_plan(rx, who, packets, src, P, max_blocks_per_flow, pl))) return rc;
     // (c), (d), (e): the data movement, asynchronous
     if ((rc = flows_winners(rx, pl)) || (rc = flows_move<true>(rx, pl, packets, 0, pl.T, sym_batch, erased_batch)) ||
-        (rc = flows_move<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)))
+        (rc = flows_move<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)) || (rc = flows_left(rx, pl, P, left)))
         return rc;
-    flows_commit(rx, pl, blocks, closes, consumed);
+    flows_commit(rx, pl, blocks, closes, consumed, P, offered);
     return pl.T;
 }
+
+extern "C" {
+
+int ldpc_amd_fec_rx_flows_push_many(ldpc_amd_fec_rx_flows *rx, const uint8_t *packets, const int64_t *flow_begin, uint8_t *sym_batch,
+                                    uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+{
+    FlowsSrc src;
+    src.flow_begin = flow_begin;
+    return flows_push(rx, "fec_rx_flows_push_many", packets, src, 0, sym_batch, erased_batch, blocks, closes, max_blocks_per_flow, consumed, nullptr,
+                      nullptr);
+}
+
+int ldpc_amd_fec_rx_flows_push_mixed(ldpc_amd_fec_rx_flows *rx, const uint8_t *packets, const int32_t *flow_of, int64_t P, uint8_t *sym_batch,
+                                     uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed,
+                                     int64_t *offered, uint8_t *left)
+{
+    FlowsSrc src;
+    src.mixed = true;
+    src.flow_of = flow_of;
+    return flows_push(rx, "fec_rx_flows_push_mixed", packets, src, P, sym_batch, erased_batch, blocks, closes, max_blocks_per_flow, consumed, offered,
+                      left);
+}
+
+int64_t ldpc_amd_fec_rx_flows_unrouted(const ldpc_amd_fec_rx_flows *rx) { return rx ? rx->unrouted : -1; }
 
 int ldpc_amd_fec_rx_flows_flush(ldpc_amd_fec_rx_flows *rx, int flow, uint8_t *sym_out, uint8_t *erased_out, int *block_out)
 {
@@ -1128,31 +1432,34 @@ int ldpc_amd_fec_rx_flows_flush(ldpc_amd_fec_rx_flows *rx, int flow, uint8_t *sy
 
 // ldpc_amd_fec_rx_dev_decode_many for all flows: ONE launch_decode over the T closed slots (composed: one per chunk of slots).  The
 // staging update of all flows is one launch BEHIND the decode, for the reason given there.
-int ldpc_amd_fec_rx_flows_decode_many(ldpc_amd_fec_rx_flows *rx, int code, const uint8_t *packets, const int64_t *flow_begin, int max_sweeps,
-                                      int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
-                                      int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+}  // extern "C"
+
+static int flows_decode(ldpc_amd_fec_rx_flows *rx, const char *who, int code, const uint8_t *packets, const FlowsSrc &src, int64_t P, int max_sweeps,
+                        int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src,
+                        int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed, int64_t *offered, uint8_t *left)
 {
     if (!rx) return LDPC_AMD_EINVAL;
     ldpc_amd_ctx *ctx = rx->ctx;
     if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    const bool mixed = src.mixed;
     int rc;
-    int64_t P = 0;
-    if ((rc = flows_check_call(rx, "fec_rx_flows_decode_many", flow_begin, max_blocks_per_flow, P))) return rc;
+    if ((rc = mixed ? flows_check_limits(rx, who, P, max_blocks_per_flow) : flows_check_call(rx, who, src.flow_begin, max_blocks_per_flow, P)))
+        return rc;
     if (P == 0) {
-        flows_nothing(rx, closes, consumed);
+        flows_nothing(rx, closes, consumed, offered);
         return 0;
     }
-    if ((rc = rx_decode_check(ctx, rx, "fec_rx_flows_decode_many", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src)))
-        return rc;
+    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
     if (!packets || !is_device_ptr(ctx, packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_decode_many: packets must be a device pointer of device %d", ctx->device);
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets must be a device pointer of device %d", who, ctx->device);
+    if (mixed && (rc = flows_check_mixed(rx, who, src.flow_of, left))) return rc;
     const DevCode &cd = ctx->codes[code]->dev;
     const int n = rx->n, S = rx->S;
     const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
     const size_t frame = (size_t)n * S;
 
     FlowsPlan pl;
-    if ((rc = flows_plan(rx, "fec_rx_flows_decode_many", packets, flow_begin, P, max_blocks_per_flow, pl))) return rc;
+    if ((rc = flows_plan(rx, who, packets, src, P, max_blocks_per_flow, pl))) return rc;
     const int T = pl.T;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kReceiverScratchMax / frame)));
     // every workspace of the call before anything moves: a refusal leaves every flow where it was
@@ -1195,10 +1502,35 @@ int ldpc_amd_fec_rx_flows_decode_many(ldpc_amd_fec_rx_flows *rx, int code, const
         }
     }
     if ((rc = flows_move<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
-    flows_commit(rx, pl, blocks, closes, consumed);
+    if ((rc = flows_left(rx, pl, P, left))) return rc;
+    flows_commit(rx, pl, blocks, closes, consumed, P, offered);
     ctx->receiver_path = fused ? 1 : 2;
     ctx->receiver_blocks = T;
     return T;
+}
+
+extern "C" {
+
+int ldpc_amd_fec_rx_flows_decode_many(ldpc_amd_fec_rx_flows *rx, int code, const uint8_t *packets, const int64_t *flow_begin, int max_sweeps,
+                                      int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
+                                      int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+{
+    FlowsSrc src;
+    src.flow_begin = flow_begin;
+    return flows_decode(rx, "fec_rx_flows_decode_many", code, packets, src, 0, max_sweeps, do_ml, out, sweeps, residual, status, erased_out,
+                        residual_src, blocks, closes, max_blocks_per_flow, consumed, nullptr, nullptr);
+}
+
+int ldpc_amd_fec_rx_flows_decode_mixed(ldpc_amd_fec_rx_flows *rx, int code, const uint8_t *packets, const int32_t *flow_of, int64_t P,
+                                       int max_sweeps, int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status,
+                                       uint8_t *erased_out, int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow,
+                                       int64_t *consumed, int64_t *offered, uint8_t *left)
+{
+    FlowsSrc src;
+    src.mixed = true;
+    src.flow_of = flow_of;
+    return flows_decode(rx, "fec_rx_flows_decode_mixed", code, packets, src, P, max_sweeps, do_ml, out, sweeps, residual, status, erased_out,
+                        residual_src, blocks, closes, max_blocks_per_flow, consumed, offered, left);
 }
 
 int ldpc_amd_fec_rx_flows_decode_flush(ldpc_amd_fec_rx_flows *rx, int flow, int code, int max_sweeps, int do_ml, uint8_t *out, int32_t *sweeps,
@@ -1220,6 +1552,47 @@ int ldpc_amd_fec_rx_flows_decode_flush(ldpc_amd_fec_rx_flows *rx, int flow, int 
     d.sweeps = sweeps; d.residual = residual; d.status = status; d.erased_out = erased_out; d.residual_src = residual_src;
     if ((rc = launch_decode(ctx, d))) return rc;
     return 1;
+}
+
+// ---- the partition on its own (include/ldpc_erasure_amd_flows_mixed.h) ----------------------------------------------------
+int64_t ldpc_amd_fec_flows_demux_dev(ldpc_amd_ctx *ctx, const int32_t *flow_of, int64_t P, int nflows, uint32_t *order, int64_t *counts)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (nflows < 1 || nflows > kMaxFlows || P < 0 || P >= ((int64_t)1 << 31))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_flows_demux_dev: need 1 <= nflows <= 4096 and 0 <= P < 2^31 (nflows=%d)", nflows);
+    if (P == 0) {
+        if (counts) std::fill(counts, counts + nflows, (int64_t)0);
+        ctx->demux_tile = kDemuxMinTile;
+        ctx->demux_tiles = 0;
+        return 0;
+    }
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!flow_of || !order || !is_device_ptr(ctx, flow_of) || !is_device_ptr(ctx, order))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_flows_demux_dev: flow_of / order must be device pointers of device %d", ctx->device);
+    if (((uintptr_t)flow_of | (uintptr_t)order) & 3) return set_error(ctx, LDPC_AMD_EINVAL, "fec_flows_demux_dev: flow_of / order must be 4-byte aligned");
+    int rc;
+    if ((rc = demux_reserve(ctx, P, nflows))) return rc;
+    int64_t tile, tiles;
+    demux_tiling(P, tile, tiles);
+    uint32_t *base = (uint32_t *)ctx->demux_tab.p + (size_t)tiles * (size_t)nflows;   // behind the table
+    if ((rc = demux_launch(ctx, flow_of, P, nflows, base, nullptr, order))) return rc;
+    std::vector<uint32_t> h((size_t)nflows + 1);
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(h.data(), base, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = check_device_error(ctx))) return rc;
+    for (int f = 0; counts && f < nflows; f++) counts[f] = (int64_t)(h[f + 1] - h[f]);
+    return (int64_t)h[nflows];
+}
+
+int ldpc_amd_fec_flows_demux_info(ldpc_amd_ctx *ctx, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_flows_demux_info: info must not be null");
+    info[0] = ctx->demux_tile;
+    info[1] = ctx->demux_tiles;
+    info[2] = (int64_t)ctx->demux_tab.cap;
+    info[3] = 0;
+    return LDPC_AMD_OK;
 }
 
 }  // extern "C"
