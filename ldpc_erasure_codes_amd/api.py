@@ -58,6 +58,9 @@ EXPORTS_FRAMES = ["ldpc_amd_decode_frames", "ldpc_amd_rs_info", "ldpc_amd_rs_dec
 # every symbol include/ldpc_erasure_amd_sender.h declares (the fused sender: source symbols straight to wire packets)
 EXPORTS_SENDER = ["ldpc_amd_fec_encode_packets_dev", "ldpc_amd_fec_sender_info"]
 SENDER_PATHS = ("none", "fused", "composed")
+# every symbol include/ldpc_erasure_amd_sender_flows.h declares (the multi-flow sender: many FEC streams to one multiplexed wire)
+EXPORTS_SENDER_FLOWS = ["ldpc_amd_fec_tx_flows_layout", "ldpc_amd_fec_encode_packets_flows_dev", "ldpc_amd_fec_sender_flows_info"]
+TX_SEGMENTED, TX_ROUND_ROBIN = 0, 1   # LDPC_AMD_FEC_TX_SEGMENTED / LDPC_AMD_FEC_TX_ROUND_ROBIN
 # every symbol include/ldpc_erasure_amd_receiver.h declares (the fused receiver: wire packets straight to decoded frames)
 EXPORTS_RECEIVER = ["ldpc_amd_fec_rx_dev_decode_many", "ldpc_amd_fec_rx_dev_decode_flush", "ldpc_amd_fec_receiver_info"]
 RECEIVER_PATHS = ("none", "fused", "composed")
@@ -185,6 +188,12 @@ def load_library():
     if hasattr(L, "ldpc_amd_fec_encode_packets_dev"):   # (absent from the older builds tools/ab_lib.py loads)
         L.ldpc_amd_fec_encode_packets_dev.argtypes = [vp, i32, i32, i64, vp, C.c_uint, C.c_uint, vp]
         L.ldpc_amd_fec_sender_info.argtypes = [vp, C.POINTER(i32)]
+    # the multi-flow sender (include/ldpc_erasure_amd_sender_flows.h)
+    if hasattr(L, "ldpc_amd_fec_tx_flows_layout"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_tx_flows_layout.argtypes = [i32, vp, i32, i32, vp, vp]
+        L.ldpc_amd_fec_tx_flows_layout.restype = i64
+        L.ldpc_amd_fec_encode_packets_flows_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+        L.ldpc_amd_fec_sender_flows_info.argtypes = [vp, C.POINTER(i64)]
     # the fused receiver (include/ldpc_erasure_amd_receiver.h)
     if hasattr(L, "ldpc_amd_fec_rx_dev_decode_many"):   # (absent from the older builds tools/ab_lib.py loads)
         L.ldpc_amd_fec_rx_dev_decode_many.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i64)]
@@ -249,6 +258,24 @@ def code_params(code_ind):
     if L.ldpc_amd_code_params(code_ind, p) != OK:
         raise LdpcAmdError(f"no built-in code {code_ind}")
     return list(p)
+
+
+def fec_tx_flows_layout(frame_begin, n, order):
+    """Where the multi-flow sender puts its packets (host arithmetic, no GPU needed): frame_begin = nflows + 1 frame indices, flow f
+    owns the frames frame_begin[f] .. frame_begin[f+1]-1.  Returns (first int64 [F], stride int32 [F]): row j of frame t is packet
+    first[t] + j * stride[t] in the order TX_SEGMENTED or TX_ROUND_ROBIN (include/ldpc_erasure_amd_sender_flows.h)."""
+    L = load_library()
+    fb = np.ascontiguousarray(frame_begin, dtype=np.int64)
+    if fb.ndim != 1 or fb.shape[0] < 2:
+        raise LdpcAmdError("fec_tx_flows_layout: frame_begin must hold nflows + 1 >= 2 entries")
+    F = max(int(fb[-1]), 0)
+    first = np.zeros(F, dtype=np.int64)
+    stride = np.zeros(F, dtype=np.int32)
+    rc = L.ldpc_amd_fec_tx_flows_layout(fb.shape[0] - 1, fb.ctypes.data, n, order, first.ctypes.data, stride.ctypes.data)
+    if rc < 0:
+        raise LdpcAmdError(f"fec_tx_flows_layout = {rc}: bad nflows / frame_begin / n / order")
+    assert rc == F * n
+    return first, stride
 
 
 def _is_torch(x):
@@ -635,6 +662,46 @@ class Context:
         self._check(self._L.ldpc_amd_fec_sender_info(self._h, info), "fec_sender_info")
         return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1])}
 
+    # -- the multi-flow sender (include/ldpc_erasure_amd_sender_flows.h)
+    def fec_encode_packets_flows_device(self, code, source, frame_begin, fec_class, block0, order, out=None, want_flow_of=True):
+        """source: torch uint8 [F][k][S] (or [F][k] for S = 1) on this context's device, the frames of nflows streams side by side:
+        flow f owns the frames frame_begin[f] .. frame_begin[f+1]-1 and sends them with class fec_class[f], numbered from block0[f]
+        on (a scalar stands for every flow).  Returns (packets torch uint8 [F*n][8+S], flow_of torch int32 [F*n] or None,
+        packet_begin int64 [nflows+1]): every flow's packets as fec_encode_packets_device makes them, flow after flow (order =
+        TX_SEGMENTED: FecRxFlows.decode_many's input with packet_begin) or one packet of every flow in turn (TX_ROUND_ROBIN:
+        decode_mixed's input with flow_of).  fec_sender_flows_info() says which path ran.  Asynchronous on the context's stream."""
+        import torch
+        assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
+        n, k, _ = self.code_info(code)
+        F = source.shape[0]
+        S = 1 if source.ndim == 2 else source.shape[2]
+        assert source.shape[1] == k
+        fb = np.ascontiguousarray(frame_begin, dtype=np.int64)
+        assert fb.ndim == 1 and fb.shape[0] >= 2 and int(fb[-1]) == F
+        nflows = fb.shape[0] - 1
+        cls = np.ascontiguousarray(np.broadcast_to(np.asarray(fec_class, dtype=np.int64) & 0xFF, (nflows,)), dtype=np.uint8)
+        blk = np.ascontiguousarray(np.broadcast_to(np.asarray(block0, dtype=np.int64) & 0xFF, (nflows,)), dtype=np.uint8)
+        if out is None:
+            out = torch.empty((F * n, 8 + S), dtype=torch.uint8, device=source.device)
+        assert tuple(out.shape) == (F * n, 8 + S) and out.dtype == torch.uint8
+        flow_of = torch.empty(F * n, dtype=torch.int32, device=source.device) if want_flow_of else None
+        pb = np.zeros(nflows + 1, dtype=np.int64)
+        self._check(self._L.ldpc_amd_fec_encode_packets_flows_dev(
+            self._h, code, S, nflows, fb.ctypes.data, _ptr(source) if F else None, cls.ctypes.data, blk.ctypes.data, order,
+            _ptr(out) if F else None, _ptr(flow_of) if want_flow_of and F else None, pb.ctypes.data), "fec_encode_packets_flows_dev")
+        return out, flow_of, pb
+
+    def fec_sender_flows_info(self):
+        """{"path": "none" | "fused" | "composed" of the last fec_encode_packets_flows_device call, "scratch_bytes": codeword scratch
+        the context holds for the composed paths, "descriptor_bytes": descriptor memory it holds, "frames": frames of that call}."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_sender_flows_info(self._h, info), "fec_sender_flows_info")
+        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "frames": int(info[3])}
+
+    def fec_tx_flows(self, code, S, nflows, fec_class=1, block0=0):
+        """nflows senders that number their blocks across calls and share one wire (FecTxFlows)."""
+        return FecTxFlows(self, code, S, nflows, fec_class, block0)
+
     def fec_tx_device(self, code, S, fec_class=1, block0=0):
         """A sender that numbers its blocks across calls (FecTxDevice)."""
         return FecTxDevice(self, code, S, fec_class, block0)
@@ -996,6 +1063,30 @@ class FecTxDevice:
         pk = self._ctx.fec_encode_packets_device(self.code, source, self.fec_class, self.next_block, out=out)
         self.next_block = (self.next_block + source.shape[0]) & 0xFF
         return pk
+
+
+class FecTxFlows:
+    """The sender's side of FecRxFlows: nflows FecTxDevice on one wire.  Its state is the reference's block counter, one per flow
+    (blockNum += 1 per frame, OpenCL/device/ldpc_erasure_encoder_VITA_in_UDP_out.cl:134): send(source, frame_begin, order) returns
+    the packets of every flow's frames numbered from next_block[f] on, in the asked order, and advances each flow's counter by its
+    frame count modulo 256.  fec_class and block0: a scalar for all flows or one value per flow."""
+
+    def __init__(self, ctx, code, S, nflows, fec_class=1, block0=0):
+        self._ctx, self.code, self.S, self.nflows = ctx, code, S, nflows
+        self.n, self.k, _ = ctx.code_info(code)
+        self.fec_class = np.ascontiguousarray(np.broadcast_to(np.asarray(fec_class, dtype=np.int64) & 0xFF, (nflows,)), dtype=np.uint8)
+        self.next_block = np.array(np.broadcast_to(np.asarray(block0, dtype=np.int64) & 0xFF, (nflows,)), dtype=np.int64)
+
+    def send(self, source, frame_begin, order=TX_ROUND_ROBIN, out=None, want_flow_of=True):
+        """source: torch uint8 [F][k][S] (or [F][k] for S = 1), flow f's frames at frame_begin[f] .. frame_begin[f+1]-1 ->
+        (packets, flow_of, packet_begin) of Context.fec_encode_packets_flows_device."""
+        assert (1 if source.ndim == 2 else source.shape[2]) == self.S
+        fb = np.ascontiguousarray(frame_begin, dtype=np.int64)
+        assert fb.shape == (self.nflows + 1,)
+        r = self._ctx.fec_encode_packets_flows_device(self.code, source, fb, self.fec_class, self.next_block, order, out=out,
+                                                      want_flow_of=want_flow_of)
+        self.next_block = (self.next_block + np.diff(fb)) & 0xFF
+        return r
 
 
 def shard_frames(nframes, nranks, rank):

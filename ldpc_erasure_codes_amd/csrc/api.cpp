@@ -845,7 +845,7 @@ void ldpc_amd_cleanup(ldpc_amd_ctx *ctx)
     }
     Scratch *all[] = {&ctx->sched, &ctx->mlws, &ctx->mlstate, &ctx->mlops, &ctx->mlrec, &ctx->mllist, &ctx->biglist, &ctx->encctr, &ctx->stage_in, &ctx->stage_er,
                       &ctx->stage_out, &ctx->stage_i32, &ctx->schedpull, &ctx->schedlists, &ctx->rsws, &ctx->rsbad, &ctx->fpga_erased, &ctx->fpga_stats,
-                      &ctx->rssel, &ctx->frstatus, &ctx->stage_fr, &ctx->sender_cw, &ctx->rx_sym, &ctx->rx_er, &ctx->rx_src, &ctx->demux_tab};
+                      &ctx->rssel, &ctx->frstatus, &ctx->stage_fr, &ctx->sender_cw, &ctx->rx_sym, &ctx->rx_er, &ctx->rx_src, &ctx->demux_tab, &ctx->txf_desc};
     for (Scratch *s : all) scratch_free(*s);
     for (auto &v : ctx->prof_events)
         for (auto &pr : v) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -854,6 +854,10 @@ void ldpc_amd_cleanup(ldpc_amd_ctx *ctx)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ml_events)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->txf_event)
+        if (e) (void)hipEventDestroy(e);
+    for (void *h : ctx->txf_stage)
+        if (h) (void)hipHostFree(h);
     if (ctx->aux_in) (void)hipStreamDestroy(ctx->aux_in);
     if (ctx->aux_out) (void)hipStreamDestroy(ctx->aux_out);
     if (ctx->aux_ml) (void)hipStreamDestroy(ctx->aux_ml);

@@ -201,6 +201,17 @@ struct ldpc_amd_ctx {
     ldpc_amd::Scratch frstatus; // decode_frames without a status array: the status words the finalise kernel reads
     ldpc_amd::Scratch sender_cw;   // fec_encode_packets_dev, composed path: codewords of one chunk of frames (at most 256 MiB)
     int sender_path = 0;           // ... path of the last call: 0 none yet, 1 fused kernel, 2 composed (ldpc_amd_fec_sender_info)
+    // fec_encode_packets_flows_dev: the frames' descriptors on the device (16 bytes each; the stream orders a call's copy behind the
+    // kernels of the call before), and their pinned staging -- two slots used in turn, each with the event of its last copy, so that a
+    // slot is never rewritten under a copy in flight
+    ldpc_amd::Scratch txf_desc;
+    void *txf_stage[2] = {nullptr, nullptr};
+    size_t txf_stage_cap[2] = {0, 0};
+    hipEvent_t txf_event[2] = {nullptr, nullptr};
+    bool txf_pending[2] = {false, false};
+    unsigned txf_calls = 0;
+    int txf_path = 0;              // ... path of the last call (ldpc_amd_fec_sender_flows_info)
+    int64_t txf_frames = 0;        // ... its frames
     ldpc_amd::Scratch rx_sym;      // fec_rx_dev_decode_many, composed path: received symbols of one chunk of closed blocks (at most 256 MiB)
     ldpc_amd::Scratch rx_er;       // ... both paths: erasure flags of the closed blocks, [closes][n]
     ldpc_amd::Scratch rx_src;      // ... fused path: row-source words of the closed blocks, [closes][n] u32 (PacketRows)
@@ -296,6 +307,11 @@ int launch_encode(ldpc_amd_ctx *ctx, const DevCode &code, int S, int64_t nframes
 constexpr int kEncodeNotFused = 1;
 int launch_encode_packets(ldpc_amd_ctx *ctx, const DevCode &code, int S, int64_t nframes, const uint8_t *src, unsigned fec_class,
                           unsigned block0, uint8_t *packets);
+// ... every frame placed and numbered by a descriptor {first packet: u64, stride in packets: u32, class << 8 | block: u32} in device
+// memory (the multi-flow sender); max_stride = the largest stride of the table.  kEncodeNotFused as above, or where max_stride * (8 + S)
+// does not fit 32 bits.
+int launch_encode_packets_flows(ldpc_amd_ctx *ctx, const DevCode &code, int S, int64_t nframes, const uint8_t *src, const void *flow_desc,
+                                int64_t max_stride, uint8_t *packets);
 int launch_fpga_halves(ldpc_amd_ctx *ctx, const DevCode &code, int64_t nframes, const uint8_t *erased, int num_iter,
                        int32_t *residual_sys, int32_t *iterations);
 int launch_selftest(ldpc_amd_ctx *ctx);

@@ -691,6 +691,10 @@ struct ScatterArgs {
     const uint8_t *pin_stage; // staging planes [2][n][S]
     int pin_plen;
     int lds_pin;              // the list of received rows of the list modes (SCATTER_DYN >= 2), [n] u16: the words keep the row kinds' region
+    // multi-flow sender (scatter_frame<..., PKT, ..., FLW>; ldpc_amd_fec_encode_packets_flows_dev): one descriptor per frame --
+    // .x | .y << 32 = the frame's first packet, .z = its stride in packets (row j is packet first + j * stride), .w = FEC class << 8 |
+    // block number of THIS frame.  pkt_hdr is not read.  The host checks stride * (8 + S) < 2^32 (launch_encode_packets_flows).
+    const uint4 *flow_desc;
 };
 
 __device__ __forceinline__ MulTab lds_multab(const uint32_t *mt, uint32_t c)
@@ -801,10 +805,16 @@ __device__ __forceinline__ void stream_store16(uint8_t *p, const U4 &v)
 // row-source words are copied to LDS at set-up, IN PLACE OF the row kinds (a word says where a received row lies, or that the row is
 // erased and never solved -- kRowNever -- or erased and solved by a step -- kRowSolved, set by put_step), and the stream reads its word
 // where it read the row kind: no global load sits between a wave and its row loads.  Only the input address changes.
-template <int LPR, int R, bool NT, bool INPLACE, int WPE = 4, bool PERSIST = false, bool WARM = false, bool PKT = false, bool PIN = false>
+// FLW (with PKT: ldpc_scatter_static_flw_kernel, the multi-flow sender): the frame's place in the packet array and its header do not
+// follow from f but come from the frame's descriptor (ScatterArgs::flow_desc), read once per item: first packet and stride.  Rows of one
+// frame are then stride * (8 + S) bytes apart -- packets of other flows lie between them -- which does not fit a 32-bit offset, so a
+// row address is one 64-bit multiply-add per row and lane, as in the packets-in form (below).  Only the output address changes.
+template <int LPR, int R, bool NT, bool INPLACE, int WPE = 4, bool PERSIST = false, bool WARM = false, bool PKT = false, bool PIN = false,
+          bool FLW = false>
 __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned char *smem, const int64_t f, const int sl)
 {
     static_assert(!PKT || (PERSIST && !INPLACE), "the packet-output form is the persistent encoder's");
+    static_assert(!FLW || PKT, "the descriptor form is the packet-output encoder's");
     static_assert(!PIN || (!PERSIST && !INPLACE && !PKT), "the packets-in form is the out-of-place decoder's");
     constexpr bool warm = WARM;
     // (the persistent form is the encoder's: the decoder's paths fold away in its instantiations)
@@ -875,6 +885,8 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     constexpr uint32_t kRowNever = 0xFFFFFFFFu, kRowSolved = 0xFFFFFFFEu;
     auto row_kind = [](uint32_t w) { return w == kRowNever ? 2 : (w == kRowSolved ? 0 : 1); };
     const uint32_t *gsrc = PIN ? a.pin_src + f * (int64_t)n : nullptr;
+    uint4 fdv = make_uint4(0u, 0u, 0u, 0u);   // FLW: the frame's descriptor, requested with the rest of the set-up's loads
+    if constexpr (FLW) fdv = a.flow_desc[f];
 #pragma unroll
     for (int u = 0; u < SPT; u++) {
         const int s = tid + u * nthr;
@@ -1125,7 +1137,11 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
     // 32-bit multiply-add instead of 64-bit multiplies -- the streaming loop is bound by vector ALU issue, not by waits.
     const uint8_t *fin0 = a.sym + f * (int64_t)a.in_rows * S + poff;
     constexpr int kPktHdr = PKT ? 8 : 0;   // LDPC_AMD_FEC_HEADER_BYTES in front of every output row
-    uint8_t *fout0 = a.out + f * (int64_t)n * (S + kPktHdr) + kPktHdr + poff;
+    // FLW: the descriptor is the same in every lane -- its words go to scalar registers, and so does everything derived from them
+    const uint32_t fd_lo = FLW ? (uint32_t)__builtin_amdgcn_readfirstlane((int)fdv.x) : 0u, fd_hi = FLW ? (uint32_t)__builtin_amdgcn_readfirstlane((int)fdv.y) : 0u;
+    const uint32_t fd_stride = FLW ? (uint32_t)__builtin_amdgcn_readfirstlane((int)fdv.z) : 0u, fd_hdr = FLW ? (uint32_t)__builtin_amdgcn_readfirstlane((int)fdv.w) : 0u;
+    const uint64_t fd_first = (uint64_t)fd_lo | ((uint64_t)fd_hi << 32);
+    uint8_t *fout0 = FLW ? a.out + fd_first * (uint64_t)(S + kPktHdr) + kPktHdr + poff : a.out + f * (int64_t)n * (S + kPktHdr) + kPktHdr + poff;
     const uint32_t lo16 = (uint32_t)gl * 16u, S32 = (uint32_t)S, O32 = (uint32_t)(S + kPktHdr);
     // (24-bit multiply: full rate, where the 32-bit one the compiler picked -- v_mad_u64_u32 -- runs at a quarter; j < 2^16 and
     // S < 2^24 are checked by the host's plan; PKT: 8 + S < 2^24 and n * (8 + S) < 2^32, checked by launch_encode)
@@ -1149,10 +1165,16 @@ __device__ __forceinline__ void scatter_frame(const ScatterArgs &a, unsigned cha
             return fin0 + (__umul24((uint32_t)j, S32) + lo16);
         }
     };
-    auto out_row = [&](int j) { return fout0 + (__umul24((uint32_t)j, O32) + lo16); };
+    // FLW: per-lane base + row * (stride * (8 + S)), the product below 2^32 by the host's check -- one v_mad_u64_u32 per row and lane
+    uint8_t *flw_b0 = FLW ? fout0 + lo16 : nullptr;
+    const uint32_t F32 = FLW ? fd_stride * O32 : 0u;
+    auto out_row = [&](int j) -> uint8_t * {
+        if constexpr (FLW) return flw_b0 + (uint64_t)(uint32_t)j * (uint64_t)F32;
+        else return fout0 + (__umul24((uint32_t)j, O32) + lo16);
+    };
     // every output row leaves through here
     const bool hdr_lane = PKT && sl == 0 && gl == 0;
-    const unsigned pkt_class = PKT ? (a.pkt_hdr >> 8) : 0u, pkt_block = PKT ? (a.pkt_hdr + (unsigned)f) : 0u;
+    const unsigned pkt_class = PKT ? ((FLW ? fd_hdr : a.pkt_hdr) >> 8) : 0u, pkt_block = PKT ? (FLW ? fd_hdr : a.pkt_hdr + (unsigned)f) : 0u;
     auto put_row = [&](int j, const U4 &v) {
         uint8_t *p = out_row(j);
         stream_store16<NT, PKT>(p, v);
@@ -1636,7 +1658,7 @@ __global__ __launch_bounds__(1024, WPE) void ldpc_scatter_pktin_big_kernel(Scatt
 // The counter resets itself: the last workgroup to find it exhausted zeroes it for the next launch of this context.
 // PKT: the packet-output form (scatter_frame).  The two forms are two kernels over one body, so that the codeword encoder keeps
 // its name in traces and profiles and the fused sender has one of its own.
-template <int LPR, int R, bool NT, int WPE, bool PKT>
+template <int LPR, int R, bool NT, int WPE, bool PKT, bool FLW = false>
 __device__ __forceinline__ void scatter_static_body(const ScatterArgs &a, unsigned char *smem)
 {
     const int items = (int)(a.nframes * a.nslices);
@@ -1651,8 +1673,8 @@ __device__ __forceinline__ void scatter_static_body(const ScatterArgs &a, unsign
     // across the loop -- 108 spilled registers against 12 of the one-item kernel)
     int it = next_item();
     if (it < items) {
-        scatter_frame<LPR, R, NT, false, WPE, true, false, PKT>(a, smem, it / a.nslices, it % a.nslices);
-        while ((it = next_item()) < items) scatter_frame<LPR, R, NT, false, WPE, true, true, PKT>(a, smem, it / a.nslices, it % a.nslices);
+        scatter_frame<LPR, R, NT, false, WPE, true, false, PKT, false, FLW>(a, smem, it / a.nslices, it % a.nslices);
+        while ((it = next_item()) < items) scatter_frame<LPR, R, NT, false, WPE, true, true, PKT, false, FLW>(a, smem, it / a.nslices, it % a.nslices);
     }
     if (threadIdx.x == 0) {
         __threadfence();
@@ -1676,6 +1698,15 @@ __global__ __launch_bounds__(1024, WPE) void ldpc_scatter_static_pkt_kernel(Scat
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     scatter_static_body<LPR, R, NT, WPE, true>(a, smem);
+}
+
+// The multi-flow sender: the same, every frame placed and numbered by its descriptor (ldpc_amd_fec_encode_packets_flows_dev).  A kernel
+// of its own, so that the two above keep their instruction streams.
+template <int LPR, int R, bool NT, int WPE>
+__global__ __launch_bounds__(1024, WPE) void ldpc_scatter_static_flw_kernel(ScatterArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    scatter_static_body<LPR, R, NT, WPE, true, true>(a, smem);
 }
 
 #include "ml_kernel.inc"
@@ -2301,12 +2332,20 @@ static int launch_scatter_persistent(ldpc_amd_ctx *ctx, const ScatterPlan &p, Sc
     }
     sa.big_list = (int32_t *)ctx->encctr.p + 16 * (ctx->enc_launches++ % kEncCtrs);
     if constexpr (!kPersistAll) {   // (the word form: NT, and one workgroup per CU)
+        if (sa.flow_desc) {   // the multi-flow sender
+            prof_name(ctx, LDPC_AMD_PROF_APPLY, "ldpc_scatter_static_flw_kernel", LPR, R, true, 4);
+            return launch_lds(ctx, ldpc_scatter_static_flw_kernel<LPR, R, true, 4>, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);
+        }
         prof_name(ctx, LDPC_AMD_PROF_APPLY, "ldpc_scatter_static_pkt_kernel", LPR, R, true, 4);
         return launch_lds(ctx, ldpc_scatter_static_pkt_kernel<LPR, R, true, 4>, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);
     } else {
         return with_nt_wpe(nt, p.two_tier, [&](auto NT, auto WPE) {
             constexpr bool kNT = decltype(NT)::value;
             constexpr int kWPE = decltype(WPE)::value;
+            if (sa.pkt_out && sa.flow_desc) {   // the multi-flow sender: packets out, placed by the frames' descriptors
+                prof_name(ctx, LDPC_AMD_PROF_APPLY, "ldpc_scatter_static_flw_kernel", LPR, R, kNT, kWPE);
+                return launch_lds(ctx, ldpc_scatter_static_flw_kernel<LPR, R, kNT, kWPE>, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);
+            }
             if (sa.pkt_out) {   // the fused sender: packets out
                 prof_name(ctx, LDPC_AMD_PROF_APPLY, "ldpc_scatter_static_pkt_kernel", LPR, R, kNT, kWPE);
                 return launch_lds(ctx, ldpc_scatter_static_pkt_kernel<LPR, R, kNT, kWPE>, gp, dim3(THREADS), (size_t)p.lds1, ctx->stream, sa);
@@ -2975,7 +3014,7 @@ bool decode_reads_packets(ldpc_amd_ctx *ctx, const DevCode &cd, int S)
 // pkt_out: cw is a packet array [nframes * n][8 + S] and pkt_hdr its header base (ScatterArgs::pkt_hdr) -- the fused sender.  Only
 // the persistent scatter encoder has that form: every other route returns kEncodeNotFused BEFORE anything is launched.
 static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, const uint8_t *src, uint8_t *cw, int pkt_out,
-                              uint32_t pkt_hdr)
+                              uint32_t pkt_hdr, const void *flow_desc = nullptr)
 {
     if (nframes <= 0) return LDPC_AMD_OK;
     if (S == 1) {
@@ -3004,7 +3043,7 @@ static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64
             sa.enc_group = e.grouped ? 1 : 0;
             ctx->last_enc_grouped = sa.enc_group;
             sa.enc_list = kn.enc_list;   // measured slower (4.62 vs 4.14 ms): off unless asked for
-            sa.pkt_out = pkt_out; sa.pkt_hdr = pkt_hdr;
+            sa.pkt_out = pkt_out; sa.pkt_hdr = pkt_hdr; sa.flow_desc = pkt_out ? (const uint4 *)flow_desc : nullptr;
             return launch_scatter(ctx, e.plan, sa, nullptr);
         }
     }
@@ -3025,6 +3064,17 @@ int launch_encode_packets(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t n
     // (word form: the source rows are 4-byte aligned whatever the array's alignment, and a packet of 8 + S bytes only every other one)
     if (ctx->knobs.enc_pkt == 0 || ((uintptr_t)packets & 7) != 0 || ((uintptr_t)src & (symbol_len_words(S) ? 3 : 15)) != 0) return kEncodeNotFused;
     return launch_encode_impl(ctx, cd, S, nframes, src, packets, 1, ((uint32_t)(fec_class & 0xffu) << 8) | (uint32_t)(block0 & 0xffu));
+}
+
+// The multi-flow sender's fused form: as launch_encode_packets, every frame placed and numbered by its 16-byte descriptor in device
+// memory (ScatterArgs::flow_desc).  max_stride: the largest stride, in packets, of any descriptor -- the row address of the kernel is
+// base + row * (stride * (8 + S)) with a 32-bit product.
+int launch_encode_packets_flows(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64_t nframes, const uint8_t *src, const void *flow_desc,
+                                int64_t max_stride, uint8_t *packets)
+{
+    if (ctx->knobs.enc_pkt == 0 || ((uintptr_t)packets & 7) != 0 || ((uintptr_t)src & (symbol_len_words(S) ? 3 : 15)) != 0) return kEncodeNotFused;
+    if (!flow_desc || ((uintptr_t)flow_desc & 15) != 0 || max_stride < 1 || (uint64_t)max_stride * (uint64_t)(S + 8) >= (1ull << 32)) return kEncodeNotFused;
+    return launch_encode_impl(ctx, cd, S, nframes, src, packets, 1, 0u, flow_desc);
 }
 
 // FRAMES: val is the frame array [nblocks][n][S], idx / nrecv what rs_select_kernel wrote (launch_rs_decode_frames)

@@ -28,11 +28,13 @@
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <vector>
 
 #include "internal.h"
 #include "fec_header_dev.h"
 #include "../../include/ldpc_erasure_amd_wire_dev.h"
 #include "../../include/ldpc_erasure_amd_sender.h"
+#include "../../include/ldpc_erasure_amd_sender_flows.h"
 #include "../../include/ldpc_erasure_amd_receiver.h"
 #include "../../include/ldpc_erasure_amd_flows.h"
 #include "../../include/ldpc_erasure_amd_flows_mixed.h"
@@ -95,6 +97,67 @@ __global__ __launch_bounds__(kThreads) void fec_packetize_bytes(const uint8_t *_
             b = frames[r * S + (o - kHdr)];
         }
         packets[t] = b;
+    }
+}
+
+// ---- multi-flow sender: the composed path's packetisers and flow_of (include/ldpc_erasure_amd_sender_flows.h) -----------------
+// One descriptor per frame: row j of the frame is packet first + j * stride, its header class = hdr >> 8, block = hdr & 0xff.  The
+// same 16 bytes the descriptor form of the packet encoder reads (ScatterArgs::flow_desc in kernels.hip).
+struct TxFrameDesc {
+    uint64_t first;
+    uint32_t stride;
+    uint32_t hdr;
+};
+static_assert(sizeof(TxFrameDesc) == 16, "the encoder reads a descriptor as one uint4");
+
+// fec_packetize_v16 with the packet of a row taken from its frame's descriptor.  frames: [nf][n][16 q] codewords of the frames
+// desc[0 .. nf-1] (the caller passes the table at the chunk's first frame).
+__global__ __launch_bounds__(kThreads) void fec_packetize_flows_v16(const uint4 *__restrict__ frames, int64_t rows, int n, int q,
+                                                                   const TxFrameDesc *__restrict__ desc, uint8_t *__restrict__ packets)
+{
+    const int64_t total = rows * q, plen = (int64_t)q * 16 + kHdr;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
+        const int64_t r = t / q;
+        const int c = (int)(t - r * q);
+        const int64_t f = r / n;
+        const unsigned j = (unsigned)(r - f * n);
+        const TxFrameDesc d = desc[f];
+        uint8_t *pk = packets + (int64_t)(d.first + (uint64_t)j * d.stride) * plen;
+        const uint4 v = frames[t];
+        uint2 *dst = reinterpret_cast<uint2 *>(pk + kHdr + (int64_t)c * 16);
+        dst[0] = make_uint2(v.x, v.y);
+        dst[1] = make_uint2(v.z, v.w);
+        if (c == 0) *reinterpret_cast<uint64_t *>(pk) = fec_header(d.hdr >> 8, d.hdr, j);
+    }
+}
+
+// fec_packetize_bytes likewise: any S and alignment (S = 1, the word form, a packet array that is not 8-byte aligned).
+__global__ __launch_bounds__(kThreads) void fec_packetize_flows_bytes(const uint8_t *__restrict__ frames, int64_t rows, int n, int S,
+                                                                     const TxFrameDesc *__restrict__ desc, uint8_t *__restrict__ packets)
+{
+    const int64_t plen = (int64_t)S + kHdr, total = rows * plen;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
+        const int64_t r = t / plen;
+        const int o = (int)(t - r * plen);
+        const int64_t f = r / n;
+        const unsigned j = (unsigned)(r - f * n);
+        const TxFrameDesc d = desc[f];
+        uint8_t b;
+        if (o < kHdr) b = (uint8_t)(fec_header(d.hdr >> 8, d.hdr, j) >> (8 * o));   // little endian
+        else b = frames[r * S + (o - kHdr)];
+        packets[(int64_t)(d.first + (uint64_t)j * d.stride) * plen + o] = b;
+    }
+}
+
+// flow_of[p] = the flow of packet p, one 4-byte store per packet: work item (frame, row) stores its frame's flow at the row's packet.
+__global__ __launch_bounds__(kThreads) void fec_tx_flow_of(const TxFrameDesc *__restrict__ desc, const int32_t *__restrict__ frame_flow,
+                                                          int64_t rows, int n, int32_t *__restrict__ flow_of)
+{
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < rows; r += (int64_t)gridDim.x * kThreads) {
+        const int64_t f = r / n;
+        const unsigned j = (unsigned)(r - f * n);
+        const TxFrameDesc d = desc[f];
+        flow_of[d.first + (uint64_t)j * d.stride] = frame_flow[f];
     }
 }
 
@@ -704,6 +767,173 @@ int ldpc_amd_fec_sender_info(ldpc_amd_ctx *ctx, int info[4])
     info[0] = ctx->sender_path;
     info[1] = (int)std::min<size_t>(ctx->sender_cw.cap, (size_t)INT32_MAX);
     info[2] = info[3] = 0;
+    return LDPC_AMD_OK;
+}
+
+// ---- the multi-flow sender (include/ldpc_erasure_amd_sender_flows.h) --------------------------------------------------------
+// The order as arithmetic.  ROUND_ROBIN: while frame i of every flow is on the wire the active flows are those with more than i
+// frames -- A_i of them -- and they take turns in ascending order, so row j of frame i of flow f is packet base_i + rank + j A_i,
+// rank = the active flows below f, base_i = n (A_0 + ... + A_{i-1}).  The active list only ever loses flows, so it is compacted
+// in place as i grows: the work is the sum of the A_i, which is F.
+int64_t ldpc_amd_fec_tx_flows_layout(int nflows, const int64_t *frame_begin, int n, int order, int64_t *first, int32_t *stride)
+{
+    if (nflows < 1 || nflows > LDPC_AMD_FEC_TX_MAX_FLOWS || !frame_begin || n < 1 || frame_begin[0] != 0) return LDPC_AMD_EINVAL;
+    if (order != LDPC_AMD_FEC_TX_SEGMENTED && order != LDPC_AMD_FEC_TX_ROUND_ROBIN) return LDPC_AMD_EINVAL;
+    for (int f = 0; f < nflows; f++)
+        if (frame_begin[f + 1] < frame_begin[f]) return LDPC_AMD_EINVAL;
+    const int64_t F = frame_begin[nflows];
+    if (F > (((int64_t)1 << 31) - 1) / n) return LDPC_AMD_EINVAL;   // F * n < 2^31
+    if (order == LDPC_AMD_FEC_TX_SEGMENTED) {
+        for (int64_t t = 0; t < F; t++) {
+            if (first) first[t] = t * n;
+            if (stride) stride[t] = 1;
+        }
+        return F * n;
+    }
+    std::vector<int> active;
+    active.reserve((size_t)nflows);
+    for (int f = 0; f < nflows; f++)
+        if (frame_begin[f + 1] > frame_begin[f]) active.push_back(f);
+    int64_t base = 0;
+    for (int64_t i = 0; !active.empty(); i++) {
+        const int64_t A = (int64_t)active.size();
+        size_t keep = 0;
+        for (size_t r = 0; r < active.size(); r++) {
+            const int f = active[r];
+            const int64_t t = frame_begin[f] + i;
+            if (first) first[t] = base + (int64_t)r;
+            if (stride) stride[t] = (int32_t)A;
+            if (frame_begin[f + 1] - frame_begin[f] > i + 1) active[keep++] = f;
+        }
+        active.resize(keep);
+        base += A * n;
+    }
+    return F * n;
+}
+
+// Fused where launch_encode_packets_flows has the descriptor form of the packet encoder for this call; else composed: encode a
+// chunk of frames into the context's codeword scratch, packetise it by the descriptors, next chunk.
+int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
+                                          const uint8_t *fec_class, const uint8_t *block0, int order, uint8_t *packets, int32_t *flow_of,
+                                          int64_t *packet_begin)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    const DevCode &cd = ctx->codes[code]->dev;
+    if (nflows < 1 || nflows > LDPC_AMD_FEC_TX_MAX_FLOWS)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: nflows must be 1..%d (got %d)", LDPC_AMD_FEC_TX_MAX_FLOWS, nflows);
+    if (!frame_begin || !fec_class || !block0) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: frame_begin / fec_class / block0 must not be null");
+    if (S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: bad S");
+    if (order != LDPC_AMD_FEC_TX_SEGMENTED && order != LDPC_AMD_FEC_TX_ROUND_ROBIN)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: unknown order %d", order);
+    if (frame_begin[0] != 0) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: frame_begin must start at 0");
+    for (int f = 0; f < nflows; f++)
+        if (frame_begin[f + 1] < frame_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: frame_begin decreases at flow %d", f);
+    const int64_t F = frame_begin[nflows];
+    if (F > (((int64_t)1 << 31) - 1) / cd.n)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: %lld frames of %d packets are not below 2^31 packets", (long long)F, cd.n);
+    if (F == 0) return LDPC_AMD_OK;
+    if (cd.enc_nlevels == 0) return set_error(ctx, LDPC_AMD_EUNSUP, "code is not in triangle form: no systematic encoder");
+    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets) || (flow_of && !is_device_ptr(ctx, flow_of)))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: source / packets / flow_of must be device pointers of device %d", ctx->device);
+    if (((uintptr_t)flow_of & 3) != 0) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: flow_of must be 4-byte aligned");
+    if (symbol_len_words(S) && ((uintptr_t)source & 3) != 0)
+        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
+    const int n = cd.n;
+    const int64_t P = F * n;
+    const size_t src_frame = (size_t)cd.k * S, cw_frame = (size_t)n * S, pk_frame = (size_t)n * ((size_t)S + kHdr);
+    {
+        const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)F, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)F;
+        const uintptr_t q0 = (uintptr_t)flow_of, q1 = q0 + sizeof(int32_t) * (size_t)P;
+        if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: source and packets overlap");
+        if (flow_of && ((q0 < p1 && p0 < q1) || (q0 < s1 && s0 < q1)))
+            return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: flow_of overlaps source or packets");
+    }
+    // the table: [F] descriptors, the frames' flows behind them
+    const size_t tab_bytes = (sizeof(TxFrameDesc) + sizeof(int32_t)) * (size_t)F;
+    int rc;
+    if ((rc = scratch_reserve(ctx, ctx->txf_desc, tab_bytes))) return rc;
+    const int slot = (int)(ctx->txf_calls & 1u);
+    if (!ctx->txf_event[slot]) LDPC_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txf_event[slot], hipEventDisableTiming));
+    if (ctx->txf_pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
+        LDPC_HIP_TRY(ctx, hipEventSynchronize(ctx->txf_event[slot]));
+        ctx->txf_pending[slot] = false;
+    }
+    if (ctx->txf_stage_cap[slot] < tab_bytes) {
+        if (ctx->txf_stage[slot]) (void)hipHostFree(ctx->txf_stage[slot]);
+        ctx->txf_stage[slot] = nullptr; ctx->txf_stage_cap[slot] = 0;
+        const size_t want = (tab_bytes + 65535) & ~(size_t)65535;
+        if (hipHostMalloc(&ctx->txf_stage[slot], want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->txf_stage[slot] = nullptr;
+            return set_error(ctx, LDPC_AMD_ENOMEM, "fec_encode_packets_flows_dev: no pinned memory for %zu descriptor bytes", want);
+        }
+        ctx->txf_stage_cap[slot] = want;
+    }
+    TxFrameDesc *hd = (TxFrameDesc *)ctx->txf_stage[slot];
+    int32_t *hflow = (int32_t *)(hd + F);
+    int64_t max_stride = 1;
+    {
+        std::vector<int64_t> first((size_t)F);
+        std::vector<int32_t> stride((size_t)F);
+        const int64_t got = ldpc_amd_fec_tx_flows_layout(nflows, frame_begin, n, order, first.data(), stride.data());
+        if (got != P) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: bad frame_begin");
+        for (int f = 0; f < nflows; f++)
+            for (int64_t t = frame_begin[f]; t < frame_begin[f + 1]; t++) {
+                hd[t].first = (uint64_t)first[(size_t)t];
+                hd[t].stride = (uint32_t)stride[(size_t)t];
+                hd[t].hdr = ((uint32_t)fec_class[f] << 8) | (((uint32_t)block0[f] + (uint32_t)(t - frame_begin[f])) & 0xffu);
+                hflow[t] = f;
+                max_stride = std::max<int64_t>(max_stride, stride[(size_t)t]);
+            }
+    }
+    const TxFrameDesc *dd = (const TxFrameDesc *)ctx->txf_desc.p;
+    const int32_t *dflow = (const int32_t *)(dd + F);
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(ctx->txf_desc.p, hd, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipEventRecord(ctx->txf_event[slot], ctx->stream));
+    ctx->txf_pending[slot] = true;
+    ctx->txf_calls++;
+    rc = launch_encode_packets_flows(ctx, cd, S, F, source, dd, max_stride, packets);
+    if (rc != LDPC_AMD_OK && rc != kEncodeNotFused) return rc;
+    const int path = rc == LDPC_AMD_OK ? 1 : 2;
+    if (path == 2) {
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)(kSenderScratchMax / cw_frame)));
+        if ((rc = scratch_reserve(ctx, ctx->sender_cw, (size_t)chunk * cw_frame))) return rc;
+        uint8_t *cw = (uint8_t *)ctx->sender_cw.p;
+        const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0;   // (the scratch is 16-byte aligned)
+        for (int64_t f0 = 0; f0 < F; f0 += chunk) {
+            const int64_t cnt = std::min(chunk, F - f0), rows = cnt * n;
+            if ((rc = launch_encode(ctx, cd, S, cnt, source + (size_t)f0 * src_frame, cw))) return rc;
+            if (v16)
+                hipLaunchKernelGGL(fec_packetize_flows_v16, dim3(grid_for(rows * (S / 16))), dim3(kThreads), 0, ctx->stream,
+                                   reinterpret_cast<const uint4 *>(cw), rows, n, S / 16, dd + f0, packets);
+            else
+                hipLaunchKernelGGL(fec_packetize_flows_bytes, dim3(grid_for(rows * (S + kHdr))), dim3(kThreads), 0, ctx->stream, cw, rows, n, S,
+                                   dd + f0, packets);
+            LDPC_HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    if (flow_of) {
+        hipLaunchKernelGGL(fec_tx_flow_of, dim3(grid_for(P)), dim3(kThreads), 0, ctx->stream, dd, dflow, P, n, flow_of);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+    }
+    if (packet_begin)
+        for (int f = 0; f <= nflows; f++) packet_begin[f] = frame_begin[f] * n;
+    ctx->txf_path = path;
+    ctx->txf_frames = F;
+    return LDPC_AMD_OK;
+}
+
+int ldpc_amd_fec_sender_flows_info(ldpc_amd_ctx *ctx, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_sender_flows_info: info must not be null");
+    info[0] = ctx->txf_path;
+    info[1] = (int64_t)ctx->sender_cw.cap;
+    info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
+    info[3] = ctx->txf_frames;
     return LDPC_AMD_OK;
 }
 
