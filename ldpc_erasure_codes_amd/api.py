@@ -76,6 +76,13 @@ EXPORTS_FLOWS_MIXED = [
     "ldpc_amd_fec_rx_flows_push_mixed", "ldpc_amd_fec_rx_flows_decode_mixed", "ldpc_amd_fec_rx_flows_unrouted", "ldpc_amd_fec_flows_demux_dev",
     "ldpc_amd_fec_flows_demux_info",
 ]
+# every symbol include/ldpc_erasure_amd_flows_flush.h declares (the multi-flow receiver's batch flush)
+EXPORTS_FLOWS_FLUSH = [
+    "ldpc_amd_fec_rx_flows_pending", "ldpc_amd_fec_rx_flows_flush_many", "ldpc_amd_fec_rx_flows_decode_flush_many",
+    "ldpc_amd_fec_flows_flush_info",
+]
+FLUSH_PATHS = ("none", "fused", "composed", "push")
+FlowsPending = collections.namedtuple("FlowsPending", "cur_block cur_cnt next_cnt blocks")
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
@@ -219,6 +226,12 @@ def load_library():
         L.ldpc_amd_fec_flows_demux_dev.argtypes = [vp, vp, i64, i32, vp, vp]
         L.ldpc_amd_fec_flows_demux_dev.restype = i64
         L.ldpc_amd_fec_flows_demux_info.argtypes = [vp, C.POINTER(i64)]
+    # ... and its batch flush (include/ldpc_erasure_amd_flows_flush.h)
+    if hasattr(L, "ldpc_amd_fec_rx_flows_flush_many"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_rx_flows_pending.argtypes = [vp, vp, vp, vp]
+        L.ldpc_amd_fec_rx_flows_flush_many.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
+        L.ldpc_amd_fec_rx_flows_decode_flush_many.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.ldpc_amd_fec_flows_flush_info.argtypes = [vp, C.POINTER(i64)]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -719,6 +732,14 @@ class Context:
         """nflows device receivers that are fed, planned and decoded together, one call for all of them (FecRxFlows)."""
         return FecRxFlows(self, nflows, n, k, S)
 
+    # -- ... its batch flush (include/ldpc_erasure_amd_flows_flush.h)
+    def fec_flows_flush_info(self):
+        """{"path": "none" | "fused" | "composed" | "push" of the last FecRxFlows.flush_many / decode_flush_many call that closed a
+        block, "blocks": the blocks it closed, "scratch_bytes": scratch it used, "launches": its decoder launches}."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_flows_flush_info(self._h, info), "fec_flows_flush_info")
+        return {"path": FLUSH_PATHS[info[0]], "blocks": int(info[1]), "scratch_bytes": int(info[2]), "launches": int(info[3])}
+
     # -- ... fed with interleaved packets (include/ldpc_erasure_amd_flows_mixed.h)
     def fec_flows_demux(self, flow_of, nflows):
         """The stable partition of packet indices by flow, on its own: flow_of torch int32 [P] on this context's device (any value
@@ -1023,6 +1044,51 @@ class FecRxFlows:
             self._h, flow, code, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status), _ptr(fr.erased_out),
             _ptr(fr.residual_src), C.byref(blk)), "fec_rx_flows_decode_flush")
         return (blk.value, fr) if rc == 1 else None
+
+    # -- the batch flush (include/ldpc_erasure_amd_flows_flush.h)
+    def pending(self):
+        """FlowsPending(cur_block int32 [nflows] (-1: the flow has not started), cur_cnt, next_cnt int32 [nflows]: packets the
+        current / the next block of every flow took so far, blocks: how many blocks a full drain would close now).  Host only."""
+        cur, cc, nc = (np.zeros(self.nflows, dtype=np.int32) for _ in range(3))
+        total = self._L.ldpc_amd_fec_rx_flows_pending(self._h, cur.ctypes.data, cc.ctypes.data, nc.ctypes.data)
+        if total < 0:
+            raise LdpcAmdError("fec_rx_flows_pending: the object is closed")
+        return FlowsPending(cur, cc, nc, total)
+
+    def _flush_list(self, flows, rounds):
+        """(flows int32 [nsel] or None, nsel, slots to allocate: the blocks the call can close at most, from pending())"""
+        sel = None if flows is None else np.ascontiguousarray(flows, dtype=np.int32).reshape(-1)
+        p = self.pending()
+        open_blocks = np.where(p.cur_block < 0, 0, (p.cur_cnt + p.next_cnt > 0).astype(np.int64) + (p.next_cnt > 0))
+        pick = open_blocks if sel is None else open_blocks[sel[(sel >= 0) & (sel < self.nflows)]]
+        nsel = self.nflows if sel is None else int(sel.shape[0])
+        return sel, nsel, max(int(np.minimum(pick, max(rounds, 0)).sum()), 1)
+
+    def flush_many(self, flows=None, rounds=2):
+        """flush() of every flow of the list `flows` (None: all flows), up to `rounds` (1 or 2) times each, in one call -> (closes
+        int32 [nsel], blocks int32 [T], sym torch uint8 [T][n][S], erased torch uint8 [T][n]).  The blocks come out dense in list
+        order, entry j's from closes[:j].sum() on; flows that are not listed are not touched."""
+        import torch
+        sel, nsel, slots = self._flush_list(flows, rounds)
+        sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=self._device())
+        er = torch.empty((slots, self.n), dtype=torch.uint8, device=self._device())
+        blocks, closes = np.zeros(max(nsel * 2, 1), dtype=np.int32), np.zeros(max(nsel, 1), dtype=np.int32)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_flush_many(self._h, None if sel is None else sel.ctypes.data, nsel, rounds, _ptr(sym),
+                                                                      _ptr(er), blocks.ctypes.data, closes.ctypes.data), "fec_rx_flows_flush_many")
+        return closes[:nsel], blocks[:T], sym[:T], er[:T]
+
+    def decode_flush_many(self, code, flows=None, rounds=2, max_sweeps=10, do_ml=1):
+        """flush_many + Context.decode_frames in one call: every block closed is decoded by ONE decoder launch, straight from the
+        staging planes where the decoder can fetch its rows itself (Context.fec_flows_flush_info() says which path ran) -> (closes
+        int32 [nsel], blocks int32 [T], DecodedFrames of the T blocks).  Equal to the loop of decode_flush calls, flow by flow."""
+        sel, nsel, slots = self._flush_list(flows, rounds)
+        fr = self._frames(slots)
+        blocks, closes = np.zeros(max(nsel * 2, 1), dtype=np.int32), np.zeros(max(nsel, 1), dtype=np.int32)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_decode_flush_many(
+            self._h, code, None if sel is None else sel.ctypes.data, nsel, rounds, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps),
+            _ptr(fr.residual), _ptr(fr.status), _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data),
+            "fec_rx_flows_decode_flush_many")
+        return closes[:nsel], blocks[:T], DecodedFrames(*(t[:T] for t in fr))
 
     @property
     def dropped(self):

@@ -13,7 +13,7 @@ OBJ="${LDPC_AMD_OBJDIR:-$HERE/obj}"
 mkdir -p "$OBJ"
 echo "$FLAGS" > "$OBJ/flags.new"
 if ! cmp -s "$OBJ/flags.new" "$OBJ/flags" 2>/dev/null; then rm -f "$OBJ"/*.o; mv "$OBJ/flags.new" "$OBJ/flags"; fi
-COMMON="$HERE/internal.h $ROOT/include/ldpc_erasure_amd.h $ROOT/include/ldpc_erasure_amd_synth.h $ROOT/include/ldpc_erasure_amd_wire.h $ROOT/include/ldpc_erasure_amd_multi.h $ROOT/include/ldpc_erasure_amd_wire_dev.h $ROOT/include/ldpc_erasure_amd_frames.h $ROOT/include/ldpc_erasure_amd_sender.h $ROOT/include/ldpc_erasure_amd_sender_flows.h $ROOT/include/ldpc_erasure_amd_receiver.h $ROOT/include/ldpc_erasure_amd_words.h $ROOT/include/ldpc_erasure_amd_flows.h $ROOT/include/ldpc_erasure_amd_flows_mixed.h"
+COMMON="$HERE/internal.h $ROOT/include/ldpc_erasure_amd.h $ROOT/include/ldpc_erasure_amd_synth.h $ROOT/include/ldpc_erasure_amd_wire.h $ROOT/include/ldpc_erasure_amd_multi.h $ROOT/include/ldpc_erasure_amd_wire_dev.h $ROOT/include/ldpc_erasure_amd_frames.h $ROOT/include/ldpc_erasure_amd_sender.h $ROOT/include/ldpc_erasure_amd_sender_flows.h $ROOT/include/ldpc_erasure_amd_receiver.h $ROOT/include/ldpc_erasure_amd_words.h $ROOT/include/ldpc_erasure_amd_flows.h $ROOT/include/ldpc_erasure_amd_flows_mixed.h $ROOT/include/ldpc_erasure_amd_flows_flush.h"
 declare -A DEPS=(
   [kernels.hip]="$HERE/gf256_dev.h $HERE/fec_header_dev.h $HERE/peel_relax.inc $HERE/ml_kernel.inc $HERE/ml_pi.inc $HERE/rs_kernels.inc $HERE/fpga_kernels.inc"
   [api.cpp]="$HERE/builtin_codes_gen.inc"

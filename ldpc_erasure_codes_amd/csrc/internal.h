@@ -219,6 +219,9 @@ struct ldpc_amd_ctx {
     int receiver_blocks = 0;       // ... blocks it decoded
     ldpc_amd::Scratch demux_tab;   // fec_flows_demux: the [tiles][nflows] u32 histogram table, the flow bases behind it (at most 16 MiB + 64 KiB)
     int64_t demux_tile = 0, demux_tiles = 0;   // ... tile length in packets and tiles of the last partition (ldpc_amd_fec_flows_demux_info)
+    // fec_rx_flows_*_flush_many: path (0 none, 1 fused, 2 composed, 3 push form), blocks, scratch bytes and decoder launches of the
+    // last call that closed a block (ldpc_amd_fec_flows_flush_info)
+    int64_t flush_info[4] = {0, 0, 0, 0};
     // FPGA-harness emulation state (ldpc_amd_data_in / _ldpc_erasure_decoder / _data_out)
     // The run is streamed in chunks like the FPGA's frame loop (ldpc_erasure_decoder_perf_tests.cl:52): fpga_erased holds the
     // flags of ONE chunk, fpga_stats the two running counters (+ per-frame results: of the whole run when it is short

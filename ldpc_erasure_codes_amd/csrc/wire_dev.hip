@@ -38,6 +38,7 @@
 #include "../../include/ldpc_erasure_amd_receiver.h"
 #include "../../include/ldpc_erasure_amd_flows.h"
 #include "../../include/ldpc_erasure_amd_flows_mixed.h"
+#include "../../include/ldpc_erasure_amd_flows_flush.h"
 
 using namespace ldpc_amd;
 
@@ -672,6 +673,63 @@ __global__ __launch_bounds__(kThreads) void fec_rx_left_flows(const FlowTab *__r
         left[order[f.begin + q]] = 1;
 }
 
+// ---- the batch flush (include/ldpc_erasure_amd_flows_flush.h) -----------------------------------------------------------------
+// Every block a flush closes lies complete in ONE staging plane, and which plane that is follows from the host's mirror of the
+// flows' states: the host writes one word per closed slot, desc[j] = the plane f * 2 + b of slot j, and the three kernels below take
+// everything else from it.  No packet array, no winners' table, no scan.
+
+// fec_rx_sources_flows for blocks that are all staged: the flag the gather would have copied, and the word of the row -- row
+// desc[j] * n + i of the planes' one base (below 2^31 - 2: create) -- or erased.
+__global__ __launch_bounds__(kThreads) void fec_rx_flush_sources(const int32_t *__restrict__ desc, const uint8_t *__restrict__ stage_er, int n,
+                                                                int T, uint32_t *__restrict__ src, uint8_t *__restrict__ er)
+{
+    const int64_t total = (int64_t)T * n;
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < total; r += (int64_t)gridDim.x * kThreads) {
+        const int j = (int)(r / n);
+        const int i = (int)(r - (int64_t)j * n);
+        const int64_t row = (int64_t)desc[j] * n + i;
+        const uint8_t e = stage_er[row];
+        src[r] = e ? kRowErased : (kRowStaged | (uint32_t)row);
+        er[r] = e;
+    }
+}
+
+// Plane -> dense slot for the slots first .. first + count - 1, grid (x, count): the rows (an erased row of a plane is zero by
+// construction) and the flags.  A plane is n * S contiguous bytes, copied in pieces of W bytes (16, 4, 1; W divides S, and S >= W, so
+// a plane has at least n pieces: piece u < n also copies flag u).  sym_out / er_out: [count][n][S] / [count][n], er_out may be null.
+template <int W>
+__global__ __launch_bounds__(kThreads) void fec_rx_flush_gather(const int32_t *__restrict__ desc, const uint8_t *__restrict__ stage_sym,
+                                                               const uint8_t *__restrict__ stage_er, int n, int S, int first,
+                                                               uint8_t *__restrict__ sym_out, uint8_t *__restrict__ er_out)
+{
+    const int64_t upp = (int64_t)n * S / W;   // pieces of a plane
+    const int64_t s = blockIdx.y, plane = desc[first + s];
+    const uint8_t *from = stage_sym + plane * upp * W;
+    uint8_t *to = sym_out + s * upp * W;
+    for (int64_t u = (int64_t)blockIdx.x * kThreads + threadIdx.x; u < upp; u += (int64_t)gridDim.x * kThreads) {
+        if (W == 16) reinterpret_cast<uint4 *>(to)[u] = reinterpret_cast<const uint4 *>(from)[u];
+        else if (W == 4) reinterpret_cast<uint32_t *>(to)[u] = reinterpret_cast<const uint32_t *>(from)[u];
+        else to[u] = from[u];
+        if (er_out && u < n) er_out[s * n + u] = stage_er[plane * n + u];
+    }
+}
+
+// The planes of the T closed slots back to symbols 0 and flags 1 (csrc/wire.cpp: close_current), grid (x, T).  W as above.
+template <int W>
+__global__ __launch_bounds__(kThreads) void fec_rx_flush_reset(const int32_t *__restrict__ desc, uint8_t *__restrict__ stage_sym,
+                                                              uint8_t *__restrict__ stage_er, int n, int S)
+{
+    const int64_t upp = (int64_t)n * S / W;
+    const int64_t plane = desc[blockIdx.y];
+    uint8_t *to = stage_sym + plane * upp * W;
+    for (int64_t u = (int64_t)blockIdx.x * kThreads + threadIdx.x; u < upp; u += (int64_t)gridDim.x * kThreads) {
+        if (W == 16) reinterpret_cast<uint4 *>(to)[u] = make_uint4(0, 0, 0, 0);
+        else if (W == 4) reinterpret_cast<uint32_t *>(to)[u] = 0u;
+        else to[u] = 0;
+        if (u < n) stage_er[plane * n + u] = 1;
+    }
+}
+
 // A pointer of this context's device (hipMalloc / torch), not host memory.
 bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
 {
@@ -1271,6 +1329,13 @@ struct ldpc_amd_fec_rx_flows {
     FlowTab *tab_dev = nullptr, *tab_host = nullptr;   // [nflows]
     int32_t *res_host = nullptr;    // pinned copy of res
     size_t res_host_cap = 0;
+    // the batch flush (allocated by its first call): the closed slots' planes on the device, [2 nflows], and their pinned staging --
+    // two slots used in turn, each with the event of its last copy, so that a slot is never rewritten under a copy in flight
+    int32_t *fl_dev = nullptr;
+    int32_t *fl_host[2] = {nullptr, nullptr};
+    hipEvent_t fl_event[2] = {nullptr, nullptr};
+    bool fl_pending[2] = {false, false};
+    unsigned fl_calls = 0;
 };
 
 // One call's PLAN for all flows: (a) + (b), ONE read-back, the slot bases.  Nothing of any flow's state changes before flows_commit.
@@ -1564,12 +1629,14 @@ void ldpc_amd_fec_rx_flows_destroy(ldpc_amd_fec_rx_flows *rx)
     Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots, &rx->order};
     for (Scratch *s : sc)
         if (s->p) (void)hipFree(s->p);
-    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev};
+    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev, rx->fl_dev};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *host[] = {rx->in_host, rx->tab_host, rx->res_host};
+    void *host[] = {rx->in_host, rx->tab_host, rx->res_host, rx->fl_host[0], rx->fl_host[1]};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : rx->fl_event)
+        if (e) (void)hipEventDestroy(e);
     delete rx;
 }
 
@@ -1782,6 +1849,264 @@ int ldpc_amd_fec_rx_flows_decode_flush(ldpc_amd_fec_rx_flows *rx, int flow, int 
     d.sweeps = sweeps; d.residual = residual; d.status = status; d.erased_out = erased_out; d.residual_src = residual_src;
     if ((rc = launch_decode(ctx, d))) return rc;
     return 1;
+}
+
+}  // extern "C"
+
+// ---- the batch flush (include/ldpc_erasure_amd_flows_flush.h) -------------------------------------------------------------
+// ldpc_amd_fec_rx_flows_flush / _decode_flush for many flows and up to two blocks of each in one call.  The PLAN is the host's: the
+// mirror knows every flow's state, so which blocks close, in which order and from which plane is decided without the device
+// (flush_plan: the rule of ldpc_amd_fec_rx_flows_flush, replayed on a copy of the flow's state).  The DATA MOVEMENT is all-staged --
+// a block that a flush closes got its last packet in an earlier call -- so the decode form is the carried-block case of
+// flows_decode for every row: fec_rx_flush_sources writes a staged (or erased) row-source word per symbol and ONE launch_decode
+// follows them into the planes; where the decoder has no packets-in form, fec_rx_flush_gather copies the planes into the context's
+// scratch, chunk by chunk, as flows_decode does.  fec_rx_flush_reset, ONE launch for all closed planes, stands BEHIND the decode,
+// which reads them.  Nothing is read back and nothing waits: the mirror is advanced on the host when everything is enqueued.
+struct FlushPlan {
+    std::vector<int> sel;          // the selected flows, in list order
+    std::vector<int> closes;       // blocks that close per list entry
+    std::vector<int> blocks;       // [T] their wire numbers, in slot order
+    std::vector<int32_t> planes;   // [T] their staging planes, f * 2 + b
+    int T = 0;
+};
+
+// how many blocks `rounds` flushes of flow f close, from its mirror; with out: their numbers and planes
+static int flush_replay(const ldpc_amd_fec_rx_flows *rx, int f, int rounds, FlushPlan *out)
+{
+    int cur = rx->cur[f], next = rx->next[f], ccnt = rx->ccnt[f], ncnt = rx->ncnt[f], cb = rx->cb[f], c = 0;
+    for (; c < rounds; c++) {
+        if (cur == -1 || (ccnt == 0 && ncnt == 0)) break;   // ldpc_amd_fec_rx_flows_flush: nothing open
+        if (out) {
+            out->blocks.push_back(cur);
+            out->planes.push_back(f * 2 + cb);
+        }
+        cur = next; next = (next + 1) & 0xff; ccnt = ncnt; ncnt = 0; cb ^= 1;
+    }
+    return c;
+}
+
+static int flush_plan(const ldpc_amd_fec_rx_flows *rx, const char *who, const int32_t *flows, int nsel, int rounds, FlushPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (rounds < 1 || rounds > 2) return set_error(ctx, LDPC_AMD_EINVAL, "%s: rounds must be 1 or 2 (got %d)", who, rounds);
+    if (flows) {
+        if (nsel < 0 || nsel > rx->nflows) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need 0 <= nsel <= nflows = %d (got %d)", who, rx->nflows, nsel);
+        std::vector<uint8_t> seen((size_t)rx->nflows, 0);
+        for (int j = 0; j < nsel; j++) {
+            const int f = flows[j];
+            if (f < 0 || f >= rx->nflows) return set_error(ctx, LDPC_AMD_EINVAL, "%s: no flow %d (nflows = %d)", who, f, rx->nflows);
+            if (seen[(size_t)f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow %d is given twice", who, f);
+            seen[(size_t)f] = 1;
+        }
+    } else {
+        nsel = rx->nflows;
+    }
+    pl.sel.resize((size_t)nsel);
+    pl.closes.resize((size_t)nsel);
+    for (int j = 0; j < nsel; j++) {
+        pl.sel[(size_t)j] = flows ? flows[j] : j;
+        pl.closes[(size_t)j] = flush_replay(rx, pl.sel[(size_t)j], rounds, &pl);
+    }
+    pl.T = (int)pl.planes.size();   // <= 2 nflows
+    return LDPC_AMD_OK;
+}
+
+// the object's descriptor buffers (first call), then the planes of the T slots to the device through the pinned slot of this call
+static int flush_upload(ldpc_amd_fec_rx_flows *rx, const char *who, const FlushPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const size_t cap = sizeof(int32_t) * 2 * (size_t)rx->nflows;
+    if (!rx->fl_dev) {
+        hipError_t e = hipMalloc((void **)&rx->fl_dev, cap);
+        for (int s = 0; s < 2 && e == hipSuccess; s++) {
+            if (!rx->fl_host[s]) e = hipHostMalloc((void **)&rx->fl_host[s], cap, hipHostMallocDefault);
+            if (e == hipSuccess && !rx->fl_event[s]) e = hipEventCreateWithFlags(&rx->fl_event[s], hipEventDisableTiming);
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (rx->fl_dev) (void)hipFree(rx->fl_dev);
+            rx->fl_dev = nullptr;   // (what the slots got is kept: the next call asks for the rest)
+            return set_error(ctx, LDPC_AMD_ENOMEM, "%s: no memory for the slot descriptors: %s", who, hipGetErrorString(e));
+        }
+    }
+    const int slot = (int)(rx->fl_calls & 1u);
+    if (rx->fl_pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
+        LDPC_HIP_TRY(ctx, hipEventSynchronize(rx->fl_event[slot]));
+        rx->fl_pending[slot] = false;
+    }
+    memcpy(rx->fl_host[slot], pl.planes.data(), sizeof(int32_t) * (size_t)pl.T);
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->fl_dev, rx->fl_host[slot], sizeof(int32_t) * (size_t)pl.T, hipMemcpyHostToDevice, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipEventRecord(rx->fl_event[slot], ctx->stream));
+    rx->fl_pending[slot] = true;
+    rx->fl_calls++;
+    return LDPC_AMD_OK;
+}
+
+// the piece of the plane kernels: the widest of 16, 4, 1 bytes that divides S and that `p` (null: the planes alone) is aligned to
+static int flush_piece(int S, const void *p)
+{
+    if (S % 16 == 0 && ((uintptr_t)p & 15) == 0) return 16;
+    if (S % 4 == 0 && ((uintptr_t)p & 3) == 0) return 4;
+    return 1;
+}
+
+static int flush_gather(ldpc_amd_fec_rx_flows *rx, int first, int count, uint8_t *sym, uint8_t *er)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, S = rx->S, W = flush_piece(S, sym);
+    const int64_t upp = (int64_t)n * S / W;
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((upp + kThreads - 1) / kThreads, 256)), (unsigned)count);
+    if (W == 16) hipLaunchKernelGGL(fec_rx_flush_gather<16>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, sym, er);
+    else if (W == 4) hipLaunchKernelGGL(fec_rx_flush_gather<4>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, sym, er);
+    else hipLaunchKernelGGL(fec_rx_flush_gather<1>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, sym, er);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+static int flush_reset(ldpc_amd_fec_rx_flows *rx, int T)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, S = rx->S, W = flush_piece(S, nullptr);
+    const int64_t upp = (int64_t)n * S / W;
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((upp + kThreads - 1) / kThreads, 256)), (unsigned)T);
+    if (W == 16) hipLaunchKernelGGL(fec_rx_flush_reset<16>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S);
+    else if (W == 4) hipLaunchKernelGGL(fec_rx_flush_reset<4>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S);
+    else hipLaunchKernelGGL(fec_rx_flush_reset<1>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// the mirror of every selected flow advanced once per closed block (ldpc_amd_fec_rx_flows_flush), the host outputs, the info words
+static void flush_commit(ldpc_amd_fec_rx_flows *rx, const FlushPlan &pl, int *blocks, int *closes, int path, size_t scratch, int launches)
+{
+    for (size_t j = 0; j < pl.sel.size(); j++) {
+        const int f = pl.sel[j];
+        for (int c = 0; c < pl.closes[j]; c++) {
+            rx->cur[f] = rx->next[f];
+            rx->next[f] = (rx->next[f] + 1) & 0xff;
+            rx->ccnt[f] = rx->ncnt[f];
+            rx->ncnt[f] = 0;
+            rx->cb[f] ^= 1;
+        }
+        if (closes) closes[j] = pl.closes[j];
+    }
+    if (blocks && pl.T > 0) memcpy(blocks, pl.blocks.data(), sizeof(int) * (size_t)pl.T);
+    ldpc_amd_ctx *ctx = rx->ctx;
+    ctx->flush_info[0] = path; ctx->flush_info[1] = pl.T; ctx->flush_info[2] = (int64_t)scratch; ctx->flush_info[3] = launches;
+}
+
+extern "C" {
+
+int ldpc_amd_fec_rx_flows_pending(const ldpc_amd_fec_rx_flows *rx, int32_t *cur_block, int32_t *cur_cnt, int32_t *next_cnt)
+{
+    if (!rx) return -1;
+    int total = 0;
+    for (int f = 0; f < rx->nflows; f++) {
+        if (cur_block) cur_block[f] = rx->cur[f];
+        if (cur_cnt) cur_cnt[f] = rx->ccnt[f];
+        if (next_cnt) next_cnt[f] = rx->ncnt[f];
+        total += flush_replay(rx, f, 2, nullptr);
+    }
+    return total;
+}
+
+int ldpc_amd_fec_rx_flows_flush_many(ldpc_amd_fec_rx_flows *rx, const int32_t *flows, int nsel, int rounds, uint8_t *sym_batch,
+                                     uint8_t *erased_batch, int *blocks, int *closes)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const char *who = "fec_rx_flows_flush_many";
+    FlushPlan pl;
+    int rc;
+    if ((rc = flush_plan(rx, who, flows, nsel, rounds, pl))) return rc;
+    if (!sym_batch || !erased_batch) return set_error(ctx, LDPC_AMD_EINVAL, "%s: sym_batch / erased_batch must not be null", who);
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: sym_batch / erased_batch must be device pointers of device %d", who, ctx->device);
+    if (pl.T == 0) {
+        if (closes) std::fill(closes, closes + pl.sel.size(), 0);
+        return 0;
+    }
+    if ((rc = flush_upload(rx, who, pl)) || (rc = flush_gather(rx, 0, pl.T, sym_batch, erased_batch)) || (rc = flush_reset(rx, pl.T))) return rc;
+    flush_commit(rx, pl, blocks, closes, 3, sizeof(int32_t) * (size_t)pl.T, 0);
+    return pl.T;
+}
+
+int ldpc_amd_fec_rx_flows_decode_flush_many(ldpc_amd_fec_rx_flows *rx, int code, const int32_t *flows, int nsel, int rounds, int max_sweeps,
+                                            int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
+                                            int32_t *residual_src, int *blocks, int *closes)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const char *who = "fec_rx_flows_decode_flush_many";
+    FlushPlan pl;
+    int rc;
+    if ((rc = flush_plan(rx, who, flows, nsel, rounds, pl))) return rc;
+    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    const int T = pl.T;
+    if (T == 0) {
+        if (closes) std::fill(closes, closes + pl.sel.size(), 0);
+        return 0;
+    }
+    const DevCode &cd = ctx->codes[code]->dev;
+    const int n = rx->n, S = rx->S;
+    // (word-sized symbols take the composed form: the header says why)
+    const bool fused = ctx->knobs.rx_pkt != 0 && S % 16 == 0 && decode_reads_packets(ctx, cd, S);
+    const size_t frame = (size_t)n * S;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kReceiverScratchMax / frame)));
+    // every workspace of the call before anything moves: a refusal leaves every flow where it was
+    if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)T * n))) return rc;
+    if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)T * n);
+    else rc = scratch_reserve(ctx, ctx->rx_sym, (size_t)chunk * frame);
+    if (rc) return rc;
+    if ((rc = flush_upload(rx, who, pl))) return rc;
+    DecodeArgs d{};
+    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
+    uint8_t *er = (uint8_t *)ctx->rx_er.p;
+    auto slots = [&](int first, int count) {   // the result arrays of closed slots first .. first + count - 1
+        d.nframes = count;
+        d.erased = er + (size_t)first * n;
+        d.out = out + (size_t)first * frame;
+        d.sweeps = sweeps ? sweeps + first : nullptr; d.residual = residual ? residual + first : nullptr;
+        d.status = status ? status + first : nullptr;
+        d.erased_out = erased_out ? erased_out + (size_t)first * n : nullptr;
+        d.residual_src = residual_src ? residual_src + first : nullptr;
+    };
+    int launches = 0;
+    if (fused) {
+        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+        hipLaunchKernelGGL(fec_rx_flush_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl_dev,
+                           (const uint8_t *)rx->stage_er, n, T, src, er);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        slots(0, T);
+        d.sym = nullptr;
+        // no word of the table names a packet (fec_rx_flush_sources), so the packet base is never added to: any valid aligned address
+        d.pin.src = src; d.pin.packets = rx->stage_sym; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
+        if ((rc = launch_decode(ctx, d))) return rc;
+        launches = 1;
+    } else {
+        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
+        for (int first = 0; first < T; first += (int)chunk) {
+            const int count = (int)std::min<int64_t>(chunk, T - first);
+            if ((rc = flush_gather(rx, first, count, sym, er + (size_t)first * n))) return rc;
+            slots(first, count);
+            d.sym = sym;
+            if ((rc = launch_decode(ctx, d))) return rc;
+            launches++;
+        }
+    }
+    if ((rc = flush_reset(rx, T))) return rc;
+    flush_commit(rx, pl, blocks, closes, fused ? 1 : 2,
+                 (fused ? sizeof(uint32_t) * (size_t)T * n : (size_t)chunk * frame) + (size_t)T * n + sizeof(int32_t) * (size_t)T, launches);
+    return T;
+}
+
+int ldpc_amd_fec_flows_flush_info(ldpc_amd_ctx *ctx, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_flows_flush_info: info must not be null");
+    for (int i = 0; i < 4; i++) info[i] = ctx->flush_info[i];
+    return LDPC_AMD_OK;
 }
 
 // ---- the partition on its own (include/ldpc_erasure_amd_flows_mixed.h) ----------------------------------------------------
