@@ -225,13 +225,20 @@ int ldpc_amd_data_out(ldpc_amd_ctx *ctx, ldpc_amd_symbol_type *data_out, int cod
 #define LDPC_AMD_PROF_APPLY_TIER2 3 /* the tier-2 launch of the packet kernel alone (already inside LDPC_AMD_PROF_APPLY) */
 #define LDPC_AMD_PROF_ML_SOLVE 4    /* ldpc_ml_solve_kernel alone (already inside LDPC_AMD_PROF_ML) */
 #define LDPC_AMD_PROF_KINDS 5
+/* Name-only kinds, for ldpc_amd_profile_kernel_name alone (no time is kept).  They are numbered after the timed kinds, relative to
+ * LDPC_AMD_PROF_KINDS, so that a new timed kind moves them instead of colliding with them: use the names, not the numbers. */
+#define LDPC_AMD_NAME_RS (LDPC_AMD_PROF_KINDS + 0)     /* the kernel of the last RS decode launch */
+#define LDPC_AMD_NAME_ENCODE (LDPC_AMD_PROF_KINDS + 1) /* the kernel of the last packet-mode (S > 1) encode launch, the gather kernel included */
+#define LDPC_AMD_NAME_KINDS 2
 /* enable: 0 off; 1 one bracket per kind of a call (PEEL, APPLY, ML); 2 additionally the nested brackets APPLY_TIER2 and ML_SOLVE
  * (two more event pairs per call: use it for break-downs, not inside a timed region that is quoted as throughput). */
 int ldpc_amd_set_profiling(ldpc_amd_ctx *ctx, int enable);
 int ldpc_amd_get_profile(ldpc_amd_ctx *ctx, double ms[LDPC_AMD_PROF_KINDS], int64_t launches[LDPC_AMD_PROF_KINDS]);
 /* Name (as rocprofv3 prints it, e.g. "ldpc_scatter_kernel<16, 2, true, 8, false>") of the kernel instantiation the LAST
  * launch of that kind used -- the launch plan depends on code, S and batch, so a report must not hard-code it.
- * "" when no kernel of the kind was launched yet. */
+ * "" when no kernel of the kind was launched yet.  kind = LDPC_AMD_NAME_RS: the last Reed-Solomon decode launch
+ * ("rs_decode_packets_kernel<VW, WPS, FRAMES>", "rs_decode_s1_kernel<FRAMES>" or "rs_decode_kernel<FRAMES>"); kind = LDPC_AMD_NAME_ENCODE: the last encode launch with S > 1 (a
+ * scatter encoder, "ldpc_apply_kernel" or "ldpc_apply_words_kernel"; the encoder's gather launch leaves LDPC_AMD_PROF_APPLY alone). */
 const char *ldpc_amd_profile_kernel_name(ldpc_amd_ctx *ctx, int kind);
 /* Launch plan of the last ldpc_amd_decode_batch (of its last chunk): info[0] frames (= wavefronts) per peel workgroup,
  * [1] frames resident per CU, [2] 1 = code tables read from global memory instead of LDS, [3] peel LDS bytes per workgroup,

@@ -31,6 +31,8 @@ RS_ST_DECODED, RS_ST_SHORT = 0, 1
 # LDPC_AMD_PROF_*: "apply" = both tiers of the packet kernel ("apply_tier2" is the tier-2 launch alone), "ml" = factorisation + solve
 # ("ml_solve" is the solve kernel alone)
 PROF_KINDS = ("peel", "apply", "ml", "apply_tier2", "ml_solve")
+# LDPC_AMD_NAME_RS / LDPC_AMD_NAME_ENCODE: names only, no time; the header numbers them after the timed kinds (LDPC_AMD_PROF_KINDS + 0, + 1)
+NAME_RS, NAME_ENCODE = len(PROF_KINDS), len(PROF_KINDS) + 1
 
 # every symbol include/ldpc_erasure_amd.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -385,6 +387,14 @@ class Context:
         """{'peel': name, 'apply': name, 'ml': name}: the kernel instantiation the last launch of each kind used."""
         return {name: self._L.ldpc_amd_profile_kernel_name(self._h, i).decode() for i, name in enumerate(PROF_KINDS)}
 
+    def rs_kernel_name(self):
+        """The kernel instantiation of the last Reed-Solomon decode launch ('' before the first)."""
+        return self._L.ldpc_amd_profile_kernel_name(self._h, NAME_RS).decode()
+
+    def encode_kernel_name(self):
+        """The kernel of the last encode launch with S > 1, the gather kernel included ('' before the first)."""
+        return self._L.ldpc_amd_profile_kernel_name(self._h, NAME_ENCODE).decode()
+
     def last_plan(self):
         info = (C.c_int * 8)()
         self._check(self._L.ldpc_amd_last_plan(self._h, info), "last_plan")
@@ -529,17 +539,22 @@ class Context:
         self._check(self._L.ldpc_amd_rs_generator(self._h, rs, g.ctypes.data), "rs_generator")
         return g
 
-    def rs_encode(self, rs, n, k, source):
+    def rs_encode(self, rs, n, k, source, out=None):
+        """source [B,k,S] or [B,k] -> codewords [B,n,S] or [B,n], into `out` (contiguous, of that shape, where source is) if given."""
         dev = _is_torch(source)
         B = source.shape[0]
         S = 1 if source.ndim == 2 else source.shape[2]
         shape = (B, n) if source.ndim == 2 else (B, n, S)
+        if out is not None:
+            assert _is_torch(out) == dev and tuple(out.shape) == shape
         if dev:
             import torch
-            out = torch.empty(shape, dtype=torch.uint8, device=source.device)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=source.device)
         else:
             source = np.ascontiguousarray(source, dtype=np.uint8)
-            out = np.empty(shape, dtype=np.uint8)
+            if out is None:
+                out = np.empty(shape, dtype=np.uint8)
         self._check(self._L.ldpc_amd_rs_encode_batch(self._h, rs, S, B, _ptr(source), _ptr(out), DEVICE_PTRS if dev else 0),
                     "rs_encode_batch")
         return out
@@ -566,17 +581,25 @@ class Context:
         self._check(self._L.ldpc_amd_rs_info(self._h, rs, C.byref(n), C.byref(k)), "rs_info")
         return n.value, k.value
 
-    def rs_decode_frames(self, rs, sym, erased):
+    def rs_decode_frames(self, rs, sym, erased, out=None):
         """sym [B,n,S] (or [B,n] for S=1) uint8, erased [B,n] uint8 -> RsDecodedFrames(msg [B,k,S] or [B,k], received [B] int32,
         status [B] int32).  Per block the first k received symbols are decoded (the rest is not read); a block that received
-        fewer than k is all zero with status RS_ST_SHORT.  numpy in -> numpy out, torch in -> torch out."""
+        fewer than k is all zero with status RS_ST_SHORT.  numpy in -> numpy out, torch in -> torch out; `out`, if given, is the
+        (msg, received, status) of those shapes to write into, where sym is."""
         n, k = self.rs_info(rs)
         dev = _is_torch(sym)
         B = sym.shape[0]
         S = 1 if sym.ndim == 2 else sym.shape[2]
         assert sym.shape[1] == n and tuple(erased.shape) == (B, n)
         shape = (B, k) if sym.ndim == 2 else (B, k, S)
-        if dev:
+        if out is not None:
+            msg, received, status = out
+            assert all(_is_torch(t) == dev for t in out) and tuple(msg.shape) == shape
+            assert tuple(received.shape) == (B,) and tuple(status.shape) == (B,)
+            if not dev:
+                sym = np.ascontiguousarray(sym, dtype=np.uint8)
+                erased = np.ascontiguousarray(erased, dtype=np.uint8)
+        elif dev:
             import torch
             msg = torch.empty(shape, dtype=torch.uint8, device=sym.device)
             received, status = (torch.empty((B,), dtype=torch.int32, device=sym.device) for _ in range(2))
@@ -888,14 +911,20 @@ class FecRxDevice:
         return DecodedFrames(torch.empty(shape, dtype=torch.uint8, device=dev), i32[0], i32[1], i32[2],
                              torch.empty((B, self.n), dtype=torch.uint8, device=dev), i32[3])
 
-    def decode_many(self, code, packets, max_blocks, max_sweeps=10, do_ml=1):
+    def decode_many(self, code, packets, max_blocks, max_sweeps=10, do_ml=1, out=None):
         """push_many + Context.decode_frames in one call (include/ldpc_erasure_amd_receiver.h): packets torch uint8 [P][8+S] on the
         device -> (blocks int32 [B], DecodedFrames of the B closed blocks, consumed).  Where the decoder can fetch its rows from the
         packets itself no array of received symbols is written (Context.fec_receiver_info() says which path ran).  Keep `packets`
-        alive until the context's stream has passed the call."""
+        alive until the context's stream has passed the call.  `out`, if given, is a DecodedFrames of device tensors with room for
+        max_blocks frames to write into (the result is its first B frames)."""
         import torch
         assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.shape[1] == 8 + self.S
-        fr = self._frames(max(max_blocks, 1))
+        if out is not None:
+            fr = DecodedFrames(*out)
+            assert all(t.shape[0] >= max(max_blocks, 1) for t in fr) and tuple(fr.erased_out.shape[1:]) == (self.n,)
+            assert tuple(fr.out.shape[1:]) == ((self.n,) if self.S == 1 else (self.n, self.S))
+        else:
+            fr = self._frames(max(max_blocks, 1))
         blocks = np.zeros(max(max_blocks, 1), dtype=np.int32)
         used = C.c_int64(0)
         nb = self._ctx._check(self._L.ldpc_amd_fec_rx_dev_decode_many(

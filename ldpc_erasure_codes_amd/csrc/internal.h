@@ -241,7 +241,7 @@ struct ldpc_amd_ctx {
     int profiling = 0;          // 0 off, 1 the three kinds of a call, 2 + the nested brackets (tier 2 alone, solve kernel alone)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events[LDPC_AMD_PROF_KINDS];
     std::vector<hipEvent_t> prof_pool;
-    std::string prof_names[LDPC_AMD_PROF_KINDS];   // template instantiation the last launch of each kind used
+    std::string prof_names[LDPC_AMD_PROF_KINDS + LDPC_AMD_NAME_KINDS];   // template instantiation the last launch of each kind used; then the name-only kinds
     int last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launch plan of the last decode (ldpc_amd_last_plan)
     int last_enc_grouped = 0;                      // the last packet-mode encode ran the grouped static schedule (ldpc_amd_encode_info)
     int symbol_unit = 16;                          // 16, or 4: word-sized symbols (include/ldpc_erasure_amd_words.h; not a knob)

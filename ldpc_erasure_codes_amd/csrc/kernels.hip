@@ -3044,12 +3044,15 @@ static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64
             ctx->last_enc_grouped = sa.enc_group;
             sa.enc_list = kn.enc_list;   // measured slower (4.62 vs 4.14 ms): off unless asked for
             sa.pkt_out = pkt_out; sa.pkt_hdr = pkt_hdr; sa.flow_desc = pkt_out ? (const uint4 *)flow_desc : nullptr;
-            return launch_scatter(ctx, e.plan, sa, nullptr);
+            const int rcs = launch_scatter(ctx, e.plan, sa, nullptr);
+            if (rcs == LDPC_AMD_OK) ctx->prof_names[LDPC_AMD_NAME_ENCODE] = ctx->prof_names[LDPC_AMD_PROF_APPLY];
+            return rcs;
         }
     }
     if (pkt_out) return kEncodeNotFused;
     ApplyArgs aa{};
     aa.code = cd; aa.S = S; aa.nframes = nframes; aa.sym = src; aa.erased = nullptr; aa.in_rows = cd.k; aa.out = cw;
+    ctx->prof_names[LDPC_AMD_NAME_ENCODE] = words ? "ldpc_apply_words_kernel" : "ldpc_apply_kernel";
     return launch_apply(ctx, aa, words, false);
 }
 
@@ -3131,6 +3134,7 @@ static int launch_rs_decode_t(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_
         // (one dword per lane compiled for four wavefronts per SIMD: 19.9 ms; for six / eight -- 80 / 64 registers, the Gauss-Jordan
         // part spills -- 31.0 / 26.6 ms)
         const dim3 g(grid), b(64 * nw);
+        prof_name(ctx, LDPC_AMD_NAME_RS, "rs_decode_packets_kernel", vw, vw == 4 ? 2 : 4, vw == 1 && FRAMES);
         if (vw == 4) return launch_lds(ctx, rs_decode_packets_kernel<4, 2, false>, g, b, (size_t)o, ctx->stream, a, L, nslices);
         if (vw == 2) return launch_lds(ctx, rs_decode_packets_kernel<2, 4, false>, g, b, (size_t)o, ctx->stream, a, L, nslices);
         return launch_lds(ctx, rs_decode_packets_kernel<1, 4, FRAMES>, g, b, (size_t)o, ctx->stream, a, L, nslices);
@@ -3148,6 +3152,7 @@ static int launch_rs_decode_t(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_
         o += nw * L.wstride;
         const int wgs = std::max(1, std::min(8, kLdsMax / o));
         const int grid = (int)std::min<int64_t>((nblocks + nw - 1) / nw, (int64_t)ctx->sm_count * wgs);
+        prof_name(ctx, LDPC_AMD_NAME_RS, "rs_decode_s1_kernel", FRAMES);
         hipLaunchKernelGGL(rs_decode_s1_kernel<FRAMES>, dim3(grid), dim3(64 * nw), (size_t)o, ctx->stream, a, L);
         LDPC_HIP_TRY(ctx, hipGetLastError());
         return LDPC_AMD_OK;
@@ -3159,6 +3164,7 @@ static int launch_rs_decode_t(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_
         if (rc) return rc;
         a.ws = (uint8_t *)ctx->rsws.p;
     }
+    prof_name(ctx, LDPC_AMD_NAME_RS, "rs_decode_kernel", FRAMES);
     return launch_lds(ctx, rs_decode_kernel<FRAMES>, dim3(grid), dim3(threads), (size_t)off, ctx->stream, a);
 }
 

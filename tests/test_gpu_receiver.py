@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from code_helpers import random_code  # noqa: F401  (other test modules take it from here)
 from ldpc_erasure_codes_amd import api, codes
 
 pytestmark = pytest.mark.gpu
@@ -30,24 +31,6 @@ def ctx():
 
 def _gen(seed):
     return torch.Generator(device="cuda").manual_seed(seed)
-
-
-def random_code(n=300, k=200, coldeg=3, seed=3):
-    """A random triangular (300,200) code: every source column sits in coldeg random checks, check i ends at its own parity column
-    k + i and also holds the parity columns k + i - 1 and (from i = 2 on) one earlier one.  Column degrees stay far below 16, the
-    scatter kernels' limit."""
-    rng = np.random.default_rng(seed)
-    m = n - k
-    H = np.zeros((m, n), dtype=np.uint8)
-    for c in range(k):
-        H[rng.choice(m, size=coldeg, replace=False), c] = rng.integers(1, 256, size=coldeg)
-    for i in range(m):
-        H[i, k + i] = rng.integers(1, 256)
-        if i >= 1:
-            H[i, k + i - 1] = rng.integers(1, 256)
-        if i >= 2:
-            H[i, k + rng.integers(0, i - 1)] = rng.integers(1, 256)
-    return codes.from_dense(H, k)
 
 
 _CODES = {}
