@@ -93,7 +93,10 @@ int ldpc_amd_code_params(int code_ind, int params[6]);
  * Returns a code handle >= 0 or a negative error. */
 int ldpc_amd_load_builtin_code(ldpc_amd_ctx *ctx, int code_ind, uint64_t coef_seed);
 /* Registers a custom code from 0-based CSR (what Matlab/ErasureCodes_NonBinaryLDPCSim.m:91-107 builds as
- * Vlist / Vlist_val): row_ptr[n-k+1], cols ascending per row, coefs 1..255.  Returns a code handle. */
+ * Vlist / Vlist_val): row_ptr[n-k+1], cols ascending per row, coefs 1..255.  Returns a code handle.
+ * Registration (n <= 65534, at most 24 entries per check) does not promise that every entry point accepts the code: which
+ * kernels can hold it depends on n, n-k, the symbol length and max_sweeps ("Code sizes").  A shape no kernel serves
+ * is refused with LDPC_AMD_EUNSUP, ldpc_amd_last_error naming the reason, before anything is launched or written. */
 int ldpc_amd_register_code(ldpc_amd_ctx *ctx, int n, int k, const uint32_t *row_ptr, const uint16_t *cols,
                            const uint8_t *coefs);
 int ldpc_amd_code_info(ldpc_amd_ctx *ctx, int code, int *n, int *k, int *nnz);

@@ -2477,15 +2477,26 @@ static int launch_scatter(ldpc_amd_ctx *ctx, const ScatterPlan &p, const Scatter
     return set_error(ctx, LDPC_AMD_EUNSUP, "scatter: bad plan");
 }
 
-// The gather kernel (LDPC_AMD_APPLY=gather, or a code whose columns are too heavy for the scatter kernel's lists), decode and encode.
+static size_t apply_lds_bytes(const DevCode &cd) { return (size_t)cd.m * 4 + (size_t)(cd.m + 2) * 2; }
+
+// The gather kernel keeps a frame's steps and level offsets in LDS: past 160 KB (m > 27306) no launch holds them.  Asked before
+// anything is launched.
+static int refuse_apply(ldpc_amd_ctx *ctx, const DevCode &cd)
+{
+    if (apply_lds_bytes(cd) > (size_t)kLdsMax) return set_error(ctx, LDPC_AMD_EUNSUP, "gather kernel: LDS need %zu bytes", apply_lds_bytes(cd));
+    return LDPC_AMD_OK;
+}
+
+// The gather kernel (LDPC_AMD_APPLY=gather, or a code whose columns are too heavy for the scatter kernel's lists, or one too large
+// for a packet plan), decode and encode.
 // `profiled`: the decoder's launch, named and bracketed for the profile
 static int launch_apply(ldpc_amd_ctx *ctx, const ApplyArgs &aa, bool words, bool profiled)
 {
-    const size_t lds = (size_t)aa.code.m * 4 + (size_t)(aa.code.m + 2) * 2;
+    const size_t lds = apply_lds_bytes(aa.code);
     if (profiled) ctx->prof_names[LDPC_AMD_PROF_APPLY] = words ? "ldpc_apply_words_kernel" : "ldpc_apply_kernel";
     hipEvent_t ev = profiled ? prof_begin(ctx) : nullptr;
-    hipLaunchKernelGGL(words ? ldpc_apply_words_kernel : ldpc_apply_kernel, dim3((unsigned)aa.nframes), dim3(512), lds, ctx->stream, aa);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
+    const int rc = launch_lds(ctx, words ? ldpc_apply_words_kernel : ldpc_apply_kernel, dim3((unsigned)aa.nframes), dim3(512), lds, ctx->stream, aa);
+    if (rc) return rc;
     prof_end(ctx, LDPC_AMD_PROF_APPLY, ev);
     return LDPC_AMD_OK;
 }
@@ -2615,6 +2626,14 @@ static MlPlan plan_ml(const Knobs &kn, const DevCode &cd, int S, bool fused, boo
     return p;
 }
 
+// The plan's refusals (neither depends on the fast path, the packet kernel or the number of frames)
+static int refuse_ml(ldpc_amd_ctx *ctx, const DevCode &cd, const MlPlan &p)
+{
+    if (p.lds_need) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: LDS need %d bytes", p.lds_need);
+    if (p.too_many_checks) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: more than 4096 checks (%d)", cd.m);
+    return LDPC_AMD_OK;
+}
+
 // One call's ML stage.  prepare() comes before the packet kernel is launched, because in packet mode the stage's pattern-only part --
 // the fast path and the factorisation of what the fast path leaves, front() -- can run beside the packet kernel (second stream);
 // finish() runs what is left of it behind the packet kernel.
@@ -2655,8 +2674,7 @@ int MlStage::prepare(bool use_scatter)
     // message passing completes.  Whatever does reach the ML stage then is factored exactly; the next batch has the fast path again.)
     const bool ml_quiet = kn.ml_pi_adaptive && ctx->ml_head_host && ctx->ml_head_valid && *ctx->ml_head_host == 0;
     p = plan_ml(kn, cd, d.S, fused, words, use_scatter, !ml_quiet, nf, ctx->sm_count);
-    if (p.lds_need) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: LDS need %d bytes", p.lds_need);
-    if (p.too_many_checks) return set_error(ctx, LDPC_AMD_EUNSUP, "ML stage: more than 4096 checks (%d)", cd.m);
+    if ((rc = refuse_ml(ctx, cd, p))) return rc;   // (decode_chunk has asked already, before the first launch)
     ma = p.ma;
     ma.code = cd;
     ma.ml_list = (const int32_t *)ctx->mllist.p; ma.ml_state = (const uint8_t *)ctx->mlstate.p; ma.nframes = nf;
@@ -2936,11 +2954,16 @@ static int decode_chunk(ldpc_amd_ctx *ctx, const DecodeArgs &d, bool fused, bool
         return set_error(ctx, LDPC_AMD_EINVAL, "internal: packets-in decode without the scatter kernel, in place, or with a row array");
     if (d.inplace && !use_scatter) return set_error(ctx, LDPC_AMD_EUNSUP, "in-place decode needs the scatter kernel");
     const PeelShape shape = plan_peel(kn, cd, fused, nf, ctx->sm_count);
-    if (shape.lds_need) return set_error(ctx, LDPC_AMD_EUNSUP, "code too large for LDS (%d bytes)", shape.lds_need);
     const RelaxPlan relax = plan_relax(kn, cd, fused ? 0 : (d.flags_only ? 1 : 2), d.erased != nullptr, d.in_rows, d.max_sweeps, nf, ctx->sm_count);
+    // Every refusal is decided here, from the plans, BEFORE the first launch or memset: a refused call has written nothing.
+    // (None of them depends on the number of frames, so a later chunk of a long batch is never refused behind an earlier one.)
+    // The serial kernel's LDS plan counts only where that kernel runs -- the relaxation has a plan of its own.
+    if (shape.lds_need && !relax.ok) return set_error(ctx, LDPC_AMD_EUNSUP, "code too large for LDS (%d bytes)", shape.lds_need);
+    int rc;
+    if (!fused && !d.flags_only && !use_scatter && (rc = refuse_apply(ctx, cd))) return rc;
+    if (d.do_ml && !d.flags_only && (rc = refuse_ml(ctx, cd, plan_ml(kn, cd, d.S, fused, words, use_scatter, true, nf, ctx->sm_count)))) return rc;
     record_plan(ctx, shape, relax, plan);
 
-    int rc;
     if ((rc = scratch_reserve(ctx, ctx->mllist, sizeof(int32_t) * ((size_t)(1 + kMlClasses) * nf + kMlHdr)))) return rc;
     if (d.do_ml && (rc = scratch_reserve(ctx, ctx->mlstate, (size_t)nf * cd.n))) return rc;
     LDPC_HIP_TRY(ctx, hipMemsetAsync(ctx->mllist.p, 0, kMlHdr * sizeof(int32_t), ctx->stream));   // (the ML stage's work counters with it)
@@ -3050,6 +3073,7 @@ static int launch_encode_impl(ldpc_amd_ctx *ctx, const DevCode &cd, int S, int64
         }
     }
     if (pkt_out) return kEncodeNotFused;
+    if (int rca = refuse_apply(ctx, cd)) return rca;
     ApplyArgs aa{};
     aa.code = cd; aa.S = S; aa.nframes = nframes; aa.sym = src; aa.erased = nullptr; aa.in_rows = cd.k; aa.out = cw;
     ctx->prof_names[LDPC_AMD_NAME_ENCODE] = words ? "ldpc_apply_words_kernel" : "ldpc_apply_kernel";
