@@ -84,6 +84,11 @@ EXPORTS_FLOWS_FLUSH = [
     "ldpc_amd_fec_flows_flush_info",
 ]
 FLUSH_PATHS = ("none", "fused", "composed", "push")
+# every symbol include/ldpc_erasure_amd_datagrams.h declares (datagrams of any length: pack to source symbols, unpack after decode)
+EXPORTS_DATAGRAMS = ["ldpc_amd_fec_dgram_pack_dev", "ldpc_amd_fec_dgram_unpack_dev", "ldpc_amd_fec_dgram_wire_len", "ldpc_amd_fec_dgram_info"]
+DGRAM_DELIVERED, DGRAM_FILLER, DGRAM_LOST, DGRAM_MALFORMED = 0, 1, 2, 3   # LDPC_AMD_DGRAM_*: the state of a row after unpack
+DGRAM_PREFIX_BYTES = 4
+Datagrams = collections.namedtuple("Datagrams", "bytes offset state")
 FlowsPending = collections.namedtuple("FlowsPending", "cur_block cur_cnt next_cnt blocks")
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
@@ -234,6 +239,14 @@ def load_library():
         L.ldpc_amd_fec_rx_flows_flush_many.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
         L.ldpc_amd_fec_rx_flows_decode_flush_many.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.ldpc_amd_fec_flows_flush_info.argtypes = [vp, C.POINTER(i64)]
+    # datagrams of any length (include/ldpc_erasure_amd_datagrams.h)
+    if hasattr(L, "ldpc_amd_fec_dgram_pack_dev"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_dgram_pack_dev.argtypes = [vp, vp, vp, i64, i32, i32, vp]
+        L.ldpc_amd_fec_dgram_pack_dev.restype = i64
+        L.ldpc_amd_fec_dgram_unpack_dev.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, i64, vp, vp]
+        L.ldpc_amd_fec_dgram_wire_len.argtypes = [i64, vp, i32, i32, i32, vp]
+        L.ldpc_amd_fec_dgram_wire_len.restype = i64
+        L.ldpc_amd_fec_dgram_info.argtypes = [vp, C.POINTER(i64)]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -291,6 +304,28 @@ def fec_tx_flows_layout(frame_begin, n, order):
         raise LdpcAmdError(f"fec_tx_flows_layout = {rc}: bad nflows / frame_begin / n / order")
     assert rc == F * n
     return first, stride
+
+
+def _dgram_offsets(offsets):
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    if off.ndim != 1 or off.shape[0] < 1:
+        raise LdpcAmdError("datagram offsets must be a 1-D array of N + 1 >= 1 entries")
+    return off
+
+
+def fec_datagram_wire_len(offsets, n, k, S):
+    """Bytes of every wire packet that have to be transmitted when the datagrams offsets[i] .. offsets[i+1] are packed and sent
+    (host arithmetic, no GPU needed; include/ldpc_erasure_amd_datagrams.h): int32 [F*n], 8 + 4 + L for a source row (12 for a
+    filler), 8 + S for a repair row.  Every byte of a packet behind that is zero."""
+    L = load_library()
+    off = _dgram_offsets(offsets)
+    N = off.shape[0] - 1
+    wl = np.zeros(max(-(-N // max(k, 1)) * max(n, 0), 0), dtype=np.int32)
+    rc = L.ldpc_amd_fec_dgram_wire_len(N, off.ctypes.data, n, k, S, wl.ctypes.data)
+    if rc < 0:
+        raise LdpcAmdError(f"fec_dgram_wire_len = {rc}: bad offsets / n / k / S")
+    assert rc == wl.shape[0]
+    return wl
 
 
 def _is_torch(x):
@@ -734,6 +769,53 @@ class Context:
         self._check(self._L.ldpc_amd_fec_sender_flows_info(self._h, info), "fec_sender_flows_info")
         return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "frames": int(info[3])}
 
+    # -- datagrams of any length (include/ldpc_erasure_amd_datagrams.h)
+    def fec_pack_datagrams(self, data, offsets, k, S, out=None):
+        """data: torch uint8 1-D on this context's device (a slice starting at any byte is fine), datagram i = data[offsets[i] :
+        offsets[i+1]] (offsets: array-like int64, N + 1 entries, lengths 0 .. S-4; length 0 = a filler) -> source torch uint8
+        [F][k][S], F = ceil(N / k): row i = the length as a little-endian uint32, the datagram, zeros.  Every byte of the result is
+        written.  Asynchronous on the context's stream."""
+        import torch
+        off = _dgram_offsets(offsets)
+        N = off.shape[0] - 1
+        F = -(-N // max(k, 1))
+        if out is None:
+            dev = data.device if _is_torch(data) else torch.device("cuda", self.device)
+            out = torch.empty((F, max(k, 0), max(S, 0)), dtype=torch.uint8, device=dev)
+        assert _is_torch(out) and out.dtype == torch.uint8 and tuple(out.shape) == (F, k, S) and out.is_contiguous()
+        got = self._check(self._L.ldpc_amd_fec_dgram_pack_dev(self._h, _ptr(data), off.ctypes.data, N, k, S, _ptr(out) if F else None),
+                          "fec_dgram_pack_dev")
+        assert got == F
+        return out
+
+    def fec_unpack_datagrams(self, frames, k, erased=None):
+        """frames: torch uint8 [B][n][S] on this context's device, erased: torch uint8 [B][n] or None (nothing erased) -- out and
+        erased_out of decode_frames / decode_many / decode_flush_many.  Returns Datagrams(bytes torch uint8 [B*k*(S-4)], offset torch
+        int64 [B*k+1], state torch uint8 [B*k]): row r of the source rows is DGRAM_DELIVERED (its datagram is bytes[offset[r] :
+        offset[r+1]]), DGRAM_FILLER, DGRAM_LOST (erased) or DGRAM_MALFORMED; offset[-1] is the total, the bytes behind it are not
+        written.  Asynchronous on the context's stream, nothing is read back."""
+        import torch
+        assert _is_torch(frames) and frames.dtype == torch.uint8 and frames.ndim == 3 and frames.is_contiguous()
+        B, n, S = frames.shape
+        if erased is not None:
+            assert _is_torch(erased) and erased.dtype == torch.uint8 and tuple(erased.shape) == (B, n)
+        R = B * k
+        out = Datagrams(torch.empty(max(R * (S - DGRAM_PREFIX_BYTES), 0), dtype=torch.uint8, device=frames.device),
+                        torch.empty(R + 1, dtype=torch.int64, device=frames.device), torch.empty(R, dtype=torch.uint8, device=frames.device))
+        self._check(self._L.ldpc_amd_fec_dgram_unpack_dev(self._h, _ptr(frames) if B else None, _ptr(erased) if B else None, B, n, k, S,
+                                                          _ptr(out.bytes), out.bytes.shape[0], _ptr(out.offset), _ptr(out.state)),
+                    "fec_dgram_unpack_dev")
+        if B == 0:
+            out.offset.zero_()   # (the library touches nothing for no frames)
+        return out
+
+    def fec_dgram_info(self):
+        """{"scratch_bytes": device scratch the context holds for pack and unpack, "staging_bytes": pinned staging of pack's offsets,
+        "pack_rows": rows of the last pack, "unpack_rows": rows of the last unpack}."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_dgram_info(self._h, info), "fec_dgram_info")
+        return dict(zip(("scratch_bytes", "staging_bytes", "pack_rows", "unpack_rows"), [int(x) for x in info]))
+
     def fec_tx_flows(self, code, S, nflows, fec_class=1, block0=0):
         """nflows senders that number their blocks across calls and share one wire (FecTxFlows)."""
         return FecTxFlows(self, code, S, nflows, fec_class, block0)
@@ -1158,6 +1240,12 @@ class FecTxDevice:
         pk = self._ctx.fec_encode_packets_device(self.code, source, self.fec_class, self.next_block, out=out)
         self.next_block = (self.next_block + source.shape[0]) & 0xFF
         return pk
+
+    def send_datagrams(self, data, offsets):
+        """Datagrams of any length up to S - 4 (Context.fec_pack_datagrams) -> (packets [F*n][8+S], wire_len int32 [F*n]): only
+        the first wire_len[p] bytes of packet p need to be transmitted, the rest of it is zero.  Advances the block counter by F."""
+        wl = fec_datagram_wire_len(offsets, self.n, self.k, self.S)
+        return self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), wl
 
 
 class FecTxFlows:

@@ -212,6 +212,15 @@ struct ldpc_amd_ctx {
     unsigned txf_calls = 0;
     int txf_path = 0;              // ... path of the last call (ldpc_amd_fec_sender_flows_info)
     int64_t txf_frames = 0;        // ... its frames
+    // fec_dgram_pack_dev / fec_dgram_unpack_dev (datagram_dev.hip): pack's offsets on the device and their pinned staging, two slots
+    // used in turn like txf_stage; unpack's per-row lengths and per-tile sums
+    ldpc_amd::Scratch dgram_off, dgram_len;
+    void *dgram_stage[2] = {nullptr, nullptr};
+    size_t dgram_stage_cap[2] = {0, 0};
+    hipEvent_t dgram_event[2] = {nullptr, nullptr};
+    bool dgram_pending[2] = {false, false};
+    unsigned dgram_calls = 0;
+    int64_t dgram_rows[2] = {0, 0};   // rows of the last pack, of the last unpack (ldpc_amd_fec_dgram_info)
     ldpc_amd::Scratch rx_sym;      // fec_rx_dev_decode_many, composed path: received symbols of one chunk of closed blocks (at most 256 MiB)
     ldpc_amd::Scratch rx_er;       // ... both paths: erasure flags of the closed blocks, [closes][n]
     ldpc_amd::Scratch rx_src;      // ... fused path: row-source words of the closed blocks, [closes][n] u32 (PacketRows)
