@@ -89,6 +89,10 @@ EXPORTS_DATAGRAMS = ["ldpc_amd_fec_dgram_pack_dev", "ldpc_amd_fec_dgram_unpack_d
 DGRAM_DELIVERED, DGRAM_FILLER, DGRAM_LOST, DGRAM_MALFORMED = 0, 1, 2, 3   # LDPC_AMD_DGRAM_*: the state of a row after unpack
 DGRAM_PREFIX_BYTES = 4
 Datagrams = collections.namedtuple("Datagrams", "bytes offset state")
+# every symbol include/ldpc_erasure_amd_wire_ragged.h declares (the trimmed wire: packets cut to their sent bytes, and landed back)
+EXPORTS_WIRE_RAGGED = ["ldpc_amd_fec_wire_trim_dev", "ldpc_amd_fec_wire_land_dev", "ldpc_amd_fec_wire_ragged_info"]
+WIRE_LANDED, WIRE_REJECTED = 0, 1   # LDPC_AMD_WIRE_*: the state of a datagram after land
+Wire = collections.namedtuple("Wire", "bytes offset")
 FlowsPending = collections.namedtuple("FlowsPending", "cur_block cur_cnt next_cnt blocks")
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
@@ -247,6 +251,11 @@ def load_library():
         L.ldpc_amd_fec_dgram_wire_len.argtypes = [i64, vp, i32, i32, i32, vp]
         L.ldpc_amd_fec_dgram_wire_len.restype = i64
         L.ldpc_amd_fec_dgram_info.argtypes = [vp, C.POINTER(i64)]
+    # the trimmed wire (include/ldpc_erasure_amd_wire_ragged.h)
+    if hasattr(L, "ldpc_amd_fec_wire_trim_dev"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_wire_trim_dev.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp]
+        L.ldpc_amd_fec_wire_land_dev.argtypes = [vp, vp, i64, vp, i64, i32, vp, vp]
+        L.ldpc_amd_fec_wire_ragged_info.argtypes = [vp, C.POINTER(i64)]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -816,6 +825,51 @@ class Context:
         self._check(self._L.ldpc_amd_fec_dgram_info(self._h, info), "fec_dgram_info")
         return dict(zip(("scratch_bytes", "staging_bytes", "pack_rows", "unpack_rows"), [int(x) for x in info]))
 
+    # -- the trimmed wire (include/ldpc_erasure_amd_wire_ragged.h)
+    def fec_trim_packets(self, packets, k, out=None):
+        """packets: torch uint8 [P][8+S] on this context's device (what any sender of the library made of packed datagrams) ->
+        Wire(bytes torch uint8 [P*(8+S)], offset torch int64 [P+1]): the bytes of every packet that have to be sent, back to back in
+        packet order -- a source row (header symbol below k) with length prefix L <= S - 4 is cut to 8 + 4 + L bytes, every other
+        packet is whole.  offset[-1] is the total, the bytes behind it are not written.  `out`, if given, is a Wire of such tensors
+        to write into.  Asynchronous on the context's stream, nothing is read back."""
+        import torch
+        assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.is_contiguous()
+        P, plen = packets.shape
+        if out is None:
+            out = Wire(torch.empty(P * plen, dtype=torch.uint8, device=packets.device), torch.empty(P + 1, dtype=torch.int64, device=packets.device))
+        out = Wire(*out)
+        assert out.bytes.dtype == torch.uint8 and out.bytes.ndim == 1 and out.offset.dtype == torch.int64 and tuple(out.offset.shape) == (P + 1,)
+        self._check(self._L.ldpc_amd_fec_wire_trim_dev(self._h, _ptr(packets) if P else None, P, k, plen - 8, _ptr(out.bytes), out.bytes.shape[0],
+                                                       _ptr(out.offset)), "fec_wire_trim_dev")
+        if P == 0:
+            out.offset.zero_()   # (the library touches nothing for no packets)
+        return out
+
+    def fec_land_packets(self, data, offset, S, out=None):
+        """data: torch uint8 1-D on this context's device (a slice starting at any byte is fine; nbytes = data.numel()), offset: torch
+        int64 [P+1] ON THE DEVICE, datagram p = data[offset[p] : offset[p+1]] -> (packets torch uint8 [P][8+S], state torch uint8 [P]):
+        slot p is the datagram and zeros (WIRE_LANDED), or -- boundaries outside data, decreasing, a length below 8 or above 8 + S --
+        eight bytes 0xFF and zeros, which every receiver drops (WIRE_REJECTED).  Every byte of packets is written.  Asynchronous on
+        the context's stream, nothing is read back."""
+        import torch
+        assert _is_torch(data) and data.dtype == torch.uint8 and data.ndim == 1
+        assert _is_torch(offset) and offset.dtype == torch.int64 and offset.ndim == 1 and offset.shape[0] >= 1 and offset.device == data.device
+        P, nbytes = offset.shape[0] - 1, data.numel()
+        if out is None:
+            out = torch.empty((P, 8 + max(S, 0)), dtype=torch.uint8, device=data.device)
+        assert _is_torch(out) and out.dtype == torch.uint8 and tuple(out.shape) == (P, 8 + S) and out.is_contiguous()
+        state = torch.empty(P, dtype=torch.uint8, device=data.device)
+        self._check(self._L.ldpc_amd_fec_wire_land_dev(self._h, _ptr(data) if nbytes else None, nbytes, _ptr(offset), P, S, _ptr(out) if P else None,
+                                                       _ptr(state) if P else None), "fec_wire_land_dev")
+        return out, state
+
+    def fec_wire_ragged_info(self):
+        """{"scratch_bytes": device scratch the context holds for trim, "trim_packets": packets of the last trim, "land_packets":
+        packets of the last land}."""
+        info = (C.c_int64 * 3)()
+        self._check(self._L.ldpc_amd_fec_wire_ragged_info(self._h, info), "fec_wire_ragged_info")
+        return dict(zip(("scratch_bytes", "trim_packets", "land_packets"), [int(x) for x in info]))
+
     def fec_tx_flows(self, code, S, nflows, fec_class=1, block0=0):
         """nflows senders that number their blocks across calls and share one wire (FecTxFlows)."""
         return FecTxFlows(self, code, S, nflows, fec_class, block0)
@@ -1246,6 +1300,12 @@ class FecTxDevice:
         the first wire_len[p] bytes of packet p need to be transmitted, the rest of it is zero.  Advances the block counter by F."""
         wl = fec_datagram_wire_len(offsets, self.n, self.k, self.S)
         return self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), wl
+
+    def send_datagrams_trimmed(self, data, offsets):
+        """Pack + encode + trim: datagrams of any length up to S - 4 -> Wire(bytes, offset) of Context.fec_trim_packets, the bytes
+        that go on the wire back to back with their boundaries on the device; no per-packet table is made on the host.  Advances
+        the block counter by F, as send_datagrams does."""
+        return self._ctx.fec_trim_packets(self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), self.k)
 
 
 class FecTxFlows:

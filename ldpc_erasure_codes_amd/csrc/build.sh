@@ -13,17 +13,18 @@ OBJ="${LDPC_AMD_OBJDIR:-$HERE/obj}"
 mkdir -p "$OBJ"
 echo "$FLAGS" > "$OBJ/flags.new"
 if ! cmp -s "$OBJ/flags.new" "$OBJ/flags" 2>/dev/null; then rm -f "$OBJ"/*.o; mv "$OBJ/flags.new" "$OBJ/flags"; fi
-COMMON="$HERE/internal.h $ROOT/include/ldpc_erasure_amd.h $ROOT/include/ldpc_erasure_amd_synth.h $ROOT/include/ldpc_erasure_amd_wire.h $ROOT/include/ldpc_erasure_amd_multi.h $ROOT/include/ldpc_erasure_amd_wire_dev.h $ROOT/include/ldpc_erasure_amd_frames.h $ROOT/include/ldpc_erasure_amd_sender.h $ROOT/include/ldpc_erasure_amd_sender_flows.h $ROOT/include/ldpc_erasure_amd_receiver.h $ROOT/include/ldpc_erasure_amd_words.h $ROOT/include/ldpc_erasure_amd_flows.h $ROOT/include/ldpc_erasure_amd_flows_mixed.h $ROOT/include/ldpc_erasure_amd_flows_flush.h $ROOT/include/ldpc_erasure_amd_datagrams.h"
+COMMON="$HERE/internal.h $ROOT/include/ldpc_erasure_amd.h $ROOT/include/ldpc_erasure_amd_synth.h $ROOT/include/ldpc_erasure_amd_wire.h $ROOT/include/ldpc_erasure_amd_multi.h $ROOT/include/ldpc_erasure_amd_wire_dev.h $ROOT/include/ldpc_erasure_amd_frames.h $ROOT/include/ldpc_erasure_amd_sender.h $ROOT/include/ldpc_erasure_amd_sender_flows.h $ROOT/include/ldpc_erasure_amd_receiver.h $ROOT/include/ldpc_erasure_amd_words.h $ROOT/include/ldpc_erasure_amd_flows.h $ROOT/include/ldpc_erasure_amd_flows_mixed.h $ROOT/include/ldpc_erasure_amd_flows_flush.h $ROOT/include/ldpc_erasure_amd_datagrams.h $ROOT/include/ldpc_erasure_amd_wire_ragged.h"
 declare -A DEPS=(
   [kernels.hip]="$HERE/gf256_dev.h $HERE/fec_header_dev.h $HERE/peel_relax.inc $HERE/ml_kernel.inc $HERE/ml_pi.inc $HERE/rs_kernels.inc $HERE/fpga_kernels.inc"
   [api.cpp]="$HERE/builtin_codes_gen.inc"
   [wire.cpp]=""
   [multi.hip]=""
   [wire_dev.hip]="$HERE/fec_header_dev.h"
-  [datagram_dev.hip]=""
+  [datagram_dev.hip]="$HERE/dgram_scan_dev.h"
+  [wire_ragged_dev.hip]="$HERE/dgram_scan_dev.h"
 )
 pids=()
-for src in kernels.hip api.cpp wire.cpp multi.hip wire_dev.hip datagram_dev.hip; do
+for src in kernels.hip api.cpp wire.cpp multi.hip wire_dev.hip datagram_dev.hip wire_ragged_dev.hip; do
   o="$OBJ/${src%.*}.o"
   stale=0
   [ -f "$o" ] || stale=1
@@ -36,5 +37,5 @@ for src in kernels.hip api.cpp wire.cpp multi.hip wire_dev.hip datagram_dev.hip;
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/kernels.o" "$OBJ/api.o" "$OBJ/wire.o" "$OBJ/multi.o" "$OBJ/wire_dev.o" "$OBJ/datagram_dev.o"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/kernels.o" "$OBJ/api.o" "$OBJ/wire.o" "$OBJ/multi.o" "$OBJ/wire_dev.o" "$OBJ/datagram_dev.o" "$OBJ/wire_ragged_dev.o"
 echo "$OUT"

@@ -221,6 +221,8 @@ struct ldpc_amd_ctx {
     bool dgram_pending[2] = {false, false};
     unsigned dgram_calls = 0;
     int64_t dgram_rows[2] = {0, 0};   // rows of the last pack, of the last unpack (ldpc_amd_fec_dgram_info)
+    ldpc_amd::Scratch wire_len;       // fec_wire_trim_dev (wire_ragged_dev.hip): the per-tile sums, then the per-packet lengths
+    int64_t wire_packets[2] = {0, 0};   // packets of the last trim, of the last land (ldpc_amd_fec_wire_ragged_info)
     ldpc_amd::Scratch rx_sym;      // fec_rx_dev_decode_many, composed path: received symbols of one chunk of closed blocks (at most 256 MiB)
     ldpc_amd::Scratch rx_er;       // ... both paths: erasure flags of the closed blocks, [closes][n]
     ldpc_amd::Scratch rx_src;      // ... fused path: row-source words of the closed blocks, [closes][n] u32 (PacketRows)
