@@ -93,6 +93,12 @@ Datagrams = collections.namedtuple("Datagrams", "bytes offset state")
 EXPORTS_WIRE_RAGGED = ["ldpc_amd_fec_wire_trim_dev", "ldpc_amd_fec_wire_land_dev", "ldpc_amd_fec_wire_ragged_info"]
 WIRE_LANDED, WIRE_REJECTED = 0, 1   # LDPC_AMD_WIRE_*: the state of a datagram after land
 Wire = collections.namedtuple("Wire", "bytes offset")
+# every symbol include/ldpc_erasure_amd_link.h declares (the link emulator: reorder, duplicate, damage, on the device)
+EXPORTS_LINK = ["ldpc_amd_fec_link_plan_dev", "ldpc_amd_fec_link_apply_dev", "ldpc_amd_fec_link_apply_ragged_dev", "ldpc_amd_fec_link_info"]
+LINK_STREAM_DUP, LINK_STREAM_DELAY, LINK_STREAM_DAMAGE = 16, 17, 18   # LDPC_AMD_LINK_STREAM_*
+LINK_MAX_WINDOW = 4096
+LINK_DUP_FLIP = 1                                                       # LDPC_AMD_LINK_DUP_FLIP, a flag of the parameters
+LINK_COPY, LINK_BADSYM, LINK_FOREIGN, LINK_FLIPPED = 1, 2, 4, 8         # LDPC_AMD_LINK_*: the fate bits (the high byte: the FOREIGN block value)
 FlowsPending = collections.namedtuple("FlowsPending", "cur_block cur_cnt next_cnt blocks")
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
@@ -105,6 +111,12 @@ class LdpcAmdError(RuntimeError):
 
 class ErrorType(C.Structure):
     _fields_ = [("num_LDPC_errors", C.c_int), ("num_RS_errors", C.c_int)]
+
+
+class LinkParams(C.Structure):
+    """ldpc_amd_link_params"""
+    _fields_ = [("seed", C.c_uint64), ("first", C.c_uint64), ("window", C.c_int32), ("flags", C.c_int32), ("dup", C.c_double),
+                ("bad_sym", C.c_double), ("foreign", C.c_double)]
 
 
 _lib = None
@@ -256,6 +268,12 @@ def load_library():
         L.ldpc_amd_fec_wire_trim_dev.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp]
         L.ldpc_amd_fec_wire_land_dev.argtypes = [vp, vp, i64, vp, i64, i32, vp, vp]
         L.ldpc_amd_fec_wire_ragged_info.argtypes = [vp, C.POINTER(i64)]
+    # the link emulator (include/ldpc_erasure_amd_link.h)
+    if hasattr(L, "ldpc_amd_fec_link_plan_dev"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_link_plan_dev.argtypes = [vp, C.POINTER(LinkParams), i64, vp, vp, vp, i64, vp]
+        L.ldpc_amd_fec_link_apply_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, vp]
+        L.ldpc_amd_fec_link_apply_ragged_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp]
+        L.ldpc_amd_fec_link_info.argtypes = [vp, C.POINTER(i64)]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -870,6 +888,19 @@ class Context:
         self._check(self._L.ldpc_amd_fec_wire_ragged_info(self._h, info), "fec_wire_ragged_info")
         return dict(zip(("scratch_bytes", "trim_packets", "land_packets"), [int(x) for x in info]))
 
+    # -- the link emulator (include/ldpc_erasure_amd_link.h)
+    def fec_link(self, seed, window=0, dup=0.0, bad_sym=0.0, foreign=0.0, dup_flip=False, first=0):
+        """A link between a sender and a receiver of this context's device that re-orders (delays of 0 .. window packet times),
+        duplicates and damages what it carries, and continues one stream of draws from call to call (FecLink)."""
+        return FecLink(self, seed, window, dup, bad_sym, foreign, dup_flip, first)
+
+    def fec_link_info(self):
+        """{"scratch_bytes": device scratch held for the context's link calls, "plan_packets" / "apply_packets" /
+        "apply_ragged_packets": packets of the last call of each kind}."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_link_info(self._h, info), "fec_link_info")
+        return dict(zip(("scratch_bytes", "plan_packets", "apply_packets", "apply_ragged_packets"), [int(x) for x in info]))
+
     def fec_tx_flows(self, code, S, nflows, fec_class=1, block0=0):
         """nflows senders that number their blocks across calls and share one wire (FecTxFlows)."""
         return FecTxFlows(self, code, S, nflows, fec_class, block0)
@@ -1306,6 +1337,84 @@ class FecTxDevice:
         that go on the wire back to back with their boundaries on the device; no per-packet table is made on the host.  Advances
         the block counter by F, as send_datagrams does."""
         return self._ctx.fec_trim_packets(self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), self.k)
+
+
+class FecLink:
+    """The link emulator of include/ldpc_erasure_amd_link.h on one context: every call takes the packets of one burst in send order
+    and returns them as they arrive.  `first`, the position of the next packet in the link's life, advances by P per call, so the
+    calls continue one stream of draws; packets do not cross a call boundary.  Loss is an input: `lost`, torch uint8 [P] on the
+    device (non-zero: the packet is lost), e.g. Context.synth_erasures_uniform / _bursty with n = 1, frame0 = link.first,
+    nframes = P.  plan() is asynchronous and reads nothing back; send() and send_wire() read the count back, one 8-byte read --
+    the only place that synchronises."""
+
+    def __init__(self, ctx, seed, window=0, dup=0.0, bad_sym=0.0, foreign=0.0, dup_flip=False, first=0):
+        self._ctx = ctx
+        self.params = LinkParams(seed & 0xFFFFFFFFFFFFFFFF, first & 0xFFFFFFFFFFFFFFFF, window, LINK_DUP_FLIP if dup_flip else 0, float(dup),
+                                 float(bad_sym), float(foreign))
+
+    @property
+    def first(self):
+        return int(self.params.first)
+
+    def _device(self):
+        import torch
+        return torch.device("cuda", self._ctx.device)
+
+    def plan(self, P, lost=None):
+        """(src torch int32 [2P], fate torch int16 [2P] -- the bits of a uint16 --, count torch int64 [1]) on the device: entries
+        0 .. count-1 say which packet arrives at each position and with what fate; the rest is not written."""
+        import torch
+        dev = self._device()
+        if lost is not None:
+            assert _is_torch(lost) and lost.dtype == torch.uint8 and tuple(lost.shape) == (P,) and lost.is_contiguous()
+        cap = 2 * max(P, 0)
+        src = torch.empty(cap, dtype=torch.int32, device=dev)
+        fate = torch.empty(cap, dtype=torch.int16, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        c = self._ctx
+        c._check(c._L.ldpc_amd_fec_link_plan_dev(c._h, C.byref(self.params), P, _ptr(lost) if P > 0 else None, _ptr(src) if cap else None,
+                                                 _ptr(fate) if cap else None, cap, _ptr(count)), "fec_link_plan_dev")
+        self.params.first = (self.first + P) & 0xFFFFFFFFFFFFFFFF
+        return src, fate, count
+
+    def send(self, packets, lost=None, flow_of=None):
+        """packets: torch uint8 [P][8+S] on this context's device in send order (flow_of: torch int32 [P], the flow of every packet
+        of a mixed wire) -> (packets_out [Q][8+S], flow_of_out [Q] or None, src [Q], fate [Q]): the packets as they arrive."""
+        import torch
+        assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.is_contiguous()
+        P, plen = packets.shape
+        if flow_of is not None:
+            assert _is_torch(flow_of) and flow_of.dtype == torch.int32 and tuple(flow_of.shape) == (P,) and flow_of.is_contiguous()
+        src, fate, count = self.plan(P, lost)
+        cap = src.shape[0]
+        out = torch.empty((cap, plen), dtype=torch.uint8, device=packets.device)
+        fo = None if flow_of is None else torch.empty(cap, dtype=torch.int32, device=packets.device)
+        c = self._ctx
+        c._check(c._L.ldpc_amd_fec_link_apply_dev(c._h, _ptr(packets) if P else None, P, plen - 8, _ptr(src), _ptr(fate), _ptr(count), cap,
+                                                  _ptr(out), _ptr(flow_of), _ptr(fo)), "fec_link_apply_dev")
+        Q = int(count.item())
+        return out[:Q], None if fo is None else fo[:Q], src[:Q], fate[:Q]
+
+    def send_wire(self, wire, lost=None):
+        """wire: Wire(bytes torch uint8 1-D, offset torch int64 [P+1]) on this context's device, the datagrams in send order (what
+        Context.fec_trim_packets and FecTxDevice.send_datagrams_trimmed make; bytes may be a slice that starts at any byte) ->
+        (Wire(bytes_out [total], offset_out [Q+1]), src [Q], fate [Q]): the datagrams as they arrive, back to back."""
+        import torch
+        wire = Wire(*wire)
+        assert _is_torch(wire.bytes) and wire.bytes.dtype == torch.uint8 and wire.bytes.ndim == 1
+        assert _is_torch(wire.offset) and wire.offset.dtype == torch.int64 and wire.offset.ndim == 1 and wire.offset.shape[0] >= 1
+        P, nbytes = wire.offset.shape[0] - 1, wire.bytes.numel()
+        src, fate, count = self.plan(P, lost)
+        cap = src.shape[0]
+        dev = wire.bytes.device
+        out = Wire(torch.empty(2 * nbytes, dtype=torch.uint8, device=dev), torch.empty(cap + 1, dtype=torch.int64, device=dev))
+        c = self._ctx
+        c._check(c._L.ldpc_amd_fec_link_apply_ragged_dev(c._h, _ptr(wire.bytes) if nbytes else None, nbytes, _ptr(wire.offset), P, _ptr(src) if cap else None,
+                                                         _ptr(fate) if cap else None, _ptr(count), cap, _ptr(out.bytes) if nbytes else None,
+                                                         2 * nbytes, _ptr(out.offset), None), "fec_link_apply_ragged_dev")
+        Q = int(count.item())
+        offset = out.offset[:Q + 1]
+        return Wire(out.bytes[:int(offset[-1].item())], offset), src[:Q], fate[:Q]
 
 
 class FecTxFlows:

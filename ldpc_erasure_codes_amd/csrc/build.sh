@@ -22,9 +22,10 @@ declare -A DEPS=(
   [wire_dev.hip]="$HERE/fec_header_dev.h"
   [datagram_dev.hip]="$HERE/dgram_scan_dev.h"
   [wire_ragged_dev.hip]="$HERE/dgram_scan_dev.h"
+  [link_dev.hip]="$HERE/dgram_scan_dev.h $ROOT/include/ldpc_erasure_amd_link.h"
 )
 pids=()
-for src in kernels.hip api.cpp wire.cpp multi.hip wire_dev.hip datagram_dev.hip wire_ragged_dev.hip; do
+for src in kernels.hip api.cpp wire.cpp multi.hip wire_dev.hip datagram_dev.hip wire_ragged_dev.hip link_dev.hip; do
   o="$OBJ/${src%.*}.o"
   stale=0
   [ -f "$o" ] || stale=1
@@ -37,5 +38,5 @@ for src in kernels.hip api.cpp wire.cpp multi.hip wire_dev.hip datagram_dev.hip 
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/kernels.o" "$OBJ/api.o" "$OBJ/wire.o" "$OBJ/multi.o" "$OBJ/wire_dev.o" "$OBJ/datagram_dev.o" "$OBJ/wire_ragged_dev.o"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/kernels.o" "$OBJ/api.o" "$OBJ/wire.o" "$OBJ/multi.o" "$OBJ/wire_dev.o" "$OBJ/datagram_dev.o" "$OBJ/wire_ragged_dev.o" "$OBJ/link_dev.o"
 echo "$OUT"
