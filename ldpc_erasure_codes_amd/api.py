@@ -100,6 +100,17 @@ LINK_MAX_WINDOW = 4096
 LINK_DUP_FLIP = 1                                                       # LDPC_AMD_LINK_DUP_FLIP, a flag of the parameters
 LINK_COPY, LINK_BADSYM, LINK_FOREIGN, LINK_FLIPPED = 1, 2, 4, 8         # LDPC_AMD_LINK_*: the fate bits (the high byte: the FOREIGN block value)
 FlowsPending = collections.namedtuple("FlowsPending", "cur_block cur_cnt next_cnt blocks")
+# every symbol include/ldpc_erasure_amd_rx_window.h declares (the windowed receiver: W open blocks, resynchronises after an outage)
+EXPORTS_RX_WINDOW = [
+    "ldpc_amd_fec_rxw_create", "ldpc_amd_fec_rxw_destroy", "ldpc_amd_fec_rxw_push", "ldpc_amd_fec_rxw_push_many", "ldpc_amd_fec_rxw_flush",
+    "ldpc_amd_fec_rxw_stats", "ldpc_amd_fec_rxw_dropped", "ldpc_amd_fec_rxw_state",
+    "ldpc_amd_fec_rxw_dev_create", "ldpc_amd_fec_rxw_dev_destroy", "ldpc_amd_fec_rxw_dev_push_many", "ldpc_amd_fec_rxw_dev_flush",
+    "ldpc_amd_fec_rxw_dev_decode_many", "ldpc_amd_fec_rxw_dev_decode_flush", "ldpc_amd_fec_rxw_dev_stats", "ldpc_amd_fec_rxw_dev_dropped",
+    "ldpc_amd_fec_rxw_dev_state", "ldpc_amd_fec_rxw_info",
+]
+RX_WINDOW_PATHS = ("none", "fused", "composed")
+RX_WINDOW_TOTALS = ("bad_symbol", "late", "ahead_total", "resyncs", "closed")   # LDPC_AMD_RXW_*: the order of the totals
+RX_WINDOW_MIN, RX_WINDOW_MAX = 2, 32
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
@@ -274,6 +285,30 @@ def load_library():
         L.ldpc_amd_fec_link_apply_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, vp]
         L.ldpc_amd_fec_link_apply_ragged_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp]
         L.ldpc_amd_fec_link_info.argtypes = [vp, C.POINTER(i64)]
+    # the windowed receiver (include/ldpc_erasure_amd_rx_window.h)
+    if hasattr(L, "ldpc_amd_fec_rxw_create"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_rxw_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
+        L.ldpc_amd_fec_rxw_destroy.argtypes = [vp]
+        L.ldpc_amd_fec_rxw_destroy.restype = None
+        L.ldpc_amd_fec_rxw_push.argtypes = [vp, vp, vp, vp, C.POINTER(i32)]
+        L.ldpc_amd_fec_rxw_push_many.argtypes = [vp, vp, C.c_long, vp, vp, vp, i32, C.POINTER(C.c_long)]
+        L.ldpc_amd_fec_rxw_flush.argtypes = [vp, vp, vp, vp]
+        L.ldpc_amd_fec_rxw_stats.argtypes = [vp, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_dropped.argtypes = [vp]
+        L.ldpc_amd_fec_rxw_dropped.restype = C.c_long
+        L.ldpc_amd_fec_rxw_state.argtypes = [vp, C.POINTER(i32), vp, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_dev_create.argtypes = [vp, i32, i32, i32, i32, i32, C.POINTER(vp)]
+        L.ldpc_amd_fec_rxw_dev_destroy.argtypes = [vp]
+        L.ldpc_amd_fec_rxw_dev_destroy.restype = None
+        L.ldpc_amd_fec_rxw_dev_push_many.argtypes = [vp, vp, i64, vp, vp, vp, i32, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_dev_flush.argtypes = [vp, vp, vp, vp]
+        L.ldpc_amd_fec_rxw_dev_decode_many.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_dev_decode_flush.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.ldpc_amd_fec_rxw_dev_stats.argtypes = [vp, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_dev_dropped.argtypes = [vp]
+        L.ldpc_amd_fec_rxw_dev_dropped.restype = i64
+        L.ldpc_amd_fec_rxw_dev_state.argtypes = [vp, C.POINTER(i32), vp, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_info.argtypes = [vp, C.POINTER(i64)]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -917,6 +952,18 @@ class Context:
         self._check(self._L.ldpc_amd_fec_receiver_info(self._h, info), "fec_receiver_info")
         return {"path": RECEIVER_PATHS[info[0]], "scratch_bytes": int(info[1]), "blocks": int(info[2])}
 
+    # -- the windowed receiver (include/ldpc_erasure_amd_rx_window.h)
+    def fec_rx_window(self, n, k, S, window=4, ahead_limit=10):
+        """A device receiver that keeps `window` blocks open and resynchronises after `ahead_limit` packets beyond them (FecRxWindow)."""
+        return FecRxWindow(self, n, k, S, window, ahead_limit)
+
+    def fec_rx_window_info(self):
+        """{"path": "none" | "fused" | "composed" of the last FecRxWindow.decode_many / decode_flush call, "blocks": the blocks it
+        decoded, "launches": its decoder launches, "scratch_bytes": received-symbol scratch it used}."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_rxw_info(self._h, info), "fec_rxw_info")
+        return {"path": RX_WINDOW_PATHS[info[0]], "blocks": int(info[1]), "launches": int(info[2]), "scratch_bytes": int(info[3])}
+
     # -- the multi-flow receiver (include/ldpc_erasure_amd_flows.h)
     def fec_rx_flows(self, nflows, n, k, S):
         """nflows device receivers that are fed, planned and decoded together, one call for all of them (FecRxFlows)."""
@@ -1129,6 +1176,170 @@ class FecRxDevice:
             self.close()
         except Exception:
             pass
+
+
+class _RxWindowState:
+    """What the host and the device object of the windowed receiver report alike (prefix of the C names in self._pre)."""
+
+    def _fn(self, name):
+        return getattr(self._L, self._pre + name)
+
+    def stats(self):
+        """{"bad_symbol", "late", "ahead_total", "resyncs", "closed"}: the totals since the object was created."""
+        t = (C.c_int64 * 5)()
+        if self._fn("stats")(self._h, t) != 0:
+            raise LdpcAmdError("fec_rxw_stats: bad arguments")
+        return dict(zip(RX_WINDOW_TOTALS, (int(v) for v in t)))
+
+    @property
+    def dropped(self):
+        return int(self._fn("dropped")(self._h))
+
+    def state(self):
+        """{"base": block number of slot 0 (-1 before the first packet), "cnt": packets stored per slot, "ahead"}."""
+        base, ahead = C.c_int(0), C.c_int64(0)
+        cnt = np.zeros(self.window, dtype=np.int32)
+        if self._fn("state")(self._h, C.byref(base), cnt.ctypes.data, C.byref(ahead)) != 0:
+            raise LdpcAmdError("fec_rxw_state: bad arguments")
+        return {"base": base.value, "cnt": cnt.tolist(), "ahead": ahead.value}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FecRxWindowHost(_RxWindowState):
+    """The windowed reassembler on the host (include/ldpc_erasure_amd_rx_window.h): `window` blocks open, a resynchronisation after
+    `ahead_limit` packets beyond them (0: never).  With window = 2 and ahead_limit = 0 it is FecRx."""
+    _pre = "ldpc_amd_fec_rxw_"
+
+    def __init__(self, n, k, S, window=4, ahead_limit=10):
+        self._L = load_library()
+        h = C.c_void_p()
+        if self._L.ldpc_amd_fec_rxw_create(n, k, S, window, ahead_limit, C.byref(h)) != 0:
+            raise LdpcAmdError("fec_rxw_create: bad arguments")
+        self._h, self.n, self.k, self.S, self.window, self.ahead_limit = h, n, k, S, window, ahead_limit
+
+    def push(self, packet):
+        """None, or (block number, sym [n][S], erased [n]) of the block this packet closed."""
+        packet = np.ascontiguousarray(packet, dtype=np.uint8)
+        assert packet.size == 8 + self.S
+        sym, er, blk = np.zeros((self.n, self.S), dtype=np.uint8), np.zeros(self.n, dtype=np.uint8), C.c_int(-1)
+        rc = self._L.ldpc_amd_fec_rxw_push(self._h, packet.ctypes.data, sym.ctypes.data, er.ctypes.data, C.byref(blk))
+        if rc < 0:
+            raise LdpcAmdError("fec_rxw_push: bad arguments")
+        return (blk.value, sym, er) if rc == 1 else None
+
+    def push_many(self, packets, max_blocks):
+        """packets: uint8 [P][8+S].  Returns (blocks int32 [B], sym uint8 [B][n][S], erased uint8 [B][n], consumed)."""
+        packets = np.ascontiguousarray(packets, dtype=np.uint8)
+        assert packets.ndim == 2 and packets.shape[1] == 8 + self.S
+        mb = max(max_blocks, 1)
+        sym = np.zeros((mb, self.n, self.S), dtype=np.uint8)
+        er = np.zeros((mb, self.n), dtype=np.uint8)
+        blocks = np.zeros(mb, dtype=np.int32)
+        used = C.c_long(0)
+        nb = self._L.ldpc_amd_fec_rxw_push_many(self._h, packets.ctypes.data if packets.shape[0] else None, packets.shape[0], sym.ctypes.data,
+                                                er.ctypes.data, blocks.ctypes.data, max_blocks, C.byref(used))
+        if nb < 0:
+            raise LdpcAmdError("fec_rxw_push_many: bad arguments")
+        return blocks[:nb], sym[:nb], er[:nb], used.value
+
+    def flush(self):
+        """(blocks int32 [B], sym [B][n][S], erased [B][n]) of the 0..window blocks the end of the stream closes."""
+        sym = np.zeros((self.window, self.n, self.S), dtype=np.uint8)
+        er = np.zeros((self.window, self.n), dtype=np.uint8)
+        blocks = np.zeros(self.window, dtype=np.int32)
+        nb = self._L.ldpc_amd_fec_rxw_flush(self._h, sym.ctypes.data, er.ctypes.data, blocks.ctypes.data)
+        if nb < 0:
+            raise LdpcAmdError("fec_rxw_flush: bad arguments")
+        return blocks[:nb], sym[:nb], er[:nb]
+
+
+class FecRxWindow(_RxWindowState):
+    """FecRxWindowHost for packets already in GPU memory: the same blocks, erasure flags, consumed, totals and state, byte for byte.
+    Shaped on FecRxDevice: payload movement is asynchronous on the context's stream; the returned block numbers and counts are final
+    when a call returns.  Close it before its Context."""
+    _pre = "ldpc_amd_fec_rxw_dev_"
+
+    def __init__(self, ctx, n, k, S, window=4, ahead_limit=10):
+        self._ctx, self._L = ctx, ctx._L
+        h = C.c_void_p()
+        ctx._check(self._L.ldpc_amd_fec_rxw_dev_create(ctx._h, n, k, S, window, ahead_limit, C.byref(h)), "fec_rxw_dev_create")
+        self._h, self.n, self.k, self.S, self.window, self.ahead_limit = h, n, k, S, window, ahead_limit
+
+    def _device(self):
+        import torch
+        return torch.device("cuda", self._ctx.device)
+
+    def _frames(self, B):
+        import torch
+        dev = self._device()
+        shape = (B, self.n) if self.S == 1 else (B, self.n, self.S)
+        i32 = [torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(4)]
+        return DecodedFrames(torch.empty(shape, dtype=torch.uint8, device=dev), i32[0], i32[1], i32[2],
+                             torch.empty((B, self.n), dtype=torch.uint8, device=dev), i32[3])
+
+    def push_many(self, packets, max_blocks):
+        """packets: torch uint8 [P][8+S] on the device.  Returns (blocks int32 [B], sym torch uint8 [B][n][S],
+        erased torch uint8 [B][n], consumed)."""
+        import torch
+        assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.shape[1] == 8 + self.S
+        mb = max(max_blocks, 1)
+        sym = torch.empty((mb, self.n, self.S), dtype=torch.uint8, device=packets.device)
+        er = torch.empty((mb, self.n), dtype=torch.uint8, device=packets.device)
+        blocks = np.zeros(mb, dtype=np.int32)
+        used = C.c_int64(0)
+        nb = self._ctx._check(self._L.ldpc_amd_fec_rxw_dev_push_many(self._h, _ptr(packets) if packets.numel() else None, packets.shape[0],
+                                                                     _ptr(sym), _ptr(er), blocks.ctypes.data, max_blocks, C.byref(used)),
+                              "fec_rxw_dev_push_many")
+        return blocks[:nb], sym[:nb], er[:nb], used.value
+
+    def flush(self):
+        """(blocks int32 [B], sym torch [B][n][S], erased torch [B][n]) of the 0..window blocks the end of the stream closes."""
+        import torch
+        sym = torch.empty((self.window, self.n, self.S), dtype=torch.uint8, device=self._device())
+        er = torch.empty((self.window, self.n), dtype=torch.uint8, device=self._device())
+        blocks = np.zeros(self.window, dtype=np.int32)
+        nb = self._ctx._check(self._L.ldpc_amd_fec_rxw_dev_flush(self._h, _ptr(sym), _ptr(er), blocks.ctypes.data), "fec_rxw_dev_flush")
+        return blocks[:nb], sym[:nb], er[:nb]
+
+    def decode_many(self, code, packets, max_blocks, max_sweeps=10, do_ml=1):
+        """push_many + Context.decode_frames in one call: packets torch uint8 [P][8+S] on the device -> (blocks int32 [B],
+        DecodedFrames of the B closed blocks, consumed).  Context.fec_rx_window_info() says which form ran.  Keep `packets` alive
+        until the context's stream has passed the call."""
+        import torch
+        assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.shape[1] == 8 + self.S
+        fr = self._frames(max(max_blocks, 1))
+        blocks = np.zeros(max(max_blocks, 1), dtype=np.int32)
+        used = C.c_int64(0)
+        nb = self._ctx._check(self._L.ldpc_amd_fec_rxw_dev_decode_many(
+            self._h, code, _ptr(packets) if packets.numel() else None, packets.shape[0], max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps),
+            _ptr(fr.residual), _ptr(fr.status), _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, max_blocks, C.byref(used)),
+            "fec_rxw_dev_decode_many")
+        return blocks[:nb], DecodedFrames(*(t[:nb] for t in fr)), used.value
+
+    def decode_flush(self, code, max_sweeps=10, do_ml=1):
+        """(blocks int32 [B], DecodedFrames of those B blocks) for the 0..window blocks the end of the stream closes."""
+        fr = self._frames(self.window)
+        blocks = np.zeros(self.window, dtype=np.int32)
+        nb = self._ctx._check(self._L.ldpc_amd_fec_rxw_dev_decode_flush(
+            self._h, code, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status), _ptr(fr.erased_out),
+            _ptr(fr.residual_src), blocks.ctypes.data), "fec_rxw_dev_decode_flush")
+        return blocks[:nb], DecodedFrames(*(t[:nb] for t in fr))
 
 
 class FecRxFlows:

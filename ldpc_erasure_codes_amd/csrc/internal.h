@@ -256,6 +256,9 @@ struct ldpc_amd_ctx {
     int last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launch plan of the last decode (ldpc_amd_last_plan)
     int last_enc_grouped = 0;                      // the last packet-mode encode ran the grouped static schedule (ldpc_amd_encode_info)
     int symbol_unit = 16;                          // 16, or 4: word-sized symbols (include/ldpc_erasure_amd_words.h; not a knob)
+    // fec_rxw_dev_decode_many / _decode_flush (rx_window_dev.hip): path (0 none, 1 fused, 2 composed), blocks, decoder launches and
+    // scratch bytes of the last call (ldpc_amd_fec_rxw_info)
+    int64_t rxw_info[4] = {0, 0, 0, 0};
 };
 
 namespace ldpc_amd {

@@ -1,0 +1,753 @@
+// rx_window_dev.hip -- the windowed FEC receiver on the device (include/ldpc_erasure_amd_rx_window.h): csrc/rx_window.cpp's object for
+// packets that are already in GPU memory, byte for byte.  The five steps of wire_dev.hip's two-buffer receiver, with W blocks open:
+//   (a) rxw_headers   every packet's header -> one dense u32, block << 16 | symbol                                        (parallel)
+//   (b) rxw_scan      one wavefront replays ldpc_amd_fec_rxw_push over the dense headers, 64 packets per step: per packet the
+//                     SERIAL of the block it went to (or -1), per close the wire block number, at the end the state and the totals
+//   (c) rxw_winners   atomicMax of the packet index into a [(closes + W)][n] table: the last copy of a symbol wins          (parallel)
+//   (d) rxw_move<1>   closed blocks -> sym_batch / erased_batch; or rxw_sources: WHERE the decoder finds each row           (parallel)
+//   (e) rxw_move<0>   the W blocks still open -> the W staging planes, in a launch behind (d)                              (parallel)
+// Serials: the blocks open when the call starts are serials 0 .. W-1 (slot d = serial d); the t-th close of the call (0-based)
+// hands out serial t -- blocks close in the order they were opened -- and opens serial t + W.  So closed slot t of the call is serial
+// t, and the blocks open at the end are serials closes .. closes + W - 1.  Serial s lives in ring plane (head + s) % W, head = the
+// plane of slot 0 when the call starts.  Serials below W were carried in: their planes hold what earlier calls received; every other
+// serial starts zero and erased.  The plane a new serial s >= W takes over is the plane of serial s - W, a block (d) may still read,
+// hence (e) behind (d).  A re-anchor happens only when every open block is empty: it consumes no serial and moves no data; it changes
+// `base`, and the packet that tripped it goes to the serial in slot 0.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+
+#include "internal.h"
+#include "../../include/ldpc_erasure_amd_rx_window.h"
+
+using namespace ldpc_amd;
+
+namespace {
+
+constexpr int kHdr = 8;   // LDPC_AMD_FEC_HEADER_BYTES
+constexpr int kThreads = 256;
+constexpr int kMaxW = LDPC_AMD_RXW_MAX_WINDOW;
+constexpr int kScanChunk = 16;   // groups of 64 dense headers per LDS chunk; the next chunk's are in flight in registers meanwhile
+constexpr size_t kScratchMax = (size_t)256 << 20;   // composed form: received symbols of one chunk of closed blocks
+
+// Result record of one scan (32-bit words): the end state, the totals of the call, the W counts, then one wire block number per close.
+enum : int {
+    R_BASE, R_AHEAD, R_CLOSES, R_ERR, R_RESYNCS, R_CONSUMED_LO, R_CONSUMED_HI, R_BAD_LO, R_BAD_HI, R_LATE_LO, R_LATE_HI, R_AHEADTOT_LO,
+    R_AHEADTOT_HI, R_CNT = 16, R_WORDS = R_CNT + kMaxW
+};
+
+inline unsigned grid_for(int64_t items)
+{
+    const int64_t b = (items + kThreads - 1) / kThreads;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(b, (int64_t)1 << 20));   // grid-stride loops cover the rest
+}
+
+// ---- (a) headers: only the first 32-bit half is read, as the host's ldpc_amd_fec_header_unpack does --------------------------------
+template <bool ALIGNED4>
+__global__ __launch_bounds__(kThreads) void rxw_headers(const uint8_t *__restrict__ packets, int64_t np, int plen, uint32_t *__restrict__ dense)
+{
+    for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < np; p += (int64_t)gridDim.x * kThreads) {
+        const uint8_t *h = packets + p * plen;
+        uint32_t w;
+        if (ALIGNED4) w = *reinterpret_cast<const uint32_t *>(h) & 0x00ffffffu;
+        else w = (uint32_t)h[0] | (uint32_t)h[1] << 8 | (uint32_t)h[2] << 16;
+        dense[p] = w;
+    }
+}
+
+// ---- (b) the plan scan -----------------------------------------------------------------------------------------------------------
+struct RxwRule {
+    int n, kd, km, W, A;
+};
+struct RxwState {   // the open state a scan starts from; cnt[j] = 0 for j >= W
+    int base, ahead;
+    int cnt[kMaxW];
+};
+
+__device__ __forceinline__ bool rxw_close_rule(int c, int later, const RxwRule &r)
+{
+    return c == r.n || (c > r.kd && later > 10) || (c > r.km && later > 100);
+}
+
+// One wavefront; every value but the lane's own packet is wave-uniform.  For a group of 64 packets from lane `start` on:
+//   is0 / isL / isA   this lane's packet goes to slot 0 / to a later slot of the window / is an ahead packet;
+//   c, lt, ah         cnt[0], cnt[1] + .. + cnt[W-1] and `ahead` after this lane's packet: the values before the group + the
+//                     ballots' inclusive prefix popcounts;
+//   bz                the lanes where step 3 fires after their packet; the first of them is the EVENT, a close or a re-anchor.
+// Exactness: the host's decision after packet l depends on the packets before it only through (base, cnt[0], the sum of the later
+// counts, ahead).  Between two events base is fixed, so every lane's class (slot d, ahead, late, bad symbol) is fixed, and each of
+// the three values after packet l is its value before the group plus the matching packets among start..l -- the prefix popcount.
+// Step 3 is a function of those three alone, so the first lane where it holds is the first packet after which the host acts, and
+// every lane up to it is assigned as the host assigns it.  Which of the two events it is follows from the three values at that
+// lane.  The event changes the state exactly as the host does and the lanes after it are evaluated again with the new state.  A
+// dropped packet changes no count but is still a point where step 3 is tested, as on the host.
+// The per-slot counts (needed only when a close makes slot 1 the new slot 0) are W counters in LDS, a ring like the planes: every
+// assigned lane adds one to its slot's counter; an event reads and resets them between two barriers of the one-wavefront workgroup.
+// The loop is bounded: every iteration assigns at least one packet, performs one event, or ends its group, so a call takes at most
+// 2 npackets + max_blocks + groups iterations (a re-anchor needs A + 1 >= 2 packets); a cap on that reports R_ERR instead of spinning.
+// The body is one function over a state record so that a per-flow kernel can call it with a segment and a state of its own.
+// cnt: LDS [kMaxW]; hbuf: LDS [kScanChunk * 64].
+__device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense, int64_t np, const RxwRule r, int max_blocks, const RxwState &st,
+                                              int *cnt, uint32_t *hbuf, int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    const int lane = threadIdx.x;
+    const uint64_t le = (lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1);   // lanes <= this one
+    int base = st.base, ahead = st.ahead, h = 0;   // slot d's counter is cnt[(h + d) % W]
+    int c0 = st.cnt[0], later = 0, own = 0;
+#pragma unroll
+    for (int j = 0; j < kMaxW; j++) {
+        if (j > 0) later += st.cnt[j];
+        if (lane == j) own = st.cnt[j];
+    }
+    if (lane < kMaxW) cnt[lane] = own;
+    int closes = 0, resyncs = 0, err = 0;
+    int64_t bad = 0, late = 0, aheadtot = 0, consumed = np, iters = 0;
+    const int64_t iter_cap = 2 * np + (int64_t)max_blocks + (np + 63) / 64 + 1;
+    bool done = false;
+    uint32_t nb[kScanChunk];
+#pragma unroll
+    for (int u = 0; u < kScanChunk; u++) {
+        const int64_t p = (int64_t)u * 64 + lane;
+        nb[u] = p < np ? dense[p] : 0u;
+    }
+    for (int64_t base0 = 0; base0 < np && !done; base0 += 64 * kScanChunk) {
+        __syncthreads();   // the chunk before has been read
+#pragma unroll
+        for (int u = 0; u < kScanChunk; u++) hbuf[u * 64 + lane] = nb[u];
+#pragma unroll
+        for (int u = 0; u < kScanChunk; u++) {   // headers of the next chunk in flight while this one is scanned
+            const int64_t p = base0 + (int64_t)(kScanChunk + u) * 64 + lane;
+            nb[u] = p < np ? dense[p] : 0u;
+        }
+        __syncthreads();
+        for (int u = 0; u < kScanChunk && !done; u++) {
+            const int64_t g0 = base0 + (int64_t)u * 64;
+            if (g0 >= np) break;
+            const int64_t p = g0 + lane;
+            const bool valid = p < np;
+            const uint32_t hw = hbuf[u * 64 + lane];
+            const int blk = (int)(hw >> 16), sym = (int)(hw & 0xffffu);
+            if (base < 0) base = __shfl(blk, 0);   // step 1: the first packet of the stream, before its symbol check
+            int d_out = -1;
+            int start = 0;
+            for (;;) {
+                if (++iters > iter_cap) { err = 1; done = true; consumed = g0; break; }
+                const bool live = valid && lane >= start;
+                const bool ok = live && sym < r.n;
+                const int d = (blk - base) & 0xff;
+                const bool in = ok && d < r.W;
+                const bool is0 = in && d == 0, isL = in && d != 0;
+                const bool isA = ok && !in && r.A > 0 && d < 128;
+                const uint64_t b0 = __ballot(is0), bL = __ballot(isL), bA = __ballot(isA);
+                const int c = c0 + __popcll(b0 & le), lt = later + __popcll(bL & le), ah = ahead + __popcll(bA & le);
+                const uint64_t bz = __ballot(live && (rxw_close_rule(c, lt, r) || (r.A > 0 && ah > r.A)));
+                const uint64_t upto = bz ? ((bz & (0ull - bz)) << 1) - 1 : ~0ull;   // lanes up to the first event (all if none)
+                const bool mine = live && ((upto >> lane) & 1);
+                if (mine) d_out = in ? closes + d : -1;
+                if (mine && in) {
+                    const int j = h + d;
+                    atomicAdd(&cnt[j >= r.W ? j - r.W : j], 1);
+                }
+                bad += __popcll(__ballot(mine && !ok));
+                late += __popcll(__ballot(mine && ok && !in && !isA));
+                aheadtot += __popcll(bA & upto);
+                c0 += __popcll(b0 & upto);
+                later += __popcll(bL & upto);
+                ahead += __popcll(bA & upto);
+                if (!bz) break;
+                const int L = __ffsll((long long)bz) - 1;   // c0, later, ahead are now the values after lane L's packet
+                if (!rxw_close_rule(c0, later, r) && c0 + later == 0) {
+                    // re-anchor: every counter is zero, the tripping packet opens slot 0 at its own block number
+                    base = __shfl(blk, L);
+                    if (lane == L) d_out = closes;
+                    if (lane == 0) cnt[h] = 1;
+                    c0 = 1;
+                    ahead = 0;
+                    resyncs++;
+                } else {
+                    // close: slot 0 is handed out, the slots shift down by one
+                    __syncthreads();   // the counters hold every packet assigned so far
+                    const int h1 = h + 1 == r.W ? 0 : h + 1;
+                    const int nc0 = cnt[h1];
+                    __syncthreads();
+                    if (lane == 0) {
+                        cnt[h] = 0;   // the new last slot
+                        res[R_WORDS + closes] = base;
+                    }
+                    closes++;
+                    h = h1;
+                    later -= nc0;
+                    c0 = nc0;
+                    base = (base + 1) & 0xff;
+                    ahead = 0;
+                    if (closes == max_blocks) { consumed = g0 + L + 1; done = true; break; }
+                }
+                start = L + 1;
+                if (start >= 64) break;
+            }
+            if (valid) dest[p] = d_out;
+        }
+    }
+    __syncthreads();
+    if (lane < kMaxW) {
+        const int j = h + lane;
+        res[R_CNT + lane] = lane < r.W ? cnt[j >= r.W ? j - r.W : j] : 0;
+    }
+    if (lane == 0) {
+        res[R_BASE] = base; res[R_AHEAD] = ahead; res[R_CLOSES] = closes; res[R_ERR] = err; res[R_RESYNCS] = resyncs;
+        res[R_CONSUMED_LO] = (int32_t)(uint32_t)consumed; res[R_CONSUMED_HI] = (int32_t)(consumed >> 32);
+        res[R_BAD_LO] = (int32_t)(uint32_t)bad; res[R_BAD_HI] = (int32_t)(bad >> 32);
+        res[R_LATE_LO] = (int32_t)(uint32_t)late; res[R_LATE_HI] = (int32_t)(late >> 32);
+        res[R_AHEADTOT_LO] = (int32_t)(uint32_t)aheadtot; res[R_AHEADTOT_HI] = (int32_t)(aheadtot >> 32);
+    }
+}
+
+__global__ __launch_bounds__(64) void rxw_scan(const uint32_t *__restrict__ dense, int64_t np, RxwRule r, int max_blocks, RxwState st,
+                                              int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    __shared__ int cnt[kMaxW];
+    __shared__ uint32_t hbuf[kScanChunk * 64];
+    rxw_scan_body(dense, np, r, max_blocks, st, cnt, hbuf, dest, res);
+}
+
+// ---- (c) last writer wins ----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void rxw_winners(const uint32_t *__restrict__ dense, const int32_t *__restrict__ dest, int64_t consumed,
+                                                       int n, int32_t *__restrict__ win)
+{
+    for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < consumed; p += (int64_t)gridDim.x * kThreads) {
+        const int s = dest[p];
+        if (s >= 0) atomicMax(&win[(int64_t)s * n + (dense[p] & 0xffffu)], (int32_t)p);   // dest >= 0 only for symbol < n
+    }
+}
+
+// ---- (d) gather into the closed slots, (e) staging planes ----------------------------------------------------------------------------
+struct MoveArgs {
+    const uint8_t *packets;
+    int64_t plen;
+    const int32_t *win;   // [(closes + W)][n]
+    uint8_t *stage_sym;   // [W][n][S]
+    uint8_t *stage_er;    // [W][n]
+    uint8_t *sym_out;     // gather: [count][n][S], the closed slots first .. first + count - 1
+    uint8_t *er_out;      // gather: [count][n]
+    int n, S, W, head, closes;
+    int first, count;
+};
+
+// Row r of the gather (slot = serial first + r / n, symbol i): the last packet that went there, else -- a block carried in from an
+// earlier call -- its staging row, else zero and erased.  Row r of the staging update (serial closes + r / n): the last packet, else
+// for a block opened in this call zero and erased; a carried block keeps its staging row.
+template <bool GATHER, bool V16>
+__global__ __launch_bounds__(kThreads) void rxw_move(MoveArgs a)
+{
+    const int q = V16 ? a.S / 16 : a.S;   // 16-byte pieces or bytes of a row
+    const int64_t rows = (int64_t)(GATHER ? a.count : a.W) * a.n;
+    const int64_t total = rows * q;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
+        const int64_t r = t / q;
+        const int c = (int)(t - r * q);
+        const int s = (int)(r / a.n) + (GATHER ? a.first : a.closes);   // serial of the block
+        const int i = (int)(r - (int64_t)(r / a.n) * a.n);
+        const int w = a.win[(int64_t)s * a.n + i];
+        const int b = (a.head + s) % a.W;
+        const bool carried = s < a.W;
+        const int64_t erow = (int64_t)b * a.n + i;   // the block's staging row
+        const int64_t srow = erow * a.S;
+        uint8_t *dst = GATHER ? a.sym_out + r * a.S : a.stage_sym + srow;
+        if (!GATHER && w < 0 && carried) continue;
+        if (V16) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (w >= 0) {
+                const uint2 *src = reinterpret_cast<const uint2 *>(a.packets + (int64_t)w * a.plen + kHdr + (int64_t)c * 16);
+                const uint2 lo = src[0], hi = src[1];
+                v = make_uint4(lo.x, lo.y, hi.x, hi.y);
+            } else if (carried) {
+                v = *reinterpret_cast<const uint4 *>(a.stage_sym + srow + (int64_t)c * 16);
+            }
+            *reinterpret_cast<uint4 *>(dst + (int64_t)c * 16) = v;
+        } else {
+            uint8_t v = 0;
+            if (w >= 0) v = a.packets[(int64_t)w * a.plen + kHdr + c];
+            else if (carried) v = a.stage_sym[srow + c];
+            dst[c] = v;
+        }
+        if (c == 0) {
+            const uint8_t e = w >= 0 ? 0 : (carried ? a.stage_er[erow] : 1);
+            if (GATHER) a.er_out[r] = e;
+            else a.stage_er[erow] = e;
+        }
+    }
+}
+
+// (d') the fused form: the gather's rule for row r as a word the packets-in decoder follows (internal.h, PacketRows) -- the W planes
+// are one `stage` base, row i of plane b is staging row b * n + i -- and the erasure flag the gather would have written.
+__global__ __launch_bounds__(kThreads) void rxw_sources(const int32_t *__restrict__ win, const uint8_t *__restrict__ stage_er, int n, int W,
+                                                       int head, int closes, uint32_t *__restrict__ src, uint8_t *__restrict__ er)
+{
+    const int64_t total = (int64_t)closes * n;
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < total; r += (int64_t)gridDim.x * kThreads) {
+        const int s = (int)(r / n);
+        const int i = (int)(r - (int64_t)s * n);
+        const int w = win[r];
+        const int row = ((head + s) % W) * n + i;   // W * n < 2^31 - 2 (create)
+        uint32_t word = kRowErased;
+        if (w >= 0) word = (uint32_t)w;
+        else if (s < W && stage_er[row] == 0) word = kRowStaged | (uint32_t)row;
+        src[r] = word;
+        er[r] = word == kRowErased ? 1 : 0;
+    }
+}
+
+// ---- flush: slots first .. first + count - 1 of the window lie complete in their planes.  Grid (x, count): plane -> dense slot, and the
+// plane back to symbols 0 / flags 1, one work item per piece of PW bytes (16 or 1; PW divides S, so a plane has at least n pieces:
+// piece u < n also moves flag u).  Each piece and flag is read and rewritten by one work item only.
+template <int PW>
+__global__ __launch_bounds__(kThreads) void rxw_flush_move(uint8_t *__restrict__ stage_sym, uint8_t *__restrict__ stage_er, int n, int S, int W,
+                                                          int head, int first, uint8_t *__restrict__ sym_out, uint8_t *__restrict__ er_out)
+{
+    const int64_t upp = (int64_t)n * S / PW;   // pieces of a plane
+    const int64_t s = blockIdx.y, plane = (head + first + s) % W;
+    uint8_t *from = stage_sym + plane * upp * PW;
+    uint8_t *to = sym_out + s * upp * PW;
+    for (int64_t u = (int64_t)blockIdx.x * kThreads + threadIdx.x; u < upp; u += (int64_t)gridDim.x * kThreads) {
+        if (PW == 16) {
+            reinterpret_cast<uint4 *>(to)[u] = reinterpret_cast<const uint4 *>(from)[u];
+            reinterpret_cast<uint4 *>(from)[u] = make_uint4(0, 0, 0, 0);
+        } else {
+            to[u] = from[u];
+            from[u] = 0;
+        }
+        if (u < n) {
+            er_out[s * n + u] = stage_er[plane * n + u];
+            stage_er[plane * n + u] = 1;
+        }
+    }
+}
+
+// A pointer of this context's device (hipMalloc / torch), not host memory.
+bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error, it is not one of ours
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice && at.device == ctx->device;
+}
+
+}  // namespace
+
+struct ldpc_amd_fec_rxw_dev {
+    ldpc_amd_ctx *ctx = nullptr;
+    int n = 0, k = 0, S = 0, W = 0, A = 0, kd = 0, km = 0;
+    // host mirror of the receiver's state (csrc/rx_window.cpp); head: staging plane of slot 0
+    int base = -1, head = 0, ahead = 0;
+    int cnt[kMaxW] = {0};
+    int64_t totals[5] = {0, 0, 0, 0, 0};
+    uint8_t *stage_sym = nullptr;   // [W][n][S]
+    uint8_t *stage_er = nullptr;    // [W][n]
+    Scratch dense, dest, win, res;  // per-call scratch, grown on demand
+    int32_t *res_host = nullptr;    // pinned copy of res
+    size_t res_host_cap = 0;
+};
+
+namespace {
+
+// One call's PLAN: (a) + (b) and the read-back.  Nothing of the receiver's state changes before rxw_commit.
+struct RxwPlan {
+    int closes = 0;
+    int64_t used = 0;
+    const int32_t *h = nullptr;   // the scan's result record (pinned)
+};
+
+inline int64_t word64(const int32_t *h, int lo) { return (int64_t)(((uint64_t)(uint32_t)h[lo + 1] << 32) | (uint32_t)h[lo]); }
+
+int rxw_plan(ldpc_amd_fec_rxw_dev *rx, const char *who, const uint8_t *packets, int64_t npackets, int max_blocks, RxwPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n;
+    const int64_t plen = (int64_t)rx->S + kHdr;
+    const size_t res_bytes = sizeof(int32_t) * ((size_t)R_WORDS + (size_t)max_blocks);
+    int rc;
+    if ((rc = scratch_reserve(ctx, rx->dense, sizeof(uint32_t) * (size_t)npackets)) ||
+        (rc = scratch_reserve(ctx, rx->dest, sizeof(int32_t) * (size_t)npackets)) ||
+        (rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)max_blocks + (size_t)rx->W) * (size_t)n)) ||
+        (rc = scratch_reserve(ctx, rx->res, res_bytes)))
+        return rc;
+    if (rx->res_host_cap < res_bytes) {
+        if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every plan ends with a synchronisation
+        rx->res_host = nullptr;
+        rx->res_host_cap = 0;
+        LDPC_HIP_TRY(ctx, hipHostMalloc((void **)&rx->res_host, res_bytes, hipHostMallocDefault));
+        rx->res_host_cap = res_bytes;
+    }
+    uint32_t *dense = (uint32_t *)rx->dense.p;
+    int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
+    if (plen % 4 == 0 && ((uintptr_t)packets & 3) == 0)
+        hipLaunchKernelGGL(rxw_headers<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
+    else
+        hipLaunchKernelGGL(rxw_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    RxwRule r{n, rx->kd, rx->km, rx->W, rx->A};
+    RxwState st{};
+    st.base = rx->base; st.ahead = rx->ahead;
+    for (int j = 0; j < rx->W; j++) st.cnt[j] = rx->cnt[j];
+    hipLaunchKernelGGL(rxw_scan, dim3(1), dim3(64), 0, ctx->stream, dense, npackets, r, max_blocks, st, dest, res);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->res_host, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = check_device_error(ctx))) return rc;
+    const int32_t *h = rx->res_host;
+    if (h[R_ERR])
+        return set_error(ctx, LDPC_AMD_EHIP, "%s: the plan scan hit its iteration cap (internal error); the receiver's state is unchanged", who);
+    pl.h = h;
+    pl.closes = h[R_CLOSES];
+    pl.used = word64(h, R_CONSUMED_LO);
+    return LDPC_AMD_OK;
+}
+
+// (c): the winners' table of the call, [(closes + W)][n]
+int rxw_winners_launch(ldpc_amd_fec_rxw_dev *rx, const RxwPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    int32_t *win = (int32_t *)rx->win.p;
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(win, 0xff, sizeof(int32_t) * ((size_t)pl.closes + (size_t)rx->W) * (size_t)rx->n, ctx->stream));   // -1: no packet
+    hipLaunchKernelGGL(rxw_winners, dim3(grid_for(pl.used)), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p,
+                       (const int32_t *)rx->dest.p, pl.used, rx->n, win);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// (d) for the closed slots first .. first + count - 1 (gather) or (e) for the W open blocks
+template <bool GATHER>
+int rxw_move_launch(ldpc_amd_fec_rxw_dev *rx, const RxwPlan &pl, const uint8_t *packets, int first, int count, uint8_t *sym, uint8_t *er)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, S = rx->S;
+    if (GATHER && count <= 0) return LDPC_AMD_OK;
+    MoveArgs a{};
+    a.packets = packets; a.plen = (int64_t)S + kHdr; a.win = (const int32_t *)rx->win.p; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
+    a.sym_out = sym; a.er_out = er; a.n = n; a.S = S; a.W = rx->W; a.head = rx->head; a.closes = pl.closes; a.first = first; a.count = count;
+    const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0 && ((uintptr_t)sym & 15) == 0;
+    const int64_t items = (int64_t)(GATHER ? count : rx->W) * n * (v16 ? S / 16 : S);
+    if (v16) hipLaunchKernelGGL((rxw_move<GATHER, true>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((rxw_move<GATHER, false>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+void rxw_commit(ldpc_amd_fec_rxw_dev *rx, const RxwPlan &pl, int *blocks, int64_t *consumed)
+{
+    const int32_t *h = pl.h;
+    rx->base = h[R_BASE]; rx->ahead = h[R_AHEAD];
+    for (int j = 0; j < rx->W; j++) rx->cnt[j] = h[R_CNT + j];
+    rx->head = (rx->head + pl.closes) % rx->W;
+    rx->totals[LDPC_AMD_RXW_BAD_SYMBOL] += word64(h, R_BAD_LO);
+    rx->totals[LDPC_AMD_RXW_LATE] += word64(h, R_LATE_LO);
+    rx->totals[LDPC_AMD_RXW_AHEAD] += word64(h, R_AHEADTOT_LO);
+    rx->totals[LDPC_AMD_RXW_RESYNCS] += h[R_RESYNCS];
+    rx->totals[LDPC_AMD_RXW_CLOSED] += pl.closes;
+    if (blocks) memcpy(blocks, h + R_WORDS, sizeof(int) * (size_t)pl.closes);
+    if (consumed) *consumed = pl.used;
+}
+
+// The blocks a flush hands out, from the mirror: every open slot up to the last non-empty one.
+int rxw_flush_count(const ldpc_amd_fec_rxw_dev *rx)
+{
+    int count = 0;
+    for (int d = 0; d < rx->W; d++)
+        if (rx->cnt[d] > 0) count = d + 1;
+    return count;
+}
+
+// slots first .. first + count - 1 of the window -> sym / er, their planes reset: one launch
+int rxw_flush_launch(ldpc_amd_fec_rxw_dev *rx, int first, int count, uint8_t *sym, uint8_t *er)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, S = rx->S;
+    const bool v16 = S % 16 == 0 && ((uintptr_t)sym & 15) == 0;
+    const int64_t pieces = (int64_t)n * (v16 ? S / 16 : S);
+    const dim3 grid((unsigned)std::min<int64_t>((pieces + kThreads - 1) / kThreads, 65535), (unsigned)count);
+    if (v16) hipLaunchKernelGGL(rxw_flush_move<16>, grid, dim3(kThreads), 0, ctx->stream, rx->stage_sym, rx->stage_er, n, S, rx->W, rx->head, first, sym, er);
+    else hipLaunchKernelGGL(rxw_flush_move<1>, grid, dim3(kThreads), 0, ctx->stream, rx->stage_sym, rx->stage_er, n, S, rx->W, rx->head, first, sym, er);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// the mirror after a flush of `count` blocks: each a close
+void rxw_flush_commit(ldpc_amd_fec_rxw_dev *rx, int count, int *blocks)
+{
+    for (int j = 0; j < count; j++)
+        if (blocks) blocks[j] = (rx->base + j) & 0xff;
+    for (int d = 0; d < rx->W; d++) rx->cnt[d] = d + count < rx->W ? rx->cnt[d + count] : 0;
+    rx->head = (rx->head + count) % rx->W;
+    rx->base = (rx->base + count) & 0xff;
+    rx->ahead = 0;
+    rx->totals[LDPC_AMD_RXW_CLOSED] += count;
+}
+
+// the decode calls' arguments, checked before anything is planned
+int rxw_decode_check(ldpc_amd_fec_rxw_dev *rx, const char *who, int code, int max_sweeps, uint8_t *out, int32_t *sweeps, int32_t *residual,
+                     int32_t *status, uint8_t *erased_out, int32_t *residual_src)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    const DevCode &cd = ctx->codes[code]->dev;
+    if (cd.n != rx->n || cd.k != rx->k)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: the code is (%d,%d), the receiver was created for (%d,%d)", who, cd.n, cd.k, rx->n, rx->k);
+    if (!symbol_len_ok(ctx, rx->S)) return refuse_symbol_len(ctx, rx->S, "S must be 1 or a multiple of 16 (got %d)");
+    if (max_sweeps < 1) return set_error(ctx, LDPC_AMD_EINVAL, "max_sweeps must be >= 1");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const void *opt[] = {sweeps, residual, status, erased_out, residual_src};
+    bool ok = out && is_device_ptr(ctx, out);
+    for (const void *p : opt) ok = ok && (!p || is_device_ptr(ctx, p));
+    if (!ok) return set_error(ctx, LDPC_AMD_EINVAL, "%s: out and the result arrays must be device pointers of device %d", who, ctx->device);
+    return LDPC_AMD_OK;
+}
+
+struct Results {
+    uint8_t *out;
+    int32_t *sweeps, *residual, *status;
+    uint8_t *erased_out;
+    int32_t *residual_src;
+};
+
+// the result arrays of slots first .. first + count - 1
+void rxw_slots(DecodeArgs &d, const Results &o, const uint8_t *er, int n, size_t frame, int first, int count)
+{
+    d.nframes = count;
+    d.erased = er + (size_t)first * n;
+    d.out = o.out + (size_t)first * frame;
+    d.sweeps = o.sweeps ? o.sweeps + first : nullptr;
+    d.residual = o.residual ? o.residual + first : nullptr;
+    d.status = o.status ? o.status + first : nullptr;
+    d.erased_out = o.erased_out ? o.erased_out + (size_t)first * n : nullptr;
+    d.residual_src = o.residual_src ? o.residual_src + first : nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_amd_fec_rxw_dev_create(ldpc_amd_ctx *ctx, int n, int k, int S, int window, int ahead_limit, ldpc_amd_fec_rxw_dev **out)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!out || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: need n <= 65536, 0 < k < n, S >= 1 (n=%d k=%d S=%d)", n, k, S);
+    if (window < LDPC_AMD_RXW_MIN_WINDOW || window > LDPC_AMD_RXW_MAX_WINDOW || ahead_limit < 0 || ahead_limit > (1 << 30))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: need 2 <= window <= 32 and 0 <= ahead_limit <= 2^30 (window=%d ahead_limit=%d)",
+                         window, ahead_limit);
+    if ((int64_t)window * n >= (int64_t)0x7ffffffe)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: window * n = %lld staging rows, a staged-row word names fewer than 2^31 - 2",
+                         (long long)window * n);
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ldpc_amd_fec_rxw_dev *rx = new (std::nothrow) ldpc_amd_fec_rxw_dev();
+    if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rxw_dev_create: out of host memory");
+    rx->ctx = ctx;
+    rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit;
+    rx->kd = k + (int)lround((n - k) * 0.8);
+    rx->km = k + (int)lround((n - k) * 0.2);
+    const size_t planes = (size_t)window * n * S, flags = (size_t)window * n;
+    hipError_t e = hipMalloc((void **)&rx->stage_sym, planes);
+    if (e == hipSuccess) e = hipMalloc((void **)&rx->stage_er, flags);
+    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_sym, 0, planes, ctx->stream);   // payload zero, every symbol erased
+    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_er, 1, flags, ctx->stream);
+    if (e != hipSuccess) {
+        ldpc_amd_fec_rxw_dev_destroy(rx);
+        return set_error(ctx, e == hipErrorOutOfMemory ? LDPC_AMD_ENOMEM : LDPC_AMD_EHIP, "fec_rxw_dev_create: %s", hipGetErrorString(e));
+    }
+    *out = rx;
+    return LDPC_AMD_OK;
+}
+
+void ldpc_amd_fec_rxw_dev_destroy(ldpc_amd_fec_rxw_dev *rx)
+{
+    if (!rx) return;
+    (void)hipSetDevice(rx->ctx->device);
+    (void)hipStreamSynchronize(rx->ctx->stream);   // pending work of this receiver may still use its buffers
+    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res};
+    for (Scratch *s : sc)
+        if (s->p) (void)hipFree(s->p);
+    if (rx->stage_sym) (void)hipFree(rx->stage_sym);
+    if (rx->stage_er) (void)hipFree(rx->stage_er);
+    if (rx->res_host) (void)hipHostFree(rx->res_host);
+    delete rx;
+}
+
+int ldpc_amd_fec_rxw_dev_stats(const ldpc_amd_fec_rxw_dev *rx, int64_t totals[5])
+{
+    if (!rx || !totals) return LDPC_AMD_EINVAL;
+    memcpy(totals, rx->totals, sizeof(rx->totals));
+    return LDPC_AMD_OK;
+}
+
+int64_t ldpc_amd_fec_rxw_dev_dropped(const ldpc_amd_fec_rxw_dev *rx)
+{
+    return rx ? rx->totals[LDPC_AMD_RXW_BAD_SYMBOL] + rx->totals[LDPC_AMD_RXW_LATE] + rx->totals[LDPC_AMD_RXW_AHEAD] : -1;
+}
+
+int ldpc_amd_fec_rxw_dev_state(const ldpc_amd_fec_rxw_dev *rx, int *base, int *cnt, int64_t *ahead)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    if (base) *base = rx->base;
+    if (cnt) memcpy(cnt, rx->cnt, sizeof(int) * (size_t)rx->W);
+    if (ahead) *ahead = rx->ahead;
+    return LDPC_AMD_OK;
+}
+
+int ldpc_amd_fec_rxw_dev_push_many(ldpc_amd_fec_rxw_dev *rx, const uint8_t *packets, int64_t npackets, uint8_t *sym_batch,
+                                   uint8_t *erased_batch, int *blocks, int max_blocks, int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (npackets < 0 || npackets >= ((int64_t)1 << 31) || max_blocks < 1)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_push_many: need 0 <= npackets < 2^31 and max_blocks >= 1");
+    if (!sym_batch || !erased_batch || (npackets > 0 && !packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_push_many: packets / sym_batch / erased_batch must not be null");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((npackets > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_push_many: packets / sym_batch / erased_batch must be device pointers of device %d",
+                         ctx->device);
+    if (consumed) *consumed = 0;
+    if (npackets == 0) return 0;
+    int rc;
+    RxwPlan pl;
+    if ((rc = rxw_plan(rx, "fec_rxw_dev_push_many", packets, npackets, max_blocks, pl))) return rc;
+    if ((rc = rxw_winners_launch(rx, pl)) || (rc = rxw_move_launch<true>(rx, pl, packets, 0, pl.closes, sym_batch, erased_batch)) ||
+        (rc = rxw_move_launch<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)))
+        return rc;
+    rxw_commit(rx, pl, blocks, consumed);
+    return pl.closes;
+}
+
+int ldpc_amd_fec_rxw_dev_flush(ldpc_amd_fec_rxw_dev *rx, uint8_t *sym_batch, uint8_t *erased_batch, int *blocks)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int count = rxw_flush_count(rx);
+    if (count == 0) return 0;
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!sym_batch || !erased_batch || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_flush: sym_batch / erased_batch must be device pointers of device %d", ctx->device);
+    int rc;
+    if ((rc = rxw_flush_launch(rx, 0, count, sym_batch, erased_batch))) return rc;
+    rxw_flush_commit(rx, count, blocks);
+    return count;
+}
+
+// push_many + decode_frames in one call.  FUSED where the decoder can fetch its rows from the packets itself (decode_reads_packets): (d)
+// shrinks to rxw_sources and the decode follows the words, the W planes being one `stage` base.  Else COMPOSED: (d) gathers a chunk of
+// closed blocks into the context's scratch, the decoder runs on it, next chunk.  (e) is launched BEHIND the decode in both forms: it
+// overwrites the staging planes of the carried blocks, which the fused decode reads.
+int ldpc_amd_fec_rxw_dev_decode_many(ldpc_amd_fec_rxw_dev *rx, int code, const uint8_t *packets, int64_t npackets, int max_sweeps,
+                                     int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status,
+                                     uint8_t *erased_out, int32_t *residual_src, int *blocks, int max_blocks, int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    if (npackets < 0 || npackets >= ((int64_t)1 << 31) || max_blocks < 1)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_decode_many: need 0 <= npackets < 2^31 and max_blocks >= 1");
+    if (npackets == 0) {
+        if (consumed) *consumed = 0;
+        return 0;
+    }
+    int rc;
+    if ((rc = rxw_decode_check(rx, "fec_rxw_dev_decode_many", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    if (!packets || !is_device_ptr(ctx, packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_decode_many: packets must be a device pointer of device %d", ctx->device);
+    const DevCode &cd = ctx->codes[code]->dev;
+    const int n = rx->n, S = rx->S;
+    const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
+    const size_t frame = (size_t)n * S;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(max_blocks, (int64_t)(kScratchMax / frame)));
+
+    RxwPlan pl;
+    if ((rc = rxw_plan(rx, "fec_rxw_dev_decode_many", packets, npackets, max_blocks, pl))) return rc;
+    const int closes = pl.closes;
+    size_t scratch = 0;
+    // every workspace of the call before anything moves: a refusal leaves the receiver where it was
+    if (closes > 0) {
+        if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)closes * n))) return rc;
+        if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)closes * n);
+        else rc = scratch_reserve(ctx, ctx->rx_sym, scratch = (size_t)std::min<int64_t>(chunk, closes) * frame);
+        if (rc) return rc;
+    }
+    if ((rc = rxw_winners_launch(rx, pl))) return rc;
+    DecodeArgs d{};
+    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
+    const Results o{out, sweeps, residual, status, erased_out, residual_src};
+    uint8_t *er = (uint8_t *)ctx->rx_er.p;
+    int launches = 0;
+    if (closes > 0 && fused) {
+        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+        hipLaunchKernelGGL(rxw_sources, dim3(grid_for((int64_t)closes * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
+                           rx->stage_er, n, rx->W, rx->head, closes, src, er);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        rxw_slots(d, o, er, n, frame, 0, closes);
+        d.sym = nullptr;
+        d.pin.src = src; d.pin.packets = packets; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
+        if ((rc = launch_decode(ctx, d))) return rc;
+        launches = 1;
+    } else if (closes > 0) {
+        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
+        for (int first = 0; first < closes; first += (int)chunk) {
+            const int count = (int)std::min<int64_t>(chunk, closes - first);
+            if ((rc = rxw_move_launch<true>(rx, pl, packets, first, count, sym, er + (size_t)first * n))) return rc;
+            rxw_slots(d, o, er, n, frame, first, count);
+            d.sym = sym;
+            if ((rc = launch_decode(ctx, d))) return rc;
+            launches++;
+        }
+    }
+    if ((rc = rxw_move_launch<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
+    rxw_commit(rx, pl, blocks, consumed);
+    ctx->rxw_info[0] = fused ? 1 : 2; ctx->rxw_info[1] = closes; ctx->rxw_info[2] = launches; ctx->rxw_info[3] = (int64_t)scratch;
+    return closes;
+}
+
+// flush + decode, composed: the blocks lie complete in their planes, a chunk of them goes to the scratch and through the decoder
+int ldpc_amd_fec_rxw_dev_decode_flush(ldpc_amd_fec_rxw_dev *rx, int code, int max_sweeps, int do_ml, uint8_t *out, int32_t *sweeps,
+                                      int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src, int *blocks)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    int rc;
+    if ((rc = rxw_decode_check(rx, "fec_rxw_dev_decode_flush", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    const int count = rxw_flush_count(rx);
+    if (count == 0) return 0;
+    const int n = rx->n;
+    const size_t frame = (size_t)n * rx->S;
+    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(count, (int64_t)(kScratchMax / frame)));
+    const size_t scratch = (size_t)chunk * frame;
+    if ((rc = scratch_reserve(ctx, ctx->rx_sym, scratch)) || (rc = scratch_reserve(ctx, ctx->rx_er, (size_t)count * n))) return rc;
+    DecodeArgs d{};
+    d.code = ctx->codes[code]->dev; d.S = rx->S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
+    const Results o{out, sweeps, residual, status, erased_out, residual_src};
+    uint8_t *sym = (uint8_t *)ctx->rx_sym.p, *er = (uint8_t *)ctx->rx_er.p;
+    int launches = 0;
+    for (int first = 0; first < count; first += chunk) {
+        const int c = std::min(chunk, count - first);
+        if ((rc = rxw_flush_launch(rx, first, c, sym, er + (size_t)first * n))) return rc;
+        rxw_slots(d, o, er, n, frame, first, c);
+        d.sym = sym;
+        if ((rc = launch_decode(ctx, d))) return rc;
+        launches++;
+    }
+    rxw_flush_commit(rx, count, blocks);
+    ctx->rxw_info[0] = 2; ctx->rxw_info[1] = count; ctx->rxw_info[2] = launches; ctx->rxw_info[3] = (int64_t)scratch;
+    return count;
+}
+
+int ldpc_amd_fec_rxw_info(ldpc_amd_ctx *ctx, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_info: info must not be null");
+    memcpy(info, ctx->rxw_info, sizeof(ctx->rxw_info));
+    return LDPC_AMD_OK;
+}
+
+}  // extern "C"
