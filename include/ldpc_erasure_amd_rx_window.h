@@ -30,7 +30,7 @@
  * The re-anchor trusts the header of the packet that trips it: a foreign block number there mis-anchors the window until the
  * next trip (A + 1 further packets ahead of it).
  *
- * Out of scope: a window for the multi-flow receiver (ldpc_erasure_amd_flows.h) and its batch flush.
+ * Out of scope here: many flows per object and their batch flush -- ldpc_erasure_amd_rx_window_flows.h has both.
  */
 #ifndef LDPC_ERASURE_AMD_RX_WINDOW_H
 #define LDPC_ERASURE_AMD_RX_WINDOW_H

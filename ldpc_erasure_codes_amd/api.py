@@ -111,6 +111,14 @@ EXPORTS_RX_WINDOW = [
 RX_WINDOW_PATHS = ("none", "fused", "composed")
 RX_WINDOW_TOTALS = ("bad_symbol", "late", "ahead_total", "resyncs", "closed")   # LDPC_AMD_RXW_*: the order of the totals
 RX_WINDOW_MIN, RX_WINDOW_MAX = 2, 32
+# every symbol include/ldpc_erasure_amd_rx_window_flows.h declares (the windowed multi-flow receiver and its batch flush)
+EXPORTS_RX_WINDOW_FLOWS = [
+    "ldpc_amd_fec_rxw_flows_create", "ldpc_amd_fec_rxw_flows_destroy", "ldpc_amd_fec_rxw_flows_push_many",
+    "ldpc_amd_fec_rxw_flows_decode_many", "ldpc_amd_fec_rxw_flows_flush_many", "ldpc_amd_fec_rxw_flows_decode_flush_many",
+    "ldpc_amd_fec_rxw_flows_pending", "ldpc_amd_fec_rxw_flows_state", "ldpc_amd_fec_rxw_flows_stats", "ldpc_amd_fec_rxw_flows_dropped",
+    "ldpc_amd_fec_rxw_flows_info",
+]
+WindowFlowsPending = collections.namedtuple("WindowFlowsPending", "base cnt blocks")
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
@@ -309,6 +317,20 @@ def load_library():
         L.ldpc_amd_fec_rxw_dev_dropped.restype = i64
         L.ldpc_amd_fec_rxw_dev_state.argtypes = [vp, C.POINTER(i32), vp, C.POINTER(i64)]
         L.ldpc_amd_fec_rxw_info.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "ldpc_amd_fec_rxw_flows_create"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_rxw_flows_create.argtypes = [vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+        L.ldpc_amd_fec_rxw_flows_destroy.argtypes = [vp]
+        L.ldpc_amd_fec_rxw_flows_destroy.restype = None
+        L.ldpc_amd_fec_rxw_flows_push_many.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
+        L.ldpc_amd_fec_rxw_flows_decode_many.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+        L.ldpc_amd_fec_rxw_flows_flush_many.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+        L.ldpc_amd_fec_rxw_flows_decode_flush_many.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.ldpc_amd_fec_rxw_flows_pending.argtypes = [vp, vp, vp]
+        L.ldpc_amd_fec_rxw_flows_state.argtypes = [vp, i32, C.POINTER(i32), vp, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_flows_stats.argtypes = [vp, i32, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_flows_dropped.argtypes = [vp, i32]
+        L.ldpc_amd_fec_rxw_flows_dropped.restype = i64
+        L.ldpc_amd_fec_rxw_flows_info.argtypes = [vp, C.POINTER(i64)]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -964,6 +986,17 @@ class Context:
         self._check(self._L.ldpc_amd_fec_rxw_info(self._h, info), "fec_rxw_info")
         return {"path": RX_WINDOW_PATHS[info[0]], "blocks": int(info[1]), "launches": int(info[2]), "scratch_bytes": int(info[3])}
 
+    # -- ... for many flows (include/ldpc_erasure_amd_rx_window_flows.h)
+    def fec_rx_window_flows(self, nflows, n, k, S, window=4, ahead_limit=10):
+        """nflows windowed receivers that are fed, planned, decoded and flushed together (FecRxWindowFlows)."""
+        return FecRxWindowFlows(self, nflows, n, k, S, window, ahead_limit)
+
+    def fec_rx_window_flows_info(self):
+        """fec_rx_window_info() for the last FecRxWindowFlows.decode_many / decode_flush_many call."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_rxw_flows_info(self._h, info), "fec_rxw_flows_info")
+        return {"path": RX_WINDOW_PATHS[info[0]], "blocks": int(info[1]), "launches": int(info[2]), "scratch_bytes": int(info[3])}
+
     # -- the multi-flow receiver (include/ldpc_erasure_amd_flows.h)
     def fec_rx_flows(self, nflows, n, k, S):
         """nflows device receivers that are fed, planned and decoded together, one call for all of them (FecRxFlows)."""
@@ -1505,6 +1538,123 @@ class FecRxFlows:
     def close(self):
         if getattr(self, "_h", None):
             self._L.ldpc_amd_fec_rx_flows_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FecRxWindowFlows:
+    """nflows FecRxWindow in one object (include/ldpc_erasure_amd_rx_window_flows.h), shaped on FecRxFlows: one packet array segmented
+    by flow -- flow f owns the packets flow_begin[f] .. flow_begin[f+1]-1 -- is planned for all flows at once (one wavefront per flow)
+    and read back once, and every block that closed, of every flow, is decoded in one launch.  Flow f behaves exactly like a
+    FecRxWindowHost fed its segment with max_blocks = max_blocks_per_flow.  The closed blocks come out dense in flow order: flow f's
+    start at closes[:f].sum().  Close it before its Context."""
+
+    def __init__(self, ctx, nflows, n, k, S, window=4, ahead_limit=10):
+        self._ctx, self._L = ctx, ctx._L
+        h = C.c_void_p()
+        ctx._check(self._L.ldpc_amd_fec_rxw_flows_create(ctx._h, nflows, n, k, S, window, ahead_limit, C.byref(h)), "fec_rxw_flows_create")
+        self._h, self.nflows, self.n, self.k, self.S, self.window, self.ahead_limit = h, nflows, n, k, S, window, ahead_limit
+
+    _device = FecRxWindow._device
+    _frames = FecRxWindow._frames
+    _segments = FecRxFlows._segments
+
+    def push_many(self, packets, flow_begin, max_blocks_per_flow):
+        """packets: torch uint8 [P][8+S] on the device, flow_begin: nflows + 1 packet indices.  Returns (closes int32 [nflows],
+        blocks int32 [T], sym torch uint8 [T][n][S], erased torch uint8 [T][n], consumed int64 [nflows])."""
+        import torch
+        fb, slots, blocks, closes, consumed, pp = self._segments(packets, flow_begin, max_blocks_per_flow)
+        sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=packets.device)
+        er = torch.empty((slots, self.n), dtype=torch.uint8, device=packets.device)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_push_many(self._h, pp, fb.ctypes.data, _ptr(sym), _ptr(er), blocks.ctypes.data,
+                                                                      closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
+                             "fec_rxw_flows_push_many")
+        return closes, blocks[:T], sym[:T], er[:T], consumed
+
+    def decode_many(self, code, packets, flow_begin, max_blocks_per_flow, max_sweeps=10, do_ml=1):
+        """push_many + Context.decode_frames of all flows in one call -> (closes int32 [nflows], blocks int32 [T], DecodedFrames of
+        the T closed blocks, consumed int64 [nflows]).  Context.fec_rx_window_flows_info() says which form ran.  Keep `packets` alive
+        until the context's stream has passed the call."""
+        fb, slots, blocks, closes, consumed, pp = self._segments(packets, flow_begin, max_blocks_per_flow)
+        fr = self._frames(slots)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_decode_many(
+            self._h, code, pp, fb.ctypes.data, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status),
+            _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
+            "fec_rxw_flows_decode_many")
+        return closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed
+
+    def pending(self):
+        """WindowFlowsPending(base int32 [nflows] (-1: the flow has not started), cnt int32 [nflows][window]: packets every open slot
+        took so far, blocks: how many blocks a flush of all flows would hand out now).  Host only."""
+        base = np.zeros(self.nflows, dtype=np.int32)
+        cnt = np.zeros((self.nflows, self.window), dtype=np.int32)
+        total = self._L.ldpc_amd_fec_rxw_flows_pending(self._h, base.ctypes.data, cnt.ctypes.data)
+        if total < 0:
+            raise LdpcAmdError("fec_rxw_flows_pending: the object is closed")
+        return WindowFlowsPending(base, cnt, total)
+
+    def _flush_list(self, flows):
+        sel = None if flows is None else np.ascontiguousarray(flows, dtype=np.int32).reshape(-1)
+        nsel = self.nflows if sel is None else int(sel.shape[0])
+        return sel, nsel, max(nsel * self.window, 1)
+
+    def flush_many(self, flows=None):
+        """FecRxWindow.flush() of every flow of the list `flows` (None: all flows) in one call -> (closes int32 [nsel], blocks int32
+        [T], sym torch uint8 [T][n][S], erased torch uint8 [T][n]).  The blocks come out dense in list order, entry j's from
+        closes[:j].sum() on; flows that are not listed are not touched."""
+        import torch
+        sel, nsel, slots = self._flush_list(flows)
+        sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=self._device())
+        er = torch.empty((slots, self.n), dtype=torch.uint8, device=self._device())
+        blocks, closes = np.zeros(slots, dtype=np.int32), np.zeros(max(nsel, 1), dtype=np.int32)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_flush_many(self._h, None if sel is None else sel.ctypes.data, nsel, _ptr(sym), _ptr(er),
+                                                                       blocks.ctypes.data, closes.ctypes.data), "fec_rxw_flows_flush_many")
+        return closes[:nsel], blocks[:T], sym[:T], er[:T]
+
+    def decode_flush_many(self, code, flows=None, max_sweeps=10, do_ml=1):
+        """flush_many + Context.decode_frames in one call -> (closes int32 [nsel], blocks int32 [T], DecodedFrames of the T blocks);
+        decoded straight from the staging planes where the decoder can fetch its rows itself."""
+        sel, nsel, slots = self._flush_list(flows)
+        fr = self._frames(slots)
+        blocks, closes = np.zeros(slots, dtype=np.int32), np.zeros(max(nsel, 1), dtype=np.int32)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_decode_flush_many(
+            self._h, code, None if sel is None else sel.ctypes.data, nsel, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual),
+            _ptr(fr.status), _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data), "fec_rxw_flows_decode_flush_many")
+        return closes[:nsel], blocks[:T], DecodedFrames(*(t[:T] for t in fr))
+
+    def stats(self, flow):
+        """FecRxWindow.stats() of flow `flow`."""
+        t = (C.c_int64 * 5)()
+        if self._L.ldpc_amd_fec_rxw_flows_stats(self._h, flow, t) != 0:
+            raise LdpcAmdError("fec_rxw_flows_stats: bad arguments")
+        return dict(zip(RX_WINDOW_TOTALS, (int(v) for v in t)))
+
+    def state(self, flow):
+        """FecRxWindow.state() of flow `flow`."""
+        base, ahead = C.c_int(0), C.c_int64(0)
+        cnt = np.zeros(self.window, dtype=np.int32)
+        if self._L.ldpc_amd_fec_rxw_flows_state(self._h, flow, C.byref(base), cnt.ctypes.data, C.byref(ahead)) != 0:
+            raise LdpcAmdError("fec_rxw_flows_state: bad arguments")
+        return {"base": base.value, "cnt": cnt.tolist(), "ahead": ahead.value}
+
+    def dropped(self, flow):
+        """packets of flow `flow` that went to no block so far (-1: no such flow)"""
+        return int(self._L.ldpc_amd_fec_rxw_flows_dropped(self._h, flow))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ldpc_amd_fec_rxw_flows_destroy(self._h)
             self._h = None
 
     def __enter__(self):

@@ -259,6 +259,8 @@ struct ldpc_amd_ctx {
     // fec_rxw_dev_decode_many / _decode_flush (rx_window_dev.hip): path (0 none, 1 fused, 2 composed), blocks, decoder launches and
     // scratch bytes of the last call (ldpc_amd_fec_rxw_info)
     int64_t rxw_info[4] = {0, 0, 0, 0};
+    // fec_rxw_flows_decode_many / _decode_flush_many (rx_window_flows_dev.hip): the same four words (ldpc_amd_fec_rxw_flows_info)
+    int64_t rxwf_info[4] = {0, 0, 0, 0};
 };
 
 namespace ldpc_amd {

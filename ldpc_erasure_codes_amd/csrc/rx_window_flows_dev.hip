@@ -1,0 +1,876 @@
+// rx_window_flows_dev.hip -- the windowed multi-flow receiver (include/ldpc_erasure_amd_rx_window_flows.h): nflows receivers of
+// rx_window_dev.hip in one object, planned together like the flows of wire_dev.hip.  The five steps, for nflows streams whose packets
+// lie in one array, flow f's in begin[f] .. begin[f] + len[f] - 1:
+//   (a) rxwf_headers        every packet's header -> one dense u32, one pass over the whole array (flow-agnostic)          (parallel)
+//   (b) rxw_scan_flows      rxw_scan_body (rx_window_scan_dev.h) once per flow, one workgroup of one wavefront each, on the flow's
+//                           segment and state: serials, and with them `dest`, are LOCAL to the flow.  ONE copy back, ONE synchronisation.
+//   (c) rxwf_winners        atomicMax of the GLOBAL packet index into the table [(T + W nflows)][n]                        (parallel)
+//   (d) rxwf_move<1>        the T closed slots -> sym_batch / erased_batch; or rxwf_sources: WHERE the decoder finds each row
+//   (e) rxwf_move<0>        the W open blocks of every flow -> their staging planes, in a launch behind (d) and the decode
+// Tables.  The host takes the prefix sum of the closes: flow f's closed blocks are the global slots base[f] .. base[f] + closes[f] - 1,
+// T in all.  The winners' table holds the T closed slots first, then the W open blocks of flow 0, of flow 1, ...: serial s of flow f is
+// row base[f] + s for s < closes[f], else row T + W f + (s - closes[f]).  The staging planes are [nflows][W][n][S] / [nflows][W][n]:
+// serial s of flow f lives in plane f W + (head[f] + s) % W, so its row i is staging row plane * n + i of ONE base -- all a row-source
+// word of the packets-in decoder (internal.h, PacketRows) needs.  A serial below W was carried in from an earlier call.
+// Order of (e).  A new serial s >= W takes over the plane of serial s - W of the same flow, a block (d) or the fused decode may still
+// read: (e) stands behind both on the stream.  Inside (e) nothing is read from the planes: a work item writes its own piece of its
+// own plane (W distinct planes per flow) from a packet or with zero, or leaves a carried row alone.
+// Flush: planned from the host mirror alone, one int32 plane number per handed-out slot (wire_dev.hip's batch flush).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "internal.h"
+#include "../../include/ldpc_erasure_amd_rx_window.h"
+#include "../../include/ldpc_erasure_amd_rx_window_flows.h"
+#include "rx_window_scan_dev.h"
+
+using namespace ldpc_amd;
+
+namespace {
+
+constexpr int kHdr = 8;   // LDPC_AMD_FEC_HEADER_BYTES
+constexpr int kThreads = 256;
+constexpr int kMaxFlows = 4096;
+constexpr size_t kScratchMax = (size_t)256 << 20;   // composed form: received symbols of one chunk of closed blocks
+
+inline unsigned grid_for(int64_t items)
+{
+    const int64_t b = (items + kThreads - 1) / kThreads;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(b, (int64_t)1 << 20));   // grid-stride loops cover the rest
+}
+
+// ---- (a) headers: only the first 32-bit half is read, as the host's ldpc_amd_fec_header_unpack does --------------------------------
+template <bool ALIGNED4>
+__global__ __launch_bounds__(kThreads) void rxwf_headers(const uint8_t *__restrict__ packets, int64_t np, int plen, uint32_t *__restrict__ dense)
+{
+    for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < np; p += (int64_t)gridDim.x * kThreads) {
+        const uint8_t *h = packets + p * plen;
+        uint32_t w;
+        if (ALIGNED4) w = *reinterpret_cast<const uint32_t *>(h) & 0x00ffffffu;
+        else w = (uint32_t)h[0] | (uint32_t)h[1] << 8 | (uint32_t)h[2] << 16;
+        dense[p] = w;
+    }
+}
+
+struct WFlowIn {    // written by the host before the plan: the flow's segment and the state its scan starts from
+    int64_t begin, len;
+    int base, ahead;
+    int cnt[kMaxW];
+};
+struct WFlowTab {   // written by the host behind the plan
+    int64_t begin, used;   // the packets the flow consumed: begin .. begin + used - 1
+    int base, closes, head, pad;   // base: the flow's first closed slot
+};
+
+// (b) grid: nflows workgroups of one wavefront, each with its own LDS; res: [nflows][R_WORDS + max_blocks]
+__global__ __launch_bounds__(64) void rxw_scan_flows(const uint32_t *__restrict__ dense, const WFlowIn *__restrict__ in, RxwRule r, int max_blocks,
+                                                    int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    __shared__ int cnt[kMaxW];
+    __shared__ uint32_t hbuf[kScanChunk * 64];
+    const WFlowIn *f = in + blockIdx.x;
+    RxwState st;
+    st.base = f->base; st.ahead = f->ahead;
+#pragma unroll
+    for (int j = 0; j < kMaxW; j++) st.cnt[j] = f->cnt[j];
+    const int64_t begin = f->begin;
+    rxw_scan_body(dense + begin, f->len, r, max_blocks, st, cnt, hbuf, dest + begin, res + (int64_t)blockIdx.x * (R_WORDS + max_blocks));
+}
+
+// slot -> flow, [T]: one workgroup per flow
+__global__ __launch_bounds__(64) void rxwf_flow_slots(const WFlowTab *__restrict__ tab, int32_t *__restrict__ slot_flow)
+{
+    const WFlowTab f = tab[blockIdx.x];
+    for (int s = threadIdx.x; s < f.closes; s += 64) slot_flow[f.base + s] = (int)blockIdx.x;
+}
+
+// (c) grid: (x, nflows); over each flow's consumed prefix only.  The packet index is the global one: the last copy wins, as on the host.
+__global__ __launch_bounds__(kThreads) void rxwf_winners(const uint32_t *__restrict__ dense, const int32_t *__restrict__ dest,
+                                                        const WFlowTab *__restrict__ tab, int n, int W, int T, int32_t *__restrict__ win)
+{
+    const WFlowTab f = tab[blockIdx.y];
+    for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < f.used; q += (int64_t)gridDim.x * kThreads) {
+        const int64_t p = f.begin + q;
+        const int s = dest[p];
+        if (s < 0) continue;   // dest >= 0 only for symbol < n, and s < closes + W
+        const int64_t row = s < f.closes ? (int64_t)f.base + s : (int64_t)T + (int64_t)W * blockIdx.y + (s - f.closes);
+        atomicMax(&win[row * n + (dense[p] & 0xffffu)], (int32_t)p);
+    }
+}
+
+struct WFlowMoveArgs {
+    const uint8_t *packets;
+    int64_t plen;
+    const int32_t *win;         // [(T + W nflows)][n]
+    const WFlowTab *tab;        // [nflows]
+    const int32_t *slot_flow;   // [T]
+    uint8_t *stage_sym;         // [nflows][W][n][S]
+    uint8_t *stage_er;          // [nflows][W][n]
+    uint8_t *sym_out;           // gather: [count][n][S], the closed slots first .. first + count - 1
+    uint8_t *er_out;            // gather: [count][n]
+    int n, S, W, T, nflows;
+    int first, count;
+};
+
+// rxw_move for all flows.  Gather: row r is symbol i of global slot j = first + r / n, which is serial j - base[f] of flow f =
+// slot_flow[j]: the last packet that went there, else -- a carried block -- its staging row, else zero and erased.  Staging update:
+// row r is symbol i of open block o = 0 .. W-1 of flow f = r / (W n), its serial closes[f] + o: the last packet, else for a block
+// opened in this call zero and erased; a carried block keeps its staging row.
+template <bool GATHER, bool V16>
+__global__ __launch_bounds__(kThreads) void rxwf_move(WFlowMoveArgs a)
+{
+    const int q = V16 ? a.S / 16 : a.S;   // 16-byte pieces or bytes of a row
+    const int64_t rows = GATHER ? (int64_t)a.count * a.n : (int64_t)a.W * a.nflows * a.n;
+    const int64_t total = rows * q;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (int64_t)gridDim.x * kThreads) {
+        const int64_t r = t / q;
+        const int c = (int)(t - r * q);
+        const int64_t blk = r / a.n;
+        const int i = (int)(r - blk * a.n);
+        int f, s;
+        int64_t wrow;
+        if (GATHER) {
+            wrow = a.first + blk;
+            f = a.slot_flow[wrow];
+            s = (int)wrow - a.tab[f].base;
+        } else {
+            f = (int)(blk / a.W);
+            s = a.tab[f].closes + (int)(blk - (int64_t)f * a.W);
+            wrow = (int64_t)a.T + blk;
+        }
+        const int w = a.win[wrow * a.n + i];
+        const int b = (a.tab[f].head + s) % a.W;
+        const bool carried = s < a.W;
+        const int64_t erow = ((int64_t)f * a.W + b) * a.n + i;   // the block's staging row
+        const int64_t srow = erow * a.S;
+        uint8_t *dst = GATHER ? a.sym_out + r * a.S : a.stage_sym + srow;
+        if (!GATHER && w < 0 && carried) continue;
+        if (V16) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (w >= 0) {
+                const uint2 *src = reinterpret_cast<const uint2 *>(a.packets + (int64_t)w * a.plen + kHdr + (int64_t)c * 16);
+                const uint2 lo = src[0], hi = src[1];
+                v = make_uint4(lo.x, lo.y, hi.x, hi.y);
+            } else if (carried) {
+                v = *reinterpret_cast<const uint4 *>(a.stage_sym + srow + (int64_t)c * 16);
+            }
+            *reinterpret_cast<uint4 *>(dst + (int64_t)c * 16) = v;
+        } else {
+            uint8_t v = 0;
+            if (w >= 0) v = a.packets[(int64_t)w * a.plen + kHdr + c];
+            else if (carried) v = a.stage_sym[srow + c];
+            dst[c] = v;
+        }
+        if (c == 0) {
+            const uint8_t e = w >= 0 ? 0 : (carried ? a.stage_er[erow] : 1);
+            if (GATHER) a.er_out[r] = e;
+            else a.stage_er[erow] = e;
+        }
+    }
+}
+
+// (d') the fused form: the gather's rule for the rows of the T closed slots as words the packets-in decoder follows, and the flags
+__global__ __launch_bounds__(kThreads) void rxwf_sources(const int32_t *__restrict__ win, const uint8_t *__restrict__ stage_er,
+                                                        const WFlowTab *__restrict__ tab, const int32_t *__restrict__ slot_flow, int n, int W,
+                                                        int T, uint32_t *__restrict__ src, uint8_t *__restrict__ er)
+{
+    const int64_t total = (int64_t)T * n;
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < total; r += (int64_t)gridDim.x * kThreads) {
+        const int j = (int)(r / n);
+        const int i = (int)(r - (int64_t)j * n);
+        const int f = slot_flow[j];
+        const int s = j - tab[f].base;
+        const int w = win[r];
+        const int64_t row = ((int64_t)f * W + (tab[f].head + s) % W) * n + i;   // the block's staging row, < 2^31 - 2 (create)
+        uint32_t word = kRowErased;
+        if (w >= 0) word = (uint32_t)w;
+        else if (s < W && stage_er[row] == 0) word = kRowStaged | (uint32_t)row;
+        src[r] = word;
+        er[r] = word == kRowErased ? 1 : 0;
+    }
+}
+
+// ---- flush: every handed-out block lies complete in ONE plane; desc[j] = the plane f W + b of slot j, written by the host -----------
+// Row-source words and flags of the T slots for the packets-in decoder: staged (row desc[j] * n + i of the planes' one base) or erased.
+__global__ __launch_bounds__(kThreads) void rxwf_flush_sources(const int32_t *__restrict__ desc, const uint8_t *__restrict__ stage_er, int n, int T,
+                                                              uint32_t *__restrict__ src, uint8_t *__restrict__ er)
+{
+    const int64_t total = (int64_t)T * n;
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < total; r += (int64_t)gridDim.x * kThreads) {
+        const int j = (int)(r / n);
+        const int i = (int)(r - (int64_t)j * n);
+        const int64_t row = (int64_t)desc[j] * n + i;
+        const uint8_t e = stage_er[row];
+        src[r] = e ? kRowErased : (kRowStaged | (uint32_t)row);
+        er[r] = e;
+    }
+}
+
+// Slots first .. first + count - 1, grid (x, slots): COPY: plane -> dense slot; and the plane back to symbols 0 / flags 1 in the same
+// work item that read it.  One work item per piece of PW bytes (16 or 1; PW divides S, so a plane has at least n pieces: piece u < n
+// also moves flag u).  Each piece and flag is read and rewritten by one work item only; a plane belongs to one slot (no flow twice).
+template <int PW, bool COPY>
+__global__ __launch_bounds__(kThreads) void rxwf_flush_move(const int32_t *__restrict__ desc, uint8_t *__restrict__ stage_sym,
+                                                           uint8_t *__restrict__ stage_er, int n, int S, int first, int count,
+                                                           uint8_t *__restrict__ sym_out, uint8_t *__restrict__ er_out)
+{
+    const int64_t upp = (int64_t)n * S / PW;   // pieces of a plane
+    for (int64_t s = blockIdx.y; s < count; s += gridDim.y) {
+        const int64_t plane = desc[first + s];
+        uint8_t *from = stage_sym + plane * upp * PW;
+        uint8_t *to = COPY ? sym_out + s * upp * PW : nullptr;
+        for (int64_t u = (int64_t)blockIdx.x * kThreads + threadIdx.x; u < upp; u += (int64_t)gridDim.x * kThreads) {
+            if (PW == 16) {
+                if (COPY) reinterpret_cast<uint4 *>(to)[u] = reinterpret_cast<const uint4 *>(from)[u];
+                reinterpret_cast<uint4 *>(from)[u] = make_uint4(0, 0, 0, 0);
+            } else {
+                if (COPY) to[u] = from[u];
+                from[u] = 0;
+            }
+            if (u < n) {
+                if (COPY) er_out[s * n + u] = stage_er[plane * n + u];
+                stage_er[plane * n + u] = 1;
+            }
+        }
+    }
+}
+
+// A pointer of this context's device (hipMalloc / torch), not host memory.
+bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error, it is not one of ours
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice && at.device == ctx->device;
+}
+
+}  // namespace
+
+struct ldpc_amd_fec_rxw_flows {
+    ldpc_amd_ctx *ctx = nullptr;
+    int nflows = 0, n = 0, k = 0, S = 0, W = 0, A = 0, kd = 0, km = 0;
+    // host mirror of every flow's state, as in ldpc_amd_fec_rxw_dev; head: staging plane (of the flow's W) of slot 0
+    std::vector<int> base, head, ahead;
+    std::vector<int> cnt;           // [nflows][W]
+    std::vector<int64_t> totals;    // [nflows][5]
+    uint8_t *stage_sym = nullptr;   // [nflows][W][n][S]
+    uint8_t *stage_er = nullptr;    // [nflows][W][n]
+    Scratch dense, dest, win, res, slots;   // per-call scratch, grown on demand
+    WFlowIn *in_dev = nullptr, *in_host = nullptr;      // [nflows]; the host copies are pinned
+    WFlowTab *tab_dev = nullptr, *tab_host = nullptr;   // [nflows]
+    int32_t *res_host = nullptr;    // pinned copy of res
+    size_t res_host_cap = 0;
+    // the flush (allocated by its first call): the handed-out slots' planes on the device, [W nflows], and their pinned staging -- two
+    // slots used in turn, each with the event of its last copy, so that a slot is never rewritten under a copy in flight
+    int32_t *fl_dev = nullptr;
+    int32_t *fl_host[2] = {nullptr, nullptr};
+    hipEvent_t fl_event[2] = {nullptr, nullptr};
+    bool fl_pending[2] = {false, false};
+    unsigned fl_calls = 0;
+};
+
+namespace {
+
+typedef ldpc_amd_fec_rxw_flows Rx;
+
+// One call's PLAN for all flows: (a) + (b), ONE read-back, the slot bases.  Nothing of any flow's state changes before rxwf_commit.
+struct WFlowsPlan {
+    int T = 0;             // closed blocks of all flows
+    int64_t max_used = 0;  // the longest consumed prefix
+    size_t rec = 0;        // words of one flow's result record
+};
+
+inline int64_t word64(const int32_t *h, int lo) { return (int64_t)(((uint64_t)(uint32_t)h[lo + 1] << 32) | (uint32_t)h[lo]); }
+
+int rxwf_check_call(Rx *rx, const char *who, const int64_t *flow_begin, int max_blocks, int64_t &P)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (!flow_begin || flow_begin[0] != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin must not be null and must start at 0", who);
+    for (int f = 0; f < rx->nflows; f++)
+        if (flow_begin[f + 1] < flow_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin decreases at flow %d", who, f);
+    P = flow_begin[rx->nflows];
+    if (P >= ((int64_t)1 << 31)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need fewer than 2^31 packets in all", who);
+    if (max_blocks < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need max_blocks_per_flow >= 1", who);
+    if ((int64_t)rx->nflows * max_blocks * rx->n >= ((int64_t)1 << 31) - 2)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows * max_blocks_per_flow * n must be below 2^31 - 2", who);
+    return LDPC_AMD_OK;
+}
+
+void rxwf_nothing(const Rx *rx, int *closes, int64_t *consumed)
+{
+    if (closes) std::fill(closes, closes + rx->nflows, 0);
+    if (consumed) std::fill(consumed, consumed + rx->nflows, (int64_t)0);
+}
+
+int rxwf_plan(Rx *rx, const char *who, const uint8_t *packets, const int64_t *flow_begin, int64_t npackets, int max_blocks, WFlowsPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, nf = rx->nflows, W = rx->W;
+    const int64_t plen = (int64_t)rx->S + kHdr;
+    pl.rec = (size_t)R_WORDS + (size_t)max_blocks;
+    const size_t res_bytes = sizeof(int32_t) * pl.rec * (size_t)nf;
+    int rc;
+    if ((rc = scratch_reserve(ctx, rx->dense, sizeof(uint32_t) * (size_t)npackets)) ||
+        (rc = scratch_reserve(ctx, rx->dest, sizeof(int32_t) * (size_t)npackets)) || (rc = scratch_reserve(ctx, rx->res, res_bytes)))
+        return rc;
+    if (rx->res_host_cap < res_bytes) {
+        if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every plan ends with a synchronisation
+        rx->res_host = nullptr;
+        rx->res_host_cap = 0;
+        LDPC_HIP_TRY(ctx, hipHostMalloc((void **)&rx->res_host, res_bytes, hipHostMallocDefault));
+        rx->res_host_cap = res_bytes;
+    }
+    uint32_t *dense = (uint32_t *)rx->dense.p;
+    int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
+    for (int f = 0; f < nf; f++) {   // (the copy of the previous call's records is behind that call's synchronisation)
+        WFlowIn &in = rx->in_host[f];
+        in.begin = flow_begin[f]; in.len = flow_begin[f + 1] - flow_begin[f];
+        in.base = rx->base[f]; in.ahead = rx->ahead[f];
+        for (int j = 0; j < kMaxW; j++) in.cnt[j] = j < W ? rx->cnt[(size_t)f * W + j] : 0;
+    }
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->in_dev, rx->in_host, sizeof(WFlowIn) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
+    if (plen % 4 == 0 && ((uintptr_t)packets & 3) == 0)
+        hipLaunchKernelGGL(rxwf_headers<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
+    else
+        hipLaunchKernelGGL(rxwf_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    RxwRule r{n, rx->kd, rx->km, W, rx->A};
+    hipLaunchKernelGGL(rxw_scan_flows, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, r, max_blocks, dest, res);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->res_host, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = check_device_error(ctx))) return rc;
+    int64_t base = 0;
+    for (int f = 0; f < nf; f++) {   // the tables of the kernels behind the plan (their copy of the previous call is behind this synchronisation)
+        const int32_t *h = rx->res_host + (size_t)f * pl.rec;
+        if (h[R_ERR])
+            return set_error(ctx, LDPC_AMD_EHIP, "%s: the plan scan of flow %d hit its iteration cap (internal error); every flow's state is unchanged",
+                             who, f);
+        const int64_t used = word64(h, R_CONSUMED_LO);
+        rx->tab_host[f] = WFlowTab{flow_begin[f], used, (int)base, h[R_CLOSES], rx->head[f], 0};
+        base += h[R_CLOSES];
+        pl.max_used = std::max(pl.max_used, used);
+    }
+    pl.T = (int)base;   // <= nflows * max_blocks < 2^31
+    if ((rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)pl.T + (size_t)W * (size_t)nf) * (size_t)n)) ||
+        (rc = scratch_reserve(ctx, rx->slots, sizeof(int32_t) * (size_t)std::max(pl.T, 1))))
+        return rc;
+    return LDPC_AMD_OK;
+}
+
+// the flow table, the slot map and (c): the winners' table of the call, [(T + W nflows)][n]
+int rxwf_winners_launch(Rx *rx, const WFlowsPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int nf = rx->nflows;
+    int32_t *win = (int32_t *)rx->win.p;
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->tab_dev, rx->tab_host, sizeof(WFlowTab) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
+    if (pl.T > 0) {
+        hipLaunchKernelGGL(rxwf_flow_slots, dim3(nf), dim3(64), 0, ctx->stream, (const WFlowTab *)rx->tab_dev, (int32_t *)rx->slots.p);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+    }
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(win, 0xff, sizeof(int32_t) * ((size_t)pl.T + (size_t)rx->W * (size_t)nf) * (size_t)rx->n, ctx->stream));   // -1: no packet
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pl.max_used + kThreads - 1) / kThreads, std::max(1, 32768 / nf)));
+    hipLaunchKernelGGL(rxwf_winners, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p, (const int32_t *)rx->dest.p,
+                       (const WFlowTab *)rx->tab_dev, rx->n, rx->W, pl.T, win);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// (d) for the closed slots first .. first + count - 1 (gather) or (e) for the W open blocks of every flow
+template <bool GATHER>
+int rxwf_move_launch(Rx *rx, const WFlowsPlan &pl, const uint8_t *packets, int first, int count, uint8_t *sym, uint8_t *er)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, S = rx->S;
+    if (GATHER && count <= 0) return LDPC_AMD_OK;
+    WFlowMoveArgs a{};
+    a.packets = packets; a.plen = (int64_t)S + kHdr; a.win = (const int32_t *)rx->win.p; a.tab = rx->tab_dev;
+    a.slot_flow = (const int32_t *)rx->slots.p; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
+    a.sym_out = sym; a.er_out = er; a.n = n; a.S = S; a.W = rx->W; a.T = pl.T; a.nflows = rx->nflows; a.first = first; a.count = count;
+    const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0 && ((uintptr_t)sym & 15) == 0;
+    const int64_t items = (GATHER ? (int64_t)count : (int64_t)rx->W * rx->nflows) * n * (v16 ? S / 16 : S);
+    if (v16) hipLaunchKernelGGL((rxwf_move<GATHER, true>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((rxwf_move<GATHER, false>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// every flow's mirror (base, head, ahead, cnt, totals) and the host outputs: the last step of a call
+void rxwf_commit(Rx *rx, const WFlowsPlan &pl, int *blocks, int *closes, int64_t *consumed)
+{
+    const int W = rx->W;
+    for (int f = 0; f < rx->nflows; f++) {
+        const int32_t *h = rx->res_host + (size_t)f * pl.rec;
+        const WFlowTab &t = rx->tab_host[f];
+        rx->base[f] = h[R_BASE]; rx->ahead[f] = h[R_AHEAD];
+        for (int j = 0; j < W; j++) rx->cnt[(size_t)f * W + j] = h[R_CNT + j];
+        rx->head[f] = (rx->head[f] + t.closes) % W;
+        int64_t *tot = &rx->totals[(size_t)f * 5];
+        tot[LDPC_AMD_RXW_BAD_SYMBOL] += word64(h, R_BAD_LO);
+        tot[LDPC_AMD_RXW_LATE] += word64(h, R_LATE_LO);
+        tot[LDPC_AMD_RXW_AHEAD] += word64(h, R_AHEADTOT_LO);
+        tot[LDPC_AMD_RXW_RESYNCS] += h[R_RESYNCS];
+        tot[LDPC_AMD_RXW_CLOSED] += t.closes;
+        if (blocks) memcpy(blocks + t.base, h + R_WORDS, sizeof(int) * (size_t)t.closes);
+        if (closes) closes[f] = t.closes;
+        if (consumed) consumed[f] = t.used;
+    }
+}
+
+// the decode calls' arguments, checked before anything is planned
+int rxwf_decode_check(Rx *rx, const char *who, int code, int max_sweeps, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status,
+                      uint8_t *erased_out, int32_t *residual_src)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    const DevCode &cd = ctx->codes[code]->dev;
+    if (cd.n != rx->n || cd.k != rx->k)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: the code is (%d,%d), the receiver was created for (%d,%d)", who, cd.n, cd.k, rx->n, rx->k);
+    if (!symbol_len_ok(ctx, rx->S)) return refuse_symbol_len(ctx, rx->S, "S must be 1 or a multiple of 16 (got %d)");
+    if (max_sweeps < 1) return set_error(ctx, LDPC_AMD_EINVAL, "max_sweeps must be >= 1");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const void *opt[] = {sweeps, residual, status, erased_out, residual_src};
+    bool ok = out && is_device_ptr(ctx, out);
+    for (const void *p : opt) ok = ok && (!p || is_device_ptr(ctx, p));
+    if (!ok) return set_error(ctx, LDPC_AMD_EINVAL, "%s: out and the result arrays must be device pointers of device %d", who, ctx->device);
+    return LDPC_AMD_OK;
+}
+
+struct Results {
+    uint8_t *out;
+    int32_t *sweeps, *residual, *status;
+    uint8_t *erased_out;
+    int32_t *residual_src;
+};
+
+// the result arrays of slots first .. first + count - 1
+void rxwf_slots(DecodeArgs &d, const Results &o, const uint8_t *er, int n, size_t frame, int first, int count)
+{
+    d.nframes = count;
+    d.erased = er + (size_t)first * n;
+    d.out = o.out + (size_t)first * frame;
+    d.sweeps = o.sweeps ? o.sweeps + first : nullptr;
+    d.residual = o.residual ? o.residual + first : nullptr;
+    d.status = o.status ? o.status + first : nullptr;
+    d.erased_out = o.erased_out ? o.erased_out + (size_t)first * n : nullptr;
+    d.residual_src = o.residual_src ? o.residual_src + first : nullptr;
+}
+
+// ---- the flush's plan: the host's, from the mirror (ldpc_amd_fec_rxw_dev_flush per listed flow) -------------------------------------
+struct WFlushPlan {
+    std::vector<int> sel;          // the listed flows, in list order
+    std::vector<int> closes;       // blocks handed out per list entry
+    std::vector<int> blocks;       // [T] their wire numbers, in slot order
+    std::vector<int32_t> planes;   // [T] their staging planes, f W + b
+    int T = 0;
+};
+
+// The blocks a flush of flow f hands out: every open slot up to the last non-empty one.
+int rxwf_flush_count(const Rx *rx, int f)
+{
+    int count = 0;
+    for (int d = 0; d < rx->W; d++)
+        if (rx->cnt[(size_t)f * rx->W + d] > 0) count = d + 1;
+    return count;
+}
+
+int rxwf_flush_plan(const Rx *rx, const char *who, const int32_t *flows, int nsel, WFlushPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (flows) {
+        if (nsel < 0 || nsel > rx->nflows) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need 0 <= nsel <= nflows = %d (got %d)", who, rx->nflows, nsel);
+        std::vector<uint8_t> seen((size_t)rx->nflows, 0);
+        for (int j = 0; j < nsel; j++) {
+            const int f = flows[j];
+            if (f < 0 || f >= rx->nflows) return set_error(ctx, LDPC_AMD_EINVAL, "%s: no flow %d (nflows = %d)", who, f, rx->nflows);
+            if (seen[(size_t)f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow %d is given twice", who, f);
+            seen[(size_t)f] = 1;
+        }
+    } else {
+        nsel = rx->nflows;
+    }
+    pl.sel.resize((size_t)nsel);
+    pl.closes.resize((size_t)nsel);
+    for (int j = 0; j < nsel; j++) {
+        const int f = flows ? flows[j] : j;
+        const int count = rxwf_flush_count(rx, f);
+        pl.sel[(size_t)j] = f;
+        pl.closes[(size_t)j] = count;
+        for (int c = 0; c < count; c++) {
+            pl.blocks.push_back((rx->base[f] + c) & 0xff);
+            pl.planes.push_back(f * rx->W + (rx->head[f] + c) % rx->W);
+        }
+    }
+    pl.T = (int)pl.planes.size();   // <= W nflows
+    return LDPC_AMD_OK;
+}
+
+// the object's descriptor buffers (first call), then the planes of the T slots to the device through the pinned slot of this call
+int rxwf_flush_upload(Rx *rx, const char *who, const WFlushPlan &pl)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const size_t cap = sizeof(int32_t) * (size_t)rx->W * (size_t)rx->nflows;
+    if (!rx->fl_dev) {
+        hipError_t e = hipMalloc((void **)&rx->fl_dev, cap);
+        for (int s = 0; s < 2 && e == hipSuccess; s++) {
+            if (!rx->fl_host[s]) e = hipHostMalloc((void **)&rx->fl_host[s], cap, hipHostMallocDefault);
+            if (e == hipSuccess && !rx->fl_event[s]) e = hipEventCreateWithFlags(&rx->fl_event[s], hipEventDisableTiming);
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (rx->fl_dev) (void)hipFree(rx->fl_dev);
+            rx->fl_dev = nullptr;   // (what the slots got is kept: the next call asks for the rest)
+            return set_error(ctx, LDPC_AMD_ENOMEM, "%s: no memory for the slot descriptors: %s", who, hipGetErrorString(e));
+        }
+    }
+    const int slot = (int)(rx->fl_calls & 1u);
+    if (rx->fl_pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
+        LDPC_HIP_TRY(ctx, hipEventSynchronize(rx->fl_event[slot]));
+        rx->fl_pending[slot] = false;
+    }
+    memcpy(rx->fl_host[slot], pl.planes.data(), sizeof(int32_t) * (size_t)pl.T);
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->fl_dev, rx->fl_host[slot], sizeof(int32_t) * (size_t)pl.T, hipMemcpyHostToDevice, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipEventRecord(rx->fl_event[slot], ctx->stream));
+    rx->fl_pending[slot] = true;
+    rx->fl_calls++;
+    return LDPC_AMD_OK;
+}
+
+// COPY: slots first .. first + count - 1 -> sym / er, their planes reset in the same launch; else: the planes of those slots reset
+template <bool COPY>
+int rxwf_flush_launch(Rx *rx, int first, int count, uint8_t *sym, uint8_t *er)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const int n = rx->n, S = rx->S;
+    const bool v16 = S % 16 == 0 && ((uintptr_t)sym & 15) == 0;
+    const int64_t pieces = (int64_t)n * (v16 ? S / 16 : S);
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((pieces + kThreads - 1) / kThreads, 256)), (unsigned)std::min(count, 16384));
+    if (v16) hipLaunchKernelGGL((rxwf_flush_move<16, COPY>), grid, dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, count, sym, er);
+    else hipLaunchKernelGGL((rxwf_flush_move<1, COPY>), grid, dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, count, sym, er);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// the mirror of every listed flow after its flush -- each handed-out block a close -- and the host outputs
+void rxwf_flush_commit(Rx *rx, const WFlushPlan &pl, int *blocks, int *closes)
+{
+    const int W = rx->W;
+    for (size_t j = 0; j < pl.sel.size(); j++) {
+        const int f = pl.sel[j], count = pl.closes[j];
+        if (closes) closes[j] = count;
+        if (count == 0) continue;
+        int *cnt = &rx->cnt[(size_t)f * W];
+        for (int d = 0; d < W; d++) cnt[d] = d + count < W ? cnt[d + count] : 0;
+        rx->head[f] = (rx->head[f] + count) % W;
+        rx->base[f] = (rx->base[f] + count) & 0xff;
+        rx->ahead[f] = 0;
+        rx->totals[(size_t)f * 5 + LDPC_AMD_RXW_CLOSED] += count;
+    }
+    if (blocks && pl.T > 0) memcpy(blocks, pl.blocks.data(), sizeof(int) * (size_t)pl.T);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_amd_fec_rxw_flows_create(ldpc_amd_ctx *ctx, int nflows, int n, int k, int S, int window, int ahead_limit, ldpc_amd_fec_rxw_flows **out)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!out || nflows < 1 || nflows > kMaxFlows || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: need 1 <= nflows <= 4096, n <= 65536, 0 < k < n, S >= 1 (nflows=%d n=%d k=%d S=%d)",
+                         nflows, n, k, S);
+    if (window < LDPC_AMD_RXW_MIN_WINDOW || window > LDPC_AMD_RXW_MAX_WINDOW || ahead_limit < 0 || ahead_limit > (1 << 30))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: need 2 <= window <= 32 and 0 <= ahead_limit <= 2^30 (window=%d ahead_limit=%d)",
+                         window, ahead_limit);
+    if ((int64_t)nflows * window * n >= (int64_t)0x7ffffffe)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: nflows * window * n = %lld staging rows, a staged-row word names fewer than 2^31 - 2",
+                         (long long)nflows * window * n);
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Rx *rx = new (std::nothrow) Rx();
+    if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rxw_flows_create: out of host memory");
+    rx->ctx = ctx;
+    rx->nflows = nflows; rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit;
+    rx->kd = k + (int)lround((n - k) * 0.8);
+    rx->km = k + (int)lround((n - k) * 0.2);
+    rx->base.assign((size_t)nflows, -1); rx->head.assign((size_t)nflows, 0); rx->ahead.assign((size_t)nflows, 0);
+    rx->cnt.assign((size_t)nflows * window, 0);
+    rx->totals.assign((size_t)nflows * 5, 0);
+    const size_t planes = (size_t)nflows * window, plane = (size_t)n * S;
+    // (a request beyond the device's memory is not always answered with hipErrorOutOfMemory: a staging plane that cannot be had is ENOMEM)
+    hipError_t e = hipMalloc((void **)&rx->stage_sym, planes * plane);
+    if (e == hipSuccess) e = hipMalloc((void **)&rx->stage_er, planes * (size_t)n);
+    const bool no_planes = e != hipSuccess;
+    if (e == hipSuccess) e = hipMalloc((void **)&rx->in_dev, sizeof(WFlowIn) * (size_t)nflows);
+    if (e == hipSuccess) e = hipMalloc((void **)&rx->tab_dev, sizeof(WFlowTab) * (size_t)nflows);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&rx->in_host, sizeof(WFlowIn) * (size_t)nflows, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&rx->tab_host, sizeof(WFlowTab) * (size_t)nflows, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_sym, 0, planes * plane, ctx->stream);   // payload zero, every symbol erased
+    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_er, 1, planes * (size_t)n, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ldpc_amd_fec_rxw_flows_destroy(rx);
+        return set_error(ctx, no_planes || e == hipErrorOutOfMemory ? LDPC_AMD_ENOMEM : LDPC_AMD_EHIP, "fec_rxw_flows_create: %s%s",
+                         no_planes ? "the staging planes do not fit: " : "", hipGetErrorString(e));
+    }
+    *out = rx;
+    return LDPC_AMD_OK;
+}
+
+void ldpc_amd_fec_rxw_flows_destroy(ldpc_amd_fec_rxw_flows *rx)
+{
+    if (!rx) return;
+    (void)hipSetDevice(rx->ctx->device);
+    (void)hipStreamSynchronize(rx->ctx->stream);   // pending work of this object may still use its buffers
+    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots};
+    for (Scratch *s : sc)
+        if (s->p) (void)hipFree(s->p);
+    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev, rx->fl_dev};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    void *host[] = {rx->in_host, rx->tab_host, rx->res_host, rx->fl_host[0], rx->fl_host[1]};
+    for (void *p : host)
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : rx->fl_event)
+        if (e) (void)hipEventDestroy(e);
+    delete rx;
+}
+
+int ldpc_amd_fec_rxw_flows_stats(const ldpc_amd_fec_rxw_flows *rx, int flow, int64_t totals[5])
+{
+    if (!rx || !totals || flow < 0 || flow >= rx->nflows) return LDPC_AMD_EINVAL;
+    memcpy(totals, &rx->totals[(size_t)flow * 5], sizeof(int64_t) * 5);
+    return LDPC_AMD_OK;
+}
+
+int64_t ldpc_amd_fec_rxw_flows_dropped(const ldpc_amd_fec_rxw_flows *rx, int flow)
+{
+    if (!rx || flow < 0 || flow >= rx->nflows) return -1;
+    const int64_t *t = &rx->totals[(size_t)flow * 5];
+    return t[LDPC_AMD_RXW_BAD_SYMBOL] + t[LDPC_AMD_RXW_LATE] + t[LDPC_AMD_RXW_AHEAD];
+}
+
+int ldpc_amd_fec_rxw_flows_state(const ldpc_amd_fec_rxw_flows *rx, int flow, int *base, int *cnt, int64_t *ahead)
+{
+    if (!rx || flow < 0 || flow >= rx->nflows) return LDPC_AMD_EINVAL;
+    if (base) *base = rx->base[flow];
+    if (cnt) memcpy(cnt, &rx->cnt[(size_t)flow * rx->W], sizeof(int) * (size_t)rx->W);
+    if (ahead) *ahead = rx->ahead[flow];
+    return LDPC_AMD_OK;
+}
+
+int ldpc_amd_fec_rxw_flows_pending(const ldpc_amd_fec_rxw_flows *rx, int32_t *base, int32_t *cnt)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    int total = 0;
+    for (int f = 0; f < rx->nflows; f++) {
+        if (base) base[f] = rx->base[f];
+        total += rxwf_flush_count(rx, f);
+    }
+    if (cnt) memcpy(cnt, rx->cnt.data(), sizeof(int32_t) * rx->cnt.size());
+    return total;
+}
+
+int ldpc_amd_fec_rxw_flows_push_many(ldpc_amd_fec_rxw_flows *rx, const uint8_t *packets, const int64_t *flow_begin, uint8_t *sym_batch,
+                                     uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const char *who = "fec_rxw_flows_push_many";
+    int rc;
+    int64_t P = 0;
+    if ((rc = rxwf_check_call(rx, who, flow_begin, max_blocks_per_flow, P))) return rc;
+    if (!sym_batch || !erased_batch || (P > 0 && !packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must not be null", who);
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((P > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must be device pointers of device %d", who, ctx->device);
+    if (P == 0) {
+        rxwf_nothing(rx, closes, consumed);
+        return 0;
+    }
+    WFlowsPlan pl;
+    if ((rc = rxwf_plan(rx, who, packets, flow_begin, P, max_blocks_per_flow, pl))) return rc;
+    // (c), (d), (e): the data movement, asynchronous
+    if ((rc = rxwf_winners_launch(rx, pl)) || (rc = rxwf_move_launch<true>(rx, pl, packets, 0, pl.T, sym_batch, erased_batch)) ||
+        (rc = rxwf_move_launch<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)))
+        return rc;
+    rxwf_commit(rx, pl, blocks, closes, consumed);
+    return pl.T;
+}
+
+// push_many + decode_frames in one call.  FUSED where the decoder can fetch its rows from the packets itself (decode_reads_packets): (d)
+// shrinks to rxwf_sources and ONE launch_decode follows the words over all T slots, the planes of all flows being one `stage` base.
+// Else COMPOSED: (d) gathers a chunk of slots into the context's scratch, the decoder runs on it, next chunk.  (e) is launched BEHIND
+// the decode in both forms: it overwrites the staging planes of the carried blocks, which the fused decode reads.
+int ldpc_amd_fec_rxw_flows_decode_many(ldpc_amd_fec_rxw_flows *rx, int code, const uint8_t *packets, const int64_t *flow_begin, int max_sweeps,
+                                       int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
+                                       int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const char *who = "fec_rxw_flows_decode_many";
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    int rc;
+    int64_t P = 0;
+    if ((rc = rxwf_check_call(rx, who, flow_begin, max_blocks_per_flow, P))) return rc;
+    if (P == 0) {
+        rxwf_nothing(rx, closes, consumed);
+        return 0;
+    }
+    if ((rc = rxwf_decode_check(rx, who, code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    if (!packets || !is_device_ptr(ctx, packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets must be a device pointer of device %d", who, ctx->device);
+    const DevCode &cd = ctx->codes[code]->dev;
+    const int n = rx->n, S = rx->S;
+    const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
+    const size_t frame = (size_t)n * S;
+
+    WFlowsPlan pl;
+    if ((rc = rxwf_plan(rx, who, packets, flow_begin, P, max_blocks_per_flow, pl))) return rc;
+    const int T = pl.T;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kScratchMax / frame)));
+    size_t scratch = 0;
+    // every workspace of the call before anything moves: a refusal leaves every flow where it was
+    if (T > 0) {
+        if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)T * n))) return rc;
+        if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)T * n);
+        else rc = scratch_reserve(ctx, ctx->rx_sym, scratch = (size_t)chunk * frame);
+        if (rc) return rc;
+    }
+    if ((rc = rxwf_winners_launch(rx, pl))) return rc;
+    DecodeArgs d{};
+    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
+    const Results o{out, sweeps, residual, status, erased_out, residual_src};
+    uint8_t *er = (uint8_t *)ctx->rx_er.p;
+    int launches = 0;
+    if (T > 0 && fused) {
+        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+        hipLaunchKernelGGL(rxwf_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
+                           (const uint8_t *)rx->stage_er, (const WFlowTab *)rx->tab_dev, (const int32_t *)rx->slots.p, n, rx->W, T, src, er);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        rxwf_slots(d, o, er, n, frame, 0, T);
+        d.sym = nullptr;
+        d.pin.src = src; d.pin.packets = packets; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
+        if ((rc = launch_decode(ctx, d))) return rc;
+        launches = 1;
+    } else if (T > 0) {
+        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
+        for (int first = 0; first < T; first += (int)chunk) {
+            const int count = (int)std::min<int64_t>(chunk, T - first);
+            if ((rc = rxwf_move_launch<true>(rx, pl, packets, first, count, sym, er + (size_t)first * n))) return rc;
+            rxwf_slots(d, o, er, n, frame, first, count);
+            d.sym = sym;
+            if ((rc = launch_decode(ctx, d))) return rc;
+            launches++;
+        }
+    }
+    if ((rc = rxwf_move_launch<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
+    rxwf_commit(rx, pl, blocks, closes, consumed);
+    ctx->rxwf_info[0] = fused ? 1 : 2; ctx->rxwf_info[1] = T; ctx->rxwf_info[2] = launches; ctx->rxwf_info[3] = (int64_t)scratch;
+    return T;
+}
+
+int ldpc_amd_fec_rxw_flows_flush_many(ldpc_amd_fec_rxw_flows *rx, const int32_t *flows, int nsel, uint8_t *sym_batch, uint8_t *erased_batch,
+                                      int *blocks, int *closes)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const char *who = "fec_rxw_flows_flush_many";
+    WFlushPlan pl;
+    int rc;
+    if ((rc = rxwf_flush_plan(rx, who, flows, nsel, pl))) return rc;
+    if (!sym_batch || !erased_batch) return set_error(ctx, LDPC_AMD_EINVAL, "%s: sym_batch / erased_batch must not be null", who);
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: sym_batch / erased_batch must be device pointers of device %d", who, ctx->device);
+    if (pl.T == 0) {
+        if (closes) std::fill(closes, closes + pl.sel.size(), 0);
+        return 0;
+    }
+    if ((rc = rxwf_flush_upload(rx, who, pl)) || (rc = rxwf_flush_launch<true>(rx, 0, pl.T, sym_batch, erased_batch))) return rc;
+    rxwf_flush_commit(rx, pl, blocks, closes);
+    return pl.T;
+}
+
+// flush_many + decode.  FUSED where the decoder has the packets-in form and S % 16 == 0: every row of every block is staged (or erased),
+// rxwf_flush_sources names it and ONE launch_decode follows the words into the planes; the planes are reset by one launch behind it.
+// Else COMPOSED: a chunk of planes goes to the scratch (and is reset in the same launch) and through the decoder.
+int ldpc_amd_fec_rxw_flows_decode_flush_many(ldpc_amd_fec_rxw_flows *rx, int code, const int32_t *flows, int nsel, int max_sweeps, int do_ml,
+                                             uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
+                                             int32_t *residual_src, int *blocks, int *closes)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const char *who = "fec_rxw_flows_decode_flush_many";
+    WFlushPlan pl;
+    int rc;
+    if ((rc = rxwf_flush_plan(rx, who, flows, nsel, pl))) return rc;
+    if ((rc = rxwf_decode_check(rx, who, code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    const int T = pl.T;
+    if (T == 0) {
+        if (closes) std::fill(closes, closes + pl.sel.size(), 0);
+        return 0;
+    }
+    const DevCode &cd = ctx->codes[code]->dev;
+    const int n = rx->n, S = rx->S;
+    const bool fused = ctx->knobs.rx_pkt != 0 && S % 16 == 0 && decode_reads_packets(ctx, cd, S);
+    const size_t frame = (size_t)n * S;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kScratchMax / frame)));
+    size_t scratch = 0;
+    // every workspace of the call before anything moves: a refusal leaves every flow where it was
+    if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)T * n))) return rc;
+    if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)T * n);
+    else rc = scratch_reserve(ctx, ctx->rx_sym, scratch = (size_t)chunk * frame);
+    if (rc) return rc;
+    if ((rc = rxwf_flush_upload(rx, who, pl))) return rc;
+    DecodeArgs d{};
+    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
+    const Results o{out, sweeps, residual, status, erased_out, residual_src};
+    uint8_t *er = (uint8_t *)ctx->rx_er.p;
+    int launches = 0;
+    if (fused) {
+        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+        hipLaunchKernelGGL(rxwf_flush_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl_dev,
+                           (const uint8_t *)rx->stage_er, n, T, src, er);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        rxwf_slots(d, o, er, n, frame, 0, T);
+        d.sym = nullptr;
+        // no word of the table names a packet (rxwf_flush_sources), so the packet base is never added to: any valid aligned address
+        d.pin.src = src; d.pin.packets = rx->stage_sym; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
+        if ((rc = launch_decode(ctx, d))) return rc;
+        launches = 1;
+        if ((rc = rxwf_flush_launch<false>(rx, 0, T, nullptr, nullptr))) return rc;   // the planes reset, behind the decode that reads them
+    } else {
+        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
+        for (int first = 0; first < T; first += (int)chunk) {
+            const int count = (int)std::min<int64_t>(chunk, T - first);
+            if ((rc = rxwf_flush_launch<true>(rx, first, count, sym, er + (size_t)first * n))) return rc;
+            rxwf_slots(d, o, er, n, frame, first, count);
+            d.sym = sym;
+            if ((rc = launch_decode(ctx, d))) return rc;
+            launches++;
+        }
+    }
+    rxwf_flush_commit(rx, pl, blocks, closes);
+    ctx->rxwf_info[0] = fused ? 1 : 2; ctx->rxwf_info[1] = T; ctx->rxwf_info[2] = launches; ctx->rxwf_info[3] = (int64_t)scratch;
+    return T;
+}
+
+int ldpc_amd_fec_rxw_flows_info(ldpc_amd_ctx *ctx, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_info: info must not be null");
+    memcpy(info, ctx->rxwf_info, sizeof(ctx->rxwf_info));
+    return LDPC_AMD_OK;
+}
+
+}  // extern "C"
