@@ -767,7 +767,7 @@ static int pinned_reserve(ldpc_amd_ctx *ctx, size_t bytes)
 }
 
 // A pointer of this context's device (hipMalloc / torch), not host memory.
-static bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
+bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
 {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {

@@ -172,17 +172,6 @@ __global__ __launch_bounds__(kThreads) void dgram_unpack_copy(const uint8_t *__r
     }
 }
 
-// A pointer of this context's device (hipMalloc / torch), not host memory.  (wire_dev.hip has the same test, private to that file.)
-bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error, it is not one of ours
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == ctx->device;
-}
-
 inline bool overlap(const void *a, size_t na, const void *b, size_t nb)
 {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;

@@ -365,6 +365,8 @@ inline bool symbol_len_words(int S) { return S != 1 && (S % 16) != 0; }
 int refuse_symbol_len(ldpc_amd_ctx *ctx, int S, const char *text16);
 // After a synchronisation: LDPC_AMD_EHIP (and the word cleared) if a kernel of this context reported a violated assumption.
 int check_device_error(ldpc_amd_ctx *ctx);
+// A pointer of this context's device (hipMalloc / torch), not host memory.
+bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p);
 
 #define LDPC_HIP_TRY(ctx, expr)                                                                   \
     do {                                                                                          \

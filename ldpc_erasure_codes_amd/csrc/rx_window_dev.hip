@@ -13,6 +13,8 @@
 // serial starts zero and erased.  The plane a new serial s >= W takes over is the plane of serial s - W, a block (d) may still read,
 // hence (e) behind (d).  A re-anchor happens only when every open block is empty: it consumes no serial and moves no data; it changes
 // `base`, and the packet that tripped it goes to the serial in slot 0.
+// The host code around the kernels that every device receiver needs -- the argument check and the decode tail of the decode calls, the
+// host mirror of the window -- is csrc/rx_host.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -21,9 +23,9 @@
 #include <cmath>
 #include <new>
 
-#include "internal.h"
 #include "../../include/ldpc_erasure_amd_rx_window.h"
-#include "rx_window_scan_dev.h"   // (b) the plan scan: RxwRule, RxwState, the result record, rxw_scan_body
+#define LDPC_AMD_RX_HOST_WINDOWED
+#include "rx_host.h"   // and with it rx_window_scan_dev.h, (b) the plan scan: RxwRule, RxwState, the result record, rxw_scan_body
 
 using namespace ldpc_amd;
 
@@ -31,7 +33,6 @@ namespace {
 
 constexpr int kHdr = 8;   // LDPC_AMD_FEC_HEADER_BYTES
 constexpr int kThreads = 256;
-constexpr size_t kScratchMax = (size_t)256 << 20;   // composed form: received symbols of one chunk of closed blocks
 
 inline unsigned grid_for(int64_t items)
 {
@@ -174,17 +175,6 @@ __global__ __launch_bounds__(kThreads) void rxw_flush_move(uint8_t *__restrict__
     }
 }
 
-// A pointer of this context's device (hipMalloc / torch), not host memory.
-bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error, it is not one of ours
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == ctx->device;
-}
-
 }  // namespace
 
 struct ldpc_amd_fec_rxw_dev {
@@ -210,7 +200,7 @@ struct RxwPlan {
     const int32_t *h = nullptr;   // the scan's result record (pinned)
 };
 
-inline int64_t word64(const int32_t *h, int lo) { return (int64_t)(((uint64_t)(uint32_t)h[lo + 1] << 32) | (uint32_t)h[lo]); }
+inline RxwMirror rxw_mirror(ldpc_amd_fec_rxw_dev *rx) { return RxwMirror{&rx->base, &rx->head, &rx->ahead, rx->cnt, rx->totals, rx->W}; }
 
 int rxw_plan(ldpc_amd_fec_rxw_dev *rx, const char *who, const uint8_t *packets, int64_t npackets, int max_blocks, RxwPlan &pl)
 {
@@ -288,26 +278,9 @@ int rxw_move_launch(ldpc_amd_fec_rxw_dev *rx, const RxwPlan &pl, const uint8_t *
 
 void rxw_commit(ldpc_amd_fec_rxw_dev *rx, const RxwPlan &pl, int *blocks, int64_t *consumed)
 {
-    const int32_t *h = pl.h;
-    rx->base = h[R_BASE]; rx->ahead = h[R_AHEAD];
-    for (int j = 0; j < rx->W; j++) rx->cnt[j] = h[R_CNT + j];
-    rx->head = (rx->head + pl.closes) % rx->W;
-    rx->totals[LDPC_AMD_RXW_BAD_SYMBOL] += word64(h, R_BAD_LO);
-    rx->totals[LDPC_AMD_RXW_LATE] += word64(h, R_LATE_LO);
-    rx->totals[LDPC_AMD_RXW_AHEAD] += word64(h, R_AHEADTOT_LO);
-    rx->totals[LDPC_AMD_RXW_RESYNCS] += h[R_RESYNCS];
-    rx->totals[LDPC_AMD_RXW_CLOSED] += pl.closes;
-    if (blocks) memcpy(blocks, h + R_WORDS, sizeof(int) * (size_t)pl.closes);
+    rxw_mirror_commit(rxw_mirror(rx), pl.h, pl.closes);
+    if (blocks) memcpy(blocks, pl.h + R_WORDS, sizeof(int) * (size_t)pl.closes);
     if (consumed) *consumed = pl.used;
-}
-
-// The blocks a flush hands out, from the mirror: every open slot up to the last non-empty one.
-int rxw_flush_count(const ldpc_amd_fec_rxw_dev *rx)
-{
-    int count = 0;
-    for (int d = 0; d < rx->W; d++)
-        if (rx->cnt[d] > 0) count = d + 1;
-    return count;
 }
 
 // slots first .. first + count - 1 of the window -> sym / er, their planes reset: one launch
@@ -324,57 +297,6 @@ int rxw_flush_launch(ldpc_amd_fec_rxw_dev *rx, int first, int count, uint8_t *sy
     return LDPC_AMD_OK;
 }
 
-// the mirror after a flush of `count` blocks: each a close
-void rxw_flush_commit(ldpc_amd_fec_rxw_dev *rx, int count, int *blocks)
-{
-    for (int j = 0; j < count; j++)
-        if (blocks) blocks[j] = (rx->base + j) & 0xff;
-    for (int d = 0; d < rx->W; d++) rx->cnt[d] = d + count < rx->W ? rx->cnt[d + count] : 0;
-    rx->head = (rx->head + count) % rx->W;
-    rx->base = (rx->base + count) & 0xff;
-    rx->ahead = 0;
-    rx->totals[LDPC_AMD_RXW_CLOSED] += count;
-}
-
-// the decode calls' arguments, checked before anything is planned
-int rxw_decode_check(ldpc_amd_fec_rxw_dev *rx, const char *who, int code, int max_sweeps, uint8_t *out, int32_t *sweeps, int32_t *residual,
-                     int32_t *status, uint8_t *erased_out, int32_t *residual_src)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
-    const DevCode &cd = ctx->codes[code]->dev;
-    if (cd.n != rx->n || cd.k != rx->k)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: the code is (%d,%d), the receiver was created for (%d,%d)", who, cd.n, cd.k, rx->n, rx->k);
-    if (!symbol_len_ok(ctx, rx->S)) return refuse_symbol_len(ctx, rx->S, "S must be 1 or a multiple of 16 (got %d)");
-    if (max_sweeps < 1) return set_error(ctx, LDPC_AMD_EINVAL, "max_sweeps must be >= 1");
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const void *opt[] = {sweeps, residual, status, erased_out, residual_src};
-    bool ok = out && is_device_ptr(ctx, out);
-    for (const void *p : opt) ok = ok && (!p || is_device_ptr(ctx, p));
-    if (!ok) return set_error(ctx, LDPC_AMD_EINVAL, "%s: out and the result arrays must be device pointers of device %d", who, ctx->device);
-    return LDPC_AMD_OK;
-}
-
-struct Results {
-    uint8_t *out;
-    int32_t *sweeps, *residual, *status;
-    uint8_t *erased_out;
-    int32_t *residual_src;
-};
-
-// the result arrays of slots first .. first + count - 1
-void rxw_slots(DecodeArgs &d, const Results &o, const uint8_t *er, int n, size_t frame, int first, int count)
-{
-    d.nframes = count;
-    d.erased = er + (size_t)first * n;
-    d.out = o.out + (size_t)first * frame;
-    d.sweeps = o.sweeps ? o.sweeps + first : nullptr;
-    d.residual = o.residual ? o.residual + first : nullptr;
-    d.status = o.status ? o.status + first : nullptr;
-    d.erased_out = o.erased_out ? o.erased_out + (size_t)first * n : nullptr;
-    d.residual_src = o.residual_src ? o.residual_src + first : nullptr;
-}
-
 }  // namespace
 
 extern "C" {
@@ -384,12 +306,8 @@ int ldpc_amd_fec_rxw_dev_create(ldpc_amd_ctx *ctx, int n, int k, int S, int wind
     if (!ctx) return LDPC_AMD_EINVAL;
     if (!out || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: need n <= 65536, 0 < k < n, S >= 1 (n=%d k=%d S=%d)", n, k, S);
-    if (window < LDPC_AMD_RXW_MIN_WINDOW || window > LDPC_AMD_RXW_MAX_WINDOW || ahead_limit < 0 || ahead_limit > (1 << 30))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: need 2 <= window <= 32 and 0 <= ahead_limit <= 2^30 (window=%d ahead_limit=%d)",
-                         window, ahead_limit);
-    if ((int64_t)window * n >= (int64_t)0x7ffffffe)
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: window * n = %lld staging rows, a staged-row word names fewer than 2^31 - 2",
-                         (long long)window * n);
+    int rc;
+    if ((rc = rxw_check_create(ctx, "fec_rxw_dev_create", window, ahead_limit, (int64_t)window * n, "window * n"))) return rc;
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     ldpc_amd_fec_rxw_dev *rx = new (std::nothrow) ldpc_amd_fec_rxw_dev();
     if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rxw_dev_create: out of host memory");
@@ -474,21 +392,21 @@ int ldpc_amd_fec_rxw_dev_flush(ldpc_amd_fec_rxw_dev *rx, uint8_t *sym_batch, uin
 {
     if (!rx) return LDPC_AMD_EINVAL;
     ldpc_amd_ctx *ctx = rx->ctx;
-    const int count = rxw_flush_count(rx);
+    const int count = rxw_mirror_flush_count(rx->cnt, rx->W);
     if (count == 0) return 0;
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!sym_batch || !erased_batch || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_flush: sym_batch / erased_batch must be device pointers of device %d", ctx->device);
     int rc;
     if ((rc = rxw_flush_launch(rx, 0, count, sym_batch, erased_batch))) return rc;
-    rxw_flush_commit(rx, count, blocks);
+    rxw_mirror_flush(rxw_mirror(rx), count, blocks);
     return count;
 }
 
-// push_many + decode_frames in one call.  FUSED where the decoder can fetch its rows from the packets itself (decode_reads_packets): (d)
-// shrinks to rxw_sources and the decode follows the words, the W planes being one `stage` base.  Else COMPOSED: (d) gathers a chunk of
-// closed blocks into the context's scratch, the decoder runs on it, next chunk.  (e) is launched BEHIND the decode in both forms: it
-// overwrites the staging planes of the carried blocks, which the fused decode reads.
+// push_many + decode_frames in one call (rx_host.h: the decode driver).  FUSED where the decoder can fetch its rows from the packets
+// itself (decode_reads_packets): (d) shrinks to rxw_sources, the W planes being one `stage` base.  Else COMPOSED: (d) gathers chunk by
+// chunk.  (e) is launched BEHIND the decode in both forms: it overwrites the staging planes of the carried blocks, which the fused
+// decode reads.
 int ldpc_amd_fec_rxw_dev_decode_many(ldpc_amd_fec_rxw_dev *rx, int code, const uint8_t *packets, int64_t npackets, int max_sweeps,
                                      int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status,
                                      uint8_t *erased_out, int32_t *residual_src, int *blocks, int max_blocks, int64_t *consumed)
@@ -503,88 +421,62 @@ int ldpc_amd_fec_rxw_dev_decode_many(ldpc_amd_fec_rxw_dev *rx, int code, const u
         return 0;
     }
     int rc;
-    if ((rc = rxw_decode_check(rx, "fec_rxw_dev_decode_many", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
+    if ((rc = rx_decode_check(ctx, rx, "fec_rxw_dev_decode_many", code, max_sweeps, o))) return rc;
     if (!packets || !is_device_ptr(ctx, packets))
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_decode_many: packets must be a device pointer of device %d", ctx->device);
     const DevCode &cd = ctx->codes[code]->dev;
     const int n = rx->n, S = rx->S;
     const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
     const size_t frame = (size_t)n * S;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(max_blocks, (int64_t)(kScratchMax / frame)));
+    const int64_t chunk = rx_chunk(max_blocks, frame);
 
     RxwPlan pl;
     if ((rc = rxw_plan(rx, "fec_rxw_dev_decode_many", packets, npackets, max_blocks, pl))) return rc;
     const int closes = pl.closes;
     size_t scratch = 0;
-    // every workspace of the call before anything moves: a refusal leaves the receiver where it was
-    if (closes > 0) {
-        if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)closes * n))) return rc;
-        if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)closes * n);
-        else rc = scratch_reserve(ctx, ctx->rx_sym, scratch = (size_t)std::min<int64_t>(chunk, closes) * frame);
-        if (rc) return rc;
-    }
+    if ((rc = rx_decode_reserve(ctx, closes, n, frame, fused, chunk, &scratch))) return rc;
     if ((rc = rxw_winners_launch(rx, pl))) return rc;
-    DecodeArgs d{};
-    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
-    const Results o{out, sweeps, residual, status, erased_out, residual_src};
-    uint8_t *er = (uint8_t *)ctx->rx_er.p;
-    int launches = 0;
-    if (closes > 0 && fused) {
-        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
+    const PacketRows pin{nullptr, packets, rx->stage_sym, S + kHdr};
+    auto sources = [&](uint32_t *src, uint8_t *er) -> int {
         hipLaunchKernelGGL(rxw_sources, dim3(grid_for((int64_t)closes * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
                            rx->stage_er, n, rx->W, rx->head, closes, src, er);
         LDPC_HIP_TRY(ctx, hipGetLastError());
-        rxw_slots(d, o, er, n, frame, 0, closes);
-        d.sym = nullptr;
-        d.pin.src = src; d.pin.packets = packets; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
-        if ((rc = launch_decode(ctx, d))) return rc;
-        launches = 1;
-    } else if (closes > 0) {
-        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
-        for (int first = 0; first < closes; first += (int)chunk) {
-            const int count = (int)std::min<int64_t>(chunk, closes - first);
-            if ((rc = rxw_move_launch<true>(rx, pl, packets, first, count, sym, er + (size_t)first * n))) return rc;
-            rxw_slots(d, o, er, n, frame, first, count);
-            d.sym = sym;
-            if ((rc = launch_decode(ctx, d))) return rc;
-            launches++;
-        }
-    }
+        return LDPC_AMD_OK;
+    };
+    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return rxw_move_launch<true>(rx, pl, packets, first, count, sym, er); };
+    int launches = 0;
+    if ((rc = rx_decode_slots(ctx, d, o, closes, chunk, fused, pin, sources, gather, &launches))) return rc;
     if ((rc = rxw_move_launch<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
     rxw_commit(rx, pl, blocks, consumed);
     ctx->rxw_info[0] = fused ? 1 : 2; ctx->rxw_info[1] = closes; ctx->rxw_info[2] = launches; ctx->rxw_info[3] = (int64_t)scratch;
     return closes;
 }
 
-// flush + decode, composed: the blocks lie complete in their planes, a chunk of them goes to the scratch and through the decoder
+// flush + decode, composed: the blocks lie complete in their planes, a chunk of them goes to the scratch (its planes reset by the same
+// launch) and through the decoder
 int ldpc_amd_fec_rxw_dev_decode_flush(ldpc_amd_fec_rxw_dev *rx, int code, int max_sweeps, int do_ml, uint8_t *out, int32_t *sweeps,
                                       int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src, int *blocks)
 {
     if (!rx) return LDPC_AMD_EINVAL;
     ldpc_amd_ctx *ctx = rx->ctx;
     int rc;
-    if ((rc = rxw_decode_check(rx, "fec_rxw_dev_decode_flush", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
-    const int count = rxw_flush_count(rx);
+    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
+    if ((rc = rx_decode_check(ctx, rx, "fec_rxw_dev_decode_flush", code, max_sweeps, o))) return rc;
+    const int count = rxw_mirror_flush_count(rx->cnt, rx->W);
     if (count == 0) return 0;
     const int n = rx->n;
     const size_t frame = (size_t)n * rx->S;
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(count, (int64_t)(kScratchMax / frame)));
-    const size_t scratch = (size_t)chunk * frame;
-    if ((rc = scratch_reserve(ctx, ctx->rx_sym, scratch)) || (rc = scratch_reserve(ctx, ctx->rx_er, (size_t)count * n))) return rc;
-    DecodeArgs d{};
-    d.code = ctx->codes[code]->dev; d.S = rx->S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
-    const Results o{out, sweeps, residual, status, erased_out, residual_src};
-    uint8_t *sym = (uint8_t *)ctx->rx_sym.p, *er = (uint8_t *)ctx->rx_er.p;
+    const int64_t chunk = rx_chunk(count, frame);
+    size_t scratch = 0;
+    if ((rc = rx_decode_reserve(ctx, count, n, frame, false, chunk, &scratch))) return rc;
+    DecodeArgs d = rx_decode_args(ctx->codes[code]->dev, n, rx->S, max_sweeps, do_ml);
+    auto sources = [](uint32_t *, uint8_t *) -> int { return LDPC_AMD_OK; };   // (never fused)
+    auto gather = [&](int first, int c, uint8_t *sym, uint8_t *er) { return rxw_flush_launch(rx, first, c, sym, er); };
     int launches = 0;
-    for (int first = 0; first < count; first += chunk) {
-        const int c = std::min(chunk, count - first);
-        if ((rc = rxw_flush_launch(rx, first, c, sym, er + (size_t)first * n))) return rc;
-        rxw_slots(d, o, er, n, frame, first, c);
-        d.sym = sym;
-        if ((rc = launch_decode(ctx, d))) return rc;
-        launches++;
-    }
-    rxw_flush_commit(rx, count, blocks);
+    if ((rc = rx_decode_slots(ctx, d, o, count, chunk, false, PacketRows{}, sources, gather, &launches))) return rc;
+    rxw_mirror_flush(rxw_mirror(rx), count, blocks);
     ctx->rxw_info[0] = 2; ctx->rxw_info[1] = count; ctx->rxw_info[2] = launches; ctx->rxw_info[3] = (int64_t)scratch;
     return count;
 }

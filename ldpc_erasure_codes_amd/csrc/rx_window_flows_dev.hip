@@ -16,6 +16,8 @@
 // read: (e) stands behind both on the stream.  Inside (e) nothing is read from the planes: a work item writes its own piece of its
 // own plane (W distinct planes per flow) from a packet or with zero, or leaves a carried row alone.
 // Flush: planned from the host mirror alone, one int32 plane number per handed-out slot (wire_dev.hip's batch flush).
+// The host code every device receiver needs -- the argument check and the decode tail of the decode calls, the host mirror of a
+// flow's window, the upload of the flush's plane numbers -- is csrc/rx_host.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -25,10 +27,10 @@
 #include <new>
 #include <vector>
 
-#include "internal.h"
 #include "../../include/ldpc_erasure_amd_rx_window.h"
 #include "../../include/ldpc_erasure_amd_rx_window_flows.h"
-#include "rx_window_scan_dev.h"
+#define LDPC_AMD_RX_HOST_WINDOWED
+#include "rx_host.h"   // and with it rx_window_scan_dev.h
 
 using namespace ldpc_amd;
 
@@ -37,7 +39,6 @@ namespace {
 constexpr int kHdr = 8;   // LDPC_AMD_FEC_HEADER_BYTES
 constexpr int kThreads = 256;
 constexpr int kMaxFlows = 4096;
-constexpr size_t kScratchMax = (size_t)256 << 20;   // composed form: received symbols of one chunk of closed blocks
 
 inline unsigned grid_for(int64_t items)
 {
@@ -241,17 +242,6 @@ __global__ __launch_bounds__(kThreads) void rxwf_flush_move(const int32_t *__res
     }
 }
 
-// A pointer of this context's device (hipMalloc / torch), not host memory.
-bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error, it is not one of ours
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == ctx->device;
-}
-
 }  // namespace
 
 struct ldpc_amd_fec_rxw_flows {
@@ -268,13 +258,7 @@ struct ldpc_amd_fec_rxw_flows {
     WFlowTab *tab_dev = nullptr, *tab_host = nullptr;   // [nflows]
     int32_t *res_host = nullptr;    // pinned copy of res
     size_t res_host_cap = 0;
-    // the flush (allocated by its first call): the handed-out slots' planes on the device, [W nflows], and their pinned staging -- two
-    // slots used in turn, each with the event of its last copy, so that a slot is never rewritten under a copy in flight
-    int32_t *fl_dev = nullptr;
-    int32_t *fl_host[2] = {nullptr, nullptr};
-    hipEvent_t fl_event[2] = {nullptr, nullptr};
-    bool fl_pending[2] = {false, false};
-    unsigned fl_calls = 0;
+    RxPlaneUpload fl;   // the flush: the handed-out slots' planes on the device, [W nflows]
 };
 
 namespace {
@@ -288,7 +272,10 @@ struct WFlowsPlan {
     size_t rec = 0;        // words of one flow's result record
 };
 
-inline int64_t word64(const int32_t *h, int lo) { return (int64_t)(((uint64_t)(uint32_t)h[lo + 1] << 32) | (uint32_t)h[lo]); }
+inline RxwMirror rxwf_mirror(Rx *rx, int f)
+{
+    return RxwMirror{&rx->base[f], &rx->head[f], &rx->ahead[f], &rx->cnt[(size_t)f * rx->W], &rx->totals[(size_t)f * 5], rx->W};
+}
 
 int rxwf_check_call(Rx *rx, const char *who, const int64_t *flow_begin, int max_blocks, int64_t &P)
 {
@@ -407,62 +394,14 @@ int rxwf_move_launch(Rx *rx, const WFlowsPlan &pl, const uint8_t *packets, int f
 // every flow's mirror (base, head, ahead, cnt, totals) and the host outputs: the last step of a call
 void rxwf_commit(Rx *rx, const WFlowsPlan &pl, int *blocks, int *closes, int64_t *consumed)
 {
-    const int W = rx->W;
     for (int f = 0; f < rx->nflows; f++) {
         const int32_t *h = rx->res_host + (size_t)f * pl.rec;
         const WFlowTab &t = rx->tab_host[f];
-        rx->base[f] = h[R_BASE]; rx->ahead[f] = h[R_AHEAD];
-        for (int j = 0; j < W; j++) rx->cnt[(size_t)f * W + j] = h[R_CNT + j];
-        rx->head[f] = (rx->head[f] + t.closes) % W;
-        int64_t *tot = &rx->totals[(size_t)f * 5];
-        tot[LDPC_AMD_RXW_BAD_SYMBOL] += word64(h, R_BAD_LO);
-        tot[LDPC_AMD_RXW_LATE] += word64(h, R_LATE_LO);
-        tot[LDPC_AMD_RXW_AHEAD] += word64(h, R_AHEADTOT_LO);
-        tot[LDPC_AMD_RXW_RESYNCS] += h[R_RESYNCS];
-        tot[LDPC_AMD_RXW_CLOSED] += t.closes;
+        rxw_mirror_commit(rxwf_mirror(rx, f), h, t.closes);
         if (blocks) memcpy(blocks + t.base, h + R_WORDS, sizeof(int) * (size_t)t.closes);
         if (closes) closes[f] = t.closes;
         if (consumed) consumed[f] = t.used;
     }
-}
-
-// the decode calls' arguments, checked before anything is planned
-int rxwf_decode_check(Rx *rx, const char *who, int code, int max_sweeps, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status,
-                      uint8_t *erased_out, int32_t *residual_src)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
-    const DevCode &cd = ctx->codes[code]->dev;
-    if (cd.n != rx->n || cd.k != rx->k)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: the code is (%d,%d), the receiver was created for (%d,%d)", who, cd.n, cd.k, rx->n, rx->k);
-    if (!symbol_len_ok(ctx, rx->S)) return refuse_symbol_len(ctx, rx->S, "S must be 1 or a multiple of 16 (got %d)");
-    if (max_sweeps < 1) return set_error(ctx, LDPC_AMD_EINVAL, "max_sweeps must be >= 1");
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const void *opt[] = {sweeps, residual, status, erased_out, residual_src};
-    bool ok = out && is_device_ptr(ctx, out);
-    for (const void *p : opt) ok = ok && (!p || is_device_ptr(ctx, p));
-    if (!ok) return set_error(ctx, LDPC_AMD_EINVAL, "%s: out and the result arrays must be device pointers of device %d", who, ctx->device);
-    return LDPC_AMD_OK;
-}
-
-struct Results {
-    uint8_t *out;
-    int32_t *sweeps, *residual, *status;
-    uint8_t *erased_out;
-    int32_t *residual_src;
-};
-
-// the result arrays of slots first .. first + count - 1
-void rxwf_slots(DecodeArgs &d, const Results &o, const uint8_t *er, int n, size_t frame, int first, int count)
-{
-    d.nframes = count;
-    d.erased = er + (size_t)first * n;
-    d.out = o.out + (size_t)first * frame;
-    d.sweeps = o.sweeps ? o.sweeps + first : nullptr;
-    d.residual = o.residual ? o.residual + first : nullptr;
-    d.status = o.status ? o.status + first : nullptr;
-    d.erased_out = o.erased_out ? o.erased_out + (size_t)first * n : nullptr;
-    d.residual_src = o.residual_src ? o.residual_src + first : nullptr;
 }
 
 // ---- the flush's plan: the host's, from the mirror (ldpc_amd_fec_rxw_dev_flush per listed flow) -------------------------------------
@@ -473,15 +412,6 @@ struct WFlushPlan {
     std::vector<int32_t> planes;   // [T] their staging planes, f W + b
     int T = 0;
 };
-
-// The blocks a flush of flow f hands out: every open slot up to the last non-empty one.
-int rxwf_flush_count(const Rx *rx, int f)
-{
-    int count = 0;
-    for (int d = 0; d < rx->W; d++)
-        if (rx->cnt[(size_t)f * rx->W + d] > 0) count = d + 1;
-    return count;
-}
 
 int rxwf_flush_plan(const Rx *rx, const char *who, const int32_t *flows, int nsel, WFlushPlan &pl)
 {
@@ -502,7 +432,7 @@ int rxwf_flush_plan(const Rx *rx, const char *who, const int32_t *flows, int nse
     pl.closes.resize((size_t)nsel);
     for (int j = 0; j < nsel; j++) {
         const int f = flows ? flows[j] : j;
-        const int count = rxwf_flush_count(rx, f);
+        const int count = rxw_mirror_flush_count(&rx->cnt[(size_t)f * rx->W], rx->W);
         pl.sel[(size_t)j] = f;
         pl.closes[(size_t)j] = count;
         for (int c = 0; c < count; c++) {
@@ -511,37 +441,6 @@ int rxwf_flush_plan(const Rx *rx, const char *who, const int32_t *flows, int nse
         }
     }
     pl.T = (int)pl.planes.size();   // <= W nflows
-    return LDPC_AMD_OK;
-}
-
-// the object's descriptor buffers (first call), then the planes of the T slots to the device through the pinned slot of this call
-int rxwf_flush_upload(Rx *rx, const char *who, const WFlushPlan &pl)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const size_t cap = sizeof(int32_t) * (size_t)rx->W * (size_t)rx->nflows;
-    if (!rx->fl_dev) {
-        hipError_t e = hipMalloc((void **)&rx->fl_dev, cap);
-        for (int s = 0; s < 2 && e == hipSuccess; s++) {
-            if (!rx->fl_host[s]) e = hipHostMalloc((void **)&rx->fl_host[s], cap, hipHostMallocDefault);
-            if (e == hipSuccess && !rx->fl_event[s]) e = hipEventCreateWithFlags(&rx->fl_event[s], hipEventDisableTiming);
-        }
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            if (rx->fl_dev) (void)hipFree(rx->fl_dev);
-            rx->fl_dev = nullptr;   // (what the slots got is kept: the next call asks for the rest)
-            return set_error(ctx, LDPC_AMD_ENOMEM, "%s: no memory for the slot descriptors: %s", who, hipGetErrorString(e));
-        }
-    }
-    const int slot = (int)(rx->fl_calls & 1u);
-    if (rx->fl_pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
-        LDPC_HIP_TRY(ctx, hipEventSynchronize(rx->fl_event[slot]));
-        rx->fl_pending[slot] = false;
-    }
-    memcpy(rx->fl_host[slot], pl.planes.data(), sizeof(int32_t) * (size_t)pl.T);
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->fl_dev, rx->fl_host[slot], sizeof(int32_t) * (size_t)pl.T, hipMemcpyHostToDevice, ctx->stream));
-    LDPC_HIP_TRY(ctx, hipEventRecord(rx->fl_event[slot], ctx->stream));
-    rx->fl_pending[slot] = true;
-    rx->fl_calls++;
     return LDPC_AMD_OK;
 }
 
@@ -554,8 +453,8 @@ int rxwf_flush_launch(Rx *rx, int first, int count, uint8_t *sym, uint8_t *er)
     const bool v16 = S % 16 == 0 && ((uintptr_t)sym & 15) == 0;
     const int64_t pieces = (int64_t)n * (v16 ? S / 16 : S);
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((pieces + kThreads - 1) / kThreads, 256)), (unsigned)std::min(count, 16384));
-    if (v16) hipLaunchKernelGGL((rxwf_flush_move<16, COPY>), grid, dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, count, sym, er);
-    else hipLaunchKernelGGL((rxwf_flush_move<1, COPY>), grid, dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, count, sym, er);
+    if (v16) hipLaunchKernelGGL((rxwf_flush_move<16, COPY>), grid, dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl.dev, rx->stage_sym, rx->stage_er, n, S, first, count, sym, er);
+    else hipLaunchKernelGGL((rxwf_flush_move<1, COPY>), grid, dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl.dev, rx->stage_sym, rx->stage_er, n, S, first, count, sym, er);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     return LDPC_AMD_OK;
 }
@@ -563,17 +462,9 @@ int rxwf_flush_launch(Rx *rx, int first, int count, uint8_t *sym, uint8_t *er)
 // the mirror of every listed flow after its flush -- each handed-out block a close -- and the host outputs
 void rxwf_flush_commit(Rx *rx, const WFlushPlan &pl, int *blocks, int *closes)
 {
-    const int W = rx->W;
     for (size_t j = 0; j < pl.sel.size(); j++) {
-        const int f = pl.sel[j], count = pl.closes[j];
-        if (closes) closes[j] = count;
-        if (count == 0) continue;
-        int *cnt = &rx->cnt[(size_t)f * W];
-        for (int d = 0; d < W; d++) cnt[d] = d + count < W ? cnt[d + count] : 0;
-        rx->head[f] = (rx->head[f] + count) % W;
-        rx->base[f] = (rx->base[f] + count) & 0xff;
-        rx->ahead[f] = 0;
-        rx->totals[(size_t)f * 5 + LDPC_AMD_RXW_CLOSED] += count;
+        if (closes) closes[j] = pl.closes[j];
+        if (pl.closes[j] > 0) rxw_mirror_flush(rxwf_mirror(rx, pl.sel[j]), pl.closes[j], nullptr);
     }
     if (blocks && pl.T > 0) memcpy(blocks, pl.blocks.data(), sizeof(int) * (size_t)pl.T);
 }
@@ -588,12 +479,8 @@ int ldpc_amd_fec_rxw_flows_create(ldpc_amd_ctx *ctx, int nflows, int n, int k, i
     if (!out || nflows < 1 || nflows > kMaxFlows || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: need 1 <= nflows <= 4096, n <= 65536, 0 < k < n, S >= 1 (nflows=%d n=%d k=%d S=%d)",
                          nflows, n, k, S);
-    if (window < LDPC_AMD_RXW_MIN_WINDOW || window > LDPC_AMD_RXW_MAX_WINDOW || ahead_limit < 0 || ahead_limit > (1 << 30))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: need 2 <= window <= 32 and 0 <= ahead_limit <= 2^30 (window=%d ahead_limit=%d)",
-                         window, ahead_limit);
-    if ((int64_t)nflows * window * n >= (int64_t)0x7ffffffe)
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: nflows * window * n = %lld staging rows, a staged-row word names fewer than 2^31 - 2",
-                         (long long)nflows * window * n);
+    int rc;
+    if ((rc = rxw_check_create(ctx, "fec_rxw_flows_create", window, ahead_limit, (int64_t)nflows * window * n, "nflows * window * n"))) return rc;
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     Rx *rx = new (std::nothrow) Rx();
     if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rxw_flows_create: out of host memory");
@@ -633,14 +520,13 @@ void ldpc_amd_fec_rxw_flows_destroy(ldpc_amd_fec_rxw_flows *rx)
     Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots};
     for (Scratch *s : sc)
         if (s->p) (void)hipFree(s->p);
-    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev, rx->fl_dev};
+    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *host[] = {rx->in_host, rx->tab_host, rx->res_host, rx->fl_host[0], rx->fl_host[1]};
+    void *host[] = {rx->in_host, rx->tab_host, rx->res_host};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : rx->fl_event)
-        if (e) (void)hipEventDestroy(e);
+    rx_upload_free(rx->fl);
     delete rx;
 }
 
@@ -673,7 +559,7 @@ int ldpc_amd_fec_rxw_flows_pending(const ldpc_amd_fec_rxw_flows *rx, int32_t *ba
     int total = 0;
     for (int f = 0; f < rx->nflows; f++) {
         if (base) base[f] = rx->base[f];
-        total += rxwf_flush_count(rx, f);
+        total += rxw_mirror_flush_count(&rx->cnt[(size_t)f * rx->W], rx->W);
     }
     if (cnt) memcpy(cnt, rx->cnt.data(), sizeof(int32_t) * rx->cnt.size());
     return total;
@@ -707,10 +593,10 @@ int ldpc_amd_fec_rxw_flows_push_many(ldpc_amd_fec_rxw_flows *rx, const uint8_t *
     return pl.T;
 }
 
-// push_many + decode_frames in one call.  FUSED where the decoder can fetch its rows from the packets itself (decode_reads_packets): (d)
-// shrinks to rxwf_sources and ONE launch_decode follows the words over all T slots, the planes of all flows being one `stage` base.
-// Else COMPOSED: (d) gathers a chunk of slots into the context's scratch, the decoder runs on it, next chunk.  (e) is launched BEHIND
-// the decode in both forms: it overwrites the staging planes of the carried blocks, which the fused decode reads.
+// push_many + decode_frames in one call (rx_host.h: the decode driver).  FUSED where the decoder can fetch its rows from the packets
+// itself (decode_reads_packets): (d) shrinks to rxwf_sources, the planes of all flows being one `stage` base.  Else COMPOSED: (d)
+// gathers chunk by chunk.  (e) is launched BEHIND the decode in both forms: it overwrites the staging planes of the carried blocks,
+// which the fused decode reads.
 int ldpc_amd_fec_rxw_flows_decode_many(ldpc_amd_fec_rxw_flows *rx, int code, const uint8_t *packets, const int64_t *flow_begin, int max_sweeps,
                                        int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
                                        int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
@@ -726,7 +612,8 @@ int ldpc_amd_fec_rxw_flows_decode_many(ldpc_amd_fec_rxw_flows *rx, int code, con
         rxwf_nothing(rx, closes, consumed);
         return 0;
     }
-    if ((rc = rxwf_decode_check(rx, who, code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
+    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, o))) return rc;
     if (!packets || !is_device_ptr(ctx, packets))
         return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets must be a device pointer of device %d", who, ctx->device);
     const DevCode &cd = ctx->codes[code]->dev;
@@ -737,42 +624,21 @@ int ldpc_amd_fec_rxw_flows_decode_many(ldpc_amd_fec_rxw_flows *rx, int code, con
     WFlowsPlan pl;
     if ((rc = rxwf_plan(rx, who, packets, flow_begin, P, max_blocks_per_flow, pl))) return rc;
     const int T = pl.T;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kScratchMax / frame)));
+    const int64_t chunk = rx_chunk(T, frame);
     size_t scratch = 0;
-    // every workspace of the call before anything moves: a refusal leaves every flow where it was
-    if (T > 0) {
-        if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)T * n))) return rc;
-        if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)T * n);
-        else rc = scratch_reserve(ctx, ctx->rx_sym, scratch = (size_t)chunk * frame);
-        if (rc) return rc;
-    }
+    if ((rc = rx_decode_reserve(ctx, T, n, frame, fused, chunk, &scratch))) return rc;
     if ((rc = rxwf_winners_launch(rx, pl))) return rc;
-    DecodeArgs d{};
-    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
-    const Results o{out, sweeps, residual, status, erased_out, residual_src};
-    uint8_t *er = (uint8_t *)ctx->rx_er.p;
-    int launches = 0;
-    if (T > 0 && fused) {
-        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
+    const PacketRows pin{nullptr, packets, rx->stage_sym, S + kHdr};
+    auto sources = [&](uint32_t *src, uint8_t *er) -> int {
         hipLaunchKernelGGL(rxwf_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
                            (const uint8_t *)rx->stage_er, (const WFlowTab *)rx->tab_dev, (const int32_t *)rx->slots.p, n, rx->W, T, src, er);
         LDPC_HIP_TRY(ctx, hipGetLastError());
-        rxwf_slots(d, o, er, n, frame, 0, T);
-        d.sym = nullptr;
-        d.pin.src = src; d.pin.packets = packets; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
-        if ((rc = launch_decode(ctx, d))) return rc;
-        launches = 1;
-    } else if (T > 0) {
-        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
-        for (int first = 0; first < T; first += (int)chunk) {
-            const int count = (int)std::min<int64_t>(chunk, T - first);
-            if ((rc = rxwf_move_launch<true>(rx, pl, packets, first, count, sym, er + (size_t)first * n))) return rc;
-            rxwf_slots(d, o, er, n, frame, first, count);
-            d.sym = sym;
-            if ((rc = launch_decode(ctx, d))) return rc;
-            launches++;
-        }
-    }
+        return LDPC_AMD_OK;
+    };
+    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return rxwf_move_launch<true>(rx, pl, packets, first, count, sym, er); };
+    int launches = 0;
+    if ((rc = rx_decode_slots(ctx, d, o, T, chunk, fused, pin, sources, gather, &launches))) return rc;
     if ((rc = rxwf_move_launch<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
     rxwf_commit(rx, pl, blocks, closes, consumed);
     ctx->rxwf_info[0] = fused ? 1 : 2; ctx->rxwf_info[1] = T; ctx->rxwf_info[2] = launches; ctx->rxwf_info[3] = (int64_t)scratch;
@@ -796,7 +662,9 @@ int ldpc_amd_fec_rxw_flows_flush_many(ldpc_amd_fec_rxw_flows *rx, const int32_t 
         if (closes) std::fill(closes, closes + pl.sel.size(), 0);
         return 0;
     }
-    if ((rc = rxwf_flush_upload(rx, who, pl)) || (rc = rxwf_flush_launch<true>(rx, 0, pl.T, sym_batch, erased_batch))) return rc;
+    if ((rc = rx_upload_planes(ctx, who, rx->fl, (size_t)rx->W * (size_t)rx->nflows, pl.planes.data(), pl.T)) ||
+        (rc = rxwf_flush_launch<true>(rx, 0, pl.T, sym_batch, erased_batch)))
+        return rc;
     rxwf_flush_commit(rx, pl, blocks, closes);
     return pl.T;
 }
@@ -814,7 +682,8 @@ int ldpc_amd_fec_rxw_flows_decode_flush_many(ldpc_amd_fec_rxw_flows *rx, int cod
     WFlushPlan pl;
     int rc;
     if ((rc = rxwf_flush_plan(rx, who, flows, nsel, pl))) return rc;
-    if ((rc = rxwf_decode_check(rx, who, code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
+    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, o))) return rc;
     const int T = pl.T;
     if (T == 0) {
         if (closes) std::fill(closes, closes + pl.sel.size(), 0);
@@ -824,42 +693,24 @@ int ldpc_amd_fec_rxw_flows_decode_flush_many(ldpc_amd_fec_rxw_flows *rx, int cod
     const int n = rx->n, S = rx->S;
     const bool fused = ctx->knobs.rx_pkt != 0 && S % 16 == 0 && decode_reads_packets(ctx, cd, S);
     const size_t frame = (size_t)n * S;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kScratchMax / frame)));
+    const int64_t chunk = rx_chunk(T, frame);
     size_t scratch = 0;
-    // every workspace of the call before anything moves: a refusal leaves every flow where it was
-    if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)T * n))) return rc;
-    if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)T * n);
-    else rc = scratch_reserve(ctx, ctx->rx_sym, scratch = (size_t)chunk * frame);
-    if (rc) return rc;
-    if ((rc = rxwf_flush_upload(rx, who, pl))) return rc;
-    DecodeArgs d{};
-    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
-    const Results o{out, sweeps, residual, status, erased_out, residual_src};
-    uint8_t *er = (uint8_t *)ctx->rx_er.p;
-    int launches = 0;
-    if (fused) {
-        uint32_t *src = (uint32_t *)ctx->rx_src.p;
-        hipLaunchKernelGGL(rxwf_flush_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl_dev,
+    if ((rc = rx_decode_reserve(ctx, T, n, frame, fused, chunk, &scratch))) return rc;
+    if ((rc = rx_upload_planes(ctx, who, rx->fl, (size_t)rx->W * (size_t)rx->nflows, pl.planes.data(), pl.T))) return rc;
+    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
+    // no word of the table names a packet (rxwf_flush_sources), so the packet base is never added to: any valid aligned address
+    const PacketRows pin{nullptr, rx->stage_sym, rx->stage_sym, S + kHdr};
+    auto sources = [&](uint32_t *src, uint8_t *er) -> int {
+        hipLaunchKernelGGL(rxwf_flush_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl.dev,
                            (const uint8_t *)rx->stage_er, n, T, src, er);
         LDPC_HIP_TRY(ctx, hipGetLastError());
-        rxwf_slots(d, o, er, n, frame, 0, T);
-        d.sym = nullptr;
-        // no word of the table names a packet (rxwf_flush_sources), so the packet base is never added to: any valid aligned address
-        d.pin.src = src; d.pin.packets = rx->stage_sym; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
-        if ((rc = launch_decode(ctx, d))) return rc;
-        launches = 1;
-        if ((rc = rxwf_flush_launch<false>(rx, 0, T, nullptr, nullptr))) return rc;   // the planes reset, behind the decode that reads them
-    } else {
-        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
-        for (int first = 0; first < T; first += (int)chunk) {
-            const int count = (int)std::min<int64_t>(chunk, T - first);
-            if ((rc = rxwf_flush_launch<true>(rx, first, count, sym, er + (size_t)first * n))) return rc;
-            rxwf_slots(d, o, er, n, frame, first, count);
-            d.sym = sym;
-            if ((rc = launch_decode(ctx, d))) return rc;
-            launches++;
-        }
-    }
+        return LDPC_AMD_OK;
+    };
+    // (composed: a chunk's planes are reset by the launch that copies them)
+    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return rxwf_flush_launch<true>(rx, first, count, sym, er); };
+    int launches = 0;
+    if ((rc = rx_decode_slots(ctx, d, o, T, chunk, fused, pin, sources, gather, &launches))) return rc;
+    if (fused && (rc = rxwf_flush_launch<false>(rx, 0, T, nullptr, nullptr))) return rc;   // the planes reset, behind the decode that reads them
     rxwf_flush_commit(rx, pl, blocks, closes);
     ctx->rxwf_info[0] = fused ? 1 : 2; ctx->rxwf_info[1] = T; ctx->rxwf_info[2] = launches; ctx->rxwf_info[3] = (int64_t)scratch;
     return T;

@@ -21,6 +21,8 @@
 // on every close, :241).  Serials 0 and 1 were carried in from earlier calls: their staging planes hold what those calls
 // received; every other serial starts erased.  (d) reads the staging planes of carried blocks that close; (e) rewrites the
 // plane of serial s >= 2, which is the plane of serial s - 2 -- a block (d) may read -- so (e) is a launch after (d).
+// The host code every device receiver needs -- the argument check and the decode tail of the decode calls, the upload of a batch
+// flush's plane numbers -- is csrc/rx_host.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -30,7 +32,7 @@
 #include <new>
 #include <vector>
 
-#include "internal.h"
+#include "rx_host.h"
 #include "fec_header_dev.h"
 #include "../../include/ldpc_erasure_amd_wire_dev.h"
 #include "../../include/ldpc_erasure_amd_sender.h"
@@ -52,7 +54,6 @@ constexpr int kScanPrefetch = 16;   // groups of 64 dense headers a scan lane ho
 enum : int { R_CUR, R_NEXT, R_CCNT, R_NCNT, R_CLOSES, R_ERR, R_CONSUMED_LO, R_CONSUMED_HI, R_DROPPED_LO, R_DROPPED_HI, R_WORDS = 16 };
 
 constexpr size_t kSenderScratchMax = (size_t)256 << 20;   // composed sender: codewords of one chunk of frames
-constexpr size_t kReceiverScratchMax = (size_t)256 << 20; // composed receiver: received symbols of one chunk of closed blocks
 
 inline unsigned grid_for(int64_t items)
 {
@@ -730,17 +731,6 @@ __global__ __launch_bounds__(kThreads) void fec_rx_flush_reset(const int32_t *__
     }
 }
 
-// A pointer of this context's device (hipMalloc / torch), not host memory.
-bool is_device_ptr(const ldpc_amd_ctx *ctx, const void *p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();   // an unregistered host pointer: clear the sticky error, it is not one of ours
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == ctx->device;
-}
-
 }  // namespace
 
 struct ldpc_amd_fec_rx_dev {
@@ -1190,25 +1180,7 @@ int ldpc_amd_fec_rx_dev_flush(ldpc_amd_fec_rx_dev *rx, uint8_t *sym_out, uint8_t
 // 214-243).  Else COMPOSED: (d) gathers a chunk of closed blocks into the context's scratch, the decoder runs on it, next chunk; the
 // chunks follow one another on the context's stream, so the scratch is free again when the next gather starts.
 // (e) is launched BEHIND the decode in both paths: it overwrites the staging planes of the carried blocks, which the fused decode reads.
-extern "C++" template <class Rx>   // ldpc_amd_fec_rx_dev or ldpc_amd_fec_rx_flows: n, k, S
-static int rx_decode_check(ldpc_amd_ctx *ctx, const Rx *rx, const char *who, int code, int max_sweeps, uint8_t *out,
-                           int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src)
-{
-    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
-    const DevCode &cd = ctx->codes[code]->dev;
-    if (cd.n != rx->n || cd.k != rx->k)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: the code is (%d,%d), the receiver was created for (%d,%d)", who, cd.n, cd.k, rx->n, rx->k);
-    // the decoder's own refusals (launch_decode), before anything is planned
-    if (!symbol_len_ok(ctx, rx->S)) return refuse_symbol_len(ctx, rx->S, "S must be 1 or a multiple of 16 (got %d)");
-    if (max_sweeps < 1) return set_error(ctx, LDPC_AMD_EINVAL, "max_sweeps must be >= 1");
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const void *opt[] = {sweeps, residual, status, erased_out, residual_src};
-    bool ok = out && is_device_ptr(ctx, out);
-    for (const void *p : opt) ok = ok && (!p || is_device_ptr(ctx, p));
-    if (!ok) return set_error(ctx, LDPC_AMD_EINVAL, "%s: out and the result arrays must be device pointers of device %d", who, ctx->device);
-    return LDPC_AMD_OK;
-}
-
+// The tail of the call -- reserve, row sources or gather, decode -- is rx_host.h's decode driver, as for every receiver below.
 int ldpc_amd_fec_rx_dev_decode_many(ldpc_amd_fec_rx_dev *rx, int code, const uint8_t *packets, int64_t npackets, int max_sweeps, int do_ml,
                                     uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
                                     int32_t *residual_src, int *blocks, int max_blocks, int64_t *consumed)
@@ -1223,58 +1195,33 @@ int ldpc_amd_fec_rx_dev_decode_many(ldpc_amd_fec_rx_dev *rx, int code, const uin
         return 0;
     }
     int rc;
-    if ((rc = rx_decode_check(ctx, rx, "fec_rx_dev_decode_many", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src)))
-        return rc;
+    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
+    if ((rc = rx_decode_check(ctx, rx, "fec_rx_dev_decode_many", code, max_sweeps, o))) return rc;
     if (!packets || !is_device_ptr(ctx, packets))
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_dev_decode_many: packets must be a device pointer of device %d", ctx->device);
     const DevCode &cd = ctx->codes[code]->dev;
     const int n = rx->n, S = rx->S;
     const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
     const size_t frame = (size_t)n * S;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(max_blocks, (int64_t)(kReceiverScratchMax / frame)));
+    const int64_t chunk = rx_chunk(max_blocks, frame);
 
     RxPlan pl;
     if ((rc = rx_plan(rx, "fec_rx_dev_decode_many", packets, npackets, max_blocks, pl))) return rc;
     const int closes = pl.closes;
-    // every workspace of the call before anything moves: a refusal leaves the receiver where it was
-    if (closes > 0) {
-        if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)closes * n))) return rc;
-        if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)closes * n);
-        else rc = scratch_reserve(ctx, ctx->rx_sym, (size_t)std::min<int64_t>(chunk, closes) * frame);
-        if (rc) return rc;
-    }
+    size_t scratch = 0;
+    if ((rc = rx_decode_reserve(ctx, closes, n, frame, fused, chunk, &scratch))) return rc;
     if ((rc = rx_winners(rx, pl))) return rc;
-    DecodeArgs d{};
-    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
-    uint8_t *er = (uint8_t *)ctx->rx_er.p;
-    auto slots = [&](int first, int count) {   // the result arrays of closed slots first .. first + count - 1
-        d.nframes = count;
-        d.erased = er + (size_t)first * n;
-        d.out = out + (size_t)first * frame;
-        d.sweeps = sweeps ? sweeps + first : nullptr; d.residual = residual ? residual + first : nullptr;
-        d.status = status ? status + first : nullptr;
-        d.erased_out = erased_out ? erased_out + (size_t)first * n : nullptr;
-        d.residual_src = residual_src ? residual_src + first : nullptr;
-    };
-    if (closes > 0 && fused) {
-        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
+    const PacketRows pin{nullptr, packets, rx->stage_sym, S + kHdr};
+    auto sources = [&](uint32_t *src, uint8_t *er) -> int {
         hipLaunchKernelGGL(fec_rx_sources, dim3(grid_for((int64_t)closes * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
                            rx->stage_er, n, rx->cb, closes, src, er);
         LDPC_HIP_TRY(ctx, hipGetLastError());
-        slots(0, closes);
-        d.sym = nullptr;
-        d.pin.src = src; d.pin.packets = packets; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
-        if ((rc = launch_decode(ctx, d))) return rc;
-    } else if (closes > 0) {
-        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
-        for (int first = 0; first < closes; first += (int)chunk) {
-            const int count = (int)std::min<int64_t>(chunk, closes - first);
-            if ((rc = rx_move<true>(rx, pl, packets, first, count, sym, er + (size_t)first * n))) return rc;
-            slots(first, count);
-            d.sym = sym;
-            if ((rc = launch_decode(ctx, d))) return rc;
-        }
-    }
+        return LDPC_AMD_OK;
+    };
+    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return rx_move<true>(rx, pl, packets, first, count, sym, er); };
+    int launches = 0;
+    if ((rc = rx_decode_slots(ctx, d, o, closes, chunk, fused, pin, sources, gather, &launches))) return rc;
     if ((rc = rx_move<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
     rx_commit(rx, pl, blocks, consumed);
     ctx->receiver_path = fused ? 1 : 2;
@@ -1288,8 +1235,8 @@ int ldpc_amd_fec_rx_dev_decode_flush(ldpc_amd_fec_rx_dev *rx, int code, int max_
     if (!rx) return LDPC_AMD_EINVAL;
     ldpc_amd_ctx *ctx = rx->ctx;
     int rc;
-    if ((rc = rx_decode_check(ctx, rx, "fec_rx_dev_decode_flush", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src)))
-        return rc;
+    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
+    if ((rc = rx_decode_check(ctx, rx, "fec_rx_dev_decode_flush", code, max_sweeps, o))) return rc;
     const size_t frame = (size_t)rx->n * rx->S;
     if ((rc = scratch_reserve(ctx, ctx->rx_sym, frame)) || (rc = scratch_reserve(ctx, ctx->rx_er, (size_t)rx->n))) return rc;
     if ((rc = ldpc_amd_fec_rx_dev_flush(rx, (uint8_t *)ctx->rx_sym.p, (uint8_t *)ctx->rx_er.p, block_out)) != 1) return rc;
@@ -1329,13 +1276,7 @@ struct ldpc_amd_fec_rx_flows {
     FlowTab *tab_dev = nullptr, *tab_host = nullptr;   // [nflows]
     int32_t *res_host = nullptr;    // pinned copy of res
     size_t res_host_cap = 0;
-    // the batch flush (allocated by its first call): the closed slots' planes on the device, [2 nflows], and their pinned staging --
-    // two slots used in turn, each with the event of its last copy, so that a slot is never rewritten under a copy in flight
-    int32_t *fl_dev = nullptr;
-    int32_t *fl_host[2] = {nullptr, nullptr};
-    hipEvent_t fl_event[2] = {nullptr, nullptr};
-    bool fl_pending[2] = {false, false};
-    unsigned fl_calls = 0;
+    RxPlaneUpload fl;   // the batch flush: the closed slots' planes on the device, [2 nflows]
 };
 
 // One call's PLAN for all flows: (a) + (b), ONE read-back, the slot bases.  Nothing of any flow's state changes before flows_commit.
@@ -1629,14 +1570,13 @@ void ldpc_amd_fec_rx_flows_destroy(ldpc_amd_fec_rx_flows *rx)
     Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots, &rx->order};
     for (Scratch *s : sc)
         if (s->p) (void)hipFree(s->p);
-    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev, rx->fl_dev};
+    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *host[] = {rx->in_host, rx->tab_host, rx->res_host, rx->fl_host[0], rx->fl_host[1]};
+    void *host[] = {rx->in_host, rx->tab_host, rx->res_host};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : rx->fl_event)
-        if (e) (void)hipEventDestroy(e);
+    rx_upload_free(rx->fl);
     delete rx;
 }
 
@@ -1746,7 +1686,8 @@ static int flows_decode(ldpc_amd_fec_rx_flows *rx, const char *who, int code, co
         flows_nothing(rx, closes, consumed, offered);
         return 0;
     }
-    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
+    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, o))) return rc;
     if (!packets || !is_device_ptr(ctx, packets))
         return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets must be a device pointer of device %d", who, ctx->device);
     if (mixed && (rc = flows_check_mixed(rx, who, src.flow_of, left))) return rc;
@@ -1758,46 +1699,21 @@ static int flows_decode(ldpc_amd_fec_rx_flows *rx, const char *who, int code, co
     FlowsPlan pl;
     if ((rc = flows_plan(rx, who, packets, src, P, max_blocks_per_flow, pl))) return rc;
     const int T = pl.T;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kReceiverScratchMax / frame)));
-    // every workspace of the call before anything moves: a refusal leaves every flow where it was
-    if (T > 0) {
-        if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)T * n))) return rc;
-        if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)T * n);
-        else rc = scratch_reserve(ctx, ctx->rx_sym, (size_t)chunk * frame);
-        if (rc) return rc;
-    }
+    const int64_t chunk = rx_chunk(T, frame);
+    size_t scratch = 0;
+    if ((rc = rx_decode_reserve(ctx, T, n, frame, fused, chunk, &scratch))) return rc;
     if ((rc = flows_winners(rx, pl))) return rc;
-    DecodeArgs d{};
-    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
-    uint8_t *er = (uint8_t *)ctx->rx_er.p;
-    auto slots = [&](int first, int count) {   // the result arrays of closed slots first .. first + count - 1
-        d.nframes = count;
-        d.erased = er + (size_t)first * n;
-        d.out = out + (size_t)first * frame;
-        d.sweeps = sweeps ? sweeps + first : nullptr; d.residual = residual ? residual + first : nullptr;
-        d.status = status ? status + first : nullptr;
-        d.erased_out = erased_out ? erased_out + (size_t)first * n : nullptr;
-        d.residual_src = residual_src ? residual_src + first : nullptr;
-    };
-    if (T > 0 && fused) {
-        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
+    const PacketRows pin{nullptr, packets, rx->stage_sym, S + kHdr};
+    auto sources = [&](uint32_t *rows, uint8_t *er) -> int {
         hipLaunchKernelGGL(fec_rx_sources_flows, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
-                           rx->stage_er, rx->tab_dev, (const int32_t *)rx->slots.p, n, T, src, er);
+                           rx->stage_er, rx->tab_dev, (const int32_t *)rx->slots.p, n, T, rows, er);
         LDPC_HIP_TRY(ctx, hipGetLastError());
-        slots(0, T);
-        d.sym = nullptr;
-        d.pin.src = src; d.pin.packets = packets; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
-        if ((rc = launch_decode(ctx, d))) return rc;
-    } else if (T > 0) {
-        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
-        for (int first = 0; first < T; first += (int)chunk) {
-            const int count = (int)std::min<int64_t>(chunk, T - first);
-            if ((rc = flows_move<true>(rx, pl, packets, first, count, sym, er + (size_t)first * n))) return rc;
-            slots(first, count);
-            d.sym = sym;
-            if ((rc = launch_decode(ctx, d))) return rc;
-        }
-    }
+        return LDPC_AMD_OK;
+    };
+    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return flows_move<true>(rx, pl, packets, first, count, sym, er); };
+    int launches = 0;
+    if ((rc = rx_decode_slots(ctx, d, o, T, chunk, fused, pin, sources, gather, &launches))) return rc;
     if ((rc = flows_move<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
     if ((rc = flows_left(rx, pl, P, left))) return rc;
     flows_commit(rx, pl, blocks, closes, consumed, P, offered);
@@ -1838,8 +1754,8 @@ int ldpc_amd_fec_rx_flows_decode_flush(ldpc_amd_fec_rx_flows *rx, int flow, int 
     if (flow < 0 || flow >= rx->nflows)
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rx_flows_decode_flush: no flow %d (nflows = %d)", flow, rx->nflows);
     int rc;
-    if ((rc = rx_decode_check(ctx, rx, "fec_rx_flows_decode_flush", code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src)))
-        return rc;
+    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
+    if ((rc = rx_decode_check(ctx, rx, "fec_rx_flows_decode_flush", code, max_sweeps, o))) return rc;
     const size_t frame = (size_t)rx->n * rx->S;
     if ((rc = scratch_reserve(ctx, ctx->rx_sym, frame)) || (rc = scratch_reserve(ctx, ctx->rx_er, (size_t)rx->n))) return rc;
     if ((rc = ldpc_amd_fec_rx_flows_flush(rx, flow, (uint8_t *)ctx->rx_sym.p, (uint8_t *)ctx->rx_er.p, block_out)) != 1) return rc;
@@ -1911,37 +1827,6 @@ static int flush_plan(const ldpc_amd_fec_rx_flows *rx, const char *who, const in
     return LDPC_AMD_OK;
 }
 
-// the object's descriptor buffers (first call), then the planes of the T slots to the device through the pinned slot of this call
-static int flush_upload(ldpc_amd_fec_rx_flows *rx, const char *who, const FlushPlan &pl)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const size_t cap = sizeof(int32_t) * 2 * (size_t)rx->nflows;
-    if (!rx->fl_dev) {
-        hipError_t e = hipMalloc((void **)&rx->fl_dev, cap);
-        for (int s = 0; s < 2 && e == hipSuccess; s++) {
-            if (!rx->fl_host[s]) e = hipHostMalloc((void **)&rx->fl_host[s], cap, hipHostMallocDefault);
-            if (e == hipSuccess && !rx->fl_event[s]) e = hipEventCreateWithFlags(&rx->fl_event[s], hipEventDisableTiming);
-        }
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            if (rx->fl_dev) (void)hipFree(rx->fl_dev);
-            rx->fl_dev = nullptr;   // (what the slots got is kept: the next call asks for the rest)
-            return set_error(ctx, LDPC_AMD_ENOMEM, "%s: no memory for the slot descriptors: %s", who, hipGetErrorString(e));
-        }
-    }
-    const int slot = (int)(rx->fl_calls & 1u);
-    if (rx->fl_pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
-        LDPC_HIP_TRY(ctx, hipEventSynchronize(rx->fl_event[slot]));
-        rx->fl_pending[slot] = false;
-    }
-    memcpy(rx->fl_host[slot], pl.planes.data(), sizeof(int32_t) * (size_t)pl.T);
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->fl_dev, rx->fl_host[slot], sizeof(int32_t) * (size_t)pl.T, hipMemcpyHostToDevice, ctx->stream));
-    LDPC_HIP_TRY(ctx, hipEventRecord(rx->fl_event[slot], ctx->stream));
-    rx->fl_pending[slot] = true;
-    rx->fl_calls++;
-    return LDPC_AMD_OK;
-}
-
 // the piece of the plane kernels: the widest of 16, 4, 1 bytes that divides S and that `p` (null: the planes alone) is aligned to
 static int flush_piece(int S, const void *p)
 {
@@ -1956,9 +1841,9 @@ static int flush_gather(ldpc_amd_fec_rx_flows *rx, int first, int count, uint8_t
     const int n = rx->n, S = rx->S, W = flush_piece(S, sym);
     const int64_t upp = (int64_t)n * S / W;
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((upp + kThreads - 1) / kThreads, 256)), (unsigned)count);
-    if (W == 16) hipLaunchKernelGGL(fec_rx_flush_gather<16>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, sym, er);
-    else if (W == 4) hipLaunchKernelGGL(fec_rx_flush_gather<4>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, sym, er);
-    else hipLaunchKernelGGL(fec_rx_flush_gather<1>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S, first, sym, er);
+    if (W == 16) hipLaunchKernelGGL(fec_rx_flush_gather<16>, grid, dim3(kThreads), 0, ctx->stream, rx->fl.dev, rx->stage_sym, rx->stage_er, n, S, first, sym, er);
+    else if (W == 4) hipLaunchKernelGGL(fec_rx_flush_gather<4>, grid, dim3(kThreads), 0, ctx->stream, rx->fl.dev, rx->stage_sym, rx->stage_er, n, S, first, sym, er);
+    else hipLaunchKernelGGL(fec_rx_flush_gather<1>, grid, dim3(kThreads), 0, ctx->stream, rx->fl.dev, rx->stage_sym, rx->stage_er, n, S, first, sym, er);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     return LDPC_AMD_OK;
 }
@@ -1969,9 +1854,9 @@ static int flush_reset(ldpc_amd_fec_rx_flows *rx, int T)
     const int n = rx->n, S = rx->S, W = flush_piece(S, nullptr);
     const int64_t upp = (int64_t)n * S / W;
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((upp + kThreads - 1) / kThreads, 256)), (unsigned)T);
-    if (W == 16) hipLaunchKernelGGL(fec_rx_flush_reset<16>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S);
-    else if (W == 4) hipLaunchKernelGGL(fec_rx_flush_reset<4>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S);
-    else hipLaunchKernelGGL(fec_rx_flush_reset<1>, grid, dim3(kThreads), 0, ctx->stream, rx->fl_dev, rx->stage_sym, rx->stage_er, n, S);
+    if (W == 16) hipLaunchKernelGGL(fec_rx_flush_reset<16>, grid, dim3(kThreads), 0, ctx->stream, rx->fl.dev, rx->stage_sym, rx->stage_er, n, S);
+    else if (W == 4) hipLaunchKernelGGL(fec_rx_flush_reset<4>, grid, dim3(kThreads), 0, ctx->stream, rx->fl.dev, rx->stage_sym, rx->stage_er, n, S);
+    else hipLaunchKernelGGL(fec_rx_flush_reset<1>, grid, dim3(kThreads), 0, ctx->stream, rx->fl.dev, rx->stage_sym, rx->stage_er, n, S);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     return LDPC_AMD_OK;
 }
@@ -2027,7 +1912,9 @@ int ldpc_amd_fec_rx_flows_flush_many(ldpc_amd_fec_rx_flows *rx, const int32_t *f
         if (closes) std::fill(closes, closes + pl.sel.size(), 0);
         return 0;
     }
-    if ((rc = flush_upload(rx, who, pl)) || (rc = flush_gather(rx, 0, pl.T, sym_batch, erased_batch)) || (rc = flush_reset(rx, pl.T))) return rc;
+    if ((rc = rx_upload_planes(ctx, who, rx->fl, 2 * (size_t)rx->nflows, pl.planes.data(), pl.T)) ||
+        (rc = flush_gather(rx, 0, pl.T, sym_batch, erased_batch)) || (rc = flush_reset(rx, pl.T)))
+        return rc;
     flush_commit(rx, pl, blocks, closes, 3, sizeof(int32_t) * (size_t)pl.T, 0);
     return pl.T;
 }
@@ -2042,7 +1929,8 @@ int ldpc_amd_fec_rx_flows_decode_flush_many(ldpc_amd_fec_rx_flows *rx, int code,
     FlushPlan pl;
     int rc;
     if ((rc = flush_plan(rx, who, flows, nsel, rounds, pl))) return rc;
-    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, out, sweeps, residual, status, erased_out, residual_src))) return rc;
+    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
+    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, o))) return rc;
     const int T = pl.T;
     if (T == 0) {
         if (closes) std::fill(closes, closes + pl.sel.size(), 0);
@@ -2053,51 +1941,25 @@ int ldpc_amd_fec_rx_flows_decode_flush_many(ldpc_amd_fec_rx_flows *rx, int code,
     // (word-sized symbols take the composed form: the header says why)
     const bool fused = ctx->knobs.rx_pkt != 0 && S % 16 == 0 && decode_reads_packets(ctx, cd, S);
     const size_t frame = (size_t)n * S;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kReceiverScratchMax / frame)));
-    // every workspace of the call before anything moves: a refusal leaves every flow where it was
-    if ((rc = scratch_reserve(ctx, ctx->rx_er, (size_t)T * n))) return rc;
-    if (fused) rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)T * n);
-    else rc = scratch_reserve(ctx, ctx->rx_sym, (size_t)chunk * frame);
-    if (rc) return rc;
-    if ((rc = flush_upload(rx, who, pl))) return rc;
-    DecodeArgs d{};
-    d.code = cd; d.S = S; d.in_rows = n; d.max_sweeps = max_sweeps; d.do_ml = do_ml ? 1 : 0;
-    uint8_t *er = (uint8_t *)ctx->rx_er.p;
-    auto slots = [&](int first, int count) {   // the result arrays of closed slots first .. first + count - 1
-        d.nframes = count;
-        d.erased = er + (size_t)first * n;
-        d.out = out + (size_t)first * frame;
-        d.sweeps = sweeps ? sweeps + first : nullptr; d.residual = residual ? residual + first : nullptr;
-        d.status = status ? status + first : nullptr;
-        d.erased_out = erased_out ? erased_out + (size_t)first * n : nullptr;
-        d.residual_src = residual_src ? residual_src + first : nullptr;
-    };
-    int launches = 0;
-    if (fused) {
-        uint32_t *src = (uint32_t *)ctx->rx_src.p;
-        hipLaunchKernelGGL(fec_rx_flush_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl_dev,
+    const int64_t chunk = rx_chunk(T, frame);
+    size_t scratch = 0;
+    if ((rc = rx_decode_reserve(ctx, T, n, frame, fused, chunk, &scratch))) return rc;
+    if ((rc = rx_upload_planes(ctx, who, rx->fl, 2 * (size_t)rx->nflows, pl.planes.data(), pl.T))) return rc;
+    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
+    // no word of the table names a packet (fec_rx_flush_sources), so the packet base is never added to: any valid aligned address
+    const PacketRows pin{nullptr, rx->stage_sym, rx->stage_sym, S + kHdr};
+    auto sources = [&](uint32_t *src, uint8_t *er) -> int {
+        hipLaunchKernelGGL(fec_rx_flush_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl.dev,
                            (const uint8_t *)rx->stage_er, n, T, src, er);
         LDPC_HIP_TRY(ctx, hipGetLastError());
-        slots(0, T);
-        d.sym = nullptr;
-        // no word of the table names a packet (fec_rx_flush_sources), so the packet base is never added to: any valid aligned address
-        d.pin.src = src; d.pin.packets = rx->stage_sym; d.pin.stage = rx->stage_sym; d.pin.plen = S + kHdr;
-        if ((rc = launch_decode(ctx, d))) return rc;
-        launches = 1;
-    } else {
-        uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
-        for (int first = 0; first < T; first += (int)chunk) {
-            const int count = (int)std::min<int64_t>(chunk, T - first);
-            if ((rc = flush_gather(rx, first, count, sym, er + (size_t)first * n))) return rc;
-            slots(first, count);
-            d.sym = sym;
-            if ((rc = launch_decode(ctx, d))) return rc;
-            launches++;
-        }
-    }
+        return LDPC_AMD_OK;
+    };
+    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return flush_gather(rx, first, count, sym, er); };
+    int launches = 0;
+    if ((rc = rx_decode_slots(ctx, d, o, T, chunk, fused, pin, sources, gather, &launches))) return rc;
     if ((rc = flush_reset(rx, T))) return rc;
     flush_commit(rx, pl, blocks, closes, fused ? 1 : 2,
-                 (fused ? sizeof(uint32_t) * (size_t)T * n : (size_t)chunk * frame) + (size_t)T * n + sizeof(int32_t) * (size_t)T, launches);
+                 (fused ? sizeof(uint32_t) * (size_t)T * n : scratch) + (size_t)T * n + sizeof(int32_t) * (size_t)T, launches);
     return T;
 }
 
