@@ -40,8 +40,8 @@
  * code, S, knobs and alignment of `packets` (decode_flush_many: where S is a multiple of 16 as well); else COMPOSED through the
  * context's received-symbol scratch of at most 256 MiB, in chunks of slots, one decoder launch per chunk.
  *
- * Out of scope: packets interleaved with a per-packet flow number (push_mixed / decode_mixed of
- * ldpc_erasure_amd_flows_mixed.h); segment the packets by flow before the call.
+ * Out of scope of this header: packets interleaved with a per-packet flow number (push_mixed / decode_mixed):
+ * ldpc_erasure_amd_rx_window_flows_mixed.h.
  */
 #ifndef LDPC_ERASURE_AMD_RX_WINDOW_FLOWS_H
 #define LDPC_ERASURE_AMD_RX_WINDOW_FLOWS_H

@@ -119,6 +119,8 @@ EXPORTS_RX_WINDOW_FLOWS = [
     "ldpc_amd_fec_rxw_flows_info",
 ]
 WindowFlowsPending = collections.namedtuple("WindowFlowsPending", "base cnt blocks")
+# every symbol include/ldpc_erasure_amd_rx_window_flows_mixed.h declares (the windowed multi-flow receiver fed with interleaved packets)
+EXPORTS_RX_WINDOW_FLOWS_MIXED = ["ldpc_amd_fec_rxw_flows_push_mixed", "ldpc_amd_fec_rxw_flows_decode_mixed", "ldpc_amd_fec_rxw_flows_unrouted"]
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
@@ -331,6 +333,12 @@ def load_library():
         L.ldpc_amd_fec_rxw_flows_dropped.argtypes = [vp, i32]
         L.ldpc_amd_fec_rxw_flows_dropped.restype = i64
         L.ldpc_amd_fec_rxw_flows_info.argtypes = [vp, C.POINTER(i64)]
+    # ... fed with interleaved packets (include/ldpc_erasure_amd_rx_window_flows_mixed.h)
+    if hasattr(L, "ldpc_amd_fec_rxw_flows_push_mixed"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_rxw_flows_push_mixed.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]
+        L.ldpc_amd_fec_rxw_flows_decode_mixed.argtypes = [vp, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+        L.ldpc_amd_fec_rxw_flows_unrouted.argtypes = [vp]
+        L.ldpc_amd_fec_rxw_flows_unrouted.restype = i64
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -1558,7 +1566,8 @@ class FecRxWindowFlows:
     by flow -- flow f owns the packets flow_begin[f] .. flow_begin[f+1]-1 -- is planned for all flows at once (one wavefront per flow)
     and read back once, and every block that closed, of every flow, is decoded in one launch.  Flow f behaves exactly like a
     FecRxWindowHost fed its segment with max_blocks = max_blocks_per_flow.  The closed blocks come out dense in flow order: flow f's
-    start at closes[:f].sum().  Close it before its Context."""
+    start at closes[:f].sum().  push_mixed / decode_mixed take the packets in arrival order with a flow number each instead
+    (include/ldpc_erasure_amd_rx_window_flows_mixed.h) and return the same; all calls mix freely.  Close it before its Context."""
 
     def __init__(self, ctx, nflows, n, k, S, window=4, ahead_limit=10):
         self._ctx, self._L = ctx, ctx._L
@@ -1569,6 +1578,7 @@ class FecRxWindowFlows:
     _device = FecRxWindow._device
     _frames = FecRxWindow._frames
     _segments = FecRxFlows._segments
+    _mixed = FecRxFlows._mixed
 
     def push_many(self, packets, flow_begin, max_blocks_per_flow):
         """packets: torch uint8 [P][8+S] on the device, flow_begin: nflows + 1 packet indices.  Returns (closes int32 [nflows],
@@ -1593,6 +1603,38 @@ class FecRxWindowFlows:
             _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
             "fec_rxw_flows_decode_many")
         return closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed
+
+    def push_mixed(self, packets, flow_of, max_blocks_per_flow, want_left=False):
+        """push_many for packets in arrival order (include/ldpc_erasure_amd_rx_window_flows_mixed.h): packets torch uint8 [P][8+S],
+        flow_of torch int32 [P] on the device, flow_of[p] = the flow of packet p (outside 0 .. nflows-1: no flow, ignored and counted
+        in `unrouted`).  Returns push_many's tuple for the per-flow segments, then offered int64 [nflows] (packets of each flow), then
+        -- want_left -- left torch uint8 [P]: 1 for the packets behind their flow's consumed prefix, to be submitted again."""
+        import torch
+        P, slots, blocks, closes, consumed, offered, pp, fp, left = self._mixed(packets, flow_of, max_blocks_per_flow, want_left)
+        sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=packets.device)
+        er = torch.empty((slots, self.n), dtype=torch.uint8, device=packets.device)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_push_mixed(
+            self._h, pp, fp, P, _ptr(sym), _ptr(er), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data,
+            offered.ctypes.data, _ptr(left) if want_left else None), "fec_rxw_flows_push_mixed")
+        r = (closes, blocks[:T], sym[:T], er[:T], consumed, offered)
+        return r + (left[:P],) if want_left else r
+
+    def decode_mixed(self, code, packets, flow_of, max_blocks_per_flow, max_sweeps=10, do_ml=1, want_left=False):
+        """decode_many for packets in arrival order with a flow number each (push_mixed): decode_many's tuple, then offered (and left
+        when asked).  No payload byte is copied to sort the packets: only their indices are partitioned by flow."""
+        P, slots, blocks, closes, consumed, offered, pp, fp, left = self._mixed(packets, flow_of, max_blocks_per_flow, want_left)
+        fr = self._frames(slots)
+        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_decode_mixed(
+            self._h, code, pp, fp, P, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status),
+            _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data,
+            offered.ctypes.data, _ptr(left) if want_left else None), "fec_rxw_flows_decode_mixed")
+        r = (closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed, offered)
+        return r + (left[:P],) if want_left else r
+
+    @property
+    def unrouted(self):
+        """packets of no flow the mixed calls were given so far"""
+        return int(self._L.ldpc_amd_fec_rxw_flows_unrouted(self._h))
 
     def pending(self):
         """WindowFlowsPending(base int32 [nflows] (-1: the flow has not started), cnt int32 [nflows][window]: packets every open slot

@@ -15,6 +15,13 @@
 // Order of (e).  A new serial s >= W takes over the plane of serial s - W of the same flow, a block (d) or the fused decode may still
 // read: (e) stands behind both on the stream.  Inside (e) nothing is read from the planes: a work item writes its own piece of its
 // own plane (W distinct planes per flow) from a packet or with zero, or leaves a carried row alone.
+// Mixed calls (include/ldpc_erasure_amd_rx_window_flows_mixed.h): the packets lie in arrival order with a flow number each.  The
+// plan runs on the PERMUTATION order[] that csrc/flows_demux_dev.h makes of the packet indices (flow by flow, arrival order inside a
+// flow; the bases kernel writes every flow's begin / len into its WFlowIn on the device):
+//   (a') rxwf_headers_idx   dense[q] = header word of packets[order[q]], q below the routed count (read from the device word)
+//   (b)  rxw_scan_flows     unchanged, on the positions q; the nflows + 1 flow bases ride back behind the scan records in the ONE copy
+//   (c') rxwf_winners<true> atomicMax of the packet index order[begin + q]: the table holds packet indices, as in a segmented call
+//   (d), (e), the flush     unchanged;  rxwf_left marks the packets behind every flow's consumed prefix through order[]
 // Flush: planned from the host mirror alone, one int32 plane number per handed-out slot (wire_dev.hip's batch flush).
 // The host code every device receiver needs -- the argument check and the decode tail of the decode calls, the host mirror of a
 // flow's window, the upload of the flush's plane numbers -- is csrc/rx_host.h.
@@ -29,8 +36,10 @@
 
 #include "../../include/ldpc_erasure_amd_rx_window.h"
 #include "../../include/ldpc_erasure_amd_rx_window_flows.h"
+#include "../../include/ldpc_erasure_amd_rx_window_flows_mixed.h"
 #define LDPC_AMD_RX_HOST_WINDOWED
 #include "rx_host.h"   // and with it rx_window_scan_dev.h
+#include "flows_demux_dev.h"   // the partition of a mixed call, and kMaxFlows
 
 using namespace ldpc_amd;
 
@@ -38,7 +47,6 @@ namespace {
 
 constexpr int kHdr = 8;   // LDPC_AMD_FEC_HEADER_BYTES
 constexpr int kThreads = 256;
-constexpr int kMaxFlows = 4096;
 
 inline unsigned grid_for(int64_t items)
 {
@@ -59,13 +67,29 @@ __global__ __launch_bounds__(kThreads) void rxwf_headers(const uint8_t *__restri
     }
 }
 
+// (a) of a mixed call, on the permutation: dense[q] = the header word of packets[order[q]] for the *routed positions q -- the word the
+// partition's bases kernel wrote, so no count comes back to the host in between
+template <bool ALIGNED4>
+__global__ __launch_bounds__(kThreads) void rxwf_headers_idx(const uint8_t *__restrict__ packets, const uint32_t *__restrict__ order,
+                                                            const uint32_t *__restrict__ routed, int plen, uint32_t *__restrict__ dense)
+{
+    const int64_t nq = *routed;
+    for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < nq; q += (int64_t)gridDim.x * kThreads) {
+        const uint8_t *h = packets + (int64_t)order[q] * plen;
+        uint32_t w;
+        if (ALIGNED4) w = *reinterpret_cast<const uint32_t *>(h) & 0x00ffffffu;
+        else w = (uint32_t)h[0] | (uint32_t)h[1] << 8 | (uint32_t)h[2] << 16;
+        dense[q] = w;
+    }
+}
+
 struct WFlowIn {    // written by the host before the plan: the flow's segment and the state its scan starts from
-    int64_t begin, len;
+    int64_t begin, len;   // (a mixed call: written by the partition, fec_demux_bases, in positions of the permutation)
     int base, ahead;
     int cnt[kMaxW];
 };
 struct WFlowTab {   // written by the host behind the plan
-    int64_t begin, used;   // the packets the flow consumed: begin .. begin + used - 1
+    int64_t begin, used;   // the packets the flow consumed: begin .. begin + used - 1 (a mixed call: positions of the permutation)
     int base, closes, head, pad;   // base: the flow's first closed slot
 };
 
@@ -92,8 +116,15 @@ __global__ __launch_bounds__(64) void rxwf_flow_slots(const WFlowTab *__restrict
 }
 
 // (c) grid: (x, nflows); over each flow's consumed prefix only.  The packet index is the global one: the last copy wins, as on the host.
+// MIXED: dense and dest are indexed by the POSITION p of the permutation, and the table takes the packet index order[p] -- what
+// everything behind the table reads -- so no second pass over the (T + W nflows) n cells translates it afterwards.  That keeps the
+// rule: a cell is only ever offered positions of ONE flow (its row belongs to the flow), the partition is stable, so order[] is
+// strictly increasing inside a flow's segment, and the maximum over the packet indices is the packet at the maximum position -- the
+// last copy in arrival order.
+template <bool MIXED>
 __global__ __launch_bounds__(kThreads) void rxwf_winners(const uint32_t *__restrict__ dense, const int32_t *__restrict__ dest,
-                                                        const WFlowTab *__restrict__ tab, int n, int W, int T, int32_t *__restrict__ win)
+                                                        const WFlowTab *__restrict__ tab, const uint32_t *__restrict__ order, int n, int W, int T,
+                                                        int32_t *__restrict__ win)
 {
     const WFlowTab f = tab[blockIdx.y];
     for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < f.used; q += (int64_t)gridDim.x * kThreads) {
@@ -101,8 +132,19 @@ __global__ __launch_bounds__(kThreads) void rxwf_winners(const uint32_t *__restr
         const int s = dest[p];
         if (s < 0) continue;   // dest >= 0 only for symbol < n, and s < closes + W
         const int64_t row = s < f.closes ? (int64_t)f.base + s : (int64_t)T + (int64_t)W * blockIdx.y + (s - f.closes);
-        atomicMax(&win[row * n + (dense[p] & 0xffffu)], (int32_t)p);
+        atomicMax(&win[row * n + (dense[p] & 0xffffu)], MIXED ? (int32_t)order[p] : (int32_t)p);   // a packet index is below 2^31
     }
+}
+
+// left[p] = 1 for the packets behind a flow's consumed prefix (the caller has zeroed left); grid: (x, nflows).  in[f].len is the
+// partition's: the packets of flow f in the call.
+__global__ __launch_bounds__(kThreads) void rxwf_left(const WFlowTab *__restrict__ tab, const WFlowIn *__restrict__ in,
+                                                     const uint32_t *__restrict__ order, uint8_t *__restrict__ left)
+{
+    const WFlowTab f = tab[blockIdx.y];
+    const int64_t len = in[blockIdx.y].len;
+    for (int64_t q = f.used + (int64_t)blockIdx.x * kThreads + threadIdx.x; q < len; q += (int64_t)gridDim.x * kThreads)
+        left[order[f.begin + q]] = 1;
 }
 
 struct WFlowMoveArgs {
@@ -251,9 +293,10 @@ struct ldpc_amd_fec_rxw_flows {
     std::vector<int> base, head, ahead;
     std::vector<int> cnt;           // [nflows][W]
     std::vector<int64_t> totals;    // [nflows][5]
+    int64_t unrouted = 0;           // packets of no flow the mixed calls were given
     uint8_t *stage_sym = nullptr;   // [nflows][W][n][S]
     uint8_t *stage_er = nullptr;    // [nflows][W][n]
-    Scratch dense, dest, win, res, slots;   // per-call scratch, grown on demand
+    Scratch dense, dest, win, res, slots, order;   // per-call scratch, grown on demand (order: the mixed calls' partition, u32 [P])
     WFlowIn *in_dev = nullptr, *in_host = nullptr;      // [nflows]; the host copies are pinned
     WFlowTab *tab_dev = nullptr, *tab_host = nullptr;   // [nflows]
     int32_t *res_host = nullptr;    // pinned copy of res
@@ -270,11 +313,25 @@ struct WFlowsPlan {
     int T = 0;             // closed blocks of all flows
     int64_t max_used = 0;  // the longest consumed prefix
     size_t rec = 0;        // words of one flow's result record
+    // a mixed call (else null / 0): the partition, the flow bases as read back behind the scan records ([nflows + 1], the last one =
+    // the routed packets), the longest remainder behind a consumed prefix
+    const uint32_t *order = nullptr, *base = nullptr;
+    int64_t max_left = 0;
 };
 
 inline RxwMirror rxwf_mirror(Rx *rx, int f)
 {
     return RxwMirror{&rx->base[f], &rx->head[f], &rx->ahead[f], &rx->cnt[(size_t)f * rx->W], &rx->totals[(size_t)f * 5], rx->W};
+}
+
+int rxwf_check_limits(Rx *rx, const char *who, int64_t P, int max_blocks)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (P < 0 || P >= ((int64_t)1 << 31)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need fewer than 2^31 packets in all", who);
+    if (max_blocks < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need max_blocks_per_flow >= 1", who);
+    if ((int64_t)rx->nflows * max_blocks * rx->n >= ((int64_t)1 << 31) - 2)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows * max_blocks_per_flow * n must be below 2^31 - 2", who);
+    return LDPC_AMD_OK;
 }
 
 int rxwf_check_call(Rx *rx, const char *who, const int64_t *flow_begin, int max_blocks, int64_t &P)
@@ -284,30 +341,48 @@ int rxwf_check_call(Rx *rx, const char *who, const int64_t *flow_begin, int max_
     for (int f = 0; f < rx->nflows; f++)
         if (flow_begin[f + 1] < flow_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin decreases at flow %d", who, f);
     P = flow_begin[rx->nflows];
-    if (P >= ((int64_t)1 << 31)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need fewer than 2^31 packets in all", who);
-    if (max_blocks < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need max_blocks_per_flow >= 1", who);
-    if ((int64_t)rx->nflows * max_blocks * rx->n >= ((int64_t)1 << 31) - 2)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows * max_blocks_per_flow * n must be below 2^31 - 2", who);
+    return rxwf_check_limits(rx, who, P, max_blocks);
+}
+
+// Where the packets of a call are: segmented by the caller (flow_begin, host) or interleaved with a flow number each (flow_of, device)
+struct WFlowsSrc {
+    bool mixed = false;
+    const int64_t *flow_begin = nullptr;
+    const int32_t *flow_of = nullptr;
+};
+
+// the mixed calls' own arguments, P > 0 (the device is set)
+int rxwf_check_mixed(Rx *rx, const char *who, const int32_t *flow_of, const uint8_t *left)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (!flow_of || !is_device_ptr(ctx, flow_of))
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be a device pointer of device %d", who, ctx->device);
+    if ((uintptr_t)flow_of & 3) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be 4-byte aligned", who);
+    if (left && !is_device_ptr(ctx, left)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: left must be a device pointer of device %d", who, ctx->device);
     return LDPC_AMD_OK;
 }
 
-void rxwf_nothing(const Rx *rx, int *closes, int64_t *consumed)
+void rxwf_nothing(const Rx *rx, int *closes, int64_t *consumed, int64_t *offered)
 {
     if (closes) std::fill(closes, closes + rx->nflows, 0);
     if (consumed) std::fill(consumed, consumed + rx->nflows, (int64_t)0);
+    if (offered) std::fill(offered, offered + rx->nflows, (int64_t)0);
 }
 
-int rxwf_plan(Rx *rx, const char *who, const uint8_t *packets, const int64_t *flow_begin, int64_t npackets, int max_blocks, WFlowsPlan &pl)
+int rxwf_plan(Rx *rx, const char *who, const uint8_t *packets, const WFlowsSrc &src, int64_t npackets, int max_blocks, WFlowsPlan &pl)
 {
     ldpc_amd_ctx *ctx = rx->ctx;
     const int n = rx->n, nf = rx->nflows, W = rx->W;
     const int64_t plen = (int64_t)rx->S + kHdr;
+    const int64_t *flow_begin = src.flow_begin;
+    const bool mixed = src.mixed;
     pl.rec = (size_t)R_WORDS + (size_t)max_blocks;
-    const size_t res_bytes = sizeof(int32_t) * pl.rec * (size_t)nf;
+    const size_t res_bytes = sizeof(int32_t) * (pl.rec * (size_t)nf + (mixed ? (size_t)nf + 1 : 0));   // mixed: the flow bases behind the records
     int rc;
     if ((rc = scratch_reserve(ctx, rx->dense, sizeof(uint32_t) * (size_t)npackets)) ||
         (rc = scratch_reserve(ctx, rx->dest, sizeof(int32_t) * (size_t)npackets)) || (rc = scratch_reserve(ctx, rx->res, res_bytes)))
         return rc;
+    if (mixed && ((rc = scratch_reserve(ctx, rx->order, sizeof(uint32_t) * (size_t)npackets)) || (rc = demux_reserve(ctx, npackets, nf)))) return rc;
     if (rx->res_host_cap < res_bytes) {
         if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every plan ends with a synchronisation
         rx->res_host = nullptr;
@@ -319,12 +394,25 @@ int rxwf_plan(Rx *rx, const char *who, const uint8_t *packets, const int64_t *fl
     int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
     for (int f = 0; f < nf; f++) {   // (the copy of the previous call's records is behind that call's synchronisation)
         WFlowIn &in = rx->in_host[f];
-        in.begin = flow_begin[f]; in.len = flow_begin[f + 1] - flow_begin[f];
+        in.begin = mixed ? 0 : flow_begin[f]; in.len = mixed ? 0 : flow_begin[f + 1] - flow_begin[f];
         in.base = rx->base[f]; in.ahead = rx->ahead[f];
         for (int j = 0; j < kMaxW; j++) in.cnt[j] = j < W ? rx->cnt[(size_t)f * W + j] : 0;
     }
     LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->in_dev, rx->in_host, sizeof(WFlowIn) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-    if (plen % 4 == 0 && ((uintptr_t)packets & 3) == 0)
+    // (a) + (b): the plan; a mixed call's on the partition, which also fills in every flow's segment (begin, len) on the device
+    const bool aligned4 = plen % 4 == 0 && ((uintptr_t)packets & 3) == 0;
+    if (mixed) {
+        uint32_t *base = (uint32_t *)res + pl.rec * (size_t)nf, *order = (uint32_t *)rx->order.p;
+        if ((rc = demux_launch(ctx, src.flow_of, npackets, nf, base, rx->in_dev, order))) return rc;
+        if (aligned4)
+            hipLaunchKernelGGL(rxwf_headers_idx<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, (const uint32_t *)order,
+                               (const uint32_t *)base + nf, (int)plen, dense);
+        else
+            hipLaunchKernelGGL(rxwf_headers_idx<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, (const uint32_t *)order,
+                               (const uint32_t *)base + nf, (int)plen, dense);
+        pl.order = order;
+        pl.base = (const uint32_t *)rx->res_host + pl.rec * (size_t)nf;
+    } else if (aligned4)
         hipLaunchKernelGGL(rxwf_headers<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
     else
         hipLaunchKernelGGL(rxwf_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
@@ -342,9 +430,10 @@ int rxwf_plan(Rx *rx, const char *who, const uint8_t *packets, const int64_t *fl
             return set_error(ctx, LDPC_AMD_EHIP, "%s: the plan scan of flow %d hit its iteration cap (internal error); every flow's state is unchanged",
                              who, f);
         const int64_t used = word64(h, R_CONSUMED_LO);
-        rx->tab_host[f] = WFlowTab{flow_begin[f], used, (int)base, h[R_CLOSES], rx->head[f], 0};
+        rx->tab_host[f] = WFlowTab{mixed ? (int64_t)pl.base[f] : flow_begin[f], used, (int)base, h[R_CLOSES], rx->head[f], 0};
         base += h[R_CLOSES];
         pl.max_used = std::max(pl.max_used, used);
+        if (mixed) pl.max_left = std::max(pl.max_left, (int64_t)(pl.base[f + 1] - pl.base[f]) - used);
     }
     pl.T = (int)base;   // <= nflows * max_blocks < 2^31
     if ((rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)pl.T + (size_t)W * (size_t)nf) * (size_t)n)) ||
@@ -366,8 +455,26 @@ int rxwf_winners_launch(Rx *rx, const WFlowsPlan &pl)
     }
     LDPC_HIP_TRY(ctx, hipMemsetAsync(win, 0xff, sizeof(int32_t) * ((size_t)pl.T + (size_t)rx->W * (size_t)nf) * (size_t)rx->n, ctx->stream));   // -1: no packet
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pl.max_used + kThreads - 1) / kThreads, std::max(1, 32768 / nf)));
-    hipLaunchKernelGGL(rxwf_winners, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p, (const int32_t *)rx->dest.p,
-                       (const WFlowTab *)rx->tab_dev, rx->n, rx->W, pl.T, win);
+    if (pl.order)   // a mixed call planned on positions: the table takes the packet indices
+        hipLaunchKernelGGL(rxwf_winners<true>, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p, (const int32_t *)rx->dest.p,
+                           (const WFlowTab *)rx->tab_dev, pl.order, rx->n, rx->W, pl.T, win);
+    else
+        hipLaunchKernelGGL(rxwf_winners<false>, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p, (const int32_t *)rx->dest.p,
+                           (const WFlowTab *)rx->tab_dev, (const uint32_t *)nullptr, rx->n, rx->W, pl.T, win);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// a mixed call's `left` (may be null): zero, then 1 behind every flow's consumed prefix
+int rxwf_left_launch(Rx *rx, const WFlowsPlan &pl, int64_t npackets, uint8_t *left)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (!left) return LDPC_AMD_OK;
+    LDPC_HIP_TRY(ctx, hipMemsetAsync(left, 0, (size_t)npackets, ctx->stream));
+    if (pl.max_left <= 0) return LDPC_AMD_OK;
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pl.max_left + kThreads - 1) / kThreads, std::max(1, 32768 / rx->nflows)));
+    hipLaunchKernelGGL(rxwf_left, dim3(gx, rx->nflows), dim3(kThreads), 0, ctx->stream, (const WFlowTab *)rx->tab_dev, (const WFlowIn *)rx->in_dev,
+                       pl.order, left);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     return LDPC_AMD_OK;
 }
@@ -392,8 +499,13 @@ int rxwf_move_launch(Rx *rx, const WFlowsPlan &pl, const uint8_t *packets, int f
 }
 
 // every flow's mirror (base, head, ahead, cnt, totals) and the host outputs: the last step of a call
-void rxwf_commit(Rx *rx, const WFlowsPlan &pl, int *blocks, int *closes, int64_t *consumed)
+// (a mixed call: offered and the unrouted count too)
+void rxwf_commit(Rx *rx, const WFlowsPlan &pl, int *blocks, int *closes, int64_t *consumed, int64_t npackets, int64_t *offered)
 {
+    if (pl.base) {
+        rx->unrouted += npackets - (int64_t)pl.base[rx->nflows];
+        for (int f = 0; offered && f < rx->nflows; f++) offered[f] = (int64_t)(pl.base[f + 1] - pl.base[f]);
+    }
     for (int f = 0; f < rx->nflows; f++) {
         const int32_t *h = rx->res_host + (size_t)f * pl.rec;
         const WFlowTab &t = rx->tab_host[f];
@@ -517,7 +629,7 @@ void ldpc_amd_fec_rxw_flows_destroy(ldpc_amd_fec_rxw_flows *rx)
     if (!rx) return;
     (void)hipSetDevice(rx->ctx->device);
     (void)hipStreamSynchronize(rx->ctx->stream);   // pending work of this object may still use its buffers
-    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots};
+    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots, &rx->order};
     for (Scratch *s : sc)
         if (s->p) (void)hipFree(s->p);
     void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev};
@@ -565,31 +677,37 @@ int ldpc_amd_fec_rxw_flows_pending(const ldpc_amd_fec_rxw_flows *rx, int32_t *ba
     return total;
 }
 
-int ldpc_amd_fec_rxw_flows_push_many(ldpc_amd_fec_rxw_flows *rx, const uint8_t *packets, const int64_t *flow_begin, uint8_t *sym_batch,
-                                     uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+}  // extern "C"
+
+namespace {
+
+// push_many and push_mixed: P is the segmented call's flow_begin[nflows], or the mixed call's argument
+int rxwf_push(Rx *rx, const char *who, const uint8_t *packets, const WFlowsSrc &src, int64_t P, uint8_t *sym_batch, uint8_t *erased_batch,
+              int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed, int64_t *offered, uint8_t *left)
 {
     if (!rx) return LDPC_AMD_EINVAL;
     ldpc_amd_ctx *ctx = rx->ctx;
-    const char *who = "fec_rxw_flows_push_many";
+    const bool mixed = src.mixed;
     int rc;
-    int64_t P = 0;
-    if ((rc = rxwf_check_call(rx, who, flow_begin, max_blocks_per_flow, P))) return rc;
+    if ((rc = mixed ? rxwf_check_limits(rx, who, P, max_blocks_per_flow) : rxwf_check_call(rx, who, src.flow_begin, max_blocks_per_flow, P)))
+        return rc;
     if (!sym_batch || !erased_batch || (P > 0 && !packets))
         return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must not be null", who);
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((P > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
         return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must be device pointers of device %d", who, ctx->device);
     if (P == 0) {
-        rxwf_nothing(rx, closes, consumed);
+        rxwf_nothing(rx, closes, consumed, offered);
         return 0;
     }
+    if (mixed && (rc = rxwf_check_mixed(rx, who, src.flow_of, left))) return rc;
     WFlowsPlan pl;
-    if ((rc = rxwf_plan(rx, who, packets, flow_begin, P, max_blocks_per_flow, pl))) return rc;
+    if ((rc = rxwf_plan(rx, who, packets, src, P, max_blocks_per_flow, pl))) return rc;
     // (c), (d), (e): the data movement, asynchronous
     if ((rc = rxwf_winners_launch(rx, pl)) || (rc = rxwf_move_launch<true>(rx, pl, packets, 0, pl.T, sym_batch, erased_batch)) ||
-        (rc = rxwf_move_launch<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)))
+        (rc = rxwf_move_launch<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)) || (rc = rxwf_left_launch(rx, pl, P, left)))
         return rc;
-    rxwf_commit(rx, pl, blocks, closes, consumed);
+    rxwf_commit(rx, pl, blocks, closes, consumed, P, offered);
     return pl.T;
 }
 
@@ -597,32 +715,33 @@ int ldpc_amd_fec_rxw_flows_push_many(ldpc_amd_fec_rxw_flows *rx, const uint8_t *
 // itself (decode_reads_packets): (d) shrinks to rxwf_sources, the planes of all flows being one `stage` base.  Else COMPOSED: (d)
 // gathers chunk by chunk.  (e) is launched BEHIND the decode in both forms: it overwrites the staging planes of the carried blocks,
 // which the fused decode reads.
-int ldpc_amd_fec_rxw_flows_decode_many(ldpc_amd_fec_rxw_flows *rx, int code, const uint8_t *packets, const int64_t *flow_begin, int max_sweeps,
-                                       int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
-                                       int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+int rxwf_decode(Rx *rx, const char *who, int code, const uint8_t *packets, const WFlowsSrc &src, int64_t P, int max_sweeps, int do_ml, uint8_t *out,
+                int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src, int *blocks, int *closes,
+                int max_blocks_per_flow, int64_t *consumed, int64_t *offered, uint8_t *left)
 {
     if (!rx) return LDPC_AMD_EINVAL;
     ldpc_amd_ctx *ctx = rx->ctx;
-    const char *who = "fec_rxw_flows_decode_many";
     if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    const bool mixed = src.mixed;
     int rc;
-    int64_t P = 0;
-    if ((rc = rxwf_check_call(rx, who, flow_begin, max_blocks_per_flow, P))) return rc;
+    if ((rc = mixed ? rxwf_check_limits(rx, who, P, max_blocks_per_flow) : rxwf_check_call(rx, who, src.flow_begin, max_blocks_per_flow, P)))
+        return rc;
     if (P == 0) {
-        rxwf_nothing(rx, closes, consumed);
+        rxwf_nothing(rx, closes, consumed, offered);
         return 0;
     }
     const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
     if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, o))) return rc;
     if (!packets || !is_device_ptr(ctx, packets))
         return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets must be a device pointer of device %d", who, ctx->device);
+    if (mixed && (rc = rxwf_check_mixed(rx, who, src.flow_of, left))) return rc;
     const DevCode &cd = ctx->codes[code]->dev;
     const int n = rx->n, S = rx->S;
     const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
     const size_t frame = (size_t)n * S;
 
     WFlowsPlan pl;
-    if ((rc = rxwf_plan(rx, who, packets, flow_begin, P, max_blocks_per_flow, pl))) return rc;
+    if ((rc = rxwf_plan(rx, who, packets, src, P, max_blocks_per_flow, pl))) return rc;
     const int T = pl.T;
     const int64_t chunk = rx_chunk(T, frame);
     size_t scratch = 0;
@@ -640,10 +759,60 @@ int ldpc_amd_fec_rxw_flows_decode_many(ldpc_amd_fec_rxw_flows *rx, int code, con
     int launches = 0;
     if ((rc = rx_decode_slots(ctx, d, o, T, chunk, fused, pin, sources, gather, &launches))) return rc;
     if ((rc = rxwf_move_launch<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
-    rxwf_commit(rx, pl, blocks, closes, consumed);
+    if ((rc = rxwf_left_launch(rx, pl, P, left))) return rc;
+    rxwf_commit(rx, pl, blocks, closes, consumed, P, offered);
     ctx->rxwf_info[0] = fused ? 1 : 2; ctx->rxwf_info[1] = T; ctx->rxwf_info[2] = launches; ctx->rxwf_info[3] = (int64_t)scratch;
     return T;
 }
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_amd_fec_rxw_flows_push_many(ldpc_amd_fec_rxw_flows *rx, const uint8_t *packets, const int64_t *flow_begin, uint8_t *sym_batch,
+                                     uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+{
+    WFlowsSrc src;
+    src.flow_begin = flow_begin;
+    return rxwf_push(rx, "fec_rxw_flows_push_many", packets, src, 0, sym_batch, erased_batch, blocks, closes, max_blocks_per_flow, consumed, nullptr,
+                     nullptr);
+}
+
+int ldpc_amd_fec_rxw_flows_decode_many(ldpc_amd_fec_rxw_flows *rx, int code, const uint8_t *packets, const int64_t *flow_begin, int max_sweeps,
+                                       int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
+                                       int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
+{
+    WFlowsSrc src;
+    src.flow_begin = flow_begin;
+    return rxwf_decode(rx, "fec_rxw_flows_decode_many", code, packets, src, 0, max_sweeps, do_ml, out, sweeps, residual, status, erased_out,
+                       residual_src, blocks, closes, max_blocks_per_flow, consumed, nullptr, nullptr);
+}
+
+// ---- interleaved packets (include/ldpc_erasure_amd_rx_window_flows_mixed.h) ---------------------------------------------------------
+int ldpc_amd_fec_rxw_flows_push_mixed(ldpc_amd_fec_rxw_flows *rx, const uint8_t *packets, const int32_t *flow_of, int64_t P, uint8_t *sym_batch,
+                                      uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed,
+                                      int64_t *offered, uint8_t *left)
+{
+    WFlowsSrc src;
+    src.mixed = true;
+    src.flow_of = flow_of;
+    return rxwf_push(rx, "fec_rxw_flows_push_mixed", packets, src, P, sym_batch, erased_batch, blocks, closes, max_blocks_per_flow, consumed, offered,
+                     left);
+}
+
+int ldpc_amd_fec_rxw_flows_decode_mixed(ldpc_amd_fec_rxw_flows *rx, int code, const uint8_t *packets, const int32_t *flow_of, int64_t P,
+                                        int max_sweeps, int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status,
+                                        uint8_t *erased_out, int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow,
+                                        int64_t *consumed, int64_t *offered, uint8_t *left)
+{
+    WFlowsSrc src;
+    src.mixed = true;
+    src.flow_of = flow_of;
+    return rxwf_decode(rx, "fec_rxw_flows_decode_mixed", code, packets, src, P, max_sweeps, do_ml, out, sweeps, residual, status, erased_out,
+                       residual_src, blocks, closes, max_blocks_per_flow, consumed, offered, left);
+}
+
+int64_t ldpc_amd_fec_rxw_flows_unrouted(const ldpc_amd_fec_rxw_flows *rx) { return rx ? rx->unrouted : -1; }
 
 int ldpc_amd_fec_rxw_flows_flush_many(ldpc_amd_fec_rxw_flows *rx, const int32_t *flows, int nsel, uint8_t *sym_batch, uint8_t *erased_batch,
                                       int *blocks, int *closes)
