@@ -30,7 +30,8 @@
  * The re-anchor trusts the header of the packet that trips it: a foreign block number there mis-anchors the window until the
  * next trip (A + 1 further packets ahead of it).
  *
- * Out of scope here: many flows per object and their batch flush -- ldpc_erasure_amd_rx_window_flows.h has both.
+ * Out of scope here: many flows per object and their batch flush -- ldpc_erasure_amd_rx_window_flows.h has both; a wire whose
+ * blocks are interleaved -- ldpc_erasure_amd_interleave.h has the depth-D form of both objects (the ones here are its depth 1).
  */
 #ifndef LDPC_ERASURE_AMD_RX_WINDOW_H
 #define LDPC_ERASURE_AMD_RX_WINDOW_H

@@ -63,6 +63,12 @@ SENDER_PATHS = ("none", "fused", "composed")
 # every symbol include/ldpc_erasure_amd_sender_flows.h declares (the multi-flow sender: many FEC streams to one multiplexed wire)
 EXPORTS_SENDER_FLOWS = ["ldpc_amd_fec_tx_flows_layout", "ldpc_amd_fec_encode_packets_flows_dev", "ldpc_amd_fec_sender_flows_info"]
 TX_SEGMENTED, TX_ROUND_ROBIN = 0, 1   # LDPC_AMD_FEC_TX_SEGMENTED / LDPC_AMD_FEC_TX_ROUND_ROBIN
+# every symbol include/ldpc_erasure_amd_interleave.h declares (the block-interleaved wire: depth-D sender, depth-D windowed receivers)
+EXPORTS_INTERLEAVE = [
+    "ldpc_amd_fec_tx_ilv_layout", "ldpc_amd_fec_encode_packets_ilv_dev", "ldpc_amd_fec_sender_ilv_info", "ldpc_amd_fec_rxw_create_depth",
+    "ldpc_amd_fec_rxw_dev_create_depth", "ldpc_amd_fec_rxw_depth", "ldpc_amd_fec_rxw_dev_depth",
+]
+ILV_DEPTHS = (1, 2, 4, 8, 16)
 # every symbol include/ldpc_erasure_amd_receiver.h declares (the fused receiver: wire packets straight to decoded frames)
 EXPORTS_RECEIVER = ["ldpc_amd_fec_rx_dev_decode_many", "ldpc_amd_fec_rx_dev_decode_flush", "ldpc_amd_fec_receiver_info"]
 RECEIVER_PATHS = ("none", "fused", "composed")
@@ -319,6 +325,15 @@ def load_library():
         L.ldpc_amd_fec_rxw_dev_dropped.restype = i64
         L.ldpc_amd_fec_rxw_dev_state.argtypes = [vp, C.POINTER(i32), vp, C.POINTER(i64)]
         L.ldpc_amd_fec_rxw_info.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "ldpc_amd_fec_tx_ilv_layout"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_tx_ilv_layout.argtypes = [i64, i32, C.c_uint, i32, vp, vp]
+        L.ldpc_amd_fec_tx_ilv_layout.restype = i64
+        L.ldpc_amd_fec_encode_packets_ilv_dev.argtypes = [vp, i32, i32, i64, vp, C.c_uint, C.c_uint, i32, vp]
+        L.ldpc_amd_fec_sender_ilv_info.argtypes = [vp, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_create_depth.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+        L.ldpc_amd_fec_rxw_dev_create_depth.argtypes = [vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+        L.ldpc_amd_fec_rxw_depth.argtypes = [vp]
+        L.ldpc_amd_fec_rxw_dev_depth.argtypes = [vp]
     if hasattr(L, "ldpc_amd_fec_rxw_flows_create"):   # (absent from the older builds tools/ab_lib.py loads)
         L.ldpc_amd_fec_rxw_flows_create.argtypes = [vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
         L.ldpc_amd_fec_rxw_flows_destroy.argtypes = [vp]
@@ -394,6 +409,21 @@ def fec_tx_flows_layout(frame_begin, n, order):
     rc = L.ldpc_amd_fec_tx_flows_layout(fb.shape[0] - 1, fb.ctypes.data, n, order, first.ctypes.data, stride.ctypes.data)
     if rc < 0:
         raise LdpcAmdError(f"fec_tx_flows_layout = {rc}: bad nflows / frame_begin / n / order")
+    assert rc == F * n
+    return first, stride
+
+
+def fec_tx_ilv_layout(nframes, n, block0, depth):
+    """Where the block-interleaved sender puts its packets (host arithmetic, no GPU needed): nframes frames of n packets numbered
+    from block0 on, `depth` (1, 2, 4, 8 or 16) consecutive blocks of one group sent one row of each in turn.  Returns (first int64
+    [nframes], stride int32 [nframes]): row j of frame f is packet first[f] + j * stride[f] (include/ldpc_erasure_amd_interleave.h)."""
+    L = load_library()
+    F = max(int(nframes), 0)
+    first = np.zeros(F, dtype=np.int64)
+    stride = np.zeros(F, dtype=np.int32)
+    rc = L.ldpc_amd_fec_tx_ilv_layout(int(nframes), n, block0 & 0xFF, depth, first.ctypes.data, stride.ctypes.data)
+    if rc < 0:
+        raise LdpcAmdError(f"fec_tx_ilv_layout = {rc}: bad nframes / n / depth")
     assert rc == F * n
     return first, stride
 
@@ -861,6 +891,36 @@ class Context:
         self._check(self._L.ldpc_amd_fec_sender_flows_info(self._h, info), "fec_sender_flows_info")
         return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "frames": int(info[3])}
 
+    # -- the block-interleaved sender (include/ldpc_erasure_amd_interleave.h)
+    def fec_encode_packets_interleaved_device(self, code, source, depth, fec_class=1, block0=0, out=None):
+        """source: torch uint8 [F][k][S] (or [F][k] for S = 1) on this context's device -> packets [F*n][8+S]: the packets of
+        fec_encode_packets_device in depth-`depth` order -- row j of frame f at index first[f] + j * stride[f] of
+        fec_tx_ilv_layout(F, n, block0, depth).  fec_sender_ilv_info() says which path ran.  Asynchronous on the context's stream."""
+        import torch
+        assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
+        n, k, _ = self.code_info(code)
+        F = source.shape[0]
+        S = 1 if source.ndim == 2 else source.shape[2]
+        assert source.shape[1] == k
+        if out is None:
+            out = torch.empty((F * n, 8 + S), dtype=torch.uint8, device=source.device)
+        assert tuple(out.shape) == (F * n, 8 + S) and out.dtype == torch.uint8
+        self._check(self._L.ldpc_amd_fec_encode_packets_ilv_dev(self._h, code, S, F, _ptr(source), fec_class, block0, depth, _ptr(out)),
+                    "fec_encode_packets_ilv_dev")
+        return out
+
+    def fec_sender_ilv_info(self):
+        """{"path": "none" | "fused" | "composed" of the last fec_encode_packets_interleaved_device call, "scratch_bytes": codeword
+        scratch the context holds for the composed paths, "descriptor_bytes": descriptor memory it holds, "frames": frames of that
+        call}."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_sender_ilv_info(self._h, info), "fec_sender_ilv_info")
+        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "frames": int(info[3])}
+
+    def fec_tx_interleaved(self, code, S, depth, fec_class=1, block0=0):
+        """A sender that numbers its blocks across calls and emits them block-interleaved (FecTxInterleaved)."""
+        return FecTxInterleaved(self, code, S, depth, fec_class, block0)
+
     # -- datagrams of any length (include/ldpc_erasure_amd_datagrams.h)
     def fec_pack_datagrams(self, data, offsets, k, S, out=None):
         """data: torch uint8 1-D on this context's device (a slice starting at any byte is fine), datagram i = data[offsets[i] :
@@ -983,9 +1043,10 @@ class Context:
         return {"path": RECEIVER_PATHS[info[0]], "scratch_bytes": int(info[1]), "blocks": int(info[2])}
 
     # -- the windowed receiver (include/ldpc_erasure_amd_rx_window.h)
-    def fec_rx_window(self, n, k, S, window=4, ahead_limit=10):
-        """A device receiver that keeps `window` blocks open and resynchronises after `ahead_limit` packets beyond them (FecRxWindow)."""
-        return FecRxWindow(self, n, k, S, window, ahead_limit)
+    def fec_rx_window(self, n, k, S, window=4, ahead_limit=10, depth=1):
+        """A device receiver that keeps `window` blocks open and resynchronises after `ahead_limit` packets beyond them (FecRxWindow);
+        depth > 1: for a wire interleaved to that depth (include/ldpc_erasure_amd_interleave.h; needs 2 * depth <= window)."""
+        return FecRxWindow(self, n, k, S, window, ahead_limit, depth)
 
     def fec_rx_window_info(self):
         """{"path": "none" | "fused" | "composed" of the last FecRxWindow.decode_many / decode_flush call, "blocks": the blocks it
@@ -1244,6 +1305,11 @@ class _RxWindowState:
             raise LdpcAmdError("fec_rxw_state: bad arguments")
         return {"base": base.value, "cnt": cnt.tolist(), "ahead": ahead.value}
 
+    @property
+    def depth(self):
+        """The interleaving depth the object was created for (include/ldpc_erasure_amd_interleave.h), 1: the plain rule."""
+        return int(self._fn("depth")(self._h))
+
     def close(self):
         if getattr(self, "_h", None):
             self._fn("destroy")(self._h)
@@ -1264,13 +1330,18 @@ class _RxWindowState:
 
 class FecRxWindowHost(_RxWindowState):
     """The windowed reassembler on the host (include/ldpc_erasure_amd_rx_window.h): `window` blocks open, a resynchronisation after
-    `ahead_limit` packets beyond them (0: never).  With window = 2 and ahead_limit = 0 it is FecRx."""
+    `ahead_limit` packets beyond them (0: never).  With window = 2 and ahead_limit = 0 it is FecRx.  depth > 1: the rule for a wire
+    interleaved to that depth (include/ldpc_erasure_amd_interleave.h; needs 2 * depth <= window)."""
     _pre = "ldpc_amd_fec_rxw_"
 
-    def __init__(self, n, k, S, window=4, ahead_limit=10):
+    def __init__(self, n, k, S, window=4, ahead_limit=10, depth=1):
         self._L = load_library()
         h = C.c_void_p()
-        if self._L.ldpc_amd_fec_rxw_create(n, k, S, window, ahead_limit, C.byref(h)) != 0:
+        if depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
+            rc = self._L.ldpc_amd_fec_rxw_create(n, k, S, window, ahead_limit, C.byref(h))
+        else:
+            rc = self._L.ldpc_amd_fec_rxw_create_depth(n, k, S, window, ahead_limit, depth, C.byref(h))
+        if rc != 0:
             raise LdpcAmdError("fec_rxw_create: bad arguments")
         self._h, self.n, self.k, self.S, self.window, self.ahead_limit = h, n, k, S, window, ahead_limit
 
@@ -1316,10 +1387,13 @@ class FecRxWindow(_RxWindowState):
     when a call returns.  Close it before its Context."""
     _pre = "ldpc_amd_fec_rxw_dev_"
 
-    def __init__(self, ctx, n, k, S, window=4, ahead_limit=10):
+    def __init__(self, ctx, n, k, S, window=4, ahead_limit=10, depth=1):
         self._ctx, self._L = ctx, ctx._L
         h = C.c_void_p()
-        ctx._check(self._L.ldpc_amd_fec_rxw_dev_create(ctx._h, n, k, S, window, ahead_limit, C.byref(h)), "fec_rxw_dev_create")
+        if depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
+            ctx._check(self._L.ldpc_amd_fec_rxw_dev_create(ctx._h, n, k, S, window, ahead_limit, C.byref(h)), "fec_rxw_dev_create")
+        else:
+            ctx._check(self._L.ldpc_amd_fec_rxw_dev_create_depth(ctx._h, n, k, S, window, ahead_limit, depth, C.byref(h)), "fec_rxw_dev_create")
         self._h, self.n, self.k, self.S, self.window, self.ahead_limit = h, n, k, S, window, ahead_limit
 
     def _device(self):
@@ -1739,6 +1813,31 @@ class FecTxDevice:
         """Pack + encode + trim: datagrams of any length up to S - 4 -> Wire(bytes, offset) of Context.fec_trim_packets, the bytes
         that go on the wire back to back with their boundaries on the device; no per-packet table is made on the host.  Advances
         the block counter by F, as send_datagrams does."""
+        return self._ctx.fec_trim_packets(self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), self.k)
+
+
+class FecTxInterleaved:
+    """FecTxDevice for the block-interleaved wire (include/ldpc_erasure_amd_interleave.h): send(source) returns the packets of F
+    frames numbered from next_block on in depth-`depth` order, the input of FecRxWindow(..., depth=depth), and advances the
+    counter by F modulo 256.  A call interleaves its own frames only: send whole groups (F a multiple of depth, from a block number
+    that is one) to keep every group at full depth.  There is no send_datagrams here: its wire_len table is in straight order."""
+
+    def __init__(self, ctx, code, S, depth, fec_class=1, block0=0):
+        if depth not in ILV_DEPTHS:
+            raise LdpcAmdError(f"FecTxInterleaved: depth must be one of {ILV_DEPTHS} (got {depth})")
+        self._ctx, self.code, self.S, self.depth, self.fec_class = ctx, code, S, depth, fec_class
+        self.n, self.k, _ = ctx.code_info(code)
+        self.next_block = block0 & 0xFF
+
+    def send(self, source, out=None):
+        """source: torch uint8 [F][k][S] (or [F][k] for S = 1) -> packets [F*n][8+S] in transmission order."""
+        assert (1 if source.ndim == 2 else source.shape[2]) == self.S
+        pk = self._ctx.fec_encode_packets_interleaved_device(self.code, source, self.depth, self.fec_class, self.next_block, out=out)
+        self.next_block = (self.next_block + source.shape[0]) & 0xFF
+        return pk
+
+    def send_datagrams_trimmed(self, data, offsets):
+        """Pack + encode + trim, as FecTxDevice.send_datagrams_trimmed: Wire(bytes, offset) of the interleaved packets."""
         return self._ctx.fec_trim_packets(self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), self.k)
 
 

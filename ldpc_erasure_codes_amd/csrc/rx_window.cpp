@@ -1,4 +1,5 @@
-// rx_window.cpp -- the windowed FEC receiver on the host: the DEFINITION of the rule (include/ldpc_erasure_amd_rx_window.h).
+// rx_window.cpp -- the windowed FEC receiver on the host: the DEFINITION of the rule (include/ldpc_erasure_amd_rx_window.h)
+// and of its depth-D form for a block-interleaved wire (include/ldpc_erasure_amd_interleave.h; D = 1 is the plain rule).
 // Plain C++, no GPU involved; csrc/wire.cpp's two-buffer receiver is the pattern, and the W = 2, A = 0 case of this one.
 #include <math.h>
 #include <stdlib.h>
@@ -7,11 +8,13 @@
 #include <new>
 #include <vector>
 
+#include "../../include/ldpc_erasure_amd_interleave.h"
 #include "../../include/ldpc_erasure_amd_rx_window.h"
 #include "../../include/ldpc_erasure_amd_wire.h"
 
 struct ldpc_amd_fec_rxw {
     int n, k, S, W, A;
+    int D;                                       // interleaving depth (ldpc_erasure_amd_interleave.h); 1 = the plain rule
     int kd, km;                                  // k + round(0.8 (n-k)), k + round(0.2 (n-k))
     int base;                                    // wire block number of slot 0, -1 before the first packet
     int head;                                    // slot d lives in plane (head + d) % W
@@ -25,11 +28,17 @@ extern "C" {
 
 int ldpc_amd_fec_rxw_create(int n, int k, int S, int window, int ahead_limit, ldpc_amd_fec_rxw **out)
 {
+    return ldpc_amd_fec_rxw_create_depth(n, k, S, window, ahead_limit, 1, out);
+}
+
+int ldpc_amd_fec_rxw_create_depth(int n, int k, int S, int window, int ahead_limit, int depth, ldpc_amd_fec_rxw **out)
+{
+    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth) || (depth > 1 && 2 * depth > window)) return -1;
     if (!out || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0) return -1;
     if (window < LDPC_AMD_RXW_MIN_WINDOW || window > LDPC_AMD_RXW_MAX_WINDOW || ahead_limit < 0 || ahead_limit > (1 << 30)) return -1;
     ldpc_amd_fec_rxw *rx = new (std::nothrow) ldpc_amd_fec_rxw();
     if (!rx) return -1;
-    rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit;
+    rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit; rx->D = depth;
     rx->kd = k + (int)lround((n - k) * 0.8);
     rx->km = k + (int)lround((n - k) * 0.2);
     rx->base = -1;
@@ -44,6 +53,8 @@ int ldpc_amd_fec_rxw_create(int n, int k, int S, int window, int ahead_limit, ld
 }
 
 void ldpc_amd_fec_rxw_destroy(ldpc_amd_fec_rxw *rx) { delete rx; }
+
+int ldpc_amd_fec_rxw_depth(const ldpc_amd_fec_rxw *rx) { return rx ? rx->D : -1; }
 
 int ldpc_amd_fec_rxw_stats(const ldpc_amd_fec_rxw *rx, int64_t totals[5])
 {
@@ -99,7 +110,7 @@ int ldpc_amd_fec_rxw_push(ldpc_amd_fec_rxw *rx, const uint8_t *packet, uint8_t *
     ldpc_amd_fec_header_unpack(word, &cls, &blk, &sym);
     (void)cls;
     const uint8_t *payload = packet + LDPC_AMD_FEC_HEADER_BYTES;
-    if (rx->base == -1) rx->base = (int)blk;                           // 1.
+    if (rx->base == -1) rx->base = (int)blk - (int)blk % rx->D;        // 1. (the start of the packet's group)
     if ((int)sym >= rx->n) {                                           // 2.
         rx->totals[LDPC_AMD_RXW_BAD_SYMBOL]++;
     } else {
@@ -115,17 +126,22 @@ int ldpc_amd_fec_rxw_push(ldpc_amd_fec_rxw *rx, const uint8_t *packet, uint8_t *
         }
     }
     const int c = rx->cnt[0];                                          // 3.
-    long later = 0;
-    for (int d = 1; d < rx->W; d++) later += rx->cnt[d];
+    const int g = rx->D - rx->base % rx->D;                            // open slots of slot 0's group; 1 when D == 1
+    long later = 0, all = 0;
+    for (int d = 0; d < rx->W; d++) {
+        all += rx->cnt[d];
+        if (d >= g) later += rx->cnt[d];
+    }
     if (c == rx->n || (c > rx->kd && later > 10) || (c > rx->km && later > 100)) {
         close_slot0(rx, sym_out, erased_out, block_out);
         return 1;
     }
     if (rx->A > 0 && rx->ahead > rx->A) {
-        if (c + later == 0) {   // re-anchor: nothing is open, the window jumps to where the stream is
-            rx->base = (int)blk;
-            store(rx, 0, sym, payload);
-            rx->cnt[0] = 1;
+        if (all == 0) {   // re-anchor: nothing is open, the window jumps to the group where the stream is
+            const int d = (int)blk % rx->D;
+            rx->base = (int)blk - d;
+            store(rx, d, sym, payload);
+            rx->cnt[d] = 1;
             rx->ahead = 0;
             rx->totals[LDPC_AMD_RXW_RESYNCS]++;
             return 0;

@@ -2,7 +2,8 @@
 // packets that are already in GPU memory, byte for byte.  The five steps of wire_dev.hip's two-buffer receiver, with W blocks open:
 //   (a) rxw_headers   every packet's header -> one dense u32, block << 16 | symbol                                        (parallel)
 //   (b) rxw_scan      one wavefront replays ldpc_amd_fec_rxw_push over the dense headers, 64 packets per step: per packet the
-//                     SERIAL of the block it went to (or -1), per close the wire block number, at the end the state and the totals
+//                     SERIAL of the block it went to (or -1), per close the wire block number, at the end the state and the totals;
+//                     rxw_scan_grouped for an object of depth > 1 (include/ldpc_erasure_amd_interleave.h), the only step that differs
 //   (c) rxw_winners   atomicMax of the packet index into a [(closes + W)][n] table: the last copy of a symbol wins          (parallel)
 //   (d) rxw_move<1>   closed blocks -> sym_batch / erased_batch; or rxw_sources: WHERE the decoder finds each row           (parallel)
 //   (e) rxw_move<0>   the W blocks still open -> the W staging planes, in a launch behind (d)                              (parallel)
@@ -59,7 +60,16 @@ __global__ __launch_bounds__(64) void rxw_scan(const uint32_t *__restrict__ dens
 {
     __shared__ int cnt[kMaxW];
     __shared__ uint32_t hbuf[kScanChunk * 64];
-    rxw_scan_body(dense, np, r, max_blocks, st, cnt, hbuf, dest, res);
+    rxw_scan_body<false>(dense, np, r, 1, max_blocks, st, cnt, hbuf, dest, res);
+}
+
+// the depth-D rule (include/ldpc_erasure_amd_interleave.h), D > 1: the objects created with a depth launch this one
+__global__ __launch_bounds__(64) void rxw_scan_grouped(const uint32_t *__restrict__ dense, int64_t np, RxwRule r, int D, int max_blocks,
+                                                      RxwState st, int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    __shared__ int cnt[kMaxW];
+    __shared__ uint32_t hbuf[kScanChunk * 64];
+    rxw_scan_body<true>(dense, np, r, D, max_blocks, st, cnt, hbuf, dest, res);
 }
 
 // ---- (c) last writer wins ----------------------------------------------------------------------------------------------------------
@@ -180,6 +190,7 @@ __global__ __launch_bounds__(kThreads) void rxw_flush_move(uint8_t *__restrict__
 struct ldpc_amd_fec_rxw_dev {
     ldpc_amd_ctx *ctx = nullptr;
     int n = 0, k = 0, S = 0, W = 0, A = 0, kd = 0, km = 0;
+    int D = 1;   // interleaving depth (include/ldpc_erasure_amd_interleave.h); only the plan scan looks at it
     // host mirror of the receiver's state (csrc/rx_window.cpp); head: staging plane of slot 0
     int base = -1, head = 0, ahead = 0;
     int cnt[kMaxW] = {0};
@@ -232,7 +243,10 @@ int rxw_plan(ldpc_amd_fec_rxw_dev *rx, const char *who, const uint8_t *packets, 
     RxwState st{};
     st.base = rx->base; st.ahead = rx->ahead;
     for (int j = 0; j < rx->W; j++) st.cnt[j] = rx->cnt[j];
-    hipLaunchKernelGGL(rxw_scan, dim3(1), dim3(64), 0, ctx->stream, dense, npackets, r, max_blocks, st, dest, res);
+    if (rx->D > 1)
+        hipLaunchKernelGGL(rxw_scan_grouped, dim3(1), dim3(64), 0, ctx->stream, dense, npackets, r, rx->D, max_blocks, st, dest, res);
+    else
+        hipLaunchKernelGGL(rxw_scan, dim3(1), dim3(64), 0, ctx->stream, dense, npackets, r, max_blocks, st, dest, res);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->res_host, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
     LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -303,16 +317,26 @@ extern "C" {
 
 int ldpc_amd_fec_rxw_dev_create(ldpc_amd_ctx *ctx, int n, int k, int S, int window, int ahead_limit, ldpc_amd_fec_rxw_dev **out)
 {
+    return ldpc_amd_fec_rxw_dev_create_depth(ctx, n, k, S, window, ahead_limit, 1, out);
+}
+
+int ldpc_amd_fec_rxw_dev_depth(const ldpc_amd_fec_rxw_dev *rx) { return rx ? rx->D : -1; }
+
+int ldpc_amd_fec_rxw_dev_create_depth(ldpc_amd_ctx *ctx, int n, int k, int S, int window, int ahead_limit, int depth, ldpc_amd_fec_rxw_dev **out)
+{
     if (!ctx) return LDPC_AMD_EINVAL;
     if (!out || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: need n <= 65536, 0 < k < n, S >= 1 (n=%d k=%d S=%d)", n, k, S);
     int rc;
     if ((rc = rxw_check_create(ctx, "fec_rxw_dev_create", window, ahead_limit, (int64_t)window * n, "window * n"))) return rc;
+    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth) || (depth > 1 && 2 * depth > window))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: depth must be 1, 2, 4, 8 or 16, and a depth > 1 needs 2 * depth <= window (depth=%d window=%d)",
+                         depth, window);
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     ldpc_amd_fec_rxw_dev *rx = new (std::nothrow) ldpc_amd_fec_rxw_dev();
     if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rxw_dev_create: out of host memory");
     rx->ctx = ctx;
-    rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit;
+    rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit; rx->D = depth;
     rx->kd = k + (int)lround((n - k) * 0.8);
     rx->km = k + (int)lround((n - k) * 0.2);
     const size_t planes = (size_t)window * n * S, flags = (size_t)window * n;

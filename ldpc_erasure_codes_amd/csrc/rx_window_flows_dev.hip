@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64) void rxw_scan_flows(const uint32_t *__restrict_
 #pragma unroll
     for (int j = 0; j < kMaxW; j++) st.cnt[j] = f->cnt[j];
     const int64_t begin = f->begin;
-    rxw_scan_body(dense + begin, f->len, r, max_blocks, st, cnt, hbuf, dest + begin, res + (int64_t)blockIdx.x * (R_WORDS + max_blocks));
+    rxw_scan_body<false>(dense + begin, f->len, r, 1, max_blocks, st, cnt, hbuf, dest + begin, res + (int64_t)blockIdx.x * (R_WORDS + max_blocks));
 }
 
 // slot -> flow, [T]: one workgroup per flow

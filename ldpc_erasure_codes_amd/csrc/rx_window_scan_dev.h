@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/ldpc_erasure_amd_interleave.h"
 #include "../../include/ldpc_erasure_amd_rx_window.h"
 
 namespace {
@@ -36,8 +37,8 @@ __device__ __forceinline__ bool rxw_close_rule(int c, int later, const RxwRule &
 
 // One wavefront; every value but the lane's own packet is wave-uniform.  For a group of 64 packets from lane `start` on:
 //   is0 / isL / isA   this lane's packet goes to slot 0 / to a later slot of the window / is an ahead packet;
-//   c, lt, ah         cnt[0], cnt[1] + .. + cnt[W-1] and `ahead` after this lane's packet: the values before the group + the
-//                     ballots' inclusive prefix popcounts;
+//   c, lt, ah         cnt[0], cnt[1] + .. + cnt[W-1] (GROUPED: cnt[g] + .. + cnt[W-1], the later groups only; isL likewise) and
+//                     `ahead` after this lane's packet: the values before the group + the ballots' inclusive prefix popcounts;
 //   bz                the lanes where step 3 fires after their packet; the first of them is the EVENT, a close or a re-anchor.
 // Exactness: the host's decision after packet l depends on the packets before it only through (base, cnt[0], the sum of the later
 // counts, ahead).  Between two events base is fixed, so every lane's class (slot d, ahead, late, bad symbol) is fixed, and each of
@@ -51,17 +52,39 @@ __device__ __forceinline__ bool rxw_close_rule(int c, int later, const RxwRule &
 // The loop is bounded: every iteration assigns at least one packet, performs one event, or ends its group, so a call takes at most
 // 2 npackets + max_blocks + groups iterations (a re-anchor needs A + 1 >= 2 packets); a cap on that reports R_ERR instead of spinning.
 // The body is one function over a state record so that a per-flow kernel can call it with a segment and a state of its own.
+//
+// GROUPED: the depth-D rule of include/ldpc_erasure_amd_interleave.h (D = 2, 4, 8 or 16, 2 D <= W; the plain instantiation ignores D
+// and carries none of what follows).  g = D - base % D open slots belong to the group of slot 0, and the window's counts split in
+// three: c0 = cnt[0], mates = cnt[1] + .. + cnt[g-1], later = cnt[g] + .. + cnt[W-1].  A fourth ballot (isM, the group-mates) joins
+// the three.  Exactness carries over: the host's decision after packet l now depends on the packets before it through (base, cnt[0],
+// the mates' sum, the later groups' sum, ahead) -- the close test reads cnt[0] and the later groups' sum, the choice between a
+// forced close and a re-anchor reads all three sums.  Between two events base is fixed, and so are g and every lane's class (slot 0,
+// mate, later group, ahead, late, bad symbol); each of the four values after packet l is its value before the group plus the
+// matching packets among start..l, a prefix popcount.  Step 3 is a function of (c, later, ahead) alone, so the first lane where it
+// holds is the first packet after which the host acts; the kind of event follows from the four values at that lane.  The events
+// restate the host's:
+//   close, g > 1    the new slot 0 is a mate: c0 = cnt[next], mates -= c0, later is unchanged, g -= 1;
+//   close, g == 1   the next group becomes the current one (base + 1 is a multiple of D, also across the 8-bit wrap, D | 256): its
+//                   D counts leave `later`.  c0 = cnt[next]; slots 1 .. D-1 are read from the LDS ring, one lane each, and summed
+//                   over the wave into mates; later -= c0 + mates; g = D;
+//   re-anchor       every count is zero; base = the group start of the tripping packet, which goes to slot blk % D:
+//                   c0 = (blk % D == 0), mates = 1 - c0, later = 0, g = D.
 // cnt: LDS [kMaxW]; hbuf: LDS [kScanChunk * 64].
-__device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense, int64_t np, const RxwRule r, int max_blocks, const RxwState &st,
-                                              int *cnt, uint32_t *hbuf, int32_t *__restrict__ dest, int32_t *__restrict__ res)
+template <bool GROUPED>
+__device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense, int64_t np, const RxwRule r, int D, int max_blocks,
+                                              const RxwState &st, int *cnt, uint32_t *hbuf, int32_t *__restrict__ dest,
+                                              int32_t *__restrict__ res)
 {
     const int lane = threadIdx.x;
     const uint64_t le = (lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1);   // lanes <= this one
     int base = st.base, ahead = st.ahead, h = 0;   // slot d's counter is cnt[(h + d) % W]
     int c0 = st.cnt[0], later = 0, own = 0;
+    int g = 1, mates = 0;   // GROUPED only
+    if (GROUPED) g = base < 0 ? D : D - (base & (D - 1));
 #pragma unroll
     for (int j = 0; j < kMaxW; j++) {
-        if (j > 0) later += st.cnt[j];
+        if (GROUPED && j > 0 && j < g) mates += st.cnt[j];
+        else if (j > 0) later += st.cnt[j];
         if (lane == j) own = st.cnt[j];
     }
     if (lane < kMaxW) cnt[lane] = own;
@@ -92,7 +115,10 @@ __device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense
             const bool valid = p < np;
             const uint32_t hw = hbuf[u * 64 + lane];
             const int blk = (int)(hw >> 16), sym = (int)(hw & 0xffffu);
-            if (base < 0) base = __shfl(blk, 0);   // step 1: the first packet of the stream, before its symbol check
+            if (base < 0) {   // step 1: the first packet of the stream, before its symbol check
+                base = __shfl(blk, 0);
+                if (GROUPED) base -= base & (D - 1);   // the start of its group; g = D already
+            }
             int d_out = -1;
             int start = 0;
             for (;;) {
@@ -101,9 +127,11 @@ __device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense
                 const bool ok = live && sym < r.n;
                 const int d = (blk - base) & 0xff;
                 const bool in = ok && d < r.W;
-                const bool is0 = in && d == 0, isL = in && d != 0;
+                const bool is0 = in && d == 0, isL = in && (GROUPED ? d >= g : d != 0);
                 const bool isA = ok && !in && r.A > 0 && d < 128;
                 const uint64_t b0 = __ballot(is0), bL = __ballot(isL), bA = __ballot(isA);
+                uint64_t bM = 0;
+                if (GROUPED) bM = __ballot(in && d != 0 && d < g);
                 const int c = c0 + __popcll(b0 & le), lt = later + __popcll(bL & le), ah = ahead + __popcll(bA & le);
                 const uint64_t bz = __ballot(live && (rxw_close_rule(c, lt, r) || (r.A > 0 && ah > r.A)));
                 const uint64_t upto = bz ? ((bz & (0ull - bz)) << 1) - 1 : ~0ull;   // lanes up to the first event (all if none)
@@ -119,14 +147,33 @@ __device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense
                 c0 += __popcll(b0 & upto);
                 later += __popcll(bL & upto);
                 ahead += __popcll(bA & upto);
+                if (GROUPED) mates += __popcll(bM & upto);
                 if (!bz) break;
                 const int L = __ffsll((long long)bz) - 1;   // c0, later, ahead are now the values after lane L's packet
-                if (!rxw_close_rule(c0, later, r) && c0 + later == 0) {
-                    // re-anchor: every counter is zero, the tripping packet opens slot 0 at its own block number
+                if (!rxw_close_rule(c0, later, r) && c0 + later + (GROUPED ? mates : 0) == 0) {
+                    // re-anchor: every counter is zero, the tripping packet opens slot 0 at its own block number (GROUPED: slot
+                    // blk % D of a window that starts at its group)
                     base = __shfl(blk, L);
-                    if (lane == L) d_out = closes;
-                    if (lane == 0) cnt[h] = 1;
-                    c0 = 1;
+                    int dd = 0;   // GROUPED: the packet's slot in its group, the window starts at the group
+                    if (GROUPED) {
+                        dd = base & (D - 1);
+                        base -= dd;
+                        g = D;
+                    }
+                    if (lane == L) d_out = closes + dd;
+                    if (lane == 0) {
+                        int j = h;
+                        if (GROUPED) {
+                            j += dd;
+                            if (j >= r.W) j -= r.W;
+                        }
+                        cnt[j] = 1;
+                    }
+                    c0 = dd == 0 ? 1 : 0;
+                    if (GROUPED) {
+                        mates = 1 - c0;
+                        later = 0;
+                    }
                     ahead = 0;
                     resyncs++;
                 } else {
@@ -134,6 +181,16 @@ __device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense
                     __syncthreads();   // the counters hold every packet assigned so far
                     const int h1 = h + 1 == r.W ? 0 : h + 1;
                     const int nc0 = cnt[h1];
+                    int nm = 0;   // GROUPED, g == 1: the counts of the new slots 1 .. D-1
+                    if (GROUPED && g == 1) {
+                        if (lane >= 1 && lane < D) {
+                            const int j = h1 + lane;   // D - 1 < W: the slot exists and is not the one handed out
+                            nm = cnt[j >= r.W ? j - r.W : j];
+                        }
+#pragma unroll
+                        for (int o = 1; o < LDPC_AMD_FEC_ILV_MAX_DEPTH; o <<= 1) nm += __shfl_xor(nm, o);
+                        nm = __shfl(nm, 0);   // lanes 0 .. 15 hold the sum
+                    }
                     __syncthreads();
                     if (lane == 0) {
                         cnt[h] = 0;   // the new last slot
@@ -141,7 +198,16 @@ __device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense
                     }
                     closes++;
                     h = h1;
-                    later -= nc0;
+                    if (!GROUPED) {
+                        later -= nc0;
+                    } else if (g > 1) {
+                        mates -= nc0;
+                        g--;
+                    } else {
+                        mates = nm;
+                        later -= nc0 + nm;
+                        g = D;
+                    }
                     c0 = nc0;
                     base = (base + 1) & 0xff;
                     ahead = 0;

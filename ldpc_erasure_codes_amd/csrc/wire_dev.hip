@@ -38,6 +38,7 @@
 #include "../../include/ldpc_erasure_amd_wire_dev.h"
 #include "../../include/ldpc_erasure_amd_sender.h"
 #include "../../include/ldpc_erasure_amd_sender_flows.h"
+#include "../../include/ldpc_erasure_amd_interleave.h"
 #include "../../include/ldpc_erasure_amd_receiver.h"
 #include "../../include/ldpc_erasure_amd_flows.h"
 #include "../../include/ldpc_erasure_amd_flows_mixed.h"
@@ -623,6 +624,76 @@ struct ldpc_amd_fec_rx_dev {
     size_t res_host_cap = 0;
 };
 
+namespace {
+
+// ---- the descriptor-driven senders' common part (ldpc_amd_fec_encode_packets_flows_dev, ldpc_amd_fec_encode_packets_ilv_dev) --------
+// Stages a call's table -- [F] descriptors and `extra` further bytes per frame behind them -- and sends the frames by it.  The table
+// is filled by fill(hd, &max_stride) in a pinned slot of the context (two slots used in turn, each with the event of its last copy, so
+// that a slot is never rewritten under a copy in flight: two calls enqueued back to back are both right), copied to the context's
+// device table on the stream, and followed by the descriptor form of the packet encoder (path 1, fused) where
+// launch_encode_packets_flows has it for this call, else by the encoder into the context's codeword scratch and the descriptor-driven
+// packetisers, chunk by chunk (path 2, composed).  *dd: the device table.
+template <class Fill>
+int tx_send_described(ldpc_amd_ctx *ctx, const char *who, const DevCode &cd, int S, int64_t F, size_t extra, const uint8_t *source,
+                      uint8_t *packets, Fill fill, const TxFrameDesc **dd_out, int *path_out)
+{
+    const int n = cd.n;
+    const size_t src_frame = (size_t)cd.k * S, cw_frame = (size_t)n * S;
+    const size_t tab_bytes = (sizeof(TxFrameDesc) + extra) * (size_t)F;
+    int rc;
+    if ((rc = scratch_reserve(ctx, ctx->txf_desc, tab_bytes))) return rc;
+    const int slot = (int)(ctx->txf_calls & 1u);
+    if (!ctx->txf_event[slot]) LDPC_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txf_event[slot], hipEventDisableTiming));
+    if (ctx->txf_pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
+        LDPC_HIP_TRY(ctx, hipEventSynchronize(ctx->txf_event[slot]));
+        ctx->txf_pending[slot] = false;
+    }
+    if (ctx->txf_stage_cap[slot] < tab_bytes) {
+        if (ctx->txf_stage[slot]) (void)hipHostFree(ctx->txf_stage[slot]);
+        ctx->txf_stage[slot] = nullptr; ctx->txf_stage_cap[slot] = 0;
+        const size_t want = (tab_bytes + 65535) & ~(size_t)65535;
+        if (hipHostMalloc(&ctx->txf_stage[slot], want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->txf_stage[slot] = nullptr;
+            return set_error(ctx, LDPC_AMD_ENOMEM, "%s: no pinned memory for %zu descriptor bytes", who, want);
+        }
+        ctx->txf_stage_cap[slot] = want;
+    }
+    TxFrameDesc *hd = (TxFrameDesc *)ctx->txf_stage[slot];
+    int64_t max_stride = 1;
+    if ((rc = fill(hd, &max_stride))) return rc;
+    const TxFrameDesc *dd = (const TxFrameDesc *)ctx->txf_desc.p;
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(ctx->txf_desc.p, hd, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    LDPC_HIP_TRY(ctx, hipEventRecord(ctx->txf_event[slot], ctx->stream));
+    ctx->txf_pending[slot] = true;
+    ctx->txf_calls++;
+    rc = launch_encode_packets_flows(ctx, cd, S, F, source, dd, max_stride, packets);
+    if (rc != LDPC_AMD_OK && rc != kEncodeNotFused) return rc;
+    const int path = rc == LDPC_AMD_OK ? 1 : 2;
+    if (path == 2) {
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)(kSenderScratchMax / cw_frame)));
+        if ((rc = scratch_reserve(ctx, ctx->sender_cw, (size_t)chunk * cw_frame))) return rc;
+        uint8_t *cw = (uint8_t *)ctx->sender_cw.p;
+        const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0;   // (the scratch is 16-byte aligned)
+        for (int64_t f0 = 0; f0 < F; f0 += chunk) {
+            const int64_t cnt = std::min(chunk, F - f0), rows = cnt * n;
+            if ((rc = launch_encode(ctx, cd, S, cnt, source + (size_t)f0 * src_frame, cw))) return rc;
+            if (v16)
+                hipLaunchKernelGGL(fec_packetize_flows_v16, dim3(grid_for(rows * (S / 16))), dim3(kThreads), 0, ctx->stream,
+                                   reinterpret_cast<const uint4 *>(cw), rows, n, S / 16, dd + f0, packets);
+            else
+                hipLaunchKernelGGL(fec_packetize_flows_bytes, dim3(grid_for(rows * (S + kHdr))), dim3(kThreads), 0, ctx->stream, cw, rows, n, S,
+                                   dd + f0, packets);
+            LDPC_HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    *dd_out = dd;
+    *path_out = path;
+    return LDPC_AMD_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int ldpc_amd_fec_packetize_dev(ldpc_amd_ctx *ctx, const uint8_t *frames, int64_t nframes, int n, int S, unsigned fec_class,
@@ -768,7 +839,7 @@ int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, in
         return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
     const int n = cd.n;
     const int64_t P = F * n;
-    const size_t src_frame = (size_t)cd.k * S, cw_frame = (size_t)n * S, pk_frame = (size_t)n * ((size_t)S + kHdr);
+    const size_t src_frame = (size_t)cd.k * S, pk_frame = (size_t)n * ((size_t)S + kHdr);
     {
         const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)F, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)F;
         const uintptr_t q0 = (uintptr_t)flow_of, q1 = q0 + sizeof(int32_t) * (size_t)P;
@@ -777,30 +848,10 @@ int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, in
             return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: flow_of overlaps source or packets");
     }
     // the table: [F] descriptors, the frames' flows behind them
-    const size_t tab_bytes = (sizeof(TxFrameDesc) + sizeof(int32_t)) * (size_t)F;
-    int rc;
-    if ((rc = scratch_reserve(ctx, ctx->txf_desc, tab_bytes))) return rc;
-    const int slot = (int)(ctx->txf_calls & 1u);
-    if (!ctx->txf_event[slot]) LDPC_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txf_event[slot], hipEventDisableTiming));
-    if (ctx->txf_pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
-        LDPC_HIP_TRY(ctx, hipEventSynchronize(ctx->txf_event[slot]));
-        ctx->txf_pending[slot] = false;
-    }
-    if (ctx->txf_stage_cap[slot] < tab_bytes) {
-        if (ctx->txf_stage[slot]) (void)hipHostFree(ctx->txf_stage[slot]);
-        ctx->txf_stage[slot] = nullptr; ctx->txf_stage_cap[slot] = 0;
-        const size_t want = (tab_bytes + 65535) & ~(size_t)65535;
-        if (hipHostMalloc(&ctx->txf_stage[slot], want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->txf_stage[slot] = nullptr;
-            return set_error(ctx, LDPC_AMD_ENOMEM, "fec_encode_packets_flows_dev: no pinned memory for %zu descriptor bytes", want);
-        }
-        ctx->txf_stage_cap[slot] = want;
-    }
-    TxFrameDesc *hd = (TxFrameDesc *)ctx->txf_stage[slot];
-    int32_t *hflow = (int32_t *)(hd + F);
-    int64_t max_stride = 1;
-    {
+    const TxFrameDesc *dd = nullptr;
+    int path = 0;
+    auto fill = [&](TxFrameDesc *hd, int64_t *max_stride) -> int {
+        int32_t *hflow = (int32_t *)(hd + F);
         std::vector<int64_t> first((size_t)F);
         std::vector<int32_t> stride((size_t)F);
         const int64_t got = ldpc_amd_fec_tx_flows_layout(nflows, frame_begin, n, order, first.data(), stride.data());
@@ -811,35 +862,13 @@ int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, in
                 hd[t].stride = (uint32_t)stride[(size_t)t];
                 hd[t].hdr = ((uint32_t)fec_class[f] << 8) | (((uint32_t)block0[f] + (uint32_t)(t - frame_begin[f])) & 0xffu);
                 hflow[t] = f;
-                max_stride = std::max<int64_t>(max_stride, stride[(size_t)t]);
+                *max_stride = std::max<int64_t>(*max_stride, stride[(size_t)t]);
             }
-    }
-    const TxFrameDesc *dd = (const TxFrameDesc *)ctx->txf_desc.p;
+        return LDPC_AMD_OK;
+    };
+    int rc;
+    if ((rc = tx_send_described(ctx, "fec_encode_packets_flows_dev", cd, S, F, sizeof(int32_t), source, packets, fill, &dd, &path))) return rc;
     const int32_t *dflow = (const int32_t *)(dd + F);
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(ctx->txf_desc.p, hd, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    LDPC_HIP_TRY(ctx, hipEventRecord(ctx->txf_event[slot], ctx->stream));
-    ctx->txf_pending[slot] = true;
-    ctx->txf_calls++;
-    rc = launch_encode_packets_flows(ctx, cd, S, F, source, dd, max_stride, packets);
-    if (rc != LDPC_AMD_OK && rc != kEncodeNotFused) return rc;
-    const int path = rc == LDPC_AMD_OK ? 1 : 2;
-    if (path == 2) {
-        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)(kSenderScratchMax / cw_frame)));
-        if ((rc = scratch_reserve(ctx, ctx->sender_cw, (size_t)chunk * cw_frame))) return rc;
-        uint8_t *cw = (uint8_t *)ctx->sender_cw.p;
-        const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0;   // (the scratch is 16-byte aligned)
-        for (int64_t f0 = 0; f0 < F; f0 += chunk) {
-            const int64_t cnt = std::min(chunk, F - f0), rows = cnt * n;
-            if ((rc = launch_encode(ctx, cd, S, cnt, source + (size_t)f0 * src_frame, cw))) return rc;
-            if (v16)
-                hipLaunchKernelGGL(fec_packetize_flows_v16, dim3(grid_for(rows * (S / 16))), dim3(kThreads), 0, ctx->stream,
-                                   reinterpret_cast<const uint4 *>(cw), rows, n, S / 16, dd + f0, packets);
-            else
-                hipLaunchKernelGGL(fec_packetize_flows_bytes, dim3(grid_for(rows * (S + kHdr))), dim3(kThreads), 0, ctx->stream, cw, rows, n, S,
-                                   dd + f0, packets);
-            LDPC_HIP_TRY(ctx, hipGetLastError());
-        }
-    }
     if (flow_of) {
         hipLaunchKernelGGL(fec_tx_flow_of, dim3(grid_for(P)), dim3(kThreads), 0, ctx->stream, dd, dflow, P, n, flow_of);
         LDPC_HIP_TRY(ctx, hipGetLastError());
@@ -859,6 +888,82 @@ int ldpc_amd_fec_sender_flows_info(ldpc_amd_ctx *ctx, int64_t info[4])
     info[1] = (int64_t)ctx->sender_cw.cap;
     info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
     info[3] = ctx->txf_frames;
+    return LDPC_AMD_OK;
+}
+
+// ---- the block-interleaved sender (include/ldpc_erasure_amd_interleave.h) ------------------------------------------------------
+// The order as arithmetic: walk the frames run by run.  A run is the frames s .. s+m-1 of one group of D block numbers; its member i
+// starts at packet n s + i and its rows are m packets apart.
+int64_t ldpc_amd_fec_tx_ilv_layout(int64_t nframes, int n, unsigned block0, int depth, int64_t *first, int32_t *stride)
+{
+    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth) || n < 1 || nframes < 0) return LDPC_AMD_EINVAL;
+    if (nframes > (((int64_t)1 << 31) - 1) / n) return LDPC_AMD_EINVAL;   // nframes * n < 2^31
+    for (int64_t s = 0; s < nframes;) {
+        const int b = (int)((block0 + (uint64_t)s) & 0xffu);
+        const int64_t m = std::min<int64_t>(depth - b % depth, nframes - s);
+        for (int64_t i = 0; i < m; i++) {
+            if (first) first[s + i] = s * n + i;
+            if (stride) stride[s + i] = (int32_t)m;
+        }
+        s += m;
+    }
+    return nframes * n;
+}
+
+// The single-flow sender's checks, then the multi-flow sender's machinery on the descriptors of the layout.
+int ldpc_amd_fec_encode_packets_ilv_dev(ldpc_amd_ctx *ctx, int code, int S, int64_t nframes, const uint8_t *source, unsigned fec_class,
+                                        unsigned block0, int depth, uint8_t *packets)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    const DevCode &cd = ctx->codes[code]->dev;
+    if (nframes < 0 || S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: bad nframes/S");
+    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth)) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: depth must be 1, 2, 4, 8 or 16 (got %d)", depth);
+    const int64_t F = nframes;
+    if (F > (((int64_t)1 << 31) - 1) / cd.n)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: %lld frames of %d packets are not below 2^31 packets", (long long)F, cd.n);
+    if (F == 0) return LDPC_AMD_OK;
+    if (cd.enc_nlevels == 0) return set_error(ctx, LDPC_AMD_EUNSUP, "code is not in triangle form: no systematic encoder");
+    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: source / packets must be device pointers of device %d", ctx->device);
+    if (symbol_len_words(S) && ((uintptr_t)source & 3) != 0)
+        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
+    const int n = cd.n;
+    const size_t src_frame = (size_t)cd.k * S, pk_frame = (size_t)n * ((size_t)S + kHdr);
+    const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)F, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)F;
+    if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: source and packets overlap");
+    const TxFrameDesc *dd = nullptr;
+    int path = 0;
+    auto fill = [&](TxFrameDesc *hd, int64_t *max_stride) -> int {
+        std::vector<int64_t> first((size_t)F);
+        std::vector<int32_t> stride((size_t)F);
+        if (ldpc_amd_fec_tx_ilv_layout(F, n, block0, depth, first.data(), stride.data()) != F * n)
+            return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: bad layout arguments");
+        for (int64_t t = 0; t < F; t++) {
+            hd[t].first = (uint64_t)first[(size_t)t];
+            hd[t].stride = (uint32_t)stride[(size_t)t];
+            hd[t].hdr = ((fec_class & 0xffu) << 8) | (uint32_t)((block0 + (uint64_t)t) & 0xffu);
+            *max_stride = std::max<int64_t>(*max_stride, stride[(size_t)t]);
+        }
+        return LDPC_AMD_OK;
+    };
+    int rc;
+    if ((rc = tx_send_described(ctx, "fec_encode_packets_ilv_dev", cd, S, F, 0, source, packets, fill, &dd, &path))) return rc;
+    ctx->txi_path = path;
+    ctx->txi_frames = F;
+    return LDPC_AMD_OK;
+}
+
+int ldpc_amd_fec_sender_ilv_info(ldpc_amd_ctx *ctx, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_sender_ilv_info: info must not be null");
+    info[0] = ctx->txi_path;
+    info[1] = (int64_t)ctx->sender_cw.cap;
+    info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
+    info[3] = ctx->txi_frames;
     return LDPC_AMD_OK;
 }
 

@@ -3,10 +3,13 @@ statement of the rule beside the C host object (csrc/rx_window.cpp) and the devi
 closed block is the list of the packet indices that won its symbols (the last copy of a symbol wins).
 
   headers(packets)                         (blk, sym) int arrays of a packet array uint8 [P][8 + S]
-  Window(n, k, W, A)                       the state; .push_many(blk, sym, max_blocks) -> (closed, consumed); .flush() -> closed
-  run(blk, sym, n, k, W, A, max_blocks)    one call over a whole stream: Result(closed, consumed, totals, state)
+  Window(n, k, W, A, D=1)                  the state; .push_many(blk, sym, max_blocks) -> (closed, consumed); .flush() -> closed
+  run(blk, sym, n, k, W, A, max_blocks, D) one call over a whole stream: Result(closed, consumed, totals, state)
   two_buffer(blk, sym, n, k)               the reference draft's two-buffer rule (csrc/wire.cpp), for comparison
-  events(blk, sym, n, k, W, A)             the packet indices after which the model closed or re-anchored
+  events(blk, sym, n, k, W, A, D=1)        the packet indices after which the model closed or re-anchored
+
+D is the interleaving depth of include/ldpc_erasure_amd_interleave.h: blocks b with equal b // D form a group, the window anchors on
+group starts, and `later` of the close test counts the slots of later groups only.  D = 1 is the plain rule.
 
 closed: a list of (block number, {symbol: winning packet index}); packet indices count from the start of the stream the Window has
 seen (its .seen counter), so results of split calls compare with those of one call.
@@ -30,15 +33,17 @@ def thresholds(n, k):
 
 
 class Window:
-    def __init__(self, n, k, W, A):
+    def __init__(self, n, k, W, A, D=1):
         assert 2 <= W <= 32 and A >= 0
-        self.n, self.k, self.W, self.A = n, k, W, A
+        assert D in (1, 2, 4, 8, 16) and (D == 1 or 2 * D <= W)
+        self.n, self.k, self.W, self.A, self.D = n, k, W, A, D
         self.kd, self.km = thresholds(n, k)
         self.base, self.ahead, self.seen = -1, 0, 0
         self.cnt = [0] * W
         self.slots = [dict() for _ in range(W)]
         self.totals = dict.fromkeys(TOTALS, 0)
         self.events = []   # (packet index, "close" | "resync")
+        self.event_base = []   # base when the event fired, one entry per event
 
     def state(self):
         return dict(base=self.base, cnt=list(self.cnt), ahead=self.ahead)
@@ -57,7 +62,7 @@ class Window:
         p = self.seen
         self.seen += 1
         if self.base == -1:
-            self.base = blk
+            self.base = blk - blk % self.D
         if sym >= self.n:
             self.totals["bad_symbol"] += 1
         else:
@@ -70,20 +75,24 @@ class Window:
                 self.totals["ahead_total"] += 1
             else:
                 self.totals["late"] += 1
-        c, later = self.cnt[0], sum(self.cnt[1:])
+        g = self.D - self.base % self.D   # open slots of slot 0's group
+        c, later, rest = self.cnt[0], sum(self.cnt[g:]), sum(self.cnt)
         if c == self.n or (c > self.kd and later > 10) or (c > self.km and later > 100):
             self.events.append((p, "close"))
+            self.event_base.append(self.base)
             return self._close()
         if self.A > 0 and self.ahead > self.A:
-            if c + later == 0:
-                self.base = blk
-                self.slots[0][sym] = p
-                self.cnt[0] = 1
+            if rest == 0:
+                self.base = blk - blk % self.D
+                self.slots[blk % self.D][sym] = p
+                self.cnt[blk % self.D] = 1
                 self.ahead = 0
                 self.totals["resyncs"] += 1
                 self.events.append((p, "resync"))
+                self.event_base.append(self.base)
                 return None
             self.events.append((p, "close"))
+            self.event_base.append(self.base)
             return self._close()
         return None
 
@@ -101,14 +110,14 @@ class Window:
         return [self._close() for _ in range(count)]
 
 
-def run(blk, sym, n, k, W, A, max_blocks=1 << 30):
-    w = Window(n, k, W, A)
+def run(blk, sym, n, k, W, A, max_blocks=1 << 30, D=1):
+    w = Window(n, k, W, A, D)
     closed, used = w.push_many(blk, sym, max_blocks)
     return Result(closed, used, dict(w.totals), w.state())
 
 
-def events(blk, sym, n, k, W, A):
-    w = Window(n, k, W, A)
+def events(blk, sym, n, k, W, A, D=1):
+    w = Window(n, k, W, A, D)
     w.push_many(blk, sym, 1 << 30)
     return list(w.events)
 
