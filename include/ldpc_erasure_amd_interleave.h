@@ -45,7 +45,7 @@
  *   - A thin group: a block that cannot reach its threshold closes through the ahead limit, and with it each of its thin mates in
  *     turn; each forced close drops A + 1 ahead packets, so a thin group costs up to D (A + 1) where a thin block cost A + 1.
  *
- * Out of scope: depth on the multi-flow receivers (they keep D = 1).
+ * Depth on the multi-flow sender and on the windowed multi-flow receiver: ldpc_erasure_amd_interleave_flows.h.
  */
 #ifndef LDPC_ERASURE_AMD_INTERLEAVE_H
 #define LDPC_ERASURE_AMD_INTERLEAVE_H

@@ -69,6 +69,11 @@ EXPORTS_INTERLEAVE = [
     "ldpc_amd_fec_rxw_dev_create_depth", "ldpc_amd_fec_rxw_depth", "ldpc_amd_fec_rxw_dev_depth",
 ]
 ILV_DEPTHS = (1, 2, 4, 8, 16)
+# every symbol include/ldpc_erasure_amd_interleave_flows.h declares (depth on the multi-flow wire: sender and windowed receiver)
+EXPORTS_INTERLEAVE_FLOWS = [
+    "ldpc_amd_fec_tx_flows_ilv_layout", "ldpc_amd_fec_encode_packets_flows_ilv_dev", "ldpc_amd_fec_sender_flows_ilv_info",
+    "ldpc_amd_fec_rxw_flows_create_depth", "ldpc_amd_fec_rxw_flows_depth",
+]
 # every symbol include/ldpc_erasure_amd_receiver.h declares (the fused receiver: wire packets straight to decoded frames)
 EXPORTS_RECEIVER = ["ldpc_amd_fec_rx_dev_decode_many", "ldpc_amd_fec_rx_dev_decode_flush", "ldpc_amd_fec_receiver_info"]
 RECEIVER_PATHS = ("none", "fused", "composed")
@@ -354,6 +359,14 @@ def load_library():
         L.ldpc_amd_fec_rxw_flows_decode_mixed.argtypes = [vp, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
         L.ldpc_amd_fec_rxw_flows_unrouted.argtypes = [vp]
         L.ldpc_amd_fec_rxw_flows_unrouted.restype = i64
+    # depth on the multi-flow wire (include/ldpc_erasure_amd_interleave_flows.h)
+    if hasattr(L, "ldpc_amd_fec_tx_flows_ilv_layout"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_tx_flows_ilv_layout.argtypes = [i32, vp, i32, vp, i32, i32, vp, vp]
+        L.ldpc_amd_fec_tx_flows_ilv_layout.restype = i64
+        L.ldpc_amd_fec_encode_packets_flows_ilv_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32]
+        L.ldpc_amd_fec_sender_flows_ilv_info.argtypes = [vp, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_flows_create_depth.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+        L.ldpc_amd_fec_rxw_flows_depth.argtypes = [vp]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -424,6 +437,27 @@ def fec_tx_ilv_layout(nframes, n, block0, depth):
     rc = L.ldpc_amd_fec_tx_ilv_layout(int(nframes), n, block0 & 0xFF, depth, first.ctypes.data, stride.ctypes.data)
     if rc < 0:
         raise LdpcAmdError(f"fec_tx_ilv_layout = {rc}: bad nframes / n / depth")
+    assert rc == F * n
+    return first, stride
+
+
+def fec_tx_flows_ilv_layout(frame_begin, n, block0, depth, order):
+    """fec_tx_flows_layout with every flow's blocks interleaved to `depth` (host arithmetic, no GPU needed): flow f's frames are
+    numbered from block0[f] on (a scalar stands for every flow) and its substream is fec_tx_ilv_layout's.  TX_ROUND_ROBIN with
+    depth > 1 needs whole aligned groups, block0[f] % depth == 0 and a frame count that is a multiple of depth for every flow
+    (include/ldpc_erasure_amd_interleave_flows.h).  Returns (first int64 [F], stride int32 [F])."""
+    L = load_library()
+    fb = np.ascontiguousarray(frame_begin, dtype=np.int64)
+    if fb.ndim != 1 or fb.shape[0] < 2:
+        raise LdpcAmdError("fec_tx_flows_ilv_layout: frame_begin must hold nflows + 1 >= 2 entries")
+    nflows = fb.shape[0] - 1
+    blk = np.ascontiguousarray(np.broadcast_to(np.asarray(block0, dtype=np.int64) & 0xFF, (nflows,)), dtype=np.uint8)
+    F = max(int(fb[-1]), 0)
+    first = np.zeros(F, dtype=np.int64)
+    stride = np.zeros(F, dtype=np.int32)
+    rc = L.ldpc_amd_fec_tx_flows_ilv_layout(nflows, fb.ctypes.data, n, blk.ctypes.data, depth, order, first.ctypes.data, stride.ctypes.data)
+    if rc < 0:
+        raise LdpcAmdError(f"fec_tx_flows_ilv_layout = {rc}: bad nflows / frame_begin / n / depth / order, or part groups in TX_ROUND_ROBIN")
     assert rc == F * n
     return first, stride
 
@@ -863,6 +897,10 @@ class Context:
         packet_begin int64 [nflows+1]): every flow's packets as fec_encode_packets_device makes them, flow after flow (order =
         TX_SEGMENTED: FecRxFlows.decode_many's input with packet_begin) or one packet of every flow in turn (TX_ROUND_ROBIN:
         decode_mixed's input with flow_of).  fec_sender_flows_info() says which path ran.  Asynchronous on the context's stream."""
+        return self._encode_packets_flows(code, source, frame_begin, fec_class, block0, order, out, want_flow_of, None)
+
+    def _encode_packets_flows(self, code, source, frame_begin, fec_class, block0, order, out, want_flow_of, depth):
+        """The two multi-flow senders' common part; depth None: ldpc_amd_fec_encode_packets_flows_dev."""
         import torch
         assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
         n, k, _ = self.code_info(code)
@@ -879,9 +917,12 @@ class Context:
         assert tuple(out.shape) == (F * n, 8 + S) and out.dtype == torch.uint8
         flow_of = torch.empty(F * n, dtype=torch.int32, device=source.device) if want_flow_of else None
         pb = np.zeros(nflows + 1, dtype=np.int64)
-        self._check(self._L.ldpc_amd_fec_encode_packets_flows_dev(
-            self._h, code, S, nflows, fb.ctypes.data, _ptr(source) if F else None, cls.ctypes.data, blk.ctypes.data, order,
-            _ptr(out) if F else None, _ptr(flow_of) if want_flow_of and F else None, pb.ctypes.data), "fec_encode_packets_flows_dev")
+        args = (self._h, code, S, nflows, fb.ctypes.data, _ptr(source) if F else None, cls.ctypes.data, blk.ctypes.data, order,
+                _ptr(out) if F else None, _ptr(flow_of) if want_flow_of and F else None, pb.ctypes.data)
+        if depth is None:
+            self._check(self._L.ldpc_amd_fec_encode_packets_flows_dev(*args), "fec_encode_packets_flows_dev")
+        else:
+            self._check(self._L.ldpc_amd_fec_encode_packets_flows_ilv_dev(*args, depth), "fec_encode_packets_flows_ilv_dev")
         return out, flow_of, pb
 
     def fec_sender_flows_info(self):
@@ -889,6 +930,21 @@ class Context:
         the context holds for the composed paths, "descriptor_bytes": descriptor memory it holds, "frames": frames of that call}."""
         info = (C.c_int64 * 4)()
         self._check(self._L.ldpc_amd_fec_sender_flows_info(self._h, info), "fec_sender_flows_info")
+        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "frames": int(info[3])}
+
+    # -- ... with every flow interleaved to a depth (include/ldpc_erasure_amd_interleave_flows.h)
+    def fec_encode_packets_flows_interleaved_device(self, code, source, frame_begin, fec_class, block0, order, depth, out=None, want_flow_of=True):
+        """fec_encode_packets_flows_device with every flow's blocks interleaved to `depth` (1, 2, 4, 8 or 16): flow f's packets are
+        those of fec_encode_packets_interleaved_device for its frames, and the flows go back to back (TX_SEGMENTED: the input of
+        FecRxWindowFlows(depth=depth).decode_many with packet_begin) or one packet of every flow in turn (TX_ROUND_ROBIN: decode_mixed's
+        with flow_of; depth > 1 then needs whole aligned groups, block0[f] % depth == 0 and a multiple of depth frames per flow).  Row j
+        of frame t sits at first[t] + j * stride[t] of fec_tx_flows_ilv_layout.  fec_sender_flows_ilv_info() says which path ran."""
+        return self._encode_packets_flows(code, source, frame_begin, fec_class, block0, order, out, want_flow_of, depth)
+
+    def fec_sender_flows_ilv_info(self):
+        """fec_sender_flows_info() for the last fec_encode_packets_flows_interleaved_device call."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_sender_flows_ilv_info(self._h, info), "fec_sender_flows_ilv_info")
         return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "frames": int(info[3])}
 
     # -- the block-interleaved sender (include/ldpc_erasure_amd_interleave.h)
@@ -1026,9 +1082,10 @@ class Context:
         self._check(self._L.ldpc_amd_fec_link_info(self._h, info), "fec_link_info")
         return dict(zip(("scratch_bytes", "plan_packets", "apply_packets", "apply_ragged_packets"), [int(x) for x in info]))
 
-    def fec_tx_flows(self, code, S, nflows, fec_class=1, block0=0):
-        """nflows senders that number their blocks across calls and share one wire (FecTxFlows)."""
-        return FecTxFlows(self, code, S, nflows, fec_class, block0)
+    def fec_tx_flows(self, code, S, nflows, fec_class=1, block0=0, depth=1):
+        """nflows senders that number their blocks across calls and share one wire (FecTxFlows); depth > 1: every flow's blocks
+        interleaved to that depth (include/ldpc_erasure_amd_interleave_flows.h)."""
+        return FecTxFlows(self, code, S, nflows, fec_class, block0, depth)
 
     def fec_tx_device(self, code, S, fec_class=1, block0=0):
         """A sender that numbers its blocks across calls (FecTxDevice)."""
@@ -1056,9 +1113,10 @@ class Context:
         return {"path": RX_WINDOW_PATHS[info[0]], "blocks": int(info[1]), "launches": int(info[2]), "scratch_bytes": int(info[3])}
 
     # -- ... for many flows (include/ldpc_erasure_amd_rx_window_flows.h)
-    def fec_rx_window_flows(self, nflows, n, k, S, window=4, ahead_limit=10):
-        """nflows windowed receivers that are fed, planned, decoded and flushed together (FecRxWindowFlows)."""
-        return FecRxWindowFlows(self, nflows, n, k, S, window, ahead_limit)
+    def fec_rx_window_flows(self, nflows, n, k, S, window=4, ahead_limit=10, depth=1):
+        """nflows windowed receivers that are fed, planned, decoded and flushed together (FecRxWindowFlows); depth > 1: every flow's
+        wire is interleaved to that depth (include/ldpc_erasure_amd_interleave_flows.h; needs 2 * depth <= window)."""
+        return FecRxWindowFlows(self, nflows, n, k, S, window, ahead_limit, depth)
 
     def fec_rx_window_flows_info(self):
         """fec_rx_window_info() for the last FecRxWindowFlows.decode_many / decode_flush_many call."""
@@ -1641,18 +1699,31 @@ class FecRxWindowFlows:
     and read back once, and every block that closed, of every flow, is decoded in one launch.  Flow f behaves exactly like a
     FecRxWindowHost fed its segment with max_blocks = max_blocks_per_flow.  The closed blocks come out dense in flow order: flow f's
     start at closes[:f].sum().  push_mixed / decode_mixed take the packets in arrival order with a flow number each instead
-    (include/ldpc_erasure_amd_rx_window_flows_mixed.h) and return the same; all calls mix freely.  Close it before its Context."""
+    (include/ldpc_erasure_amd_rx_window_flows_mixed.h) and return the same; all calls mix freely.  depth > 1: every flow follows the
+    rule for a wire interleaved to that depth, FecRxWindowHost(..., depth=depth) per flow (include/ldpc_erasure_amd_interleave_flows.h;
+    needs 2 * depth <= window).  Close it before its Context."""
 
-    def __init__(self, ctx, nflows, n, k, S, window=4, ahead_limit=10):
+    def __init__(self, ctx, nflows, n, k, S, window=4, ahead_limit=10, depth=1):
         self._ctx, self._L = ctx, ctx._L
         h = C.c_void_p()
-        ctx._check(self._L.ldpc_amd_fec_rxw_flows_create(ctx._h, nflows, n, k, S, window, ahead_limit, C.byref(h)), "fec_rxw_flows_create")
+        if depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
+            ctx._check(self._L.ldpc_amd_fec_rxw_flows_create(ctx._h, nflows, n, k, S, window, ahead_limit, C.byref(h)), "fec_rxw_flows_create")
+        else:
+            ctx._check(self._L.ldpc_amd_fec_rxw_flows_create_depth(ctx._h, nflows, n, k, S, window, ahead_limit, depth, C.byref(h)),
+                       "fec_rxw_flows_create")
         self._h, self.nflows, self.n, self.k, self.S, self.window, self.ahead_limit = h, nflows, n, k, S, window, ahead_limit
 
     _device = FecRxWindow._device
     _frames = FecRxWindow._frames
     _segments = FecRxFlows._segments
     _mixed = FecRxFlows._mixed
+
+    @property
+    def depth(self):
+        """The interleaving depth the object was created for (include/ldpc_erasure_amd_interleave_flows.h), 1: the plain rule."""
+        if not hasattr(self._L, "ldpc_amd_fec_rxw_flows_depth"):   # (the older builds tools/ab_lib.py loads)
+            return 1
+        return int(self._L.ldpc_amd_fec_rxw_flows_depth(self._h))
 
     def push_many(self, packets, flow_begin, max_blocks_per_flow):
         """packets: torch uint8 [P][8+S] on the device, flow_begin: nflows + 1 packet indices.  Returns (closes int32 [nflows],
@@ -1923,9 +1994,15 @@ class FecTxFlows:
     """The sender's side of FecRxFlows: nflows FecTxDevice on one wire.  Its state is the reference's block counter, one per flow
     (blockNum += 1 per frame, OpenCL/device/ldpc_erasure_encoder_VITA_in_UDP_out.cl:134): send(source, frame_begin, order) returns
     the packets of every flow's frames numbered from next_block[f] on, in the asked order, and advances each flow's counter by its
-    frame count modulo 256.  fec_class and block0: a scalar for all flows or one value per flow."""
+    frame count modulo 256.  fec_class and block0: a scalar for all flows or one value per flow.  depth > 1: every flow's blocks
+    are interleaved to that depth inside a call (include/ldpc_erasure_amd_interleave_flows.h), the input of
+    FecRxWindowFlows(..., depth=depth); TX_ROUND_ROBIN then takes whole aligned groups only -- every flow's next_block and frame
+    count a multiple of depth -- and send raises otherwise, with the counters unchanged."""
 
-    def __init__(self, ctx, code, S, nflows, fec_class=1, block0=0):
+    def __init__(self, ctx, code, S, nflows, fec_class=1, block0=0, depth=1):
+        if depth not in ILV_DEPTHS:
+            raise LdpcAmdError(f"FecTxFlows: depth must be one of {ILV_DEPTHS} (got {depth})")
+        self.depth = depth
         self._ctx, self.code, self.S, self.nflows = ctx, code, S, nflows
         self.n, self.k, _ = ctx.code_info(code)
         self.fec_class = np.ascontiguousarray(np.broadcast_to(np.asarray(fec_class, dtype=np.int64) & 0xFF, (nflows,)), dtype=np.uint8)
@@ -1937,8 +2014,12 @@ class FecTxFlows:
         assert (1 if source.ndim == 2 else source.shape[2]) == self.S
         fb = np.ascontiguousarray(frame_begin, dtype=np.int64)
         assert fb.shape == (self.nflows + 1,)
-        r = self._ctx.fec_encode_packets_flows_device(self.code, source, fb, self.fec_class, self.next_block, order, out=out,
-                                                      want_flow_of=want_flow_of)
+        if self.depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
+            r = self._ctx.fec_encode_packets_flows_device(self.code, source, fb, self.fec_class, self.next_block, order, out=out,
+                                                          want_flow_of=want_flow_of)
+        else:
+            r = self._ctx.fec_encode_packets_flows_interleaved_device(self.code, source, fb, self.fec_class, self.next_block, order, self.depth,
+                                                                      out=out, want_flow_of=want_flow_of)
         self.next_block = (self.next_block + np.diff(fb)) & 0xFF
         return r
 

@@ -214,6 +214,8 @@ struct ldpc_amd_ctx {
     int64_t txf_frames = 0;        // ... its frames
     int txi_path = 0;              // fec_encode_packets_ilv_dev (the same descriptor memory): path of the last call (ldpc_amd_fec_sender_ilv_info)
     int64_t txi_frames = 0;        // ... its frames
+    int txfi_path = 0;             // fec_encode_packets_flows_ilv_dev (the same descriptor memory): path of the last call (ldpc_amd_fec_sender_flows_ilv_info)
+    int64_t txfi_frames = 0;       // ... its frames
     // fec_dgram_pack_dev / fec_dgram_unpack_dev (datagram_dev.hip): pack's offsets on the device and their pinned staging, two slots
     // used in turn like txf_stage; unpack's per-row lengths and per-tile sums
     ldpc_amd::Scratch dgram_off, dgram_len;

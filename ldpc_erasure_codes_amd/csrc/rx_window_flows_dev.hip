@@ -4,6 +4,8 @@
 //   (a) rxwf_headers        every packet's header -> one dense u32, one pass over the whole array (flow-agnostic)          (parallel)
 //   (b) rxw_scan_flows      rxw_scan_body (rx_window_scan_dev.h) once per flow, one workgroup of one wavefront each, on the flow's
 //                           segment and state: serials, and with them `dest`, are LOCAL to the flow.  ONE copy back, ONE synchronisation.
+//                           rxw_scan_flows_grouped for an object of depth > 1 (include/ldpc_erasure_amd_interleave_flows.h): the only
+//                           step that looks at the depth, in segmented and mixed calls alike.
 //   (c) rxwf_winners        atomicMax of the GLOBAL packet index into the table [(T + W nflows)][n]                        (parallel)
 //   (d) rxwf_move<1>        the T closed slots -> sym_batch / erased_batch; or rxwf_sources: WHERE the decoder finds each row
 //   (e) rxwf_move<0>        the W open blocks of every flow -> their staging planes, in a launch behind (d) and the decode
@@ -37,6 +39,7 @@
 #include "../../include/ldpc_erasure_amd_rx_window.h"
 #include "../../include/ldpc_erasure_amd_rx_window_flows.h"
 #include "../../include/ldpc_erasure_amd_rx_window_flows_mixed.h"
+#include "../../include/ldpc_erasure_amd_interleave_flows.h"
 #define LDPC_AMD_RX_HOST_WINDOWED
 #include "rx_host.h"   // and with it rx_window_scan_dev.h
 #include "flows_demux_dev.h"   // the partition of a mixed call, and kMaxFlows
@@ -284,11 +287,28 @@ __global__ __launch_bounds__(kThreads) void rxwf_flush_move(const int32_t *__res
     }
 }
 
+// (b) for an object of depth D > 1 (include/ldpc_erasure_amd_interleave_flows.h): rxw_scan_flows with the depth-D rule.  It stands
+// behind the other kernels of the unit so that theirs keep their places in the code object.
+__global__ __launch_bounds__(64) void rxw_scan_flows_grouped(const uint32_t *__restrict__ dense, const WFlowIn *__restrict__ in, RxwRule r, int D,
+                                                            int max_blocks, int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    __shared__ int cnt[kMaxW];
+    __shared__ uint32_t hbuf[kScanChunk * 64];
+    const WFlowIn *f = in + blockIdx.x;
+    RxwState st;
+    st.base = f->base; st.ahead = f->ahead;
+#pragma unroll
+    for (int j = 0; j < kMaxW; j++) st.cnt[j] = f->cnt[j];
+    const int64_t begin = f->begin;
+    rxw_scan_body<true>(dense + begin, f->len, r, D, max_blocks, st, cnt, hbuf, dest + begin, res + (int64_t)blockIdx.x * (R_WORDS + max_blocks));
+}
+
 }  // namespace
 
 struct ldpc_amd_fec_rxw_flows {
     ldpc_amd_ctx *ctx = nullptr;
     int nflows = 0, n = 0, k = 0, S = 0, W = 0, A = 0, kd = 0, km = 0;
+    int D = 1;   // interleaving depth (include/ldpc_erasure_amd_interleave_flows.h); only the plan scan looks at it
     // host mirror of every flow's state, as in ldpc_amd_fec_rxw_dev; head: staging plane (of the flow's W) of slot 0
     std::vector<int> base, head, ahead;
     std::vector<int> cnt;           // [nflows][W]
@@ -418,7 +438,11 @@ int rxwf_plan(Rx *rx, const char *who, const uint8_t *packets, const WFlowsSrc &
         hipLaunchKernelGGL(rxwf_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     RxwRule r{n, rx->kd, rx->km, W, rx->A};
-    hipLaunchKernelGGL(rxw_scan_flows, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, r, max_blocks, dest, res);
+    if (rx->D > 1)
+        hipLaunchKernelGGL(rxw_scan_flows_grouped, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, r, rx->D,
+                           max_blocks, dest, res);
+    else
+        hipLaunchKernelGGL(rxw_scan_flows, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, r, max_blocks, dest, res);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->res_host, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
     LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -587,17 +611,28 @@ extern "C" {
 
 int ldpc_amd_fec_rxw_flows_create(ldpc_amd_ctx *ctx, int nflows, int n, int k, int S, int window, int ahead_limit, ldpc_amd_fec_rxw_flows **out)
 {
+    return ldpc_amd_fec_rxw_flows_create_depth(ctx, nflows, n, k, S, window, ahead_limit, 1, out);
+}
+
+int ldpc_amd_fec_rxw_flows_depth(const ldpc_amd_fec_rxw_flows *rx) { return rx ? rx->D : -1; }
+
+int ldpc_amd_fec_rxw_flows_create_depth(ldpc_amd_ctx *ctx, int nflows, int n, int k, int S, int window, int ahead_limit, int depth,
+                                        ldpc_amd_fec_rxw_flows **out)
+{
     if (!ctx) return LDPC_AMD_EINVAL;
     if (!out || nflows < 1 || nflows > kMaxFlows || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: need 1 <= nflows <= 4096, n <= 65536, 0 < k < n, S >= 1 (nflows=%d n=%d k=%d S=%d)",
                          nflows, n, k, S);
     int rc;
     if ((rc = rxw_check_create(ctx, "fec_rxw_flows_create", window, ahead_limit, (int64_t)nflows * window * n, "nflows * window * n"))) return rc;
+    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth) || (depth > 1 && 2 * depth > window))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: depth must be 1, 2, 4, 8 or 16, and a depth > 1 needs 2 * depth <= window (depth=%d window=%d)",
+                         depth, window);
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     Rx *rx = new (std::nothrow) Rx();
     if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rxw_flows_create: out of host memory");
     rx->ctx = ctx;
-    rx->nflows = nflows; rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit;
+    rx->nflows = nflows; rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit; rx->D = depth;
     rx->kd = k + (int)lround((n - k) * 0.8);
     rx->km = k + (int)lround((n - k) * 0.2);
     rx->base.assign((size_t)nflows, -1); rx->head.assign((size_t)nflows, 0); rx->ahead.assign((size_t)nflows, 0);

@@ -39,6 +39,7 @@
 #include "../../include/ldpc_erasure_amd_sender.h"
 #include "../../include/ldpc_erasure_amd_sender_flows.h"
 #include "../../include/ldpc_erasure_amd_interleave.h"
+#include "../../include/ldpc_erasure_amd_interleave_flows.h"
 #include "../../include/ldpc_erasure_amd_receiver.h"
 #include "../../include/ldpc_erasure_amd_flows.h"
 #include "../../include/ldpc_erasure_amd_flows_mixed.h"
@@ -807,34 +808,106 @@ int64_t ldpc_amd_fec_tx_flows_layout(int nflows, const int64_t *frame_begin, int
     return F * n;
 }
 
+// ---- depth on the multi-flow sender (include/ldpc_erasure_amd_interleave_flows.h) ----------------------------------------------
+// the first flow that breaks the whole-group condition of ROUND_ROBIN at depth D > 1 (a non-empty flow whose block0 or frame count
+// is no multiple of D), -1: none
+static int tx_flows_part_group(int nflows, const int64_t *frame_begin, const uint8_t *block0, int depth)
+{
+    if (depth <= 1) return -1;
+    for (int f = 0; f < nflows; f++) {
+        const int64_t c = frame_begin[f + 1] - frame_begin[f];
+        if (c > 0 && (block0[f] % depth != 0 || c % depth != 0)) return f;
+    }
+    return -1;
+}
+
+// The order as arithmetic.  SEGMENTED: every flow's single-flow interleaved layout, shifted to the flow's first packet.  ROUND_ROBIN:
+// ldpc_amd_fec_tx_flows_layout on GROUPS -- while group r of every flow is on the wire the active flows are those with more than
+// r D frames, A_r of them, and a round takes one packet of each: member i' of the group starts at base_r + rank + i' A_r, its rows
+// are D A_r packets apart, base_r = n D (A_0 + ... + A_{r-1}).  The active list is compacted in place as r grows.
+int64_t ldpc_amd_fec_tx_flows_ilv_layout(int nflows, const int64_t *frame_begin, int n, const uint8_t *block0, int depth, int order, int64_t *first,
+                                         int32_t *stride)
+{
+    if (!block0 || !LDPC_AMD_FEC_ILV_DEPTH_OK(depth)) return LDPC_AMD_EINVAL;
+    if (depth == 1) return ldpc_amd_fec_tx_flows_layout(nflows, frame_begin, n, order, first, stride);
+    if (nflows < 1 || nflows > LDPC_AMD_FEC_TX_MAX_FLOWS || !frame_begin || n < 1 || frame_begin[0] != 0) return LDPC_AMD_EINVAL;
+    if (order != LDPC_AMD_FEC_TX_SEGMENTED && order != LDPC_AMD_FEC_TX_ROUND_ROBIN) return LDPC_AMD_EINVAL;
+    for (int f = 0; f < nflows; f++)
+        if (frame_begin[f + 1] < frame_begin[f]) return LDPC_AMD_EINVAL;
+    const int64_t F = frame_begin[nflows];
+    if (F > (((int64_t)1 << 31) - 1) / n) return LDPC_AMD_EINVAL;   // F * n < 2^31
+    if (order == LDPC_AMD_FEC_TX_SEGMENTED) {
+        for (int f = 0; f < nflows; f++) {
+            const int64_t t0 = frame_begin[f], c = frame_begin[f + 1] - t0;
+            if (ldpc_amd_fec_tx_ilv_layout(c, n, block0[f], depth, first ? first + t0 : nullptr, stride ? stride + t0 : nullptr) != c * n)
+                return LDPC_AMD_EINVAL;
+            for (int64_t i = 0; first && i < c; i++) first[t0 + i] += t0 * n;
+        }
+        return F * n;
+    }
+    if (tx_flows_part_group(nflows, frame_begin, block0, depth) >= 0) return LDPC_AMD_EINVAL;
+    std::vector<int> active;
+    active.reserve((size_t)nflows);
+    for (int f = 0; f < nflows; f++)
+        if (frame_begin[f + 1] > frame_begin[f]) active.push_back(f);
+    int64_t base = 0;
+    for (int64_t r = 0; !active.empty(); r++) {
+        const int64_t A = (int64_t)active.size();
+        size_t keep = 0;
+        for (size_t rank = 0; rank < active.size(); rank++) {
+            const int f = active[rank];
+            const int64_t t = frame_begin[f] + r * depth;
+            for (int i = 0; i < depth; i++) {
+                if (first) first[t + i] = base + (int64_t)rank + i * A;
+                if (stride) stride[t + i] = (int32_t)(depth * A);
+            }
+            if (frame_begin[f + 1] - frame_begin[f] > (r + 1) * depth) active[keep++] = f;
+        }
+        active.resize(keep);
+        base += A * n * depth;
+    }
+    return F * n;
+}
+
 // Fused where launch_encode_packets_flows has the descriptor form of the packet encoder for this call; else composed: encode a
 // chunk of frames into the context's codeword scratch, packetise it by the descriptors, next chunk.
-int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
-                                          const uint8_t *fec_class, const uint8_t *block0, int order, uint8_t *packets, int32_t *flow_of,
-                                          int64_t *packet_begin)
+// The body of both multi-flow senders: depth 1 is the order of include/ldpc_erasure_amd_sender_flows.h, a depth above 1 that of
+// include/ldpc_erasure_amd_interleave_flows.h.  *path_out: 0 when nothing was sent (F == 0), else the path taken.
+static int tx_flows_send(ldpc_amd_ctx *ctx, const char *who, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
+                         const uint8_t *fec_class, const uint8_t *block0, int order, int depth, uint8_t *packets, int32_t *flow_of,
+                         int64_t *packet_begin, int *path_out)
 {
-    if (!ctx) return LDPC_AMD_EINVAL;
+    *path_out = 0;
     if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
     const DevCode &cd = ctx->codes[code]->dev;
     if (nflows < 1 || nflows > LDPC_AMD_FEC_TX_MAX_FLOWS)
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: nflows must be 1..%d (got %d)", LDPC_AMD_FEC_TX_MAX_FLOWS, nflows);
-    if (!frame_begin || !fec_class || !block0) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: frame_begin / fec_class / block0 must not be null");
-    if (S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: bad S");
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows must be 1..%d (got %d)", who, LDPC_AMD_FEC_TX_MAX_FLOWS, nflows);
+    if (!frame_begin || !fec_class || !block0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: frame_begin / fec_class / block0 must not be null", who);
+    if (S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: bad S", who);
     if (order != LDPC_AMD_FEC_TX_SEGMENTED && order != LDPC_AMD_FEC_TX_ROUND_ROBIN)
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: unknown order %d", order);
-    if (frame_begin[0] != 0) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: frame_begin must start at 0");
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: unknown order %d", who, order);
+    if (frame_begin[0] != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: frame_begin must start at 0", who);
     for (int f = 0; f < nflows; f++)
-        if (frame_begin[f + 1] < frame_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: frame_begin decreases at flow %d", f);
+        if (frame_begin[f + 1] < frame_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: frame_begin decreases at flow %d", who, f);
+    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: depth must be 1, 2, 4, 8 or 16 (got %d)", who, depth);
+    if (order == LDPC_AMD_FEC_TX_ROUND_ROBIN) {
+        const int f = tx_flows_part_group(nflows, frame_begin, block0, depth);
+        if (f >= 0)
+            return set_error(ctx, LDPC_AMD_EINVAL,
+                             "%s: round robin at depth %d needs whole aligned groups, block0 %% depth == 0 and frames %% depth == 0 for every flow "
+                             "(flow %d: block0=%d frames=%lld)",
+                             who, depth, f, (int)block0[f], (long long)(frame_begin[f + 1] - frame_begin[f]));
+    }
     const int64_t F = frame_begin[nflows];
     if (F > (((int64_t)1 << 31) - 1) / cd.n)
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: %lld frames of %d packets are not below 2^31 packets", (long long)F, cd.n);
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: %lld frames of %d packets are not below 2^31 packets", who, (long long)F, cd.n);
     if (F == 0) return LDPC_AMD_OK;
     if (cd.enc_nlevels == 0) return set_error(ctx, LDPC_AMD_EUNSUP, "code is not in triangle form: no systematic encoder");
     if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets) || (flow_of && !is_device_ptr(ctx, flow_of)))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: source / packets / flow_of must be device pointers of device %d", ctx->device);
-    if (((uintptr_t)flow_of & 3) != 0) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: flow_of must be 4-byte aligned");
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: source / packets / flow_of must be device pointers of device %d", who, ctx->device);
+    if (((uintptr_t)flow_of & 3) != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be 4-byte aligned", who);
     if (symbol_len_words(S) && ((uintptr_t)source & 3) != 0)
         return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
     const int n = cd.n;
@@ -843,9 +916,9 @@ int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, in
     {
         const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)F, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)F;
         const uintptr_t q0 = (uintptr_t)flow_of, q1 = q0 + sizeof(int32_t) * (size_t)P;
-        if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: source and packets overlap");
+        if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: source and packets overlap", who);
         if (flow_of && ((q0 < p1 && p0 < q1) || (q0 < s1 && s0 < q1)))
-            return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: flow_of overlaps source or packets");
+            return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of overlaps source or packets", who);
     }
     // the table: [F] descriptors, the frames' flows behind them
     const TxFrameDesc *dd = nullptr;
@@ -854,8 +927,8 @@ int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, in
         int32_t *hflow = (int32_t *)(hd + F);
         std::vector<int64_t> first((size_t)F);
         std::vector<int32_t> stride((size_t)F);
-        const int64_t got = ldpc_amd_fec_tx_flows_layout(nflows, frame_begin, n, order, first.data(), stride.data());
-        if (got != P) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_flows_dev: bad frame_begin");
+        const int64_t got = ldpc_amd_fec_tx_flows_ilv_layout(nflows, frame_begin, n, block0, depth, order, first.data(), stride.data());
+        if (got != P) return set_error(ctx, LDPC_AMD_EINVAL, "%s: bad frame_begin", who);
         for (int f = 0; f < nflows; f++)
             for (int64_t t = frame_begin[f]; t < frame_begin[f + 1]; t++) {
                 hd[t].first = (uint64_t)first[(size_t)t];
@@ -867,7 +940,7 @@ int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, in
         return LDPC_AMD_OK;
     };
     int rc;
-    if ((rc = tx_send_described(ctx, "fec_encode_packets_flows_dev", cd, S, F, sizeof(int32_t), source, packets, fill, &dd, &path))) return rc;
+    if ((rc = tx_send_described(ctx, who, cd, S, F, sizeof(int32_t), source, packets, fill, &dd, &path))) return rc;
     const int32_t *dflow = (const int32_t *)(dd + F);
     if (flow_of) {
         hipLaunchKernelGGL(fec_tx_flow_of, dim3(grid_for(P)), dim3(kThreads), 0, ctx->stream, dd, dflow, P, n, flow_of);
@@ -875,9 +948,23 @@ int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, in
     }
     if (packet_begin)
         for (int f = 0; f <= nflows; f++) packet_begin[f] = frame_begin[f] * n;
-    ctx->txf_path = path;
-    ctx->txf_frames = F;
+    *path_out = path;
     return LDPC_AMD_OK;
+}
+
+int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
+                                          const uint8_t *fec_class, const uint8_t *block0, int order, uint8_t *packets, int32_t *flow_of,
+                                          int64_t *packet_begin)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    int path = 0;
+    const int rc = tx_flows_send(ctx, "fec_encode_packets_flows_dev", code, S, nflows, frame_begin, source, fec_class, block0, order, 1, packets, flow_of,
+                                 packet_begin, &path);
+    if (rc == LDPC_AMD_OK && path) {
+        ctx->txf_path = path;
+        ctx->txf_frames = frame_begin[nflows];
+    }
+    return rc;
 }
 
 int ldpc_amd_fec_sender_flows_info(ldpc_amd_ctx *ctx, int64_t info[4])
@@ -964,6 +1051,33 @@ int ldpc_amd_fec_sender_ilv_info(ldpc_amd_ctx *ctx, int64_t info[4])
     info[1] = (int64_t)ctx->sender_cw.cap;
     info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
     info[3] = ctx->txi_frames;
+    return LDPC_AMD_OK;
+}
+
+// ---- the multi-flow sender with a depth (include/ldpc_erasure_amd_interleave_flows.h): tx_flows_send above ------------------------
+int ldpc_amd_fec_encode_packets_flows_ilv_dev(ldpc_amd_ctx *ctx, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
+                                              const uint8_t *fec_class, const uint8_t *block0, int order, uint8_t *packets, int32_t *flow_of,
+                                              int64_t *packet_begin, int depth)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    int path = 0;
+    const int rc = tx_flows_send(ctx, "fec_encode_packets_flows_ilv_dev", code, S, nflows, frame_begin, source, fec_class, block0, order, depth, packets,
+                                 flow_of, packet_begin, &path);
+    if (rc == LDPC_AMD_OK && path) {
+        ctx->txfi_path = path;
+        ctx->txfi_frames = frame_begin[nflows];
+    }
+    return rc;
+}
+
+int ldpc_amd_fec_sender_flows_ilv_info(ldpc_amd_ctx *ctx, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_sender_flows_ilv_info: info must not be null");
+    info[0] = ctx->txfi_path;
+    info[1] = (int64_t)ctx->sender_cw.cap;
+    info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
+    info[3] = ctx->txfi_frames;
     return LDPC_AMD_OK;
 }
 
