@@ -75,6 +75,12 @@ EXPORTS_INTERLEAVE_FLOWS = [
     "ldpc_amd_fec_rxw_flows_create_depth", "ldpc_amd_fec_rxw_flows_depth",
 ]
 # every symbol include/ldpc_erasure_amd_receiver.h declares (the fused receiver: wire packets straight to decoded frames)
+# include/ldpc_erasure_amd_rs_wire.h: Reed-Solomon on the FEC wire
+EXPORTS_RS_WIRE = [
+    "ldpc_amd_fec_rs_encode_packets_dev", "ldpc_amd_fec_rs_sender_info", "ldpc_amd_fec_rxw_dev_rs_decode_many",
+    "ldpc_amd_fec_rxw_dev_rs_decode_flush", "ldpc_amd_fec_rs_receiver_info",
+]
+FEC_CLASS_RS = 2   # LDPC_AMD_FEC_CLASS_RS
 EXPORTS_RECEIVER = ["ldpc_amd_fec_rx_dev_decode_many", "ldpc_amd_fec_rx_dev_decode_flush", "ldpc_amd_fec_receiver_info"]
 RECEIVER_PATHS = ("none", "fused", "composed")
 # every symbol include/ldpc_erasure_amd_words.h declares (word-sized symbols: any S that is a multiple of 4)
@@ -360,6 +366,12 @@ def load_library():
         L.ldpc_amd_fec_rxw_flows_unrouted.argtypes = [vp]
         L.ldpc_amd_fec_rxw_flows_unrouted.restype = i64
     # depth on the multi-flow wire (include/ldpc_erasure_amd_interleave_flows.h)
+    if hasattr(L, "ldpc_amd_fec_rs_encode_packets_dev"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_fec_rs_encode_packets_dev.argtypes = [vp, i32, i32, i64, vp, C.c_uint, C.c_uint, i32, vp]
+        L.ldpc_amd_fec_rs_sender_info.argtypes = [vp, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_dev_rs_decode_many.argtypes = [vp, i32, vp, i64, vp, vp, vp, vp, vp, i32, C.POINTER(i64)]
+        L.ldpc_amd_fec_rxw_dev_rs_decode_flush.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+        L.ldpc_amd_fec_rs_receiver_info.argtypes = [vp, C.POINTER(i64)]
     if hasattr(L, "ldpc_amd_fec_tx_flows_ilv_layout"):   # (absent from the older builds tools/ab_lib.py loads)
         L.ldpc_amd_fec_tx_flows_ilv_layout.argtypes = [i32, vp, i32, vp, i32, i32, vp, vp]
         L.ldpc_amd_fec_tx_flows_ilv_layout.restype = i64
@@ -977,6 +989,43 @@ class Context:
         """A sender that numbers its blocks across calls and emits them block-interleaved (FecTxInterleaved)."""
         return FecTxInterleaved(self, code, S, depth, fec_class, block0)
 
+    # -- Reed-Solomon on the wire (include/ldpc_erasure_amd_rs_wire.h)
+    def fec_rs_encode_packets_device(self, rs, source, depth=1, fec_class=FEC_CLASS_RS, block0=0, out=None):
+        """source: torch uint8 [B][k][S] (or [B][k] for S = 1) on this context's device, B blocks of the RS code `rs` -> packets
+        [B*n][8+S]: the packets of rs_encode + fec_packetize_device in depth-`depth` order -- row j of block b at index
+        first[b] + j * stride[b] of fec_tx_ilv_layout(B, n, block0, depth).  fec_rs_sender_info() says which path ran.
+        Asynchronous on the context's stream."""
+        import torch
+        assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
+        n, k = self.rs_info(rs)
+        B = source.shape[0]
+        S = 1 if source.ndim == 2 else source.shape[2]
+        assert source.shape[1] == k
+        if out is None:
+            out = torch.empty((B * n, 8 + S), dtype=torch.uint8, device=source.device)
+        assert tuple(out.shape) == (B * n, 8 + S) and out.dtype == torch.uint8
+        self._check(self._L.ldpc_amd_fec_rs_encode_packets_dev(self._h, rs, S, B, _ptr(source), fec_class, block0, depth, _ptr(out)),
+                    "fec_rs_encode_packets_dev")
+        return out
+
+    def fec_rs_sender_info(self):
+        """{"path": "none" | "fused" | "composed" of the last fec_rs_encode_packets_device call, "scratch_bytes": codeword scratch
+        the context holds for the composed paths, "descriptor_bytes": descriptor memory it holds, "blocks": blocks of that call}."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_rs_sender_info(self._h, info), "fec_rs_sender_info")
+        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "blocks": int(info[3])}
+
+    def fec_rs_receiver_info(self):
+        """{"blocks": blocks RS-decoded by the last FecRxWindow.rs_decode_many / rs_decode_flush of this context, "launches": its RS
+        decode launches, "scratch_bytes": received-symbol scratch it used}."""
+        info = (C.c_int64 * 4)()
+        self._check(self._L.ldpc_amd_fec_rs_receiver_info(self._h, info), "fec_rs_receiver_info")
+        return {"blocks": int(info[0]), "launches": int(info[1]), "scratch_bytes": int(info[2])}
+
+    def fec_tx_rs(self, rs, S, depth=1, block0=0):
+        """A sender of RS blocks that numbers them across calls and emits them block-interleaved (FecTxRs)."""
+        return FecTxRs(self, rs, S, depth, block0)
+
     # -- datagrams of any length (include/ldpc_erasure_amd_datagrams.h)
     def fec_pack_datagrams(self, data, offsets, k, S, out=None):
         """data: torch uint8 1-D on this context's device (a slice starting at any byte is fine), datagram i = data[offsets[i] :
@@ -1514,6 +1563,41 @@ class FecRxWindow(_RxWindowState):
             _ptr(fr.residual_src), blocks.ctypes.data), "fec_rxw_dev_decode_flush")
         return blocks[:nb], DecodedFrames(*(t[:nb] for t in fr))
 
+    def _rs_out(self, B, out):
+        import torch
+        dev = self._device()
+        if out is None:
+            out = (torch.empty((B, self.k, self.S), dtype=torch.uint8, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+                   torch.empty((B,), dtype=torch.int32, device=dev))
+        msg, received, status = out
+        assert tuple(msg.shape) == (B, self.k, self.S) and msg.dtype == torch.uint8 and msg.is_contiguous()
+        assert all(tuple(t.shape) == (B,) and t.dtype == torch.int32 for t in (received, status))
+        return msg, received, status
+
+    def rs_decode_many(self, rs, packets, max_blocks, out=None):
+        """push_many + Context.rs_decode_frames in one call (include/ldpc_erasure_amd_rs_wire.h): packets torch uint8 [P][8+S] on the
+        device -> (blocks int32 [B], msg torch uint8 [B][k][S], received torch int32 [B], status torch int32 [B], consumed).  `out`,
+        if given, is the (msg [max_blocks][k][S], received [max_blocks], status [max_blocks]) to write into.  Keep `packets` alive
+        until the context's stream has passed the call."""
+        import torch
+        assert _is_torch(packets) and packets.dtype == torch.uint8 and packets.ndim == 2 and packets.shape[1] == 8 + self.S
+        mb = max(max_blocks, 1)
+        msg, received, status = self._rs_out(mb, out)
+        blocks = np.zeros(mb, dtype=np.int32)
+        used = C.c_int64(0)
+        nb = self._ctx._check(self._L.ldpc_amd_fec_rxw_dev_rs_decode_many(
+            self._h, rs, _ptr(packets) if packets.numel() else None, packets.shape[0], _ptr(msg), _ptr(received), _ptr(status), None,
+            blocks.ctypes.data, max_blocks, C.byref(used)), "fec_rxw_dev_rs_decode_many")
+        return blocks[:nb], msg[:nb], received[:nb], status[:nb], used.value
+
+    def rs_decode_flush(self, rs):
+        """(blocks int32 [B], msg [B][k][S], received [B], status [B]) for the 0..window blocks the end of the stream closes."""
+        msg, received, status = self._rs_out(self.window, None)
+        blocks = np.zeros(self.window, dtype=np.int32)
+        nb = self._ctx._check(self._L.ldpc_amd_fec_rxw_dev_rs_decode_flush(self._h, rs, _ptr(msg), _ptr(received), _ptr(status), None,
+                                                                           blocks.ctypes.data), "fec_rxw_dev_rs_decode_flush")
+        return blocks[:nb], msg[:nb], received[:nb], status[:nb]
+
 
 class FecRxFlows:
     """nflows FecRxDevice in one object (include/ldpc_erasure_amd_flows.h): one packet array segmented by flow -- flow f owns the
@@ -1910,6 +1994,26 @@ class FecTxInterleaved:
     def send_datagrams_trimmed(self, data, offsets):
         """Pack + encode + trim, as FecTxDevice.send_datagrams_trimmed: Wire(bytes, offset) of the interleaved packets."""
         return self._ctx.fec_trim_packets(self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), self.k)
+
+
+class FecTxRs:
+    """FecTxInterleaved for the blocks of a Reed-Solomon code (include/ldpc_erasure_amd_rs_wire.h): send(source) returns the packets
+    of B blocks numbered from next_block on in depth-`depth` order, class FEC_CLASS_RS, the input of
+    FecRxWindow(n, k, S, ..., depth=depth).rs_decode_many, and advances the counter by B modulo 256."""
+
+    def __init__(self, ctx, rs, S, depth=1, block0=0):
+        if depth not in ILV_DEPTHS:
+            raise LdpcAmdError(f"FecTxRs: depth must be one of {ILV_DEPTHS} (got {depth})")
+        self._ctx, self.rs, self.S, self.depth = ctx, rs, S, depth
+        self.n, self.k = ctx.rs_info(rs)
+        self.next_block = block0 & 0xFF
+
+    def send(self, source, out=None):
+        """source: torch uint8 [B][k][S] (or [B][k] for S = 1) -> packets [B*n][8+S] in transmission order."""
+        assert (1 if source.ndim == 2 else source.shape[2]) == self.S
+        pk = self._ctx.fec_rs_encode_packets_device(self.rs, source, self.depth, FEC_CLASS_RS, self.next_block, out=out)
+        self.next_block = (self.next_block + source.shape[0]) & 0xFF
+        return pk
 
 
 class FecLink:

@@ -265,6 +265,14 @@ struct ldpc_amd_ctx {
     int64_t rxw_info[4] = {0, 0, 0, 0};
     // fec_rxw_flows_decode_many / _decode_flush_many (rx_window_flows_dev.hip): the same four words (ldpc_amd_fec_rxw_flows_info)
     int64_t rxwf_info[4] = {0, 0, 0, 0};
+    // fec_rs_encode_packets_dev (include/ldpc_erasure_amd_rs_wire.h): the packed-multiply table and the padded coefficients the packet
+    // encoder of rs_wire_dev.hip reads; path (0 none, 1 fused, 2 composed) and blocks of the last call (ldpc_amd_fec_rs_sender_info)
+    ldpc_amd::Scratch rsw_tab, rsw_coef;
+    int rsw_path = 0;
+    int64_t rsw_blocks = 0;
+    // fec_rxw_dev_rs_decode_many / _rs_decode_flush (rx_window_dev.hip): blocks, RS decode launches and scratch bytes of the last call
+    // (ldpc_amd_fec_rs_receiver_info)
+    int64_t rsrx_info[4] = {0, 0, 0, 0};
 };
 
 namespace ldpc_amd {
@@ -351,6 +359,12 @@ int launch_rs_decode(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks
 int launch_rs_decode_frames(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks, const uint8_t *sym, const uint8_t *erased,
                             uint8_t *msg, int32_t *received, int32_t *status);
 int launch_rs_encode(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks, const uint8_t *src, uint8_t *cw);
+// The RS sender's fused form (rs_wire_dev.hip): source [nblocks][k][S] -> packets [nblocks * n][8 + S], every block placed and numbered
+// by its 16-byte descriptor in device memory, as launch_encode_packets_flows places a frame.  Returns kEncodeNotFused, with nothing
+// launched, where the kernel does not apply: S = 1, ENC_PKT = 0, packets not 8-byte aligned, a source the fused LDPC sender would not
+// take, max_stride * (8 + S) beyond 32 bits.
+int launch_rs_encode_packets(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks, const uint8_t *src, const void *desc, int64_t max_stride,
+                             uint8_t *packets);
 int launch_fpga_stats(ldpc_amd_ctx *ctx, const DevCode &code, int rs_n, int rs_k, int64_t nframes,
                       const uint8_t *erased0, const int32_t *residual_k, unsigned long long *stats /* [2], accumulated */);
 

@@ -25,6 +25,7 @@
 #include <new>
 
 #include "../../include/ldpc_erasure_amd_rx_window.h"
+#include "../../include/ldpc_erasure_amd_rs_wire.h"
 #define LDPC_AMD_RX_HOST_WINDOWED
 #include "rx_host.h"   // and with it rx_window_scan_dev.h, (b) the plan scan: RxwRule, RxwState, the result record, rxw_scan_body
 
@@ -503,6 +504,134 @@ int ldpc_amd_fec_rxw_dev_decode_flush(ldpc_amd_fec_rxw_dev *rx, int code, int ma
     rxw_mirror_flush(rxw_mirror(rx), count, blocks);
     ctx->rxw_info[0] = 2; ctx->rxw_info[1] = count; ctx->rxw_info[2] = launches; ctx->rxw_info[3] = (int64_t)scratch;
     return count;
+}
+
+}  // extern "C"
+
+// ---- the RS decode tail (include/ldpc_erasure_amd_rs_wire.h) -------------------------------------------------------------------------
+// The checks both RS calls share.  *r: the code.
+static int rxw_rs_check(ldpc_amd_fec_rxw_dev *rx, const char *who, int rs, uint8_t *msg, int32_t *received, int32_t *status, uint8_t *erased_batch,
+                        const HostRs **r)
+{
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (rs < 0 || rs >= (int)ctx->rs.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown RS handle %d", rs);
+    *r = ctx->rs[rs];
+    if ((*r)->n != rx->n || (*r)->k != rx->k)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: the RS code is (%d,%d), the receiver was created for (%d,%d)", who, (*r)->n, (*r)->k, rx->n, rx->k);
+    if (!symbol_len_ok(ctx, rx->S)) return refuse_symbol_len(ctx, rx->S, "S must be 1 or a multiple of 16 (got %d)");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const void *opt[] = {received, status, erased_batch};
+    bool ok = msg && is_device_ptr(ctx, msg);
+    for (const void *p : opt) ok = ok && (!p || is_device_ptr(ctx, p));
+    if (!ok) return set_error(ctx, LDPC_AMD_EINVAL, "%s: msg and the result arrays must be device pointers of device %d", who, ctx->device);
+    return LDPC_AMD_OK;
+}
+
+// Everything T blocks of the call will need (rx_host.h, rule 1): the flags unless the caller takes them, the received symbols of one
+// chunk, and what launch_rs_decode_frames reserves for a chunk -- the selection, the malformed-block counter, the generic kernel's rows.
+static int rxw_rs_reserve(ldpc_amd_ctx *ctx, const HostRs &r, int S, int T, int64_t chunk, bool own_flags, size_t *scratch_bytes)
+{
+    *scratch_bytes = 0;
+    if (T <= 0) return LDPC_AMD_OK;
+    const size_t count = (size_t)std::min<int64_t>(chunk, T);
+    int rc;
+    if (own_flags && (rc = scratch_reserve(ctx, ctx->rx_er, (size_t)T * r.n))) return rc;
+    if ((rc = scratch_reserve(ctx, ctx->rx_sym, *scratch_bytes = count * (size_t)r.n * S))) return rc;
+    const size_t o_idx = (sizeof(int32_t) * count + 255) & ~(size_t)255;
+    if ((rc = scratch_reserve(ctx, ctx->rssel, o_idx + count * r.k * sizeof(uint16_t))) || (rc = scratch_reserve(ctx, ctx->rsbad, 64))) return rc;
+    if (S != 1 && (rc = scratch_reserve(ctx, ctx->rsws, std::min(count, (size_t)ctx->sm_count * 4) * (size_t)(r.n - r.k) * S))) return rc;
+    return LDPC_AMD_OK;
+}
+
+// gather(first, count, sym, er) a chunk of the T handed-out blocks, RS-decode it, next chunk
+template <class Gather>
+static int rxw_rs_slots(ldpc_amd_ctx *ctx, const HostRs &r, int S, int T, int64_t chunk, uint8_t *er, uint8_t *msg, int32_t *received, int32_t *status,
+                        Gather gather, int *launches)
+{
+    *launches = 0;
+    uint8_t *sym = (uint8_t *)ctx->rx_sym.p;
+    int rc;
+    for (int first = 0; first < T; first += (int)chunk) {
+        const int count = (int)std::min<int64_t>(chunk, T - first);
+        if ((rc = gather(first, count, sym, er + (size_t)first * r.n))) return rc;
+        if ((rc = launch_rs_decode_frames(ctx, r, S, count, sym, er + (size_t)first * r.n, msg + (size_t)first * r.k * S, received ? received + first : nullptr,
+                                          status ? status + first : nullptr)))
+            return rc;
+        ++*launches;
+    }
+    return LDPC_AMD_OK;
+}
+
+extern "C" {
+
+// push_many + rs_decode_frames in one call, composed: (d) gathers the closed blocks chunk by chunk into the context's scratch, the RS
+// decoder follows each chunk; (e) behind the decode, as in decode_many.
+int ldpc_amd_fec_rxw_dev_rs_decode_many(ldpc_amd_fec_rxw_dev *rx, int rs, const uint8_t *packets, int64_t npackets, uint8_t *msg,
+                                        int32_t *received, int32_t *status, uint8_t *erased_batch, int *blocks, int max_blocks,
+                                        int64_t *consumed)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    if (rs < 0 || rs >= (int)ctx->rs.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown RS handle %d", rs);
+    if (npackets < 0 || npackets >= ((int64_t)1 << 31) || max_blocks < 1)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_rs_decode_many: need 0 <= npackets < 2^31 and max_blocks >= 1");
+    const HostRs *r = nullptr;
+    int rc;
+    if ((rc = rxw_rs_check(rx, "fec_rxw_dev_rs_decode_many", rs, msg, received, status, erased_batch, &r))) return rc;
+    if (consumed) *consumed = 0;
+    if (npackets == 0) return 0;
+    if (!packets || !is_device_ptr(ctx, packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_rs_decode_many: packets must be a device pointer of device %d", ctx->device);
+    const int S = rx->S;
+    const int64_t chunk = rx_chunk(max_blocks, (size_t)rx->n * S);
+
+    RxwPlan pl;
+    if ((rc = rxw_plan(rx, "fec_rxw_dev_rs_decode_many", packets, npackets, max_blocks, pl))) return rc;
+    const int closes = pl.closes;
+    size_t scratch = 0;
+    if ((rc = rxw_rs_reserve(ctx, *r, S, closes, chunk, erased_batch == nullptr, &scratch))) return rc;
+    if ((rc = rxw_winners_launch(rx, pl))) return rc;
+    uint8_t *er = erased_batch ? erased_batch : (uint8_t *)ctx->rx_er.p;
+    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *e) { return rxw_move_launch<true>(rx, pl, packets, first, count, sym, e); };
+    int launches = 0;
+    if ((rc = rxw_rs_slots(ctx, *r, S, closes, chunk, er, msg, received, status, gather, &launches))) return rc;
+    if ((rc = rxw_move_launch<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
+    rxw_commit(rx, pl, blocks, consumed);
+    ctx->rsrx_info[0] = closes; ctx->rsrx_info[1] = launches; ctx->rsrx_info[2] = (int64_t)scratch; ctx->rsrx_info[3] = 0;
+    return closes;
+}
+
+// flush + RS decode: the blocks lie complete in their planes, a chunk of them goes to the scratch (its planes reset by the same launch)
+// and through the RS decoder
+int ldpc_amd_fec_rxw_dev_rs_decode_flush(ldpc_amd_fec_rxw_dev *rx, int rs, uint8_t *msg, int32_t *received, int32_t *status,
+                                         uint8_t *erased_batch, int *blocks)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    ldpc_amd_ctx *ctx = rx->ctx;
+    const HostRs *r = nullptr;
+    int rc;
+    if ((rc = rxw_rs_check(rx, "fec_rxw_dev_rs_decode_flush", rs, msg, received, status, erased_batch, &r))) return rc;
+    const int count = rxw_mirror_flush_count(rx->cnt, rx->W);
+    if (count == 0) return 0;
+    const int S = rx->S;
+    const int64_t chunk = rx_chunk(count, (size_t)rx->n * S);
+    size_t scratch = 0;
+    if ((rc = rxw_rs_reserve(ctx, *r, S, count, chunk, erased_batch == nullptr, &scratch))) return rc;
+    uint8_t *er = erased_batch ? erased_batch : (uint8_t *)ctx->rx_er.p;
+    auto gather = [&](int first, int c, uint8_t *sym, uint8_t *e) { return rxw_flush_launch(rx, first, c, sym, e); };
+    int launches = 0;
+    if ((rc = rxw_rs_slots(ctx, *r, S, count, chunk, er, msg, received, status, gather, &launches))) return rc;
+    rxw_mirror_flush(rxw_mirror(rx), count, blocks);
+    ctx->rsrx_info[0] = count; ctx->rsrx_info[1] = launches; ctx->rsrx_info[2] = (int64_t)scratch; ctx->rsrx_info[3] = 0;
+    return count;
+}
+
+int ldpc_amd_fec_rs_receiver_info(ldpc_amd_ctx *ctx, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_receiver_info: info must not be null");
+    memcpy(info, ctx->rsrx_info, sizeof(ctx->rsrx_info));
+    return LDPC_AMD_OK;
 }
 
 int ldpc_amd_fec_rxw_info(ldpc_amd_ctx *ctx, int64_t info[4])

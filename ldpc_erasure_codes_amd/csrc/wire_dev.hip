@@ -40,6 +40,7 @@
 #include "../../include/ldpc_erasure_amd_sender_flows.h"
 #include "../../include/ldpc_erasure_amd_interleave.h"
 #include "../../include/ldpc_erasure_amd_interleave_flows.h"
+#include "../../include/ldpc_erasure_amd_rs_wire.h"
 #include "../../include/ldpc_erasure_amd_receiver.h"
 #include "../../include/ldpc_erasure_amd_flows.h"
 #include "../../include/ldpc_erasure_amd_flows_mixed.h"
@@ -627,19 +628,15 @@ struct ldpc_amd_fec_rx_dev {
 
 namespace {
 
-// ---- the descriptor-driven senders' common part (ldpc_amd_fec_encode_packets_flows_dev, ldpc_amd_fec_encode_packets_ilv_dev) --------
-// Stages a call's table -- [F] descriptors and `extra` further bytes per frame behind them -- and sends the frames by it.  The table
-// is filled by fill(hd, &max_stride) in a pinned slot of the context (two slots used in turn, each with the event of its last copy, so
-// that a slot is never rewritten under a copy in flight: two calls enqueued back to back are both right), copied to the context's
-// device table on the stream, and followed by the descriptor form of the packet encoder (path 1, fused) where
-// launch_encode_packets_flows has it for this call, else by the encoder into the context's codeword scratch and the descriptor-driven
-// packetisers, chunk by chunk (path 2, composed).  *dd: the device table.
+// ---- the descriptor-driven senders' common part (ldpc_amd_fec_encode_packets_flows_dev, ldpc_amd_fec_encode_packets_ilv_dev,
+// ldpc_amd_fec_rs_encode_packets_dev) --------
+// tx_stage_described stages a call's table -- [F] descriptors and `extra` further bytes per frame behind them.  The table is filled by
+// fill(hd, &max_stride) in a pinned slot of the context (two slots used in turn, each with the event of its last copy, so that a slot
+// is never rewritten under a copy in flight: two calls enqueued back to back are both right) and copied to the context's device table
+// on the stream.  *dd_out: the device table.
 template <class Fill>
-int tx_send_described(ldpc_amd_ctx *ctx, const char *who, const DevCode &cd, int S, int64_t F, size_t extra, const uint8_t *source,
-                      uint8_t *packets, Fill fill, const TxFrameDesc **dd_out, int *path_out)
+int tx_stage_described(ldpc_amd_ctx *ctx, const char *who, int64_t F, size_t extra, Fill fill, const TxFrameDesc **dd_out, int64_t *max_stride_out)
 {
-    const int n = cd.n;
-    const size_t src_frame = (size_t)cd.k * S, cw_frame = (size_t)n * S;
     const size_t tab_bytes = (sizeof(TxFrameDesc) + extra) * (size_t)F;
     int rc;
     if ((rc = scratch_reserve(ctx, ctx->txf_desc, tab_bytes))) return rc;
@@ -663,11 +660,41 @@ int tx_send_described(ldpc_amd_ctx *ctx, const char *who, const DevCode &cd, int
     TxFrameDesc *hd = (TxFrameDesc *)ctx->txf_stage[slot];
     int64_t max_stride = 1;
     if ((rc = fill(hd, &max_stride))) return rc;
-    const TxFrameDesc *dd = (const TxFrameDesc *)ctx->txf_desc.p;
     LDPC_HIP_TRY(ctx, hipMemcpyAsync(ctx->txf_desc.p, hd, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
     LDPC_HIP_TRY(ctx, hipEventRecord(ctx->txf_event[slot], ctx->stream));
     ctx->txf_pending[slot] = true;
     ctx->txf_calls++;
+    *dd_out = (const TxFrameDesc *)ctx->txf_desc.p;
+    *max_stride_out = max_stride;
+    return LDPC_AMD_OK;
+}
+
+// the composed senders' packetiser: the codewords cw of the `cnt` frames that dd describes -> their packets
+inline int tx_packetize_described(ldpc_amd_ctx *ctx, const uint8_t *cw, int64_t cnt, int n, int S, const TxFrameDesc *dd, uint8_t *packets)
+{
+    const int64_t rows = cnt * n;
+    if (S % 16 == 0 && ((uintptr_t)packets & 7) == 0)   // (the scratch is 16-byte aligned)
+        hipLaunchKernelGGL(fec_packetize_flows_v16, dim3(grid_for(rows * (S / 16))), dim3(kThreads), 0, ctx->stream, reinterpret_cast<const uint4 *>(cw),
+                           rows, n, S / 16, dd, packets);
+    else
+        hipLaunchKernelGGL(fec_packetize_flows_bytes, dim3(grid_for(rows * (S + kHdr))), dim3(kThreads), 0, ctx->stream, cw, rows, n, S, dd, packets);
+    LDPC_HIP_TRY(ctx, hipGetLastError());
+    return LDPC_AMD_OK;
+}
+
+// Stages the table and sends the LDPC frames by it: the descriptor form of the packet encoder (path 1, fused) where
+// launch_encode_packets_flows has it for this call, else the encoder into the context's codeword scratch and the descriptor-driven
+// packetisers, chunk by chunk (path 2, composed).  *dd: the device table.
+template <class Fill>
+int tx_send_described(ldpc_amd_ctx *ctx, const char *who, const DevCode &cd, int S, int64_t F, size_t extra, const uint8_t *source,
+                      uint8_t *packets, Fill fill, const TxFrameDesc **dd_out, int *path_out)
+{
+    const int n = cd.n;
+    const size_t src_frame = (size_t)cd.k * S, cw_frame = (size_t)n * S;
+    int rc;
+    const TxFrameDesc *dd = nullptr;
+    int64_t max_stride = 1;
+    if ((rc = tx_stage_described(ctx, who, F, extra, fill, &dd, &max_stride))) return rc;
     rc = launch_encode_packets_flows(ctx, cd, S, F, source, dd, max_stride, packets);
     if (rc != LDPC_AMD_OK && rc != kEncodeNotFused) return rc;
     const int path = rc == LDPC_AMD_OK ? 1 : 2;
@@ -675,17 +702,10 @@ int tx_send_described(ldpc_amd_ctx *ctx, const char *who, const DevCode &cd, int
         const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)(kSenderScratchMax / cw_frame)));
         if ((rc = scratch_reserve(ctx, ctx->sender_cw, (size_t)chunk * cw_frame))) return rc;
         uint8_t *cw = (uint8_t *)ctx->sender_cw.p;
-        const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0;   // (the scratch is 16-byte aligned)
         for (int64_t f0 = 0; f0 < F; f0 += chunk) {
-            const int64_t cnt = std::min(chunk, F - f0), rows = cnt * n;
+            const int64_t cnt = std::min(chunk, F - f0);
             if ((rc = launch_encode(ctx, cd, S, cnt, source + (size_t)f0 * src_frame, cw))) return rc;
-            if (v16)
-                hipLaunchKernelGGL(fec_packetize_flows_v16, dim3(grid_for(rows * (S / 16))), dim3(kThreads), 0, ctx->stream,
-                                   reinterpret_cast<const uint4 *>(cw), rows, n, S / 16, dd + f0, packets);
-            else
-                hipLaunchKernelGGL(fec_packetize_flows_bytes, dim3(grid_for(rows * (S + kHdr))), dim3(kThreads), 0, ctx->stream, cw, rows, n, S,
-                                   dd + f0, packets);
-            LDPC_HIP_TRY(ctx, hipGetLastError());
+            if ((rc = tx_packetize_described(ctx, cw, cnt, n, S, dd + f0, packets))) return rc;
         }
     }
     *dd_out = dd;
@@ -1051,6 +1071,78 @@ int ldpc_amd_fec_sender_ilv_info(ldpc_amd_ctx *ctx, int64_t info[4])
     info[1] = (int64_t)ctx->sender_cw.cap;
     info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
     info[3] = ctx->txi_frames;
+    return LDPC_AMD_OK;
+}
+
+// ---- the Reed-Solomon sender (include/ldpc_erasure_amd_rs_wire.h) ------------------------------------------------------------------
+// The interleaved sender's checks, layout and descriptor staging for the blocks of an RS code; then the packet encoder of
+// rs_wire_dev.hip (path 1, fused) where launch_rs_encode_packets has it for this call, else the RS encoder into the context's codeword
+// scratch and the descriptor-driven packetisers, chunk by chunk (path 2, composed).
+int ldpc_amd_fec_rs_encode_packets_dev(ldpc_amd_ctx *ctx, int rs, int S, int64_t nblocks, const uint8_t *source, unsigned fec_class,
+                                       unsigned block0, int depth, uint8_t *packets)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (rs < 0 || rs >= (int)ctx->rs.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown RS handle %d", rs);
+    const HostRs &r = *ctx->rs[rs];
+    if (nblocks < 0 || S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: bad nblocks/S");
+    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth)) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: depth must be 1, 2, 4, 8 or 16 (got %d)", depth);
+    const int64_t F = nblocks;
+    const int n = r.n;
+    if (F > (((int64_t)1 << 31) - 1) / n)
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: %lld blocks of %d packets are not below 2^31 packets", (long long)F, n);
+    if (F == 0) return LDPC_AMD_OK;
+    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: source / packets must be device pointers of device %d", ctx->device);
+    if (symbol_len_words(S) && ((uintptr_t)source & 3) != 0)
+        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
+    const size_t src_frame = (size_t)r.k * S, cw_frame = (size_t)n * S, pk_frame = (size_t)n * ((size_t)S + kHdr);
+    const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)F, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)F;
+    if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: source and packets overlap");
+    auto fill = [&](TxFrameDesc *hd, int64_t *max_stride) -> int {
+        std::vector<int64_t> first((size_t)F);
+        std::vector<int32_t> stride((size_t)F);
+        if (ldpc_amd_fec_tx_ilv_layout(F, n, block0, depth, first.data(), stride.data()) != F * n)
+            return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: bad layout arguments");
+        for (int64_t t = 0; t < F; t++) {
+            hd[t].first = (uint64_t)first[(size_t)t];
+            hd[t].stride = (uint32_t)stride[(size_t)t];
+            hd[t].hdr = ((fec_class & 0xffu) << 8) | (uint32_t)((block0 + (uint64_t)t) & 0xffu);
+            *max_stride = std::max<int64_t>(*max_stride, stride[(size_t)t]);
+        }
+        return LDPC_AMD_OK;
+    };
+    int rc;
+    const TxFrameDesc *dd = nullptr;
+    int64_t max_stride = 1;
+    if ((rc = tx_stage_described(ctx, "fec_rs_encode_packets_dev", F, 0, fill, &dd, &max_stride))) return rc;
+    rc = launch_rs_encode_packets(ctx, r, S, F, source, dd, max_stride, packets);
+    if (rc != LDPC_AMD_OK && rc != kEncodeNotFused) return rc;
+    const int path = rc == LDPC_AMD_OK ? 1 : 2;
+    if (path == 2) {
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)(kSenderScratchMax / cw_frame)));
+        if ((rc = scratch_reserve(ctx, ctx->sender_cw, (size_t)chunk * cw_frame))) return rc;
+        uint8_t *cw = (uint8_t *)ctx->sender_cw.p;
+        for (int64_t f0 = 0; f0 < F; f0 += chunk) {
+            const int64_t cnt = std::min(chunk, F - f0);
+            if ((rc = launch_rs_encode(ctx, r, S, cnt, source + (size_t)f0 * src_frame, cw))) return rc;
+            if ((rc = tx_packetize_described(ctx, cw, cnt, n, S, dd + f0, packets))) return rc;
+        }
+    }
+    ctx->rsw_path = path;
+    ctx->rsw_blocks = F;
+    return LDPC_AMD_OK;
+}
+
+int ldpc_amd_fec_rs_sender_info(ldpc_amd_ctx *ctx, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_sender_info: info must not be null");
+    info[0] = ctx->rsw_path;
+    info[1] = (int64_t)ctx->sender_cw.cap;
+    info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
+    info[3] = ctx->rsw_blocks;
     return LDPC_AMD_OK;
 }
 
