@@ -43,12 +43,15 @@
  * rewritten behind the decode: a refused call leaves the receiver where it was.  RS calls, the LDPC decode calls, push_many and the
  * flushes mix freely on one object.
  *
- * THE CLOSE RULE ON SHORT BLOCKS.  The receiver closes a block early when it holds more than k + round(0.2 (n-k)) symbols and later
+ * THE CLOSE RULE ON SHORT BLOCKS.  A receiver made without a rule follows the default rule: it closes a block early when it holds more than k + round(0.2 (n-k)) symbols and later
  * blocks have sent more than 100 packets, or more than k + round(0.8 (n-k)) and more than 10.  For RS(255,192) these are 205 and 242 of
  * 255: on the reference's bursty channel (mean bad-state run of 10 packets) one burst takes a short block under 205 where a
  * (2040,1530) block, eight times as long, stays far above its 1632.  Such a block leaves through the ahead limit or the flush -- it is still
  * decoded if it holds k symbols -- and each forced close drops the packets that were ahead of the window.  An RS receiver wants a
- * window of at least two interleaving groups and an ahead limit sized for it.
+ * window of at least two interleaving groups and an ahead limit sized for it -- and a close rule set from k: create it with
+ * ldpc_amd_fec_rxw_dev_create_rule and the rule of ldpc_amd_fec_rx_rule_mds(n, k, depth, 0) (ldpc_erasure_amd_rx_rule.h), under
+ * which a block leaves at its k-th symbol once the next group has begun, or once the stream has moved on by depth * k / 2 packets,
+ * and the ahead limit is not reached.  Both RS calls work on an object of any rule.
  */
 #ifndef LDPC_ERASURE_AMD_RS_WIRE_H
 #define LDPC_ERASURE_AMD_RS_WIRE_H

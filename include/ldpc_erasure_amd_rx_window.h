@@ -31,7 +31,9 @@
  * next trip (A + 1 further packets ahead of it).
  *
  * Out of scope here: many flows per object and their batch flush -- ldpc_erasure_amd_rx_window_flows.h has both; a wire whose
- * blocks are interleaved -- ldpc_erasure_amd_interleave.h has the depth-D form of both objects (the ones here are its depth 1).
+ * blocks are interleaved -- ldpc_erasure_amd_interleave.h has the depth-D form of both objects (the ones here are its depth 1);
+ * other thresholds in step 3's close test -- ldpc_erasure_amd_rx_rule.h has the rule as a value (the objects here follow its
+ * default rule, the one written out above).
  */
 #ifndef LDPC_ERASURE_AMD_RX_WINDOW_H
 #define LDPC_ERASURE_AMD_RX_WINDOW_H

@@ -138,6 +138,12 @@ EXPORTS_RX_WINDOW_FLOWS = [
 WindowFlowsPending = collections.namedtuple("WindowFlowsPending", "base cnt blocks")
 # every symbol include/ldpc_erasure_amd_rx_window_flows_mixed.h declares (the windowed multi-flow receiver fed with interleaved packets)
 EXPORTS_RX_WINDOW_FLOWS_MIXED = ["ldpc_amd_fec_rxw_flows_push_mixed", "ldpc_amd_fec_rxw_flows_decode_mixed", "ldpc_amd_fec_rxw_flows_unrouted"]
+# every symbol include/ldpc_erasure_amd_rx_rule.h declares (the close rule of the windowed receivers as a value)
+EXPORTS_RX_RULE = [
+    "ldpc_amd_fec_rx_rule_default", "ldpc_amd_fec_rx_rule_mds", "ldpc_amd_fec_rx_rule_check", "ldpc_amd_fec_rxw_create_rule",
+    "ldpc_amd_fec_rxw_dev_create_rule", "ldpc_amd_fec_rxw_flows_create_rule", "ldpc_amd_fec_rxw_get_rule", "ldpc_amd_fec_rxw_dev_get_rule",
+    "ldpc_amd_fec_rxw_flows_get_rule",
+]
 
 DecodedFrames = collections.namedtuple("DecodedFrames", "out sweeps residual status erased_out residual_src")
 RsDecodedFrames = collections.namedtuple("RsDecodedFrames", "msg received status")
@@ -149,6 +155,11 @@ class LdpcAmdError(RuntimeError):
 
 class ErrorType(C.Structure):
     _fields_ = [("num_LDPC_errors", C.c_int), ("num_RS_errors", C.c_int)]
+
+
+class RxRule(C.Structure):
+    """ldpc_amd_fec_rx_rule"""
+    _fields_ = [("c_hi", C.c_int32), ("later_hi", C.c_int32), ("c_lo", C.c_int32), ("later_lo", C.c_int32)]
 
 
 class LinkParams(C.Structure):
@@ -379,6 +390,18 @@ def load_library():
         L.ldpc_amd_fec_sender_flows_ilv_info.argtypes = [vp, C.POINTER(i64)]
         L.ldpc_amd_fec_rxw_flows_create_depth.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
         L.ldpc_amd_fec_rxw_flows_depth.argtypes = [vp]
+    # the close rule as a value (include/ldpc_erasure_amd_rx_rule.h)
+    if hasattr(L, "ldpc_amd_fec_rx_rule_default"):   # (absent from the older builds tools/ab_lib.py loads)
+        rp = C.POINTER(RxRule)
+        L.ldpc_amd_fec_rx_rule_default.argtypes = [i32, i32, rp]
+        L.ldpc_amd_fec_rx_rule_mds.argtypes = [i32, i32, i32, i32, rp]
+        L.ldpc_amd_fec_rx_rule_check.argtypes = [i32, rp]
+        L.ldpc_amd_fec_rxw_create_rule.argtypes = [i32, i32, i32, i32, i32, i32, rp, C.POINTER(vp)]
+        L.ldpc_amd_fec_rxw_dev_create_rule.argtypes = [vp, i32, i32, i32, i32, i32, i32, rp, C.POINTER(vp)]
+        L.ldpc_amd_fec_rxw_flows_create_rule.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, rp, C.POINTER(vp)]
+        L.ldpc_amd_fec_rxw_get_rule.argtypes = [vp, rp]
+        L.ldpc_amd_fec_rxw_dev_get_rule.argtypes = [vp, rp]
+        L.ldpc_amd_fec_rxw_flows_get_rule.argtypes = [vp, rp]
     # frames out / frames in (include/ldpc_erasure_amd_frames.h)
     L.ldpc_amd_decode_frames.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint]
     L.ldpc_amd_rs_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -410,6 +433,33 @@ def gf_tables():
     inv = np.zeros(256, dtype=np.uint8)
     L.ldpc_amd_gf_tables(mult.ctypes.data, inv.ctypes.data)
     return mult, inv
+
+
+def fec_rx_rule_default(n, k):
+    """The close rule the windowed receivers follow when none is given (include/ldpc_erasure_amd_rx_rule.h), as the 4-tuple
+    (c_hi, later_hi, c_lo, later_lo) = (kd + 1, 11, km + 1, 101).  Host arithmetic, no GPU needed."""
+    r = RxRule()
+    if load_library().ldpc_amd_fec_rx_rule_default(n, k, C.byref(r)) != 0:
+        raise LdpcAmdError(f"fec_rx_rule_default: need 0 < k < n <= 65536 (n={n} k={k})")
+    return (r.c_hi, r.later_hi, r.c_lo, r.later_lo)
+
+
+def fec_rx_rule_mds(n, k, depth=1, giveup=0):
+    """The close rule for a code that decodes from any k symbols (Reed-Solomon) on a wire that is roughly in order: (k, 1, 0, giveup),
+    giveup == 0 meaning max(1, depth * k // 2).  Slot 0 leaves at its k-th symbol once a later group has begun, and in any case once
+    the later groups have sent `giveup` packets (include/ldpc_erasure_amd_rx_rule.h)."""
+    r = RxRule()
+    if load_library().ldpc_amd_fec_rx_rule_mds(n, k, depth, giveup, C.byref(r)) != 0:
+        raise LdpcAmdError(f"fec_rx_rule_mds: bad arguments (n={n} k={k} depth={depth} giveup={giveup})")
+    return (r.c_hi, r.later_hi, r.c_lo, r.later_lo)
+
+
+def _rx_rule(rule):
+    """A 4-tuple (c_hi, later_hi, c_lo, later_lo) as the C struct."""
+    rule = tuple(int(v) for v in rule)
+    if len(rule) != 4:
+        raise LdpcAmdError("a close rule is a 4-tuple (c_hi, later_hi, c_lo, later_lo)")
+    return RxRule(*rule)
 
 
 def code_params(code_ind):
@@ -1149,10 +1199,11 @@ class Context:
         return {"path": RECEIVER_PATHS[info[0]], "scratch_bytes": int(info[1]), "blocks": int(info[2])}
 
     # -- the windowed receiver (include/ldpc_erasure_amd_rx_window.h)
-    def fec_rx_window(self, n, k, S, window=4, ahead_limit=10, depth=1):
+    def fec_rx_window(self, n, k, S, window=4, ahead_limit=10, depth=1, rule=None):
         """A device receiver that keeps `window` blocks open and resynchronises after `ahead_limit` packets beyond them (FecRxWindow);
-        depth > 1: for a wire interleaved to that depth (include/ldpc_erasure_amd_interleave.h; needs 2 * depth <= window)."""
-        return FecRxWindow(self, n, k, S, window, ahead_limit, depth)
+        depth > 1: for a wire interleaved to that depth (include/ldpc_erasure_amd_interleave.h; needs 2 * depth <= window); rule: its
+        close rule as a 4-tuple (include/ldpc_erasure_amd_rx_rule.h), None: the default rule."""
+        return FecRxWindow(self, n, k, S, window, ahead_limit, depth, rule)
 
     def fec_rx_window_info(self):
         """{"path": "none" | "fused" | "composed" of the last FecRxWindow.decode_many / decode_flush call, "blocks": the blocks it
@@ -1162,10 +1213,11 @@ class Context:
         return {"path": RX_WINDOW_PATHS[info[0]], "blocks": int(info[1]), "launches": int(info[2]), "scratch_bytes": int(info[3])}
 
     # -- ... for many flows (include/ldpc_erasure_amd_rx_window_flows.h)
-    def fec_rx_window_flows(self, nflows, n, k, S, window=4, ahead_limit=10, depth=1):
+    def fec_rx_window_flows(self, nflows, n, k, S, window=4, ahead_limit=10, depth=1, rule=None):
         """nflows windowed receivers that are fed, planned, decoded and flushed together (FecRxWindowFlows); depth > 1: every flow's
-        wire is interleaved to that depth (include/ldpc_erasure_amd_interleave_flows.h; needs 2 * depth <= window)."""
-        return FecRxWindowFlows(self, nflows, n, k, S, window, ahead_limit, depth)
+        wire is interleaved to that depth (include/ldpc_erasure_amd_interleave_flows.h; needs 2 * depth <= window); rule: the close
+        rule of every flow as a 4-tuple (include/ldpc_erasure_amd_rx_rule.h), None: the default rule."""
+        return FecRxWindowFlows(self, nflows, n, k, S, window, ahead_limit, depth, rule)
 
     def fec_rx_window_flows_info(self):
         """fec_rx_window_info() for the last FecRxWindowFlows.decode_many / decode_flush_many call."""
@@ -1417,6 +1469,14 @@ class _RxWindowState:
         """The interleaving depth the object was created for (include/ldpc_erasure_amd_interleave.h), 1: the plain rule."""
         return int(self._fn("depth")(self._h))
 
+    @property
+    def rule(self):
+        """The close rule the object follows, (c_hi, later_hi, c_lo, later_lo) (include/ldpc_erasure_amd_rx_rule.h)."""
+        r = RxRule()
+        if self._fn("get_rule")(self._h, C.byref(r)) != 0:
+            raise LdpcAmdError("fec_rxw_get_rule: bad arguments")
+        return (r.c_hi, r.later_hi, r.c_lo, r.later_lo)
+
     def close(self):
         if getattr(self, "_h", None):
             self._fn("destroy")(self._h)
@@ -1438,13 +1498,16 @@ class _RxWindowState:
 class FecRxWindowHost(_RxWindowState):
     """The windowed reassembler on the host (include/ldpc_erasure_amd_rx_window.h): `window` blocks open, a resynchronisation after
     `ahead_limit` packets beyond them (0: never).  With window = 2 and ahead_limit = 0 it is FecRx.  depth > 1: the rule for a wire
-    interleaved to that depth (include/ldpc_erasure_amd_interleave.h; needs 2 * depth <= window)."""
+    interleaved to that depth (include/ldpc_erasure_amd_interleave.h; needs 2 * depth <= window).  rule: the close rule as a 4-tuple
+    (include/ldpc_erasure_amd_rx_rule.h; fec_rx_rule_mds(n, k, depth) for Reed-Solomon blocks), None: the default rule."""
     _pre = "ldpc_amd_fec_rxw_"
 
-    def __init__(self, n, k, S, window=4, ahead_limit=10, depth=1):
+    def __init__(self, n, k, S, window=4, ahead_limit=10, depth=1, rule=None):
         self._L = load_library()
         h = C.c_void_p()
-        if depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
+        if rule is not None:
+            rc = self._L.ldpc_amd_fec_rxw_create_rule(n, k, S, window, ahead_limit, depth, C.byref(_rx_rule(rule)), C.byref(h))
+        elif depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
             rc = self._L.ldpc_amd_fec_rxw_create(n, k, S, window, ahead_limit, C.byref(h))
         else:
             rc = self._L.ldpc_amd_fec_rxw_create_depth(n, k, S, window, ahead_limit, depth, C.byref(h))
@@ -1491,13 +1554,17 @@ class FecRxWindowHost(_RxWindowState):
 class FecRxWindow(_RxWindowState):
     """FecRxWindowHost for packets already in GPU memory: the same blocks, erasure flags, consumed, totals and state, byte for byte.
     Shaped on FecRxDevice: payload movement is asynchronous on the context's stream; the returned block numbers and counts are final
-    when a call returns.  Close it before its Context."""
+    when a call returns.  rule: the close rule as a 4-tuple (include/ldpc_erasure_amd_rx_rule.h), None: the default rule.  Close it
+    before its Context."""
     _pre = "ldpc_amd_fec_rxw_dev_"
 
-    def __init__(self, ctx, n, k, S, window=4, ahead_limit=10, depth=1):
+    def __init__(self, ctx, n, k, S, window=4, ahead_limit=10, depth=1, rule=None):
         self._ctx, self._L = ctx, ctx._L
         h = C.c_void_p()
-        if depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
+        if rule is not None:
+            ctx._check(self._L.ldpc_amd_fec_rxw_dev_create_rule(ctx._h, n, k, S, window, ahead_limit, depth, C.byref(_rx_rule(rule)), C.byref(h)),
+                       "fec_rxw_dev_create")
+        elif depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
             ctx._check(self._L.ldpc_amd_fec_rxw_dev_create(ctx._h, n, k, S, window, ahead_limit, C.byref(h)), "fec_rxw_dev_create")
         else:
             ctx._check(self._L.ldpc_amd_fec_rxw_dev_create_depth(ctx._h, n, k, S, window, ahead_limit, depth, C.byref(h)), "fec_rxw_dev_create")
@@ -1785,12 +1852,16 @@ class FecRxWindowFlows:
     start at closes[:f].sum().  push_mixed / decode_mixed take the packets in arrival order with a flow number each instead
     (include/ldpc_erasure_amd_rx_window_flows_mixed.h) and return the same; all calls mix freely.  depth > 1: every flow follows the
     rule for a wire interleaved to that depth, FecRxWindowHost(..., depth=depth) per flow (include/ldpc_erasure_amd_interleave_flows.h;
-    needs 2 * depth <= window).  Close it before its Context."""
+    needs 2 * depth <= window).  rule: the close rule of every flow as a 4-tuple (include/ldpc_erasure_amd_rx_rule.h), None: the
+    default rule.  Close it before its Context."""
 
-    def __init__(self, ctx, nflows, n, k, S, window=4, ahead_limit=10, depth=1):
+    def __init__(self, ctx, nflows, n, k, S, window=4, ahead_limit=10, depth=1, rule=None):
         self._ctx, self._L = ctx, ctx._L
         h = C.c_void_p()
-        if depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
+        if rule is not None:
+            ctx._check(self._L.ldpc_amd_fec_rxw_flows_create_rule(ctx._h, nflows, n, k, S, window, ahead_limit, depth, C.byref(_rx_rule(rule)),
+                                                                  C.byref(h)), "fec_rxw_flows_create")
+        elif depth == 1:   # (the older builds tools/ab_lib.py loads have this call only)
             ctx._check(self._L.ldpc_amd_fec_rxw_flows_create(ctx._h, nflows, n, k, S, window, ahead_limit, C.byref(h)), "fec_rxw_flows_create")
         else:
             ctx._check(self._L.ldpc_amd_fec_rxw_flows_create_depth(ctx._h, nflows, n, k, S, window, ahead_limit, depth, C.byref(h)),
@@ -1808,6 +1879,13 @@ class FecRxWindowFlows:
         if not hasattr(self._L, "ldpc_amd_fec_rxw_flows_depth"):   # (the older builds tools/ab_lib.py loads)
             return 1
         return int(self._L.ldpc_amd_fec_rxw_flows_depth(self._h))
+
+    @property
+    def rule(self):
+        """The close rule every flow follows, (c_hi, later_hi, c_lo, later_lo) (include/ldpc_erasure_amd_rx_rule.h)."""
+        r = RxRule()
+        self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_get_rule(self._h, C.byref(r)), "fec_rxw_flows_get_rule")
+        return (r.c_hi, r.later_hi, r.c_lo, r.later_lo)
 
     def push_many(self, packets, flow_begin, max_blocks_per_flow):
         """packets: torch uint8 [P][8+S] on the device, flow_begin: nflows + 1 packet indices.  Returns (closes int32 [nflows],

@@ -1,5 +1,6 @@
-// rx_window.cpp -- the windowed FEC receiver on the host: the DEFINITION of the rule (include/ldpc_erasure_amd_rx_window.h)
-// and of its depth-D form for a block-interleaved wire (include/ldpc_erasure_amd_interleave.h; D = 1 is the plain rule).
+// rx_window.cpp -- the windowed FEC receiver on the host: the DEFINITION of the rule (include/ldpc_erasure_amd_rx_window.h),
+// of its depth-D form for a block-interleaved wire (include/ldpc_erasure_amd_interleave.h; D = 1 is the plain rule) and of the
+// close rule as a value (include/ldpc_erasure_amd_rx_rule.h; no rule given = the default rule).
 // Plain C++, no GPU involved; csrc/wire.cpp's two-buffer receiver is the pattern, and the W = 2, A = 0 case of this one.
 #include <math.h>
 #include <stdlib.h>
@@ -9,13 +10,14 @@
 #include <vector>
 
 #include "../../include/ldpc_erasure_amd_interleave.h"
+#include "../../include/ldpc_erasure_amd_rx_rule.h"
 #include "../../include/ldpc_erasure_amd_rx_window.h"
 #include "../../include/ldpc_erasure_amd_wire.h"
 
 struct ldpc_amd_fec_rxw {
     int n, k, S, W, A;
     int D;                                       // interleaving depth (ldpc_erasure_amd_interleave.h); 1 = the plain rule
-    int kd, km;                                  // k + round(0.8 (n-k)), k + round(0.2 (n-k))
+    ldpc_amd_fec_rx_rule rule;                   // the close rule of step 3 (include/ldpc_erasure_amd_rx_rule.h)
     int base;                                    // wire block number of slot 0, -1 before the first packet
     int head;                                    // slot d lives in plane (head + d) % W
     std::vector<int> cnt;                        // [W] by slot
@@ -26,21 +28,61 @@ struct ldpc_amd_fec_rxw {
 
 extern "C" {
 
+// ---- the rule as a value (include/ldpc_erasure_amd_rx_rule.h) --------------------------------------------------------------------
+int ldpc_amd_fec_rx_rule_default(int n, int k, ldpc_amd_fec_rx_rule *rule)
+{
+    if (!rule || n <= 0 || n > 65536 || k <= 0 || k >= n) return -1;
+    const int kd = k + (int)lround((n - k) * 0.8), km = k + (int)lround((n - k) * 0.2);
+    // c > kd && later > 10 || c > km && later > 100, on integers.  n - k <= 2 gives kd = n: `c > n` never holds, and `c >= n` adds
+    // nothing to the rule's own c == n, so the threshold stays within 0 .. n
+    *rule = ldpc_amd_fec_rx_rule{kd + 1 < n ? kd + 1 : n, 11, km + 1, 101};
+    return 0;
+}
+
+int ldpc_amd_fec_rx_rule_mds(int n, int k, int depth, int giveup, ldpc_amd_fec_rx_rule *rule)
+{
+    if (!rule || n <= 0 || n > 65536 || k <= 0 || k >= n || !LDPC_AMD_FEC_ILV_DEPTH_OK(depth)) return -1;
+    if (giveup < 0 || giveup > LDPC_AMD_FEC_RX_RULE_MAX_LATER) return -1;
+    if (giveup == 0) giveup = depth * k / 2 > 1 ? depth * k / 2 : 1;
+    *rule = ldpc_amd_fec_rx_rule{k, 1, 0, giveup};
+    return 0;
+}
+
+int ldpc_amd_fec_rx_rule_check(int n, const ldpc_amd_fec_rx_rule *rule)
+{
+    if (!rule || n <= 0) return -1;
+    const int32_t c[2] = {rule->c_hi, rule->c_lo}, l[2] = {rule->later_hi, rule->later_lo};
+    for (int i = 0; i < 2; i++) {
+        if (c[i] < 0 || c[i] > n || l[i] < 0 || l[i] > LDPC_AMD_FEC_RX_RULE_MAX_LATER) return -1;
+        if (c[i] == 0 && l[i] < 1) return -1;   // an empty window would close on every packet and never re-anchor
+    }
+    return 0;
+}
+
 int ldpc_amd_fec_rxw_create(int n, int k, int S, int window, int ahead_limit, ldpc_amd_fec_rxw **out)
 {
-    return ldpc_amd_fec_rxw_create_depth(n, k, S, window, ahead_limit, 1, out);
+    return ldpc_amd_fec_rxw_create_rule(n, k, S, window, ahead_limit, 1, nullptr, out);
 }
 
 int ldpc_amd_fec_rxw_create_depth(int n, int k, int S, int window, int ahead_limit, int depth, ldpc_amd_fec_rxw **out)
 {
+    return ldpc_amd_fec_rxw_create_rule(n, k, S, window, ahead_limit, depth, nullptr, out);
+}
+
+int ldpc_amd_fec_rxw_create_rule(int n, int k, int S, int window, int ahead_limit, int depth, const ldpc_amd_fec_rx_rule *rule,
+                                 ldpc_amd_fec_rxw **out)
+{
     if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth) || (depth > 1 && 2 * depth > window)) return -1;
     if (!out || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0) return -1;
     if (window < LDPC_AMD_RXW_MIN_WINDOW || window > LDPC_AMD_RXW_MAX_WINDOW || ahead_limit < 0 || ahead_limit > (1 << 30)) return -1;
+    ldpc_amd_fec_rx_rule r;
+    if (rule) r = *rule;
+    else if (ldpc_amd_fec_rx_rule_default(n, k, &r)) return -1;
+    if (ldpc_amd_fec_rx_rule_check(n, &r)) return -1;
     ldpc_amd_fec_rxw *rx = new (std::nothrow) ldpc_amd_fec_rxw();
     if (!rx) return -1;
     rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit; rx->D = depth;
-    rx->kd = k + (int)lround((n - k) * 0.8);
-    rx->km = k + (int)lround((n - k) * 0.2);
+    rx->rule = r;
     rx->base = -1;
     rx->head = 0;
     rx->cnt.assign((size_t)window, 0);
@@ -55,6 +97,13 @@ int ldpc_amd_fec_rxw_create_depth(int n, int k, int S, int window, int ahead_lim
 void ldpc_amd_fec_rxw_destroy(ldpc_amd_fec_rxw *rx) { delete rx; }
 
 int ldpc_amd_fec_rxw_depth(const ldpc_amd_fec_rxw *rx) { return rx ? rx->D : -1; }
+
+int ldpc_amd_fec_rxw_get_rule(const ldpc_amd_fec_rxw *rx, ldpc_amd_fec_rx_rule *rule)
+{
+    if (!rx || !rule) return -1;
+    *rule = rx->rule;
+    return 0;
+}
 
 int ldpc_amd_fec_rxw_stats(const ldpc_amd_fec_rxw *rx, int64_t totals[5])
 {
@@ -132,7 +181,8 @@ int ldpc_amd_fec_rxw_push(ldpc_amd_fec_rxw *rx, const uint8_t *packet, uint8_t *
         all += rx->cnt[d];
         if (d >= g) later += rx->cnt[d];
     }
-    if (c == rx->n || (c > rx->kd && later > 10) || (c > rx->km && later > 100)) {
+    const ldpc_amd_fec_rx_rule &r = rx->rule;
+    if (c == rx->n || (c >= r.c_hi && later >= r.later_hi) || (c >= r.c_lo && later >= r.later_lo)) {
         close_slot0(rx, sym_out, erased_out, block_out);
         return 1;
     }

@@ -3,7 +3,9 @@
 //   (a) rxw_headers   every packet's header -> one dense u32, block << 16 | symbol                                        (parallel)
 //   (b) rxw_scan      one wavefront replays ldpc_amd_fec_rxw_push over the dense headers, 64 packets per step: per packet the
 //                     SERIAL of the block it went to (or -1), per close the wire block number, at the end the state and the totals;
-//                     rxw_scan_grouped for an object of depth > 1 (include/ldpc_erasure_amd_interleave.h), the only step that differs
+//                     rxw_scan_grouped for an object of depth > 1 (include/ldpc_erasure_amd_interleave.h), the only step that differs;
+//                     rxw_scan_ruled / rxw_scan_grouped_ruled for an object whose close rule is not the default rule
+//                     (include/ldpc_erasure_amd_rx_rule.h): the only step that looks at the rule
 //   (c) rxw_winners   atomicMax of the packet index into a [(closes + W)][n] table: the last copy of a symbol wins          (parallel)
 //   (d) rxw_move<1>   closed blocks -> sym_batch / erased_batch; or rxw_sources: WHERE the decoder finds each row           (parallel)
 //   (e) rxw_move<0>   the W blocks still open -> the W staging planes, in a launch behind (d)                              (parallel)
@@ -186,12 +188,33 @@ __global__ __launch_bounds__(kThreads) void rxw_flush_move(uint8_t *__restrict__
     }
 }
 
+// ---- (b) for an object whose close rule is not the default rule (include/ldpc_erasure_amd_rx_rule.h): the same scan with step 3's
+// four thresholds read from its argument, plain and grouped.  They stand behind the other kernels of the unit so that theirs keep
+// their places in the code object.
+__global__ __launch_bounds__(64) void rxw_scan_ruled(const uint32_t *__restrict__ dense, int64_t np, RxwRuleV r, int max_blocks, RxwState st,
+                                                    int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    __shared__ int cnt[kMaxW];
+    __shared__ uint32_t hbuf[kScanChunk * 64];
+    rxw_scan_body<false>(dense, np, r, 1, max_blocks, st, cnt, hbuf, dest, res);
+}
+
+__global__ __launch_bounds__(64) void rxw_scan_grouped_ruled(const uint32_t *__restrict__ dense, int64_t np, RxwRuleV r, int D, int max_blocks,
+                                                            RxwState st, int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    __shared__ int cnt[kMaxW];
+    __shared__ uint32_t hbuf[kScanChunk * 64];
+    rxw_scan_body<true>(dense, np, r, D, max_blocks, st, cnt, hbuf, dest, res);
+}
+
 }  // namespace
 
 struct ldpc_amd_fec_rxw_dev {
     ldpc_amd_ctx *ctx = nullptr;
     int n = 0, k = 0, S = 0, W = 0, A = 0, kd = 0, km = 0;
     int D = 1;   // interleaving depth (include/ldpc_erasure_amd_interleave.h); only the plan scan looks at it
+    ldpc_amd_fec_rx_rule rule{};   // the close rule (include/ldpc_erasure_amd_rx_rule.h); only the plan scan looks at it
+    bool ruled = false;            // the rule is not the default rule: the ruled scan kernels (else kd, km and the kernels there always were)
     // host mirror of the receiver's state (csrc/rx_window.cpp); head: staging plane of slot 0
     int base = -1, head = 0, ahead = 0;
     int cnt[kMaxW] = {0};
@@ -244,7 +267,13 @@ int rxw_plan(ldpc_amd_fec_rxw_dev *rx, const char *who, const uint8_t *packets, 
     RxwState st{};
     st.base = rx->base; st.ahead = rx->ahead;
     for (int j = 0; j < rx->W; j++) st.cnt[j] = rx->cnt[j];
-    if (rx->D > 1)
+    if (rx->ruled) {
+        const RxwRuleV rv{n, rx->rule.c_hi, rx->rule.later_hi, rx->rule.c_lo, rx->rule.later_lo, rx->W, rx->A};
+        if (rx->D > 1)
+            hipLaunchKernelGGL(rxw_scan_grouped_ruled, dim3(1), dim3(64), 0, ctx->stream, dense, npackets, rv, rx->D, max_blocks, st, dest, res);
+        else
+            hipLaunchKernelGGL(rxw_scan_ruled, dim3(1), dim3(64), 0, ctx->stream, dense, npackets, rv, max_blocks, st, dest, res);
+    } else if (rx->D > 1)
         hipLaunchKernelGGL(rxw_scan_grouped, dim3(1), dim3(64), 0, ctx->stream, dense, npackets, r, rx->D, max_blocks, st, dest, res);
     else
         hipLaunchKernelGGL(rxw_scan, dim3(1), dim3(64), 0, ctx->stream, dense, npackets, r, max_blocks, st, dest, res);
@@ -318,12 +347,25 @@ extern "C" {
 
 int ldpc_amd_fec_rxw_dev_create(ldpc_amd_ctx *ctx, int n, int k, int S, int window, int ahead_limit, ldpc_amd_fec_rxw_dev **out)
 {
-    return ldpc_amd_fec_rxw_dev_create_depth(ctx, n, k, S, window, ahead_limit, 1, out);
+    return ldpc_amd_fec_rxw_dev_create_rule(ctx, n, k, S, window, ahead_limit, 1, nullptr, out);
 }
 
 int ldpc_amd_fec_rxw_dev_depth(const ldpc_amd_fec_rxw_dev *rx) { return rx ? rx->D : -1; }
 
+int ldpc_amd_fec_rxw_dev_get_rule(const ldpc_amd_fec_rxw_dev *rx, ldpc_amd_fec_rx_rule *rule)
+{
+    if (!rx || !rule) return LDPC_AMD_EINVAL;
+    *rule = rx->rule;
+    return LDPC_AMD_OK;
+}
+
 int ldpc_amd_fec_rxw_dev_create_depth(ldpc_amd_ctx *ctx, int n, int k, int S, int window, int ahead_limit, int depth, ldpc_amd_fec_rxw_dev **out)
+{
+    return ldpc_amd_fec_rxw_dev_create_rule(ctx, n, k, S, window, ahead_limit, depth, nullptr, out);
+}
+
+int ldpc_amd_fec_rxw_dev_create_rule(ldpc_amd_ctx *ctx, int n, int k, int S, int window, int ahead_limit, int depth,
+                                     const ldpc_amd_fec_rx_rule *rule, ldpc_amd_fec_rxw_dev **out)
 {
     if (!ctx) return LDPC_AMD_EINVAL;
     if (!out || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
@@ -333,11 +375,17 @@ int ldpc_amd_fec_rxw_dev_create_depth(ldpc_amd_ctx *ctx, int n, int k, int S, in
     if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth) || (depth > 1 && 2 * depth > window))
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: depth must be 1, 2, 4, 8 or 16, and a depth > 1 needs 2 * depth <= window (depth=%d window=%d)",
                          depth, window);
+    ldpc_amd_fec_rx_rule rl{};
+    bool ruled = false;
+    if (rxw_rule_resolve(n, k, rule, &rl, &ruled))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_create: invalid close rule (%d, %d, %d, %d): need 0 <= c <= n = %d, 0 <= later <= 2^30, and later >= 1 where c == 0",
+                         rl.c_hi, rl.later_hi, rl.c_lo, rl.later_lo, n);
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     ldpc_amd_fec_rxw_dev *rx = new (std::nothrow) ldpc_amd_fec_rxw_dev();
     if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rxw_dev_create: out of host memory");
     rx->ctx = ctx;
     rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit; rx->D = depth;
+    rx->rule = rl; rx->ruled = ruled;
     rx->kd = k + (int)lround((n - k) * 0.8);
     rx->km = k + (int)lround((n - k) * 0.2);
     const size_t planes = (size_t)window * n * S, flags = (size_t)window * n;

@@ -5,7 +5,9 @@
 //   (b) rxw_scan_flows      rxw_scan_body (rx_window_scan_dev.h) once per flow, one workgroup of one wavefront each, on the flow's
 //                           segment and state: serials, and with them `dest`, are LOCAL to the flow.  ONE copy back, ONE synchronisation.
 //                           rxw_scan_flows_grouped for an object of depth > 1 (include/ldpc_erasure_amd_interleave_flows.h): the only
-//                           step that looks at the depth, in segmented and mixed calls alike.
+//                           step that looks at the depth, in segmented and mixed calls alike.  rxw_scan_flows_ruled /
+//                           rxw_scan_flows_grouped_ruled for an object whose close rule is not the default rule
+//                           (include/ldpc_erasure_amd_rx_rule.h): the only step that looks at the rule.
 //   (c) rxwf_winners        atomicMax of the GLOBAL packet index into the table [(T + W nflows)][n]                        (parallel)
 //   (d) rxwf_move<1>        the T closed slots -> sym_batch / erased_batch; or rxwf_sources: WHERE the decoder finds each row
 //   (e) rxwf_move<0>        the W open blocks of every flow -> their staging planes, in a launch behind (d) and the decode
@@ -303,12 +305,44 @@ __global__ __launch_bounds__(64) void rxw_scan_flows_grouped(const uint32_t *__r
     rxw_scan_body<true>(dense + begin, f->len, r, D, max_blocks, st, cnt, hbuf, dest + begin, res + (int64_t)blockIdx.x * (R_WORDS + max_blocks));
 }
 
+// (b) for an object whose close rule is not the default rule (include/ldpc_erasure_amd_rx_rule.h): the two scans above with step 3's
+// four thresholds read from the argument.  Behind every other kernel of the unit, for the same reason.
+__global__ __launch_bounds__(64) void rxw_scan_flows_ruled(const uint32_t *__restrict__ dense, const WFlowIn *__restrict__ in, RxwRuleV r,
+                                                          int max_blocks, int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    __shared__ int cnt[kMaxW];
+    __shared__ uint32_t hbuf[kScanChunk * 64];
+    const WFlowIn *f = in + blockIdx.x;
+    RxwState st;
+    st.base = f->base; st.ahead = f->ahead;
+#pragma unroll
+    for (int j = 0; j < kMaxW; j++) st.cnt[j] = f->cnt[j];
+    const int64_t begin = f->begin;
+    rxw_scan_body<false>(dense + begin, f->len, r, 1, max_blocks, st, cnt, hbuf, dest + begin, res + (int64_t)blockIdx.x * (R_WORDS + max_blocks));
+}
+
+__global__ __launch_bounds__(64) void rxw_scan_flows_grouped_ruled(const uint32_t *__restrict__ dense, const WFlowIn *__restrict__ in, RxwRuleV r,
+                                                                  int D, int max_blocks, int32_t *__restrict__ dest, int32_t *__restrict__ res)
+{
+    __shared__ int cnt[kMaxW];
+    __shared__ uint32_t hbuf[kScanChunk * 64];
+    const WFlowIn *f = in + blockIdx.x;
+    RxwState st;
+    st.base = f->base; st.ahead = f->ahead;
+#pragma unroll
+    for (int j = 0; j < kMaxW; j++) st.cnt[j] = f->cnt[j];
+    const int64_t begin = f->begin;
+    rxw_scan_body<true>(dense + begin, f->len, r, D, max_blocks, st, cnt, hbuf, dest + begin, res + (int64_t)blockIdx.x * (R_WORDS + max_blocks));
+}
+
 }  // namespace
 
 struct ldpc_amd_fec_rxw_flows {
     ldpc_amd_ctx *ctx = nullptr;
     int nflows = 0, n = 0, k = 0, S = 0, W = 0, A = 0, kd = 0, km = 0;
     int D = 1;   // interleaving depth (include/ldpc_erasure_amd_interleave_flows.h); only the plan scan looks at it
+    ldpc_amd_fec_rx_rule rule{};   // the close rule of every flow (include/ldpc_erasure_amd_rx_rule.h); only the plan scan looks at it
+    bool ruled = false;            // the rule is not the default rule: the ruled scan kernels (else kd, km and the kernels there always were)
     // host mirror of every flow's state, as in ldpc_amd_fec_rxw_dev; head: staging plane (of the flow's W) of slot 0
     std::vector<int> base, head, ahead;
     std::vector<int> cnt;           // [nflows][W]
@@ -438,7 +472,15 @@ int rxwf_plan(Rx *rx, const char *who, const uint8_t *packets, const WFlowsSrc &
         hipLaunchKernelGGL(rxwf_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
     LDPC_HIP_TRY(ctx, hipGetLastError());
     RxwRule r{n, rx->kd, rx->km, W, rx->A};
-    if (rx->D > 1)
+    if (rx->ruled) {
+        const RxwRuleV rv{n, rx->rule.c_hi, rx->rule.later_hi, rx->rule.c_lo, rx->rule.later_lo, W, rx->A};
+        if (rx->D > 1)
+            hipLaunchKernelGGL(rxw_scan_flows_grouped_ruled, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, rv,
+                               rx->D, max_blocks, dest, res);
+        else
+            hipLaunchKernelGGL(rxw_scan_flows_ruled, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, rv, max_blocks,
+                               dest, res);
+    } else if (rx->D > 1)
         hipLaunchKernelGGL(rxw_scan_flows_grouped, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, r, rx->D,
                            max_blocks, dest, res);
     else
@@ -611,13 +653,26 @@ extern "C" {
 
 int ldpc_amd_fec_rxw_flows_create(ldpc_amd_ctx *ctx, int nflows, int n, int k, int S, int window, int ahead_limit, ldpc_amd_fec_rxw_flows **out)
 {
-    return ldpc_amd_fec_rxw_flows_create_depth(ctx, nflows, n, k, S, window, ahead_limit, 1, out);
+    return ldpc_amd_fec_rxw_flows_create_rule(ctx, nflows, n, k, S, window, ahead_limit, 1, nullptr, out);
 }
 
 int ldpc_amd_fec_rxw_flows_depth(const ldpc_amd_fec_rxw_flows *rx) { return rx ? rx->D : -1; }
 
+int ldpc_amd_fec_rxw_flows_get_rule(const ldpc_amd_fec_rxw_flows *rx, ldpc_amd_fec_rx_rule *rule)
+{
+    if (!rx || !rule) return LDPC_AMD_EINVAL;
+    *rule = rx->rule;
+    return LDPC_AMD_OK;
+}
+
 int ldpc_amd_fec_rxw_flows_create_depth(ldpc_amd_ctx *ctx, int nflows, int n, int k, int S, int window, int ahead_limit, int depth,
                                         ldpc_amd_fec_rxw_flows **out)
+{
+    return ldpc_amd_fec_rxw_flows_create_rule(ctx, nflows, n, k, S, window, ahead_limit, depth, nullptr, out);
+}
+
+int ldpc_amd_fec_rxw_flows_create_rule(ldpc_amd_ctx *ctx, int nflows, int n, int k, int S, int window, int ahead_limit, int depth,
+                                       const ldpc_amd_fec_rx_rule *rule, ldpc_amd_fec_rxw_flows **out)
 {
     if (!ctx) return LDPC_AMD_EINVAL;
     if (!out || nflows < 1 || nflows > kMaxFlows || n <= 0 || n > 65536 || k <= 0 || k >= n || S <= 0)
@@ -628,11 +683,17 @@ int ldpc_amd_fec_rxw_flows_create_depth(ldpc_amd_ctx *ctx, int nflows, int n, in
     if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth) || (depth > 1 && 2 * depth > window))
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: depth must be 1, 2, 4, 8 or 16, and a depth > 1 needs 2 * depth <= window (depth=%d window=%d)",
                          depth, window);
+    ldpc_amd_fec_rx_rule rl{};
+    bool ruled = false;
+    if (rxw_rule_resolve(n, k, rule, &rl, &ruled))
+        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_flows_create: invalid close rule (%d, %d, %d, %d): need 0 <= c <= n = %d, 0 <= later <= 2^30, and later >= 1 where c == 0",
+                         rl.c_hi, rl.later_hi, rl.c_lo, rl.later_lo, n);
     LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     Rx *rx = new (std::nothrow) Rx();
     if (!rx) return set_error(ctx, LDPC_AMD_ENOMEM, "fec_rxw_flows_create: out of host memory");
     rx->ctx = ctx;
     rx->nflows = nflows; rx->n = n; rx->k = k; rx->S = S; rx->W = window; rx->A = ahead_limit; rx->D = depth;
+    rx->rule = rl; rx->ruled = ruled;
     rx->kd = k + (int)lround((n - k) * 0.8);
     rx->km = k + (int)lround((n - k) * 0.2);
     rx->base.assign((size_t)nflows, -1); rx->head.assign((size_t)nflows, 0); rx->ahead.assign((size_t)nflows, 0);

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/ldpc_erasure_amd_interleave.h"
+#include "../../include/ldpc_erasure_amd_rx_rule.h"
 #include "../../include/ldpc_erasure_amd_rx_window.h"
 
 namespace {
@@ -33,6 +34,25 @@ struct RxwState {   // the open state a scan starts from; cnt[j] = 0 for j >= W
 __device__ __forceinline__ bool rxw_close_rule(int c, int later, const RxwRule &r)
 {
     return c == r.n || (c > r.kd && later > 10) || (c > r.km && later > 100);
+}
+
+// The RULED form (include/ldpc_erasure_amd_rx_rule.h): all four thresholds of step 3 are runtime values.  The objects whose rule
+// is not the default rule scan with this record; the default rule keeps RxwRule, its two immediates and its kernels.  Step 3 stays a
+// function of (c, later, ahead) alone, which is all the exactness argument below asks of it, and two things the body relies on hold
+// for every VALID rule:
+//   re-anchor      the body takes the re-anchor branch when the close test fails and every count is zero.  A clause with c_* == 0
+//                  has later_* >= 1, so the close test is false on an empty window (c = later = 0, n >= 1) and the branch is reached
+//                  exactly when the host reaches it.
+//   close cascade  after a close by the give-up clause the slots behind may hold their threshold already and close on consecutive
+//                  packets, one per packet, so a group of 64 can carry up to 64 events.  Every pass of the inner loop that finds an
+//                  event resumes at start = L + 1, so a group takes at most 64 such passes and the iteration cap covers them.
+struct RxwRuleV {
+    int n, c_hi, later_hi, c_lo, later_lo, W, A;
+};
+
+__device__ __forceinline__ bool rxw_close_rule(int c, int later, const RxwRuleV &r)
+{
+    return c == r.n || (c >= r.c_hi && later >= r.later_hi) || (c >= r.c_lo && later >= r.later_lo);
 }
 
 // One wavefront; every value but the lane's own packet is wave-uniform.  For a group of 64 packets from lane `start` on:
@@ -69,9 +89,9 @@ __device__ __forceinline__ bool rxw_close_rule(int c, int later, const RxwRule &
 //                   over the wave into mates; later -= c0 + mates; g = D;
 //   re-anchor       every count is zero; base = the group start of the tripping packet, which goes to slot blk % D:
 //                   c0 = (blk % D == 0), mates = 1 - c0, later = 0, g = D.
-// cnt: LDS [kMaxW]; hbuf: LDS [kScanChunk * 64].
-template <bool GROUPED>
-__device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense, int64_t np, const RxwRule r, int D, int max_blocks,
+// cnt: LDS [kMaxW]; hbuf: LDS [kScanChunk * 64].  Rule: RxwRule, or RxwRuleV for the ruled form (deduced from r).
+template <bool GROUPED, class Rule>
+__device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense, int64_t np, const Rule r, int D, int max_blocks,
                                               const RxwState &st, int *cnt, uint32_t *hbuf, int32_t *__restrict__ dest,
                                               int32_t *__restrict__ res)
 {
@@ -231,6 +251,18 @@ __device__ __forceinline__ void rxw_scan_body(const uint32_t *__restrict__ dense
         res[R_LATE_LO] = (int32_t)(uint32_t)late; res[R_LATE_HI] = (int32_t)(late >> 32);
         res[R_AHEADTOT_LO] = (int32_t)(uint32_t)aheadtot; res[R_AHEADTOT_HI] = (int32_t)(aheadtot >> 32);
     }
+}
+
+// What a create call makes of its rule argument (null: the default rule): the rule the object follows, and whether it scans with
+// the ruled kernels -- for every rule but the default one, spelled out or not.  -1 for an invalid rule.
+inline int rxw_rule_resolve(int n, int k, const ldpc_amd_fec_rx_rule *given, ldpc_amd_fec_rx_rule *rule, bool *ruled)
+{
+    ldpc_amd_fec_rx_rule def;
+    if (ldpc_amd_fec_rx_rule_default(n, k, &def)) return -1;
+    *rule = given ? *given : def;
+    if (ldpc_amd_fec_rx_rule_check(n, rule)) return -1;
+    *ruled = rule->c_hi != def.c_hi || rule->later_hi != def.later_hi || rule->c_lo != def.c_lo || rule->later_lo != def.later_lo;
+    return 0;
 }
 
 }  // namespace
