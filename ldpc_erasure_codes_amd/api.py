@@ -60,6 +60,7 @@ EXPORTS_FRAMES = ["ldpc_amd_decode_frames", "ldpc_amd_rs_info", "ldpc_amd_rs_dec
 # every symbol include/ldpc_erasure_amd_sender.h declares (the fused sender: source symbols straight to wire packets)
 EXPORTS_SENDER = ["ldpc_amd_fec_encode_packets_dev", "ldpc_amd_fec_sender_info"]
 SENDER_PATHS = ("none", "fused", "composed")
+_SENDER_KEYS = ("path", "scratch_bytes", "descriptor_bytes", "frames")   # the four words of the descriptor-driven senders' info calls
 # every symbol include/ldpc_erasure_amd_sender_flows.h declares (the multi-flow sender: many FEC streams to one multiplexed wire)
 EXPORTS_SENDER_FLOWS = ["ldpc_amd_fec_tx_flows_layout", "ldpc_amd_fec_encode_packets_flows_dev", "ldpc_amd_fec_sender_flows_info"]
 TX_SEGMENTED, TX_ROUND_ROBIN = 0, 1   # LDPC_AMD_FEC_TX_SEGMENTED / LDPC_AMD_FEC_TX_ROUND_ROBIN
@@ -126,6 +127,7 @@ EXPORTS_RX_WINDOW = [
     "ldpc_amd_fec_rxw_dev_state", "ldpc_amd_fec_rxw_info",
 ]
 RX_WINDOW_PATHS = ("none", "fused", "composed")
+_RXW_KEYS = ("path", "blocks", "launches", "scratch_bytes")   # the four words of the windowed receivers' info calls
 RX_WINDOW_TOTALS = ("bad_symbol", "late", "ahead_total", "resyncs", "closed")   # LDPC_AMD_RXW_*: the order of the totals
 RX_WINDOW_MIN, RX_WINDOW_MAX = 2, 32
 # every symbol include/ldpc_erasure_amd_rx_window_flows.h declares (the windowed multi-flow receiver and its batch flush)
@@ -550,6 +552,20 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _sender_shape(source, n, k, out):
+    """The single-stream senders' shape contract: source a torch uint8 tensor [F][k][S] (or [F][k] for S = 1), out None (allocated
+    beside source) or a torch uint8 tensor [F*n][8+S].  Returns (F, S, out)."""
+    import torch
+    assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
+    F = source.shape[0]
+    S = 1 if source.ndim == 2 else source.shape[2]
+    assert source.shape[1] == k
+    if out is None:
+        out = torch.empty((F * n, 8 + S), dtype=torch.uint8, device=source.device)
+    assert tuple(out.shape) == (F * n, 8 + S) and out.dtype == torch.uint8
+    return F, S, out
+
+
 def _ptr(x):
     if x is None:
         return None
@@ -592,6 +608,15 @@ class Context:
         if rc < 0:
             raise LdpcAmdError(f"{what} = {rc}: {self._L.ldpc_amd_last_error(self._h).decode()}")
         return rc
+
+    def _info(self, fn, ctype, keys, paths=None):
+        """The ..._info pattern: the leading words of ldpc_amd_<fn>'s four under `keys`; paths: the names of the word "path"."""
+        info = (ctype * 4)()
+        self._check(getattr(self._L, "ldpc_amd_" + fn)(self._h, info), fn)
+        d = {kd: int(v) for kd, v in zip(keys, info)}
+        if paths:
+            d["path"] = paths[d["path"]]
+        return d
 
     def set_stream(self, stream_handle):
         self._check(self._L.ldpc_amd_set_stream(self._h, C.c_void_p(stream_handle)), "set_stream")
@@ -931,15 +956,8 @@ class Context:
         """source: torch uint8 [F][k][S] (or [F][k] for S = 1) on this context's device -> packets [F*n][8+S], the bytes of
         fec_packetize_device(encode(code, source)) without the codeword array in between where the encoder can write the
         packets itself (fec_sender_info() says which path ran).  Asynchronous on the context's stream."""
-        import torch
-        assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
         n, k, _ = self.code_info(code)
-        F = source.shape[0]
-        S = 1 if source.ndim == 2 else source.shape[2]
-        assert source.shape[1] == k
-        if out is None:
-            out = torch.empty((F * n, 8 + S), dtype=torch.uint8, device=source.device)
-        assert tuple(out.shape) == (F * n, 8 + S) and out.dtype == torch.uint8
+        F, S, out = _sender_shape(source, n, k, out)
         self._check(self._L.ldpc_amd_fec_encode_packets_dev(self._h, code, S, F, _ptr(source), fec_class, block0, _ptr(out)),
                     "fec_encode_packets_dev")
         return out
@@ -947,9 +965,7 @@ class Context:
     def fec_sender_info(self):
         """{"path": "none" | "fused" | "composed" of the last fec_encode_packets_device call, "scratch_bytes": codeword scratch the
         context holds for the composed path}."""
-        info = (C.c_int * 4)()
-        self._check(self._L.ldpc_amd_fec_sender_info(self._h, info), "fec_sender_info")
-        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1])}
+        return self._info("fec_sender_info", C.c_int, ("path", "scratch_bytes"), SENDER_PATHS)
 
     # -- the multi-flow sender (include/ldpc_erasure_amd_sender_flows.h)
     def fec_encode_packets_flows_device(self, code, source, frame_begin, fec_class, block0, order, out=None, want_flow_of=True):
@@ -964,19 +980,13 @@ class Context:
     def _encode_packets_flows(self, code, source, frame_begin, fec_class, block0, order, out, want_flow_of, depth):
         """The two multi-flow senders' common part; depth None: ldpc_amd_fec_encode_packets_flows_dev."""
         import torch
-        assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
         n, k, _ = self.code_info(code)
-        F = source.shape[0]
-        S = 1 if source.ndim == 2 else source.shape[2]
-        assert source.shape[1] == k
+        F, S, out = _sender_shape(source, n, k, out)
         fb = np.ascontiguousarray(frame_begin, dtype=np.int64)
         assert fb.ndim == 1 and fb.shape[0] >= 2 and int(fb[-1]) == F
         nflows = fb.shape[0] - 1
         cls = np.ascontiguousarray(np.broadcast_to(np.asarray(fec_class, dtype=np.int64) & 0xFF, (nflows,)), dtype=np.uint8)
         blk = np.ascontiguousarray(np.broadcast_to(np.asarray(block0, dtype=np.int64) & 0xFF, (nflows,)), dtype=np.uint8)
-        if out is None:
-            out = torch.empty((F * n, 8 + S), dtype=torch.uint8, device=source.device)
-        assert tuple(out.shape) == (F * n, 8 + S) and out.dtype == torch.uint8
         flow_of = torch.empty(F * n, dtype=torch.int32, device=source.device) if want_flow_of else None
         pb = np.zeros(nflows + 1, dtype=np.int64)
         args = (self._h, code, S, nflows, fb.ctypes.data, _ptr(source) if F else None, cls.ctypes.data, blk.ctypes.data, order,
@@ -990,9 +1000,7 @@ class Context:
     def fec_sender_flows_info(self):
         """{"path": "none" | "fused" | "composed" of the last fec_encode_packets_flows_device call, "scratch_bytes": codeword scratch
         the context holds for the composed paths, "descriptor_bytes": descriptor memory it holds, "frames": frames of that call}."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_sender_flows_info(self._h, info), "fec_sender_flows_info")
-        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "frames": int(info[3])}
+        return self._info("fec_sender_flows_info", C.c_int64, _SENDER_KEYS, SENDER_PATHS)
 
     # -- ... with every flow interleaved to a depth (include/ldpc_erasure_amd_interleave_flows.h)
     def fec_encode_packets_flows_interleaved_device(self, code, source, frame_begin, fec_class, block0, order, depth, out=None, want_flow_of=True):
@@ -1005,24 +1013,15 @@ class Context:
 
     def fec_sender_flows_ilv_info(self):
         """fec_sender_flows_info() for the last fec_encode_packets_flows_interleaved_device call."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_sender_flows_ilv_info(self._h, info), "fec_sender_flows_ilv_info")
-        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "frames": int(info[3])}
+        return self._info("fec_sender_flows_ilv_info", C.c_int64, _SENDER_KEYS, SENDER_PATHS)
 
     # -- the block-interleaved sender (include/ldpc_erasure_amd_interleave.h)
     def fec_encode_packets_interleaved_device(self, code, source, depth, fec_class=1, block0=0, out=None):
         """source: torch uint8 [F][k][S] (or [F][k] for S = 1) on this context's device -> packets [F*n][8+S]: the packets of
         fec_encode_packets_device in depth-`depth` order -- row j of frame f at index first[f] + j * stride[f] of
         fec_tx_ilv_layout(F, n, block0, depth).  fec_sender_ilv_info() says which path ran.  Asynchronous on the context's stream."""
-        import torch
-        assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
         n, k, _ = self.code_info(code)
-        F = source.shape[0]
-        S = 1 if source.ndim == 2 else source.shape[2]
-        assert source.shape[1] == k
-        if out is None:
-            out = torch.empty((F * n, 8 + S), dtype=torch.uint8, device=source.device)
-        assert tuple(out.shape) == (F * n, 8 + S) and out.dtype == torch.uint8
+        F, S, out = _sender_shape(source, n, k, out)
         self._check(self._L.ldpc_amd_fec_encode_packets_ilv_dev(self._h, code, S, F, _ptr(source), fec_class, block0, depth, _ptr(out)),
                     "fec_encode_packets_ilv_dev")
         return out
@@ -1031,9 +1030,7 @@ class Context:
         """{"path": "none" | "fused" | "composed" of the last fec_encode_packets_interleaved_device call, "scratch_bytes": codeword
         scratch the context holds for the composed paths, "descriptor_bytes": descriptor memory it holds, "frames": frames of that
         call}."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_sender_ilv_info(self._h, info), "fec_sender_ilv_info")
-        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "frames": int(info[3])}
+        return self._info("fec_sender_ilv_info", C.c_int64, _SENDER_KEYS, SENDER_PATHS)
 
     def fec_tx_interleaved(self, code, S, depth, fec_class=1, block0=0):
         """A sender that numbers its blocks across calls and emits them block-interleaved (FecTxInterleaved)."""
@@ -1045,15 +1042,8 @@ class Context:
         [B*n][8+S]: the packets of rs_encode + fec_packetize_device in depth-`depth` order -- row j of block b at index
         first[b] + j * stride[b] of fec_tx_ilv_layout(B, n, block0, depth).  fec_rs_sender_info() says which path ran.
         Asynchronous on the context's stream."""
-        import torch
-        assert _is_torch(source) and source.dtype == torch.uint8 and source.ndim in (2, 3)
         n, k = self.rs_info(rs)
-        B = source.shape[0]
-        S = 1 if source.ndim == 2 else source.shape[2]
-        assert source.shape[1] == k
-        if out is None:
-            out = torch.empty((B * n, 8 + S), dtype=torch.uint8, device=source.device)
-        assert tuple(out.shape) == (B * n, 8 + S) and out.dtype == torch.uint8
+        B, S, out = _sender_shape(source, n, k, out)
         self._check(self._L.ldpc_amd_fec_rs_encode_packets_dev(self._h, rs, S, B, _ptr(source), fec_class, block0, depth, _ptr(out)),
                     "fec_rs_encode_packets_dev")
         return out
@@ -1061,16 +1051,12 @@ class Context:
     def fec_rs_sender_info(self):
         """{"path": "none" | "fused" | "composed" of the last fec_rs_encode_packets_device call, "scratch_bytes": codeword scratch
         the context holds for the composed paths, "descriptor_bytes": descriptor memory it holds, "blocks": blocks of that call}."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_rs_sender_info(self._h, info), "fec_rs_sender_info")
-        return {"path": SENDER_PATHS[info[0]], "scratch_bytes": int(info[1]), "descriptor_bytes": int(info[2]), "blocks": int(info[3])}
+        return self._info("fec_rs_sender_info", C.c_int64, ("path", "scratch_bytes", "descriptor_bytes", "blocks"), SENDER_PATHS)
 
     def fec_rs_receiver_info(self):
         """{"blocks": blocks RS-decoded by the last FecRxWindow.rs_decode_many / rs_decode_flush of this context, "launches": its RS
         decode launches, "scratch_bytes": received-symbol scratch it used}."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_rs_receiver_info(self._h, info), "fec_rs_receiver_info")
-        return {"blocks": int(info[0]), "launches": int(info[1]), "scratch_bytes": int(info[2])}
+        return self._info("fec_rs_receiver_info", C.c_int64, ("blocks", "launches", "scratch_bytes"))
 
     def fec_tx_rs(self, rs, S, depth=1, block0=0):
         """A sender of RS blocks that numbers them across calls and emits them block-interleaved (FecTxRs)."""
@@ -1119,9 +1105,7 @@ class Context:
     def fec_dgram_info(self):
         """{"scratch_bytes": device scratch the context holds for pack and unpack, "staging_bytes": pinned staging of pack's offsets,
         "pack_rows": rows of the last pack, "unpack_rows": rows of the last unpack}."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_dgram_info(self._h, info), "fec_dgram_info")
-        return dict(zip(("scratch_bytes", "staging_bytes", "pack_rows", "unpack_rows"), [int(x) for x in info]))
+        return self._info("fec_dgram_info", C.c_int64, ("scratch_bytes", "staging_bytes", "pack_rows", "unpack_rows"))
 
     # -- the trimmed wire (include/ldpc_erasure_amd_wire_ragged.h)
     def fec_trim_packets(self, packets, k, out=None):
@@ -1164,9 +1148,7 @@ class Context:
     def fec_wire_ragged_info(self):
         """{"scratch_bytes": device scratch the context holds for trim, "trim_packets": packets of the last trim, "land_packets":
         packets of the last land}."""
-        info = (C.c_int64 * 3)()
-        self._check(self._L.ldpc_amd_fec_wire_ragged_info(self._h, info), "fec_wire_ragged_info")
-        return dict(zip(("scratch_bytes", "trim_packets", "land_packets"), [int(x) for x in info]))
+        return self._info("fec_wire_ragged_info", C.c_int64, ("scratch_bytes", "trim_packets", "land_packets"))
 
     # -- the link emulator (include/ldpc_erasure_amd_link.h)
     def fec_link(self, seed, window=0, dup=0.0, bad_sym=0.0, foreign=0.0, dup_flip=False, first=0):
@@ -1177,9 +1159,7 @@ class Context:
     def fec_link_info(self):
         """{"scratch_bytes": device scratch held for the context's link calls, "plan_packets" / "apply_packets" /
         "apply_ragged_packets": packets of the last call of each kind}."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_link_info(self._h, info), "fec_link_info")
-        return dict(zip(("scratch_bytes", "plan_packets", "apply_packets", "apply_ragged_packets"), [int(x) for x in info]))
+        return self._info("fec_link_info", C.c_int64, ("scratch_bytes", "plan_packets", "apply_packets", "apply_ragged_packets"))
 
     def fec_tx_flows(self, code, S, nflows, fec_class=1, block0=0, depth=1):
         """nflows senders that number their blocks across calls and share one wire (FecTxFlows); depth > 1: every flow's blocks
@@ -1194,9 +1174,7 @@ class Context:
     def fec_receiver_info(self):
         """{"path": "none" | "fused" | "composed" of the last FecRxDevice.decode_many call, "scratch_bytes": received-symbol scratch
         the context holds for the composed path, "blocks": blocks that call decoded}."""
-        info = (C.c_int * 4)()
-        self._check(self._L.ldpc_amd_fec_receiver_info(self._h, info), "fec_receiver_info")
-        return {"path": RECEIVER_PATHS[info[0]], "scratch_bytes": int(info[1]), "blocks": int(info[2])}
+        return self._info("fec_receiver_info", C.c_int, ("path", "scratch_bytes", "blocks"), RECEIVER_PATHS)
 
     # -- the windowed receiver (include/ldpc_erasure_amd_rx_window.h)
     def fec_rx_window(self, n, k, S, window=4, ahead_limit=10, depth=1, rule=None):
@@ -1208,9 +1186,7 @@ class Context:
     def fec_rx_window_info(self):
         """{"path": "none" | "fused" | "composed" of the last FecRxWindow.decode_many / decode_flush call, "blocks": the blocks it
         decoded, "launches": its decoder launches, "scratch_bytes": received-symbol scratch it used}."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_rxw_info(self._h, info), "fec_rxw_info")
-        return {"path": RX_WINDOW_PATHS[info[0]], "blocks": int(info[1]), "launches": int(info[2]), "scratch_bytes": int(info[3])}
+        return self._info("fec_rxw_info", C.c_int64, _RXW_KEYS, RX_WINDOW_PATHS)
 
     # -- ... for many flows (include/ldpc_erasure_amd_rx_window_flows.h)
     def fec_rx_window_flows(self, nflows, n, k, S, window=4, ahead_limit=10, depth=1, rule=None):
@@ -1221,9 +1197,7 @@ class Context:
 
     def fec_rx_window_flows_info(self):
         """fec_rx_window_info() for the last FecRxWindowFlows.decode_many / decode_flush_many call."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_rxw_flows_info(self._h, info), "fec_rxw_flows_info")
-        return {"path": RX_WINDOW_PATHS[info[0]], "blocks": int(info[1]), "launches": int(info[2]), "scratch_bytes": int(info[3])}
+        return self._info("fec_rxw_flows_info", C.c_int64, _RXW_KEYS, RX_WINDOW_PATHS)
 
     # -- the multi-flow receiver (include/ldpc_erasure_amd_flows.h)
     def fec_rx_flows(self, nflows, n, k, S):
@@ -1234,9 +1208,7 @@ class Context:
     def fec_flows_flush_info(self):
         """{"path": "none" | "fused" | "composed" | "push" of the last FecRxFlows.flush_many / decode_flush_many call that closed a
         block, "blocks": the blocks it closed, "scratch_bytes": scratch it used, "launches": its decoder launches}."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_flows_flush_info(self._h, info), "fec_flows_flush_info")
-        return {"path": FLUSH_PATHS[info[0]], "blocks": int(info[1]), "scratch_bytes": int(info[2]), "launches": int(info[3])}
+        return self._info("fec_flows_flush_info", C.c_int64, ("path", "blocks", "scratch_bytes", "launches"), FLUSH_PATHS)
 
     # -- ... fed with interleaved packets (include/ldpc_erasure_amd_flows_mixed.h)
     def fec_flows_demux(self, flow_of, nflows):
@@ -1254,9 +1226,7 @@ class Context:
 
     def fec_flows_demux_info(self):
         """{"tile": tile length in packets of the last partition, "tiles": its tiles, "scratch_bytes": table bytes the context holds}."""
-        info = (C.c_int64 * 4)()
-        self._check(self._L.ldpc_amd_fec_flows_demux_info(self._h, info), "fec_flows_demux_info")
-        return {"tile": int(info[0]), "tiles": int(info[1]), "scratch_bytes": int(info[2])}
+        return self._info("fec_flows_demux_info", C.c_int64, ("tile", "tiles", "scratch_bytes"))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -2019,7 +1989,25 @@ class FecRxWindowFlows:
             pass
 
 
-class FecTxDevice:
+class _FecTxCounter:
+    """The single-stream senders' one piece of state, the block counter: send(source) hands _encode the block number next_block
+    and advances it by the frames sent modulo 256."""
+
+    def send(self, source, out=None):
+        """source: torch uint8 [F][k][S] (or [F][k] for S = 1) -> packets [F*n][8+S] in transmission order."""
+        assert (1 if source.ndim == 2 else source.shape[2]) == self.S
+        pk = self._encode(source, self.next_block, out)
+        self.next_block = (self.next_block + source.shape[0]) & 0xFF
+        return pk
+
+    def send_datagrams_trimmed(self, data, offsets):
+        """Pack + encode + trim: datagrams of any length up to S - 4 -> Wire(bytes, offset) of Context.fec_trim_packets, the bytes
+        that go on the wire back to back with their boundaries on the device; no per-packet table is made on the host.  Advances
+        the block counter by F, as send does."""
+        return self._ctx.fec_trim_packets(self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), self.k)
+
+
+class FecTxDevice(_FecTxCounter):
     """The sender's side of FecRxDevice.  Its one piece of state is the reference's block counter (blockNum += 1 per frame,
     OpenCL/device/ldpc_erasure_encoder_VITA_in_UDP_out.cl:134): send(source) returns the packets of F frames numbered from
     next_block on and advances it by F modulo 256."""
@@ -2029,12 +2017,8 @@ class FecTxDevice:
         self.n, self.k, _ = ctx.code_info(code)
         self.next_block = block0 & 0xFF
 
-    def send(self, source, out=None):
-        """source: torch uint8 [F][k][S] (or [F][k] for S = 1) -> packets [F*n][8+S] in transmission order."""
-        assert (1 if source.ndim == 2 else source.shape[2]) == self.S
-        pk = self._ctx.fec_encode_packets_device(self.code, source, self.fec_class, self.next_block, out=out)
-        self.next_block = (self.next_block + source.shape[0]) & 0xFF
-        return pk
+    def _encode(self, source, block0, out):
+        return self._ctx.fec_encode_packets_device(self.code, source, self.fec_class, block0, out=out)
 
     def send_datagrams(self, data, offsets):
         """Datagrams of any length up to S - 4 (Context.fec_pack_datagrams) -> (packets [F*n][8+S], wire_len int32 [F*n]): only
@@ -2042,14 +2026,8 @@ class FecTxDevice:
         wl = fec_datagram_wire_len(offsets, self.n, self.k, self.S)
         return self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), wl
 
-    def send_datagrams_trimmed(self, data, offsets):
-        """Pack + encode + trim: datagrams of any length up to S - 4 -> Wire(bytes, offset) of Context.fec_trim_packets, the bytes
-        that go on the wire back to back with their boundaries on the device; no per-packet table is made on the host.  Advances
-        the block counter by F, as send_datagrams does."""
-        return self._ctx.fec_trim_packets(self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), self.k)
 
-
-class FecTxInterleaved:
+class FecTxInterleaved(_FecTxCounter):
     """FecTxDevice for the block-interleaved wire (include/ldpc_erasure_amd_interleave.h): send(source) returns the packets of F
     frames numbered from next_block on in depth-`depth` order, the input of FecRxWindow(..., depth=depth), and advances the
     counter by F modulo 256.  A call interleaves its own frames only: send whole groups (F a multiple of depth, from a block number
@@ -2062,19 +2040,11 @@ class FecTxInterleaved:
         self.n, self.k, _ = ctx.code_info(code)
         self.next_block = block0 & 0xFF
 
-    def send(self, source, out=None):
-        """source: torch uint8 [F][k][S] (or [F][k] for S = 1) -> packets [F*n][8+S] in transmission order."""
-        assert (1 if source.ndim == 2 else source.shape[2]) == self.S
-        pk = self._ctx.fec_encode_packets_interleaved_device(self.code, source, self.depth, self.fec_class, self.next_block, out=out)
-        self.next_block = (self.next_block + source.shape[0]) & 0xFF
-        return pk
-
-    def send_datagrams_trimmed(self, data, offsets):
-        """Pack + encode + trim, as FecTxDevice.send_datagrams_trimmed: Wire(bytes, offset) of the interleaved packets."""
-        return self._ctx.fec_trim_packets(self.send(self._ctx.fec_pack_datagrams(data, offsets, self.k, self.S)), self.k)
+    def _encode(self, source, block0, out):
+        return self._ctx.fec_encode_packets_interleaved_device(self.code, source, self.depth, self.fec_class, block0, out=out)
 
 
-class FecTxRs:
+class FecTxRs(_FecTxCounter):
     """FecTxInterleaved for the blocks of a Reed-Solomon code (include/ldpc_erasure_amd_rs_wire.h): send(source) returns the packets
     of B blocks numbered from next_block on in depth-`depth` order, class FEC_CLASS_RS, the input of
     FecRxWindow(n, k, S, ..., depth=depth).rs_decode_many, and advances the counter by B modulo 256."""
@@ -2086,12 +2056,8 @@ class FecTxRs:
         self.n, self.k = ctx.rs_info(rs)
         self.next_block = block0 & 0xFF
 
-    def send(self, source, out=None):
-        """source: torch uint8 [B][k][S] (or [B][k] for S = 1) -> packets [B*n][8+S] in transmission order."""
-        assert (1 if source.ndim == 2 else source.shape[2]) == self.S
-        pk = self._ctx.fec_rs_encode_packets_device(self.rs, source, self.depth, FEC_CLASS_RS, self.next_block, out=out)
-        self.next_block = (self.next_block + source.shape[0]) & 0xFF
-        return pk
+    def _encode(self, source, block0, out):
+        return self._ctx.fec_rs_encode_packets_device(self.rs, source, self.depth, FEC_CLASS_RS, block0, out=out)
 
 
 class FecLink:

@@ -213,6 +213,47 @@ int scratch_reserve(ldpc_amd_ctx *ctx, Scratch &s, size_t bytes)
     return LDPC_AMD_OK;
 }
 
+int pinned_ring_acquire(ldpc_amd_ctx *ctx, PinnedRing &r, size_t bytes, void **host, size_t *want)
+{
+    const int slot = (int)(r.calls & 1u);
+    if (!r.event[slot]) LDPC_HIP_TRY(ctx, hipEventCreateWithFlags(&r.event[slot], hipEventDisableTiming));
+    if (r.pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
+        LDPC_HIP_TRY(ctx, hipEventSynchronize(r.event[slot]));
+        r.pending[slot] = false;
+    }
+    if (r.cap[slot] < bytes) {
+        if (r.slot[slot]) (void)hipHostFree(r.slot[slot]);
+        r.slot[slot] = nullptr; r.cap[slot] = 0;
+        *want = (bytes + 65535) & ~(size_t)65535;
+        if (hipHostMalloc(&r.slot[slot], *want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            r.slot[slot] = nullptr;
+            return LDPC_AMD_ENOMEM;
+        }
+        r.cap[slot] = *want;
+    }
+    *host = r.slot[slot];
+    return LDPC_AMD_OK;
+}
+
+int pinned_ring_commit(ldpc_amd_ctx *ctx, PinnedRing &r)
+{
+    const int slot = (int)(r.calls & 1u);
+    LDPC_HIP_TRY(ctx, hipEventRecord(r.event[slot], ctx->stream));
+    r.pending[slot] = true;
+    r.calls++;
+    return LDPC_AMD_OK;
+}
+
+void pinned_ring_free(PinnedRing &r)
+{
+    for (hipEvent_t e : r.event)
+        if (e) (void)hipEventDestroy(e);
+    for (void *h : r.slot)
+        if (h) (void)hipHostFree(h);
+    r = PinnedRing();
+}
+
 static hipEvent_t prof_take(ldpc_amd_ctx *ctx)
 {
     hipEvent_t e = nullptr;
@@ -855,14 +896,8 @@ void ldpc_amd_cleanup(ldpc_amd_ctx *ctx)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ml_events)
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->txf_event)
-        if (e) (void)hipEventDestroy(e);
-    for (void *h : ctx->txf_stage)
-        if (h) (void)hipHostFree(h);
-    for (hipEvent_t e : ctx->dgram_event)
-        if (e) (void)hipEventDestroy(e);
-    for (void *h : ctx->dgram_stage)
-        if (h) (void)hipHostFree(h);
+    pinned_ring_free(ctx->txf_ring);
+    pinned_ring_free(ctx->dgram_ring);
     if (ctx->aux_in) (void)hipStreamDestroy(ctx->aux_in);
     if (ctx->aux_out) (void)hipStreamDestroy(ctx->aux_out);
     if (ctx->aux_ml) (void)hipStreamDestroy(ctx->aux_ml);

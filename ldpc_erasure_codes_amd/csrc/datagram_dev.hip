@@ -240,32 +240,17 @@ int64_t ldpc_amd_fec_dgram_pack_dev(ldpc_amd_ctx *ctx, const uint8_t *bytes, con
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_dgram_pack_dev: bytes / source must be device pointers of device %d", ctx->device);
     if (((uintptr_t)source & 3) != 0) return set_error(ctx, LDPC_AMD_EINVAL, "fec_dgram_pack_dev: source must be 4-byte aligned");
     if (nbytes && overlap(bytes + offset[0], nbytes, source, nsource)) return set_error(ctx, LDPC_AMD_EINVAL, "fec_dgram_pack_dev: bytes and source overlap");
-    // the offsets: pinned staging, two slots in turn, each with the event of its last copy (as the multi-flow sender's descriptors)
+    // the offsets: through the context's pinned ring to the device (internal.h: PinnedRing)
     const size_t tab_bytes = sizeof(int64_t) * (size_t)(ndgrams + 1);
     int rc;
     if ((rc = scratch_reserve(ctx, ctx->dgram_off, tab_bytes))) return rc;
-    const int slot = (int)(ctx->dgram_calls & 1u);
-    if (!ctx->dgram_event[slot]) LDPC_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->dgram_event[slot], hipEventDisableTiming));
-    if (ctx->dgram_pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
-        LDPC_HIP_TRY(ctx, hipEventSynchronize(ctx->dgram_event[slot]));
-        ctx->dgram_pending[slot] = false;
-    }
-    if (ctx->dgram_stage_cap[slot] < tab_bytes) {
-        if (ctx->dgram_stage[slot]) (void)hipHostFree(ctx->dgram_stage[slot]);
-        ctx->dgram_stage[slot] = nullptr; ctx->dgram_stage_cap[slot] = 0;
-        const size_t want = (tab_bytes + 65535) & ~(size_t)65535;
-        if (hipHostMalloc(&ctx->dgram_stage[slot], want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->dgram_stage[slot] = nullptr;
-            return set_error(ctx, LDPC_AMD_ENOMEM, "fec_dgram_pack_dev: no pinned memory for %zu offset bytes", want);
-        }
-        ctx->dgram_stage_cap[slot] = want;
-    }
-    memcpy(ctx->dgram_stage[slot], offset, tab_bytes);
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(ctx->dgram_off.p, ctx->dgram_stage[slot], tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    LDPC_HIP_TRY(ctx, hipEventRecord(ctx->dgram_event[slot], ctx->stream));
-    ctx->dgram_pending[slot] = true;
-    ctx->dgram_calls++;
+    void *stage = nullptr;
+    size_t want = 0;
+    if ((rc = pinned_ring_acquire(ctx, ctx->dgram_ring, tab_bytes, &stage, &want)))
+        return rc == LDPC_AMD_ENOMEM ? set_error(ctx, LDPC_AMD_ENOMEM, "fec_dgram_pack_dev: no pinned memory for %zu offset bytes", want) : rc;
+    memcpy(stage, offset, tab_bytes);
+    LDPC_HIP_TRY(ctx, hipMemcpyAsync(ctx->dgram_off.p, stage, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = pinned_ring_commit(ctx, ctx->dgram_ring))) return rc;
     const int W = S / 4, G = lanes_per_row(W);
     const dim3 grid(grid_for((R + (int64_t)kWaves * (64 / G) - 1) / ((int64_t)kWaves * (64 / G)))), block(kThreads);
     const int64_t *doff = (const int64_t *)ctx->dgram_off.p;
@@ -337,7 +322,7 @@ int ldpc_amd_fec_dgram_info(ldpc_amd_ctx *ctx, int64_t info[4])
     if (!ctx) return LDPC_AMD_EINVAL;
     if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_dgram_info: info must not be null");
     info[0] = (int64_t)(ctx->dgram_off.cap + ctx->dgram_len.cap);
-    info[1] = (int64_t)(ctx->dgram_stage_cap[0] + ctx->dgram_stage_cap[1]);
+    info[1] = (int64_t)ctx->dgram_ring.bytes();
     info[2] = ctx->dgram_rows[0];
     info[3] = ctx->dgram_rows[1];
     return LDPC_AMD_OK;

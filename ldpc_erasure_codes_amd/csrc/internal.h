@@ -162,6 +162,25 @@ struct Scratch {
     size_t cap = 0;
 };
 
+// Pinned host staging of a table that is copied to the device on the context's stream: two slots used in turn, each with the event of
+// its last copy, so that a slot is never rewritten under a copy in flight (two calls enqueued back to back are both right).
+// pinned_ring_acquire / pinned_ring_commit / pinned_ring_free below.
+struct PinnedRing {
+    void *slot[2] = {nullptr, nullptr};
+    size_t cap[2] = {0, 0};
+    hipEvent_t event[2] = {nullptr, nullptr};
+    bool pending[2] = {false, false};
+    unsigned calls = 0;
+    size_t bytes() const { return cap[0] + cap[1]; }
+};
+
+// The packet senders of wire_dev.hip, and what the context keeps of the last call of each that sent something
+enum TxKind { kTxPlain, kTxFlows, kTxIlv, kTxFlowsIlv, kTxRs, kTxKinds };
+struct TxLast {
+    int path = 0;        // 0 none yet, 1 fused kernel, 2 composed
+    int64_t count = 0;   // its frames (kTxRs: blocks)
+};
+
 }  // namespace ldpc_amd
 
 struct ldpc_amd_ctx {
@@ -199,31 +218,18 @@ struct ldpc_amd_ctx {
     ldpc_amd::Scratch rsbad;    // int: malformed blocks of the last RS decode (decoded to zeros)
     ldpc_amd::Scratch rssel;    // RS from frames: [nblocks] int32 symbols received, then [nblocks][k] u16 the first k received positions
     ldpc_amd::Scratch frstatus; // decode_frames without a status array: the status words the finalise kernel reads
-    ldpc_amd::Scratch sender_cw;   // fec_encode_packets_dev, composed path: codewords of one chunk of frames (at most 256 MiB)
-    int sender_path = 0;           // ... path of the last call: 0 none yet, 1 fused kernel, 2 composed (ldpc_amd_fec_sender_info)
-    // fec_encode_packets_flows_dev: the frames' descriptors on the device (16 bytes each; the stream orders a call's copy behind the
-    // kernels of the call before), and their pinned staging -- two slots used in turn, each with the event of its last copy, so that a
-    // slot is never rewritten under a copy in flight
+    ldpc_amd::Scratch sender_cw;   // the packet senders' composed paths: codewords of one chunk of frames (at most 256 MiB)
+    // the last call of every packet sender that sent something, by ldpc_amd::TxKind: never written on a refusal or for a call of no
+    // frames (ldpc_amd_fec_sender_info, _sender_flows_info, _sender_ilv_info, _sender_flows_ilv_info, _rs_sender_info)
+    ldpc_amd::TxLast tx_last[ldpc_amd::kTxKinds];
+    // the descriptor-driven senders (all but kTxPlain): the frames' descriptors on the device (16 bytes each, the multi-flow senders'
+    // flow table behind them; the stream orders a call's copy behind the kernels of the call before), and their pinned staging
     ldpc_amd::Scratch txf_desc;
-    void *txf_stage[2] = {nullptr, nullptr};
-    size_t txf_stage_cap[2] = {0, 0};
-    hipEvent_t txf_event[2] = {nullptr, nullptr};
-    bool txf_pending[2] = {false, false};
-    unsigned txf_calls = 0;
-    int txf_path = 0;              // ... path of the last call (ldpc_amd_fec_sender_flows_info)
-    int64_t txf_frames = 0;        // ... its frames
-    int txi_path = 0;              // fec_encode_packets_ilv_dev (the same descriptor memory): path of the last call (ldpc_amd_fec_sender_ilv_info)
-    int64_t txi_frames = 0;        // ... its frames
-    int txfi_path = 0;             // fec_encode_packets_flows_ilv_dev (the same descriptor memory): path of the last call (ldpc_amd_fec_sender_flows_ilv_info)
-    int64_t txfi_frames = 0;       // ... its frames
-    // fec_dgram_pack_dev / fec_dgram_unpack_dev (datagram_dev.hip): pack's offsets on the device and their pinned staging, two slots
-    // used in turn like txf_stage; unpack's per-row lengths and per-tile sums
+    ldpc_amd::PinnedRing txf_ring;
+    // fec_dgram_pack_dev / fec_dgram_unpack_dev (datagram_dev.hip): pack's offsets on the device and their pinned staging; unpack's
+    // per-row lengths and per-tile sums
     ldpc_amd::Scratch dgram_off, dgram_len;
-    void *dgram_stage[2] = {nullptr, nullptr};
-    size_t dgram_stage_cap[2] = {0, 0};
-    hipEvent_t dgram_event[2] = {nullptr, nullptr};
-    bool dgram_pending[2] = {false, false};
-    unsigned dgram_calls = 0;
+    ldpc_amd::PinnedRing dgram_ring;
     int64_t dgram_rows[2] = {0, 0};   // rows of the last pack, of the last unpack (ldpc_amd_fec_dgram_info)
     ldpc_amd::Scratch wire_len;       // fec_wire_trim_dev (wire_ragged_dev.hip): the per-tile sums, then the per-packet lengths
     int64_t wire_packets[2] = {0, 0};   // packets of the last trim, of the last land (ldpc_amd_fec_wire_ragged_info)
@@ -266,10 +272,8 @@ struct ldpc_amd_ctx {
     // fec_rxw_flows_decode_many / _decode_flush_many (rx_window_flows_dev.hip): the same four words (ldpc_amd_fec_rxw_flows_info)
     int64_t rxwf_info[4] = {0, 0, 0, 0};
     // fec_rs_encode_packets_dev (include/ldpc_erasure_amd_rs_wire.h): the packed-multiply table and the padded coefficients the packet
-    // encoder of rs_wire_dev.hip reads; path (0 none, 1 fused, 2 composed) and blocks of the last call (ldpc_amd_fec_rs_sender_info)
+    // encoder of rs_wire_dev.hip reads (its last call: tx_last[kTxRs])
     ldpc_amd::Scratch rsw_tab, rsw_coef;
-    int rsw_path = 0;
-    int64_t rsw_blocks = 0;
     // fec_rxw_dev_rs_decode_many / _rs_decode_flush (rx_window_dev.hip): blocks, RS decode launches and scratch bytes of the last call
     // (ldpc_amd_fec_rs_receiver_info)
     int64_t rsrx_info[4] = {0, 0, 0, 0};
@@ -369,6 +373,13 @@ int launch_fpga_stats(ldpc_amd_ctx *ctx, const DevCode &code, int rs_n, int rs_k
                       const uint8_t *erased0, const int32_t *residual_k, unsigned long long *stats /* [2], accumulated */);
 
 int scratch_reserve(ldpc_amd_ctx *ctx, Scratch &s, size_t bytes);
+// This call's slot of a ring, at least `bytes` long: waits for the copy that last read the slot (two calls ago), grows the slot in
+// 64 KiB steps.  LDPC_AMD_ENOMEM, with *want = the bytes asked for and NO error text (the caller has its own), when there is no
+// pinned memory.  The caller fills *host, enqueues its copy on ctx->stream and commits.
+int pinned_ring_acquire(ldpc_amd_ctx *ctx, PinnedRing &r, size_t bytes, void **host, size_t *want);
+// Behind the copy: records the slot's event on ctx->stream and turns to the other slot.
+int pinned_ring_commit(ldpc_amd_ctx *ctx, PinnedRing &r);
+void pinned_ring_free(PinnedRing &r);
 // Brackets one kernel launch with events when profiling is on (no-ops otherwise).
 hipEvent_t prof_begin(ldpc_amd_ctx *ctx, int level = 1);
 void prof_end(ldpc_amd_ctx *ctx, int kind, hipEvent_t start);

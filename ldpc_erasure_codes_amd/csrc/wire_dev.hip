@@ -628,44 +628,213 @@ struct ldpc_amd_fec_rx_dev {
 
 namespace {
 
-// ---- the descriptor-driven senders' common part (ldpc_amd_fec_encode_packets_flows_dev, ldpc_amd_fec_encode_packets_ilv_dev,
-// ldpc_amd_fec_rs_encode_packets_dev) --------
-// tx_stage_described stages a call's table -- [F] descriptors and `extra` further bytes per frame behind them.  The table is filled by
-// fill(hd, &max_stride) in a pinned slot of the context (two slots used in turn, each with the event of its last copy, so that a slot
-// is never rewritten under a copy in flight: two calls enqueued back to back are both right) and copied to the context's device table
-// on the stream.  *dd_out: the device table.
-template <class Fill>
-int tx_stage_described(ldpc_amd_ctx *ctx, const char *who, int64_t F, size_t extra, Fill fill, const TxFrameDesc **dd_out, int64_t *max_stride_out)
+// ---- the packet senders' common part (ldpc_amd_fec_encode_packets_dev, _flows_dev, _ilv_dev, _flows_ilv_dev and
+// ldpc_amd_fec_rs_encode_packets_dev) ----------------------------------------------------------------------------------------------
+// What an entry point has of its call.  A single stream is the one-flow case: its constructor describes it as flow 0 of one, in
+// segmented order.  Where the entry points differ in WHICH checks tx_check makes, the difference is a flag here, set at the entry
+// point (DESIGN.md has the table); the ORDER of the checks is tx_check's, one for all.
+struct TxCall {
+    const char *who;
+    const char *unit;   // what the call counts, in the texts that say so: "frames", or "blocks" (the RS sender)
+    int n, k, S;
+    bool triangle;      // the code has a systematic encoder
+    int64_t F;          // a single stream: the caller's count; a multi-flow call: frame_begin[nflows], set by tx_check
+    int depth;
+    const uint8_t *source;
+    uint8_t *packets;
+    bool multi;         // a multi-flow call: nflows .. flow_of are the caller's
+    int nflows;
+    const int64_t *frame_begin;
+    const uint8_t *fec_class, *block0;
+    int order;
+    int32_t *flow_of;
+    bool check_range = true;   // refuse F * n >= 2^31
+    bool check_words = true;   // refuse a source off the 4-byte grid when S is word-sized
+    int64_t one_begin[2];      // a single stream as one flow
+    uint8_t one_class, one_block0;
+
+    TxCall(const char *who_, const char *unit_, int n_, int k_, bool triangle_, int S_, int64_t F_, unsigned fec_class_, unsigned block0_, int depth_,
+           const uint8_t *source_, uint8_t *packets_)
+        : who(who_), unit(unit_), n(n_), k(k_), S(S_), triangle(triangle_), F(F_), depth(depth_), source(source_), packets(packets_), multi(false),
+          nflows(1), frame_begin(one_begin), fec_class(&one_class), block0(&one_block0), order(LDPC_AMD_FEC_TX_SEGMENTED), flow_of(nullptr),
+          one_begin{0, F_}, one_class((uint8_t)(fec_class_ & 0xffu)), one_block0((uint8_t)(block0_ & 0xffu))
+    {
+    }
+    TxCall(const char *who_, int n_, int k_, bool triangle_, int S_, int nflows_, const int64_t *frame_begin_, const uint8_t *fec_class_,
+           const uint8_t *block0_, int order_, int depth_, const uint8_t *source_, uint8_t *packets_, int32_t *flow_of_)
+        : who(who_), unit("frames"), n(n_), k(k_), S(S_), triangle(triangle_), F(0), depth(depth_), source(source_), packets(packets_), multi(true),
+          nflows(nflows_), frame_begin(frame_begin_), fec_class(fec_class_), block0(block0_), order(order_), flow_of(flow_of_), one_begin{0, 0},
+          one_class(0), one_block0(0)
+    {
+    }
+    TxCall(const TxCall &) = delete;   // (frame_begin .. block0 may point into the object)
+};
+
+// the code of an LDPC sender's handle; nullptr: LDPC_AMD_ENOCODE is set
+const DevCode *tx_code(ldpc_amd_ctx *ctx, int code)
 {
-    const size_t tab_bytes = (sizeof(TxFrameDesc) + extra) * (size_t)F;
+    if (code >= 0 && code < (int)ctx->codes.size()) return &ctx->codes[code]->dev;
+    set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
+    return nullptr;
+}
+
+// the first flow that breaks the whole-group condition of ROUND_ROBIN at depth D > 1 (a non-empty flow whose block0 or frame count
+// is no multiple of D), -1: none
+int tx_flows_part_group(int nflows, const int64_t *frame_begin, const uint8_t *block0, int depth)
+{
+    if (depth <= 1) return -1;
+    for (int f = 0; f < nflows; f++) {
+        const int64_t c = frame_begin[f + 1] - frame_begin[f];
+        if (c > 0 && (block0[f] % depth != 0 || c % depth != 0)) return f;
+    }
+    return -1;
+}
+
+// A sender call's checks, in the one order all five entry points refuse in.  OK with c.F == 0: nothing to send, and nothing below the
+// count was looked at (an unsupported S, null pointers and a code without encoder all pass).
+int tx_check(ldpc_amd_ctx *ctx, TxCall &c)
+{
+    const char *who = c.who;
+    if (c.multi) {
+        if (c.nflows < 1 || c.nflows > LDPC_AMD_FEC_TX_MAX_FLOWS)
+            return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows must be 1..%d (got %d)", who, LDPC_AMD_FEC_TX_MAX_FLOWS, c.nflows);
+        if (!c.frame_begin || !c.fec_class || !c.block0)
+            return set_error(ctx, LDPC_AMD_EINVAL, "%s: frame_begin / fec_class / block0 must not be null", who);
+        if (c.S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: bad S", who);
+        if (c.order != LDPC_AMD_FEC_TX_SEGMENTED && c.order != LDPC_AMD_FEC_TX_ROUND_ROBIN)
+            return set_error(ctx, LDPC_AMD_EINVAL, "%s: unknown order %d", who, c.order);
+        if (c.frame_begin[0] != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: frame_begin must start at 0", who);
+        for (int f = 0; f < c.nflows; f++)
+            if (c.frame_begin[f + 1] < c.frame_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: frame_begin decreases at flow %d", who, f);
+    } else if (c.F < 0 || c.S < 1)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: bad n%s/S", who, c.unit);
+    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(c.depth)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: depth must be 1, 2, 4, 8 or 16 (got %d)", who, c.depth);
+    if (c.multi) {
+        const int f = c.order == LDPC_AMD_FEC_TX_ROUND_ROBIN ? tx_flows_part_group(c.nflows, c.frame_begin, c.block0, c.depth) : -1;
+        if (f >= 0)
+            return set_error(ctx, LDPC_AMD_EINVAL,
+                             "%s: round robin at depth %d needs whole aligned groups, block0 %% depth == 0 and frames %% depth == 0 for every flow "
+                             "(flow %d: block0=%d frames=%lld)",
+                             who, c.depth, f, (int)c.block0[f], (long long)(c.frame_begin[f + 1] - c.frame_begin[f]));
+        c.F = c.frame_begin[c.nflows];
+    }
+    const int64_t F = c.F;
+    if (c.check_range && F > (((int64_t)1 << 31) - 1) / c.n)
+        return set_error(ctx, LDPC_AMD_EINVAL, "%s: %lld %s of %d packets are not below 2^31 packets", who, (long long)F, c.unit, c.n);
+    if (F == 0) return LDPC_AMD_OK;
+    if (!c.triangle) return set_error(ctx, LDPC_AMD_EUNSUP, "code is not in triangle form: no systematic encoder");
+    if (!symbol_len_ok(ctx, c.S)) return refuse_symbol_len(ctx, c.S, "S must be 1 or a multiple of 16 (got %d)");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!c.source || !c.packets || !is_device_ptr(ctx, c.source) || !is_device_ptr(ctx, c.packets) || (c.flow_of && !is_device_ptr(ctx, c.flow_of)))
+        return set_error(ctx, LDPC_AMD_EINVAL, c.multi ? "%s: source / packets / flow_of must be device pointers of device %d"
+                                                       : "%s: source / packets must be device pointers of device %d", who, ctx->device);
+    if (((uintptr_t)c.flow_of & 3) != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be 4-byte aligned", who);
+    if (c.check_words && symbol_len_words(c.S) && ((uintptr_t)c.source & 3) != 0)
+        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", c.S);
+    const uintptr_t s0 = (uintptr_t)c.source, s1 = s0 + (size_t)c.k * c.S * (size_t)F;
+    const uintptr_t p0 = (uintptr_t)c.packets, p1 = p0 + (size_t)c.n * ((size_t)c.S + kHdr) * (size_t)F;
+    const uintptr_t q0 = (uintptr_t)c.flow_of, q1 = q0 + sizeof(int32_t) * (size_t)(F * c.n);
+    if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: source and packets overlap", who);
+    if (c.flow_of && ((q0 < p1 && p0 < q1) || (q0 < s1 && s0 < q1))) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of overlaps source or packets", who);
+    return LDPC_AMD_OK;
+}
+
+// The composed paths go through the context's codeword scratch, at most kSenderScratchMax bytes of it: reserves it for F frames of
+// cw_frame bytes.  *chunk: the frames of one round.  The rounds follow one another on the context's stream, so the scratch is free
+// again when the next encode starts.
+int tx_reserve_chunk(ldpc_amd_ctx *ctx, int64_t F, size_t cw_frame, int64_t *chunk)
+{
+    *chunk = std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)(kSenderScratchMax / cw_frame)));
+    return scratch_reserve(ctx, ctx->sender_cw, (size_t)*chunk * cw_frame);
+}
+
+// The multi-flow orders as arithmetic, the body of ldpc_amd_fec_tx_flows_layout (depth 1; block0 may be null there) and
+// ldpc_amd_fec_tx_flows_ilv_layout.  SEGMENTED: every flow's single-flow interleaved layout, shifted to the flow's first packet.
+// ROUND_ROBIN on GROUPS of `depth` frames -- while group r of every flow is on the wire the active flows are those with more than r D
+// frames, A_r of them, and a round takes one packet of each in ascending order: member i' of the group starts at base_r + rank + i' A_r
+// (rank: the active flows below it), its rows are D A_r packets apart, base_r = n D (A_0 + ... + A_{r-1}).  The active list only ever
+// loses flows, so it is compacted in place as r grows: the work is the sum of the A_r.  At depth 1 a group is a frame: first =
+// base_i + rank, stride = A_i.
+int64_t tx_flows_layout(int nflows, const int64_t *frame_begin, int n, const uint8_t *block0, int depth, int order, int64_t *first, int32_t *stride)
+{
+    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth) || (!block0 && depth != 1)) return LDPC_AMD_EINVAL;
+    if (nflows < 1 || nflows > LDPC_AMD_FEC_TX_MAX_FLOWS || !frame_begin || n < 1 || frame_begin[0] != 0) return LDPC_AMD_EINVAL;
+    if (order != LDPC_AMD_FEC_TX_SEGMENTED && order != LDPC_AMD_FEC_TX_ROUND_ROBIN) return LDPC_AMD_EINVAL;
+    for (int f = 0; f < nflows; f++)
+        if (frame_begin[f + 1] < frame_begin[f]) return LDPC_AMD_EINVAL;
+    const int64_t F = frame_begin[nflows];
+    if (F > (((int64_t)1 << 31) - 1) / n) return LDPC_AMD_EINVAL;   // F * n < 2^31
+    if (order == LDPC_AMD_FEC_TX_SEGMENTED) {
+        for (int f = 0; f < nflows; f++) {
+            const int64_t t0 = frame_begin[f], c = frame_begin[f + 1] - t0;
+            if (ldpc_amd_fec_tx_ilv_layout(c, n, block0 ? block0[f] : 0, depth, first ? first + t0 : nullptr, stride ? stride + t0 : nullptr) != c * n)
+                return LDPC_AMD_EINVAL;
+            for (int64_t i = 0; first && i < c; i++) first[t0 + i] += t0 * n;
+        }
+        return F * n;
+    }
+    if (tx_flows_part_group(nflows, frame_begin, block0, depth) >= 0) return LDPC_AMD_EINVAL;
+    std::vector<int> active;
+    active.reserve((size_t)nflows);
+    for (int f = 0; f < nflows; f++)
+        if (frame_begin[f + 1] > frame_begin[f]) active.push_back(f);
+    int64_t base = 0;
+    for (int64_t r = 0; !active.empty(); r++) {
+        const int64_t A = (int64_t)active.size();
+        size_t keep = 0;
+        for (size_t rank = 0; rank < active.size(); rank++) {
+            const int f = active[rank];
+            const int64_t t = frame_begin[f] + r * depth;
+            for (int i = 0; i < depth; i++) {
+                if (first) first[t + i] = base + (int64_t)rank + i * A;
+                if (stride) stride[t + i] = (int32_t)(depth * A);
+            }
+            if (frame_begin[f + 1] - frame_begin[f] > (r + 1) * depth) active[keep++] = f;
+        }
+        active.resize(keep);
+        base += A * n * depth;
+    }
+    return F * n;
+}
+
+// ---- the descriptor-driven senders (all but ldpc_amd_fec_encode_packets_dev) -------------------------------------------------------
+// The call's table on the host: [F] descriptors {first packet, stride, class << 8 | block} by the layout of its flows, a multi-flow
+// call's [F] flow numbers behind them.  *max_stride: the largest stride.
+int tx_fill_described(ldpc_amd_ctx *ctx, const TxCall &c, TxFrameDesc *hd, int64_t *max_stride)
+{
+    const int64_t F = c.F;
+    int32_t *hflow = c.multi ? (int32_t *)(hd + F) : nullptr;
+    std::vector<int64_t> first((size_t)F);
+    std::vector<int32_t> stride((size_t)F);
+    if (tx_flows_layout(c.nflows, c.frame_begin, c.n, c.block0, c.depth, c.order, first.data(), stride.data()) != F * c.n)
+        return set_error(ctx, LDPC_AMD_EINVAL, c.multi ? "%s: bad frame_begin" : "%s: bad layout arguments", c.who);
+    for (int f = 0; f < c.nflows; f++)
+        for (int64_t t = c.frame_begin[f]; t < c.frame_begin[f + 1]; t++) {
+            hd[t].first = (uint64_t)first[(size_t)t];
+            hd[t].stride = (uint32_t)stride[(size_t)t];
+            hd[t].hdr = ((uint32_t)c.fec_class[f] << 8) | (((uint32_t)c.block0[f] + (uint32_t)(t - c.frame_begin[f])) & 0xffu);
+            if (hflow) hflow[t] = f;
+            *max_stride = std::max<int64_t>(*max_stride, stride[(size_t)t]);
+        }
+    return LDPC_AMD_OK;
+}
+
+// Stages the table: filled in a slot of the context's pinned ring (internal.h: PinnedRing) and copied to the context's device table
+// on the stream.  *dd_out: the device table.
+int tx_stage_described(ldpc_amd_ctx *ctx, const TxCall &c, const TxFrameDesc **dd_out, int64_t *max_stride_out)
+{
+    const size_t tab_bytes = (sizeof(TxFrameDesc) + (c.multi ? sizeof(int32_t) : 0)) * (size_t)c.F;
     int rc;
     if ((rc = scratch_reserve(ctx, ctx->txf_desc, tab_bytes))) return rc;
-    const int slot = (int)(ctx->txf_calls & 1u);
-    if (!ctx->txf_event[slot]) LDPC_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txf_event[slot], hipEventDisableTiming));
-    if (ctx->txf_pending[slot]) {   // the copy that last read this slot (two calls ago) must be through
-        LDPC_HIP_TRY(ctx, hipEventSynchronize(ctx->txf_event[slot]));
-        ctx->txf_pending[slot] = false;
-    }
-    if (ctx->txf_stage_cap[slot] < tab_bytes) {
-        if (ctx->txf_stage[slot]) (void)hipHostFree(ctx->txf_stage[slot]);
-        ctx->txf_stage[slot] = nullptr; ctx->txf_stage_cap[slot] = 0;
-        const size_t want = (tab_bytes + 65535) & ~(size_t)65535;
-        if (hipHostMalloc(&ctx->txf_stage[slot], want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->txf_stage[slot] = nullptr;
-            return set_error(ctx, LDPC_AMD_ENOMEM, "%s: no pinned memory for %zu descriptor bytes", who, want);
-        }
-        ctx->txf_stage_cap[slot] = want;
-    }
-    TxFrameDesc *hd = (TxFrameDesc *)ctx->txf_stage[slot];
-    int64_t max_stride = 1;
-    if ((rc = fill(hd, &max_stride))) return rc;
+    void *hd = nullptr;
+    size_t want = 0;
+    if ((rc = pinned_ring_acquire(ctx, ctx->txf_ring, tab_bytes, &hd, &want)))
+        return rc == LDPC_AMD_ENOMEM ? set_error(ctx, LDPC_AMD_ENOMEM, "%s: no pinned memory for %zu descriptor bytes", c.who, want) : rc;
+    *max_stride_out = 1;
+    if ((rc = tx_fill_described(ctx, c, (TxFrameDesc *)hd, max_stride_out))) return rc;
     LDPC_HIP_TRY(ctx, hipMemcpyAsync(ctx->txf_desc.p, hd, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    LDPC_HIP_TRY(ctx, hipEventRecord(ctx->txf_event[slot], ctx->stream));
-    ctx->txf_pending[slot] = true;
-    ctx->txf_calls++;
+    if ((rc = pinned_ring_commit(ctx, ctx->txf_ring))) return rc;
     *dd_out = (const TxFrameDesc *)ctx->txf_desc.p;
-    *max_stride_out = max_stride;
     return LDPC_AMD_OK;
 }
 
@@ -682,34 +851,60 @@ inline int tx_packetize_described(ldpc_amd_ctx *ctx, const uint8_t *cw, int64_t 
     return LDPC_AMD_OK;
 }
 
-// Stages the table and sends the LDPC frames by it: the descriptor form of the packet encoder (path 1, fused) where
-// launch_encode_packets_flows has it for this call, else the encoder into the context's codeword scratch and the descriptor-driven
-// packetisers, chunk by chunk (path 2, composed).  *dd: the device table.
-template <class Fill>
-int tx_send_described(ldpc_amd_ctx *ctx, const char *who, const DevCode &cd, int S, int64_t F, size_t extra, const uint8_t *source,
-                      uint8_t *packets, Fill fill, const TxFrameDesc **dd_out, int *path_out)
+// Sends a checked call of c.F > 0 frames by its descriptors: stages the table; then fused(dd, max_stride), the descriptor form of the
+// code's packet encoder (path 1), where that has the call -- it answers kEncodeNotFused, with nothing launched, where not --, else
+// encode(cnt, source, cw) into the context's codeword scratch and the descriptor-driven packetisers, chunk by chunk (path 2,
+// composed); then a multi-flow call's flow_of; and records the call as the last of its kind.
+template <class Fused, class Encode>
+int tx_send_described(ldpc_amd_ctx *ctx, const TxCall &c, TxKind kind, Fused fused, Encode encode)
 {
-    const int n = cd.n;
-    const size_t src_frame = (size_t)cd.k * S, cw_frame = (size_t)n * S;
+    const int64_t F = c.F;
+    const size_t src_frame = (size_t)c.k * c.S, cw_frame = (size_t)c.n * c.S;
     int rc;
     const TxFrameDesc *dd = nullptr;
     int64_t max_stride = 1;
-    if ((rc = tx_stage_described(ctx, who, F, extra, fill, &dd, &max_stride))) return rc;
-    rc = launch_encode_packets_flows(ctx, cd, S, F, source, dd, max_stride, packets);
+    if ((rc = tx_stage_described(ctx, c, &dd, &max_stride))) return rc;
+    rc = fused(dd, max_stride);
     if (rc != LDPC_AMD_OK && rc != kEncodeNotFused) return rc;
     const int path = rc == LDPC_AMD_OK ? 1 : 2;
     if (path == 2) {
-        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)(kSenderScratchMax / cw_frame)));
-        if ((rc = scratch_reserve(ctx, ctx->sender_cw, (size_t)chunk * cw_frame))) return rc;
+        int64_t chunk = 0;
+        if ((rc = tx_reserve_chunk(ctx, F, cw_frame, &chunk))) return rc;
         uint8_t *cw = (uint8_t *)ctx->sender_cw.p;
         for (int64_t f0 = 0; f0 < F; f0 += chunk) {
             const int64_t cnt = std::min(chunk, F - f0);
-            if ((rc = launch_encode(ctx, cd, S, cnt, source + (size_t)f0 * src_frame, cw))) return rc;
-            if ((rc = tx_packetize_described(ctx, cw, cnt, n, S, dd + f0, packets))) return rc;
+            if ((rc = encode(cnt, c.source + (size_t)f0 * src_frame, cw))) return rc;
+            if ((rc = tx_packetize_described(ctx, cw, cnt, c.n, c.S, dd + f0, c.packets))) return rc;
         }
     }
-    *dd_out = dd;
-    *path_out = path;
+    if (c.flow_of) {   // (a multi-flow call's: the frames' flows lie behind the descriptors)
+        const int64_t P = F * c.n;
+        hipLaunchKernelGGL(fec_tx_flow_of, dim3(grid_for(P)), dim3(kThreads), 0, ctx->stream, dd, (const int32_t *)(dd + F), P, c.n, c.flow_of);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+    }
+    ctx->tx_last[kind] = TxLast{path, F};
+    return LDPC_AMD_OK;
+}
+
+// the checks, then the LDPC launchers behind tx_send_described: the three descriptor-driven LDPC senders
+int tx_send_ldpc(ldpc_amd_ctx *ctx, const DevCode &cd, TxCall &c, TxKind kind)
+{
+    const int rc = tx_check(ctx, c);
+    if (rc || c.F == 0) return rc;
+    return tx_send_described(
+        ctx, c, kind, [&](const TxFrameDesc *dd, int64_t max_stride) { return launch_encode_packets_flows(ctx, cd, c.S, c.F, c.source, dd, max_stride, c.packets); },
+        [&](int64_t cnt, const uint8_t *src, uint8_t *cw) { return launch_encode(ctx, cd, c.S, cnt, src, cw); });
+}
+
+// the four words of the descriptor-driven senders' info calls
+int tx_info(ldpc_amd_ctx *ctx, const char *who, TxKind kind, int64_t info[4])
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "%s: info must not be null", who);
+    info[0] = ctx->tx_last[kind].path;
+    info[1] = (int64_t)ctx->sender_cw.cap;
+    info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_ring.bytes());
+    info[3] = ctx->tx_last[kind].count;
     return LDPC_AMD_OK;
 }
 
@@ -741,31 +936,28 @@ int ldpc_amd_fec_packetize_dev(ldpc_amd_ctx *ctx, const uint8_t *frames, int64_t
 // ---- the sender (include/ldpc_erasure_amd_sender.h) ---------------------------------------------------------------------
 // Fused where the encoder has a packet-output form (launch_encode_packets: the persistent scatter encoder stores its rows at their
 // places in the packet array and the headers beside them -- the reference's one-kernel sender, ...VITA_in_UDP_out.cl:84-129,168-211);
-// else composed: encode a chunk of frames into the context's scratch, packetise it, next chunk.  The chunks follow one another on
-// the context's stream, so the scratch is free again when the next encode starts.
+// else composed: encode a chunk of frames into the context's scratch, packetise it, next chunk.  Its kernels take a class and a first
+// block number, no descriptors: of the common part it shares the checks and the chunks.
 int ldpc_amd_fec_encode_packets_dev(ldpc_amd_ctx *ctx, int code, int S, int64_t nframes, const uint8_t *source, unsigned fec_class,
                                     unsigned block0, uint8_t *packets)
 {
     if (!ctx) return LDPC_AMD_EINVAL;
-    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
-    const DevCode &cd = ctx->codes[code]->dev;
-    if (nframes < 0 || S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_dev: bad nframes/S");
-    if (nframes == 0) return LDPC_AMD_OK;
-    if (cd.enc_nlevels == 0) return set_error(ctx, LDPC_AMD_EUNSUP, "code is not in triangle form: no systematic encoder");
-    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_dev: source / packets must be device pointers of device %d", ctx->device);
-    const size_t src_frame = (size_t)cd.k * S, cw_frame = (size_t)cd.n * S, pk_frame = (size_t)cd.n * ((size_t)S + kHdr);
-    const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)nframes, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)nframes;
-    if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_dev: source and packets overlap");
-    int rc = launch_encode_packets(ctx, cd, S, nframes, source, fec_class, block0, packets);
+    const DevCode *cdp = tx_code(ctx, code);
+    if (!cdp) return LDPC_AMD_ENOCODE;
+    const DevCode &cd = *cdp;
+    TxCall c("fec_encode_packets_dev", "frames", cd.n, cd.k, cd.enc_nlevels != 0, S, nframes, fec_class, block0, 1, source, packets);
+    c.check_range = false;   // this sender has never refused a count: its packetisers index the packets in 64 bits
+    c.check_words = false;   // ... nor a word-sized S's source off the 4-byte grid itself: the encoder it launches does (launch_encode)
+    int rc = tx_check(ctx, c);
+    if (rc || nframes == 0) return rc;
+    rc = launch_encode_packets(ctx, cd, S, nframes, source, fec_class, block0, packets);
     if (rc != kEncodeNotFused) {
-        if (rc == LDPC_AMD_OK) ctx->sender_path = 1;
+        if (rc == LDPC_AMD_OK) ctx->tx_last[kTxPlain] = TxLast{1, nframes};
         return rc;
     }
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nframes, (int64_t)(kSenderScratchMax / cw_frame)));
-    if ((rc = scratch_reserve(ctx, ctx->sender_cw, (size_t)chunk * cw_frame))) return rc;
+    const size_t src_frame = (size_t)cd.k * S, pk_frame = (size_t)cd.n * ((size_t)S + kHdr);
+    int64_t chunk = 0;
+    if ((rc = tx_reserve_chunk(ctx, nframes, (size_t)cd.n * S, &chunk))) return rc;
     uint8_t *cw = (uint8_t *)ctx->sender_cw.p;
     for (int64_t f0 = 0; f0 < nframes; f0 += chunk) {
         const int64_t cnt = std::min(chunk, nframes - f0);
@@ -773,7 +965,7 @@ int ldpc_amd_fec_encode_packets_dev(ldpc_amd_ctx *ctx, int code, int S, int64_t 
         if ((rc = ldpc_amd_fec_packetize_dev(ctx, cw, cnt, cd.n, S, fec_class, (block0 + (unsigned)(f0 & 0xff)) & 0xffu, packets + (size_t)f0 * pk_frame)))
             return rc;
     }
-    ctx->sender_path = 2;
+    ctx->tx_last[kTxPlain] = TxLast{2, nframes};
     return LDPC_AMD_OK;
 }
 
@@ -781,222 +973,58 @@ int ldpc_amd_fec_sender_info(ldpc_amd_ctx *ctx, int info[4])
 {
     if (!ctx) return LDPC_AMD_EINVAL;
     if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_sender_info: info must not be null");
-    info[0] = ctx->sender_path;
+    info[0] = ctx->tx_last[kTxPlain].path;
     info[1] = (int)std::min<size_t>(ctx->sender_cw.cap, (size_t)INT32_MAX);
     info[2] = info[3] = 0;
     return LDPC_AMD_OK;
 }
 
-// ---- the multi-flow sender (include/ldpc_erasure_amd_sender_flows.h) --------------------------------------------------------
-// The order as arithmetic.  ROUND_ROBIN: while frame i of every flow is on the wire the active flows are those with more than i
-// frames -- A_i of them -- and they take turns in ascending order, so row j of frame i of flow f is packet base_i + rank + j A_i,
-// rank = the active flows below f, base_i = n (A_0 + ... + A_{i-1}).  The active list only ever loses flows, so it is compacted
-// in place as i grows: the work is the sum of the A_i, which is F.
+// ---- the multi-flow senders (include/ldpc_erasure_amd_sender_flows.h; with a depth: include/ldpc_erasure_amd_interleave_flows.h) ----
 int64_t ldpc_amd_fec_tx_flows_layout(int nflows, const int64_t *frame_begin, int n, int order, int64_t *first, int32_t *stride)
 {
-    if (nflows < 1 || nflows > LDPC_AMD_FEC_TX_MAX_FLOWS || !frame_begin || n < 1 || frame_begin[0] != 0) return LDPC_AMD_EINVAL;
-    if (order != LDPC_AMD_FEC_TX_SEGMENTED && order != LDPC_AMD_FEC_TX_ROUND_ROBIN) return LDPC_AMD_EINVAL;
-    for (int f = 0; f < nflows; f++)
-        if (frame_begin[f + 1] < frame_begin[f]) return LDPC_AMD_EINVAL;
-    const int64_t F = frame_begin[nflows];
-    if (F > (((int64_t)1 << 31) - 1) / n) return LDPC_AMD_EINVAL;   // F * n < 2^31
-    if (order == LDPC_AMD_FEC_TX_SEGMENTED) {
-        for (int64_t t = 0; t < F; t++) {
-            if (first) first[t] = t * n;
-            if (stride) stride[t] = 1;
-        }
-        return F * n;
-    }
-    std::vector<int> active;
-    active.reserve((size_t)nflows);
-    for (int f = 0; f < nflows; f++)
-        if (frame_begin[f + 1] > frame_begin[f]) active.push_back(f);
-    int64_t base = 0;
-    for (int64_t i = 0; !active.empty(); i++) {
-        const int64_t A = (int64_t)active.size();
-        size_t keep = 0;
-        for (size_t r = 0; r < active.size(); r++) {
-            const int f = active[r];
-            const int64_t t = frame_begin[f] + i;
-            if (first) first[t] = base + (int64_t)r;
-            if (stride) stride[t] = (int32_t)A;
-            if (frame_begin[f + 1] - frame_begin[f] > i + 1) active[keep++] = f;
-        }
-        active.resize(keep);
-        base += A * n;
-    }
-    return F * n;
+    return tx_flows_layout(nflows, frame_begin, n, nullptr, 1, order, first, stride);
 }
 
-// ---- depth on the multi-flow sender (include/ldpc_erasure_amd_interleave_flows.h) ----------------------------------------------
-// the first flow that breaks the whole-group condition of ROUND_ROBIN at depth D > 1 (a non-empty flow whose block0 or frame count
-// is no multiple of D), -1: none
-static int tx_flows_part_group(int nflows, const int64_t *frame_begin, const uint8_t *block0, int depth)
-{
-    if (depth <= 1) return -1;
-    for (int f = 0; f < nflows; f++) {
-        const int64_t c = frame_begin[f + 1] - frame_begin[f];
-        if (c > 0 && (block0[f] % depth != 0 || c % depth != 0)) return f;
-    }
-    return -1;
-}
-
-// The order as arithmetic.  SEGMENTED: every flow's single-flow interleaved layout, shifted to the flow's first packet.  ROUND_ROBIN:
-// ldpc_amd_fec_tx_flows_layout on GROUPS -- while group r of every flow is on the wire the active flows are those with more than
-// r D frames, A_r of them, and a round takes one packet of each: member i' of the group starts at base_r + rank + i' A_r, its rows
-// are D A_r packets apart, base_r = n D (A_0 + ... + A_{r-1}).  The active list is compacted in place as r grows.
 int64_t ldpc_amd_fec_tx_flows_ilv_layout(int nflows, const int64_t *frame_begin, int n, const uint8_t *block0, int depth, int order, int64_t *first,
                                          int32_t *stride)
 {
-    if (!block0 || !LDPC_AMD_FEC_ILV_DEPTH_OK(depth)) return LDPC_AMD_EINVAL;
-    if (depth == 1) return ldpc_amd_fec_tx_flows_layout(nflows, frame_begin, n, order, first, stride);
-    if (nflows < 1 || nflows > LDPC_AMD_FEC_TX_MAX_FLOWS || !frame_begin || n < 1 || frame_begin[0] != 0) return LDPC_AMD_EINVAL;
-    if (order != LDPC_AMD_FEC_TX_SEGMENTED && order != LDPC_AMD_FEC_TX_ROUND_ROBIN) return LDPC_AMD_EINVAL;
-    for (int f = 0; f < nflows; f++)
-        if (frame_begin[f + 1] < frame_begin[f]) return LDPC_AMD_EINVAL;
-    const int64_t F = frame_begin[nflows];
-    if (F > (((int64_t)1 << 31) - 1) / n) return LDPC_AMD_EINVAL;   // F * n < 2^31
-    if (order == LDPC_AMD_FEC_TX_SEGMENTED) {
-        for (int f = 0; f < nflows; f++) {
-            const int64_t t0 = frame_begin[f], c = frame_begin[f + 1] - t0;
-            if (ldpc_amd_fec_tx_ilv_layout(c, n, block0[f], depth, first ? first + t0 : nullptr, stride ? stride + t0 : nullptr) != c * n)
-                return LDPC_AMD_EINVAL;
-            for (int64_t i = 0; first && i < c; i++) first[t0 + i] += t0 * n;
-        }
-        return F * n;
-    }
-    if (tx_flows_part_group(nflows, frame_begin, block0, depth) >= 0) return LDPC_AMD_EINVAL;
-    std::vector<int> active;
-    active.reserve((size_t)nflows);
-    for (int f = 0; f < nflows; f++)
-        if (frame_begin[f + 1] > frame_begin[f]) active.push_back(f);
-    int64_t base = 0;
-    for (int64_t r = 0; !active.empty(); r++) {
-        const int64_t A = (int64_t)active.size();
-        size_t keep = 0;
-        for (size_t rank = 0; rank < active.size(); rank++) {
-            const int f = active[rank];
-            const int64_t t = frame_begin[f] + r * depth;
-            for (int i = 0; i < depth; i++) {
-                if (first) first[t + i] = base + (int64_t)rank + i * A;
-                if (stride) stride[t + i] = (int32_t)(depth * A);
-            }
-            if (frame_begin[f + 1] - frame_begin[f] > (r + 1) * depth) active[keep++] = f;
-        }
-        active.resize(keep);
-        base += A * n * depth;
-    }
-    return F * n;
+    if (!block0) return LDPC_AMD_EINVAL;
+    return tx_flows_layout(nflows, frame_begin, n, block0, depth, order, first, stride);
 }
 
-// Fused where launch_encode_packets_flows has the descriptor form of the packet encoder for this call; else composed: encode a
-// chunk of frames into the context's codeword scratch, packetise it by the descriptors, next chunk.
-// The body of both multi-flow senders: depth 1 is the order of include/ldpc_erasure_amd_sender_flows.h, a depth above 1 that of
-// include/ldpc_erasure_amd_interleave_flows.h.  *path_out: 0 when nothing was sent (F == 0), else the path taken.
-static int tx_flows_send(ldpc_amd_ctx *ctx, const char *who, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
+// The body of both: depth 1 is the order of include/ldpc_erasure_amd_sender_flows.h.  packet_begin is written when something was sent.
+static int tx_flows_send(ldpc_amd_ctx *ctx, const char *who, TxKind kind, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
                          const uint8_t *fec_class, const uint8_t *block0, int order, int depth, uint8_t *packets, int32_t *flow_of,
-                         int64_t *packet_begin, int *path_out)
+                         int64_t *packet_begin)
 {
-    *path_out = 0;
-    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
-    const DevCode &cd = ctx->codes[code]->dev;
-    if (nflows < 1 || nflows > LDPC_AMD_FEC_TX_MAX_FLOWS)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows must be 1..%d (got %d)", who, LDPC_AMD_FEC_TX_MAX_FLOWS, nflows);
-    if (!frame_begin || !fec_class || !block0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: frame_begin / fec_class / block0 must not be null", who);
-    if (S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: bad S", who);
-    if (order != LDPC_AMD_FEC_TX_SEGMENTED && order != LDPC_AMD_FEC_TX_ROUND_ROBIN)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: unknown order %d", who, order);
-    if (frame_begin[0] != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: frame_begin must start at 0", who);
-    for (int f = 0; f < nflows; f++)
-        if (frame_begin[f + 1] < frame_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: frame_begin decreases at flow %d", who, f);
-    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: depth must be 1, 2, 4, 8 or 16 (got %d)", who, depth);
-    if (order == LDPC_AMD_FEC_TX_ROUND_ROBIN) {
-        const int f = tx_flows_part_group(nflows, frame_begin, block0, depth);
-        if (f >= 0)
-            return set_error(ctx, LDPC_AMD_EINVAL,
-                             "%s: round robin at depth %d needs whole aligned groups, block0 %% depth == 0 and frames %% depth == 0 for every flow "
-                             "(flow %d: block0=%d frames=%lld)",
-                             who, depth, f, (int)block0[f], (long long)(frame_begin[f + 1] - frame_begin[f]));
-    }
-    const int64_t F = frame_begin[nflows];
-    if (F > (((int64_t)1 << 31) - 1) / cd.n)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: %lld frames of %d packets are not below 2^31 packets", who, (long long)F, cd.n);
-    if (F == 0) return LDPC_AMD_OK;
-    if (cd.enc_nlevels == 0) return set_error(ctx, LDPC_AMD_EUNSUP, "code is not in triangle form: no systematic encoder");
-    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets) || (flow_of && !is_device_ptr(ctx, flow_of)))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: source / packets / flow_of must be device pointers of device %d", who, ctx->device);
-    if (((uintptr_t)flow_of & 3) != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be 4-byte aligned", who);
-    if (symbol_len_words(S) && ((uintptr_t)source & 3) != 0)
-        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
-    const int n = cd.n;
-    const int64_t P = F * n;
-    const size_t src_frame = (size_t)cd.k * S, pk_frame = (size_t)n * ((size_t)S + kHdr);
-    {
-        const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)F, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)F;
-        const uintptr_t q0 = (uintptr_t)flow_of, q1 = q0 + sizeof(int32_t) * (size_t)P;
-        if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: source and packets overlap", who);
-        if (flow_of && ((q0 < p1 && p0 < q1) || (q0 < s1 && s0 < q1)))
-            return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of overlaps source or packets", who);
-    }
-    // the table: [F] descriptors, the frames' flows behind them
-    const TxFrameDesc *dd = nullptr;
-    int path = 0;
-    auto fill = [&](TxFrameDesc *hd, int64_t *max_stride) -> int {
-        int32_t *hflow = (int32_t *)(hd + F);
-        std::vector<int64_t> first((size_t)F);
-        std::vector<int32_t> stride((size_t)F);
-        const int64_t got = ldpc_amd_fec_tx_flows_ilv_layout(nflows, frame_begin, n, block0, depth, order, first.data(), stride.data());
-        if (got != P) return set_error(ctx, LDPC_AMD_EINVAL, "%s: bad frame_begin", who);
-        for (int f = 0; f < nflows; f++)
-            for (int64_t t = frame_begin[f]; t < frame_begin[f + 1]; t++) {
-                hd[t].first = (uint64_t)first[(size_t)t];
-                hd[t].stride = (uint32_t)stride[(size_t)t];
-                hd[t].hdr = ((uint32_t)fec_class[f] << 8) | (((uint32_t)block0[f] + (uint32_t)(t - frame_begin[f])) & 0xffu);
-                hflow[t] = f;
-                *max_stride = std::max<int64_t>(*max_stride, stride[(size_t)t]);
-            }
-        return LDPC_AMD_OK;
-    };
-    int rc;
-    if ((rc = tx_send_described(ctx, who, cd, S, F, sizeof(int32_t), source, packets, fill, &dd, &path))) return rc;
-    const int32_t *dflow = (const int32_t *)(dd + F);
-    if (flow_of) {
-        hipLaunchKernelGGL(fec_tx_flow_of, dim3(grid_for(P)), dim3(kThreads), 0, ctx->stream, dd, dflow, P, n, flow_of);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-    }
-    if (packet_begin)
-        for (int f = 0; f <= nflows; f++) packet_begin[f] = frame_begin[f] * n;
-    *path_out = path;
-    return LDPC_AMD_OK;
+    if (!ctx) return LDPC_AMD_EINVAL;
+    const DevCode *cd = tx_code(ctx, code);
+    if (!cd) return LDPC_AMD_ENOCODE;
+    TxCall c(who, cd->n, cd->k, cd->enc_nlevels != 0, S, nflows, frame_begin, fec_class, block0, order, depth, source, packets, flow_of);
+    const int rc = tx_send_ldpc(ctx, *cd, c, kind);
+    if (rc == LDPC_AMD_OK && c.F > 0 && packet_begin)
+        for (int f = 0; f <= nflows; f++) packet_begin[f] = frame_begin[f] * cd->n;
+    return rc;
 }
 
 int ldpc_amd_fec_encode_packets_flows_dev(ldpc_amd_ctx *ctx, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
                                           const uint8_t *fec_class, const uint8_t *block0, int order, uint8_t *packets, int32_t *flow_of,
                                           int64_t *packet_begin)
 {
-    if (!ctx) return LDPC_AMD_EINVAL;
-    int path = 0;
-    const int rc = tx_flows_send(ctx, "fec_encode_packets_flows_dev", code, S, nflows, frame_begin, source, fec_class, block0, order, 1, packets, flow_of,
-                                 packet_begin, &path);
-    if (rc == LDPC_AMD_OK && path) {
-        ctx->txf_path = path;
-        ctx->txf_frames = frame_begin[nflows];
-    }
-    return rc;
+    return tx_flows_send(ctx, "fec_encode_packets_flows_dev", kTxFlows, code, S, nflows, frame_begin, source, fec_class, block0, order, 1, packets, flow_of,
+                         packet_begin);
 }
 
-int ldpc_amd_fec_sender_flows_info(ldpc_amd_ctx *ctx, int64_t info[4])
+int ldpc_amd_fec_encode_packets_flows_ilv_dev(ldpc_amd_ctx *ctx, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
+                                              const uint8_t *fec_class, const uint8_t *block0, int order, uint8_t *packets, int32_t *flow_of,
+                                              int64_t *packet_begin, int depth)
 {
-    if (!ctx) return LDPC_AMD_EINVAL;
-    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_sender_flows_info: info must not be null");
-    info[0] = ctx->txf_path;
-    info[1] = (int64_t)ctx->sender_cw.cap;
-    info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
-    info[3] = ctx->txf_frames;
-    return LDPC_AMD_OK;
+    return tx_flows_send(ctx, "fec_encode_packets_flows_ilv_dev", kTxFlowsIlv, code, S, nflows, frame_begin, source, fec_class, block0, order, depth,
+                         packets, flow_of, packet_begin);
 }
+
+int ldpc_amd_fec_sender_flows_info(ldpc_amd_ctx *ctx, int64_t info[4]) { return tx_info(ctx, "fec_sender_flows_info", kTxFlows, info); }
+int ldpc_amd_fec_sender_flows_ilv_info(ldpc_amd_ctx *ctx, int64_t info[4]) { return tx_info(ctx, "fec_sender_flows_ilv_info", kTxFlowsIlv, info); }
 
 // ---- the block-interleaved sender (include/ldpc_erasure_amd_interleave.h) ------------------------------------------------------
 // The order as arithmetic: walk the frames run by run.  A run is the frames s .. s+m-1 of one group of D block numbers; its member i
@@ -1017,161 +1045,37 @@ int64_t ldpc_amd_fec_tx_ilv_layout(int64_t nframes, int n, unsigned block0, int 
     return nframes * n;
 }
 
-// The single-flow sender's checks, then the multi-flow sender's machinery on the descriptors of the layout.
 int ldpc_amd_fec_encode_packets_ilv_dev(ldpc_amd_ctx *ctx, int code, int S, int64_t nframes, const uint8_t *source, unsigned fec_class,
                                         unsigned block0, int depth, uint8_t *packets)
 {
     if (!ctx) return LDPC_AMD_EINVAL;
-    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
-    const DevCode &cd = ctx->codes[code]->dev;
-    if (nframes < 0 || S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: bad nframes/S");
-    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth)) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: depth must be 1, 2, 4, 8 or 16 (got %d)", depth);
-    const int64_t F = nframes;
-    if (F > (((int64_t)1 << 31) - 1) / cd.n)
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: %lld frames of %d packets are not below 2^31 packets", (long long)F, cd.n);
-    if (F == 0) return LDPC_AMD_OK;
-    if (cd.enc_nlevels == 0) return set_error(ctx, LDPC_AMD_EUNSUP, "code is not in triangle form: no systematic encoder");
-    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: source / packets must be device pointers of device %d", ctx->device);
-    if (symbol_len_words(S) && ((uintptr_t)source & 3) != 0)
-        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
-    const int n = cd.n;
-    const size_t src_frame = (size_t)cd.k * S, pk_frame = (size_t)n * ((size_t)S + kHdr);
-    const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)F, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)F;
-    if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: source and packets overlap");
-    const TxFrameDesc *dd = nullptr;
-    int path = 0;
-    auto fill = [&](TxFrameDesc *hd, int64_t *max_stride) -> int {
-        std::vector<int64_t> first((size_t)F);
-        std::vector<int32_t> stride((size_t)F);
-        if (ldpc_amd_fec_tx_ilv_layout(F, n, block0, depth, first.data(), stride.data()) != F * n)
-            return set_error(ctx, LDPC_AMD_EINVAL, "fec_encode_packets_ilv_dev: bad layout arguments");
-        for (int64_t t = 0; t < F; t++) {
-            hd[t].first = (uint64_t)first[(size_t)t];
-            hd[t].stride = (uint32_t)stride[(size_t)t];
-            hd[t].hdr = ((fec_class & 0xffu) << 8) | (uint32_t)((block0 + (uint64_t)t) & 0xffu);
-            *max_stride = std::max<int64_t>(*max_stride, stride[(size_t)t]);
-        }
-        return LDPC_AMD_OK;
-    };
-    int rc;
-    if ((rc = tx_send_described(ctx, "fec_encode_packets_ilv_dev", cd, S, F, 0, source, packets, fill, &dd, &path))) return rc;
-    ctx->txi_path = path;
-    ctx->txi_frames = F;
-    return LDPC_AMD_OK;
+    const DevCode *cd = tx_code(ctx, code);
+    if (!cd) return LDPC_AMD_ENOCODE;
+    TxCall c("fec_encode_packets_ilv_dev", "frames", cd->n, cd->k, cd->enc_nlevels != 0, S, nframes, fec_class, block0, depth, source, packets);
+    return tx_send_ldpc(ctx, *cd, c, kTxIlv);
 }
 
-int ldpc_amd_fec_sender_ilv_info(ldpc_amd_ctx *ctx, int64_t info[4])
-{
-    if (!ctx) return LDPC_AMD_EINVAL;
-    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_sender_ilv_info: info must not be null");
-    info[0] = ctx->txi_path;
-    info[1] = (int64_t)ctx->sender_cw.cap;
-    info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
-    info[3] = ctx->txi_frames;
-    return LDPC_AMD_OK;
-}
+int ldpc_amd_fec_sender_ilv_info(ldpc_amd_ctx *ctx, int64_t info[4]) { return tx_info(ctx, "fec_sender_ilv_info", kTxIlv, info); }
 
 // ---- the Reed-Solomon sender (include/ldpc_erasure_amd_rs_wire.h) ------------------------------------------------------------------
-// The interleaved sender's checks, layout and descriptor staging for the blocks of an RS code; then the packet encoder of
-// rs_wire_dev.hip (path 1, fused) where launch_rs_encode_packets has it for this call, else the RS encoder into the context's codeword
-// scratch and the descriptor-driven packetisers, chunk by chunk (path 2, composed).
+// The interleaved sender for the blocks of an RS code: the packet encoder of rs_wire_dev.hip (path 1, fused) where
+// launch_rs_encode_packets has it for this call, else the RS encoder into the context's codeword scratch (path 2, composed).
 int ldpc_amd_fec_rs_encode_packets_dev(ldpc_amd_ctx *ctx, int rs, int S, int64_t nblocks, const uint8_t *source, unsigned fec_class,
                                        unsigned block0, int depth, uint8_t *packets)
 {
     if (!ctx) return LDPC_AMD_EINVAL;
     if (rs < 0 || rs >= (int)ctx->rs.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown RS handle %d", rs);
     const HostRs &r = *ctx->rs[rs];
-    if (nblocks < 0 || S < 1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: bad nblocks/S");
-    if (!LDPC_AMD_FEC_ILV_DEPTH_OK(depth)) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: depth must be 1, 2, 4, 8 or 16 (got %d)", depth);
-    const int64_t F = nblocks;
-    const int n = r.n;
-    if (F > (((int64_t)1 << 31) - 1) / n)
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: %lld blocks of %d packets are not below 2^31 packets", (long long)F, n);
-    if (F == 0) return LDPC_AMD_OK;
-    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be 1 or a multiple of 16 (got %d)");
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!source || !packets || !is_device_ptr(ctx, source) || !is_device_ptr(ctx, packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: source / packets must be device pointers of device %d", ctx->device);
-    if (symbol_len_words(S) && ((uintptr_t)source & 3) != 0)
-        return set_error(ctx, LDPC_AMD_EINVAL, "word-sized symbols (S = %d) need 4-byte aligned symbol arrays", S);
-    const size_t src_frame = (size_t)r.k * S, cw_frame = (size_t)n * S, pk_frame = (size_t)n * ((size_t)S + kHdr);
-    const uintptr_t s0 = (uintptr_t)source, s1 = s0 + src_frame * (size_t)F, p0 = (uintptr_t)packets, p1 = p0 + pk_frame * (size_t)F;
-    if (s0 < p1 && p0 < s1) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: source and packets overlap");
-    auto fill = [&](TxFrameDesc *hd, int64_t *max_stride) -> int {
-        std::vector<int64_t> first((size_t)F);
-        std::vector<int32_t> stride((size_t)F);
-        if (ldpc_amd_fec_tx_ilv_layout(F, n, block0, depth, first.data(), stride.data()) != F * n)
-            return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_encode_packets_dev: bad layout arguments");
-        for (int64_t t = 0; t < F; t++) {
-            hd[t].first = (uint64_t)first[(size_t)t];
-            hd[t].stride = (uint32_t)stride[(size_t)t];
-            hd[t].hdr = ((fec_class & 0xffu) << 8) | (uint32_t)((block0 + (uint64_t)t) & 0xffu);
-            *max_stride = std::max<int64_t>(*max_stride, stride[(size_t)t]);
-        }
-        return LDPC_AMD_OK;
-    };
-    int rc;
-    const TxFrameDesc *dd = nullptr;
-    int64_t max_stride = 1;
-    if ((rc = tx_stage_described(ctx, "fec_rs_encode_packets_dev", F, 0, fill, &dd, &max_stride))) return rc;
-    rc = launch_rs_encode_packets(ctx, r, S, F, source, dd, max_stride, packets);
-    if (rc != LDPC_AMD_OK && rc != kEncodeNotFused) return rc;
-    const int path = rc == LDPC_AMD_OK ? 1 : 2;
-    if (path == 2) {
-        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(F, (int64_t)(kSenderScratchMax / cw_frame)));
-        if ((rc = scratch_reserve(ctx, ctx->sender_cw, (size_t)chunk * cw_frame))) return rc;
-        uint8_t *cw = (uint8_t *)ctx->sender_cw.p;
-        for (int64_t f0 = 0; f0 < F; f0 += chunk) {
-            const int64_t cnt = std::min(chunk, F - f0);
-            if ((rc = launch_rs_encode(ctx, r, S, cnt, source + (size_t)f0 * src_frame, cw))) return rc;
-            if ((rc = tx_packetize_described(ctx, cw, cnt, n, S, dd + f0, packets))) return rc;
-        }
-    }
-    ctx->rsw_path = path;
-    ctx->rsw_blocks = F;
-    return LDPC_AMD_OK;
+    TxCall c("fec_rs_encode_packets_dev", "blocks", r.n, r.k, /* every RS code has a systematic encoder */ true, S, nblocks, fec_class, block0, depth, source,
+             packets);
+    const int rc = tx_check(ctx, c);
+    if (rc || nblocks == 0) return rc;
+    return tx_send_described(
+        ctx, c, kTxRs, [&](const TxFrameDesc *dd, int64_t max_stride) { return launch_rs_encode_packets(ctx, r, S, nblocks, source, dd, max_stride, packets); },
+        [&](int64_t cnt, const uint8_t *src, uint8_t *cw) { return launch_rs_encode(ctx, r, S, cnt, src, cw); });
 }
 
-int ldpc_amd_fec_rs_sender_info(ldpc_amd_ctx *ctx, int64_t info[4])
-{
-    if (!ctx) return LDPC_AMD_EINVAL;
-    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_rs_sender_info: info must not be null");
-    info[0] = ctx->rsw_path;
-    info[1] = (int64_t)ctx->sender_cw.cap;
-    info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
-    info[3] = ctx->rsw_blocks;
-    return LDPC_AMD_OK;
-}
-
-// ---- the multi-flow sender with a depth (include/ldpc_erasure_amd_interleave_flows.h): tx_flows_send above ------------------------
-int ldpc_amd_fec_encode_packets_flows_ilv_dev(ldpc_amd_ctx *ctx, int code, int S, int nflows, const int64_t *frame_begin, const uint8_t *source,
-                                              const uint8_t *fec_class, const uint8_t *block0, int order, uint8_t *packets, int32_t *flow_of,
-                                              int64_t *packet_begin, int depth)
-{
-    if (!ctx) return LDPC_AMD_EINVAL;
-    int path = 0;
-    const int rc = tx_flows_send(ctx, "fec_encode_packets_flows_ilv_dev", code, S, nflows, frame_begin, source, fec_class, block0, order, depth, packets,
-                                 flow_of, packet_begin, &path);
-    if (rc == LDPC_AMD_OK && path) {
-        ctx->txfi_path = path;
-        ctx->txfi_frames = frame_begin[nflows];
-    }
-    return rc;
-}
-
-int ldpc_amd_fec_sender_flows_ilv_info(ldpc_amd_ctx *ctx, int64_t info[4])
-{
-    if (!ctx) return LDPC_AMD_EINVAL;
-    if (!info) return set_error(ctx, LDPC_AMD_EINVAL, "fec_sender_flows_ilv_info: info must not be null");
-    info[0] = ctx->txfi_path;
-    info[1] = (int64_t)ctx->sender_cw.cap;
-    info[2] = (int64_t)(ctx->txf_desc.cap + ctx->txf_stage_cap[0] + ctx->txf_stage_cap[1]);
-    info[3] = ctx->txfi_frames;
-    return LDPC_AMD_OK;
-}
+int ldpc_amd_fec_rs_sender_info(ldpc_amd_ctx *ctx, int64_t info[4]) { return tx_info(ctx, "fec_rs_sender_info", kTxRs, info); }
 
 int ldpc_amd_fec_rx_dev_create(ldpc_amd_ctx *ctx, int n, int k, int S, ldpc_amd_fec_rx_dev **out)
 {
