@@ -1310,20 +1310,55 @@ class FecRx:
             pass
 
 
-class FecRxDevice:
+class _Closes:
+    """close() through the C destroy call of the object (prefix of its C names in self._pre), once; a context manager; closed when
+    collected."""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._pre + "destroy")(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _OnDevice:
+    """What the receivers of packets in GPU memory allocate alike: the device of their context, the result arrays of B frames."""
+
+    def _device(self):
+        import torch
+        return torch.device("cuda", self._ctx.device)
+
+    def _frames(self, B):
+        import torch
+        dev = self._device()
+        shape = (B, self.n) if self.S == 1 else (B, self.n, self.S)
+        i32 = [torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(4)]
+        return DecodedFrames(torch.empty(shape, dtype=torch.uint8, device=dev), i32[0], i32[1], i32[2],
+                             torch.empty((B, self.n), dtype=torch.uint8, device=dev), i32[3])
+
+
+class FecRxDevice(_OnDevice, _Closes):
     """FecRx for packets already in GPU memory (include/ldpc_erasure_amd_wire_dev.h): the same blocks, erasure flags,
     consumed and dropped counts, byte for byte.  Payload movement is asynchronous on the context's stream; the returned
     block numbers and counts are final when a call returns.  Close it before its Context."""
+    _pre = "ldpc_amd_fec_rx_dev_"
 
     def __init__(self, ctx, n, k, S):
         self._ctx, self._L = ctx, ctx._L
         h = C.c_void_p()
         ctx._check(self._L.ldpc_amd_fec_rx_dev_create(ctx._h, n, k, S, C.byref(h)), "fec_rx_dev_create")
         self._h, self.n, self.k, self.S = h, n, k, S
-
-    def _device(self):
-        import torch
-        return torch.device("cuda", self._ctx.device)
 
     def push_many(self, packets, max_blocks):
         """packets: torch uint8 [P][8+S] on the device.  Returns (blocks int32 [B], sym torch uint8 [B][n][S],
@@ -1347,14 +1382,6 @@ class FecRxDevice:
         blk = C.c_int(-1)
         rc = self._ctx._check(self._L.ldpc_amd_fec_rx_dev_flush(self._h, _ptr(sym), _ptr(er), C.byref(blk)), "fec_rx_dev_flush")
         return (blk.value, sym, er) if rc == 1 else None
-
-    def _frames(self, B):
-        import torch
-        dev = self._device()
-        shape = (B, self.n) if self.S == 1 else (B, self.n, self.S)
-        i32 = [torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(4)]
-        return DecodedFrames(torch.empty(shape, dtype=torch.uint8, device=dev), i32[0], i32[1], i32[2],
-                             torch.empty((B, self.n), dtype=torch.uint8, device=dev), i32[3])
 
     def decode_many(self, code, packets, max_blocks, max_sweeps=10, do_ml=1, out=None):
         """push_many + Context.decode_frames in one call (include/ldpc_erasure_amd_receiver.h): packets torch uint8 [P][8+S] on the
@@ -1391,25 +1418,8 @@ class FecRxDevice:
     def dropped(self):
         return int(self._L.ldpc_amd_fec_rx_dev_dropped(self._h))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.ldpc_amd_fec_rx_dev_destroy(self._h)
-            self._h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class _RxWindowState:
+class _RxWindowState(_Closes):
     """What the host and the device object of the windowed receiver report alike (prefix of the C names in self._pre)."""
 
     def _fn(self, name):
@@ -1446,23 +1456,6 @@ class _RxWindowState:
         if self._fn("get_rule")(self._h, C.byref(r)) != 0:
             raise LdpcAmdError("fec_rxw_get_rule: bad arguments")
         return (r.c_hi, r.later_hi, r.c_lo, r.later_lo)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._fn("destroy")(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class FecRxWindowHost(_RxWindowState):
@@ -1521,7 +1514,7 @@ class FecRxWindowHost(_RxWindowState):
         return blocks[:nb], sym[:nb], er[:nb]
 
 
-class FecRxWindow(_RxWindowState):
+class FecRxWindow(_RxWindowState, _OnDevice):
     """FecRxWindowHost for packets already in GPU memory: the same blocks, erasure flags, consumed, totals and state, byte for byte.
     Shaped on FecRxDevice: payload movement is asynchronous on the context's stream; the returned block numbers and counts are final
     when a call returns.  rule: the close rule as a 4-tuple (include/ldpc_erasure_amd_rx_rule.h), None: the default rule.  Close it
@@ -1539,18 +1532,6 @@ class FecRxWindow(_RxWindowState):
         else:
             ctx._check(self._L.ldpc_amd_fec_rxw_dev_create_depth(ctx._h, n, k, S, window, ahead_limit, depth, C.byref(h)), "fec_rxw_dev_create")
         self._h, self.n, self.k, self.S, self.window, self.ahead_limit = h, n, k, S, window, ahead_limit
-
-    def _device(self):
-        import torch
-        return torch.device("cuda", self._ctx.device)
-
-    def _frames(self, B):
-        import torch
-        dev = self._device()
-        shape = (B, self.n) if self.S == 1 else (B, self.n, self.S)
-        i32 = [torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(4)]
-        return DecodedFrames(torch.empty(shape, dtype=torch.uint8, device=dev), i32[0], i32[1], i32[2],
-                             torch.empty((B, self.n), dtype=torch.uint8, device=dev), i32[3])
 
     def push_many(self, packets, max_blocks):
         """packets: torch uint8 [P][8+S] on the device.  Returns (blocks int32 [B], sym torch uint8 [B][n][S],
@@ -1636,22 +1617,15 @@ class FecRxWindow(_RxWindowState):
         return blocks[:nb], msg[:nb], received[:nb], status[:nb]
 
 
-class FecRxFlows:
-    """nflows FecRxDevice in one object (include/ldpc_erasure_amd_flows.h): one packet array segmented by flow -- flow f owns the
-    packets flow_begin[f] .. flow_begin[f+1]-1 -- is planned for all flows at once and read back once, and every block that closed, of
-    every flow, is decoded in one launch.  Flow f behaves exactly like a FecRxDevice fed its segment with max_blocks =
-    max_blocks_per_flow.  The closed blocks come out dense in flow order: flow 0's in closing order, then flow 1's, ...; flow f's
-    start at closes[:f].sum().  push_mixed / decode_mixed take the packets in arrival order with a flow number each instead
-    (include/ldpc_erasure_amd_flows_mixed.h) and return the same; all four calls mix freely.  Close it before its Context."""
+class _RxFlows(_OnDevice, _Closes):
+    """What FecRxFlows and FecRxWindowFlows call alike (prefix of the C names in self._pre): the segmented and the mixed push and decode
+    calls, `unrouted`, close.  The docstrings are FecRxFlows'; FecRxWindowFlows gives its own where its text differs."""
 
-    def __init__(self, ctx, nflows, n, k, S):
-        self._ctx, self._L = ctx, ctx._L
-        h = C.c_void_p()
-        ctx._check(self._L.ldpc_amd_fec_rx_flows_create(ctx._h, nflows, n, k, S, C.byref(h)), "fec_rx_flows_create")
-        self._h, self.nflows, self.n, self.k, self.S = h, nflows, n, k, S
+    def _fn(self, name):
+        return getattr(self._L, self._pre + name)
 
-    _device = FecRxDevice._device
-    _frames = FecRxDevice._frames
+    def _what(self, name):
+        return self._pre[len("ldpc_amd_"):] + name
 
     def _segments(self, packets, flow_begin, max_blocks_per_flow):
         import torch
@@ -1669,9 +1643,8 @@ class FecRxFlows:
         fb, slots, blocks, closes, consumed, pp = self._segments(packets, flow_begin, max_blocks_per_flow)
         sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=packets.device)
         er = torch.empty((slots, self.n), dtype=torch.uint8, device=packets.device)
-        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_push_many(self._h, pp, fb.ctypes.data, _ptr(sym), _ptr(er), blocks.ctypes.data,
-                                                                     closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
-                             "fec_rx_flows_push_many")
+        T = self._ctx._check(self._fn("push_many")(self._h, pp, fb.ctypes.data, _ptr(sym), _ptr(er), blocks.ctypes.data, closes.ctypes.data,
+                                                   max_blocks_per_flow, consumed.ctypes.data), self._what("push_many"))
         return closes, blocks[:T], sym[:T], er[:T], consumed
 
     def decode_many(self, code, packets, flow_begin, max_blocks_per_flow, max_sweeps=10, do_ml=1):
@@ -1680,10 +1653,10 @@ class FecRxFlows:
         (Context.fec_receiver_info() says which path ran).  Keep `packets` alive until the context's stream has passed the call."""
         fb, slots, blocks, closes, consumed, pp = self._segments(packets, flow_begin, max_blocks_per_flow)
         fr = self._frames(slots)
-        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_decode_many(
+        T = self._ctx._check(self._fn("decode_many")(
             self._h, code, pp, fb.ctypes.data, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status),
             _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
-            "fec_rx_flows_decode_many")
+            self._what("decode_many"))
         return closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed
 
     def _mixed(self, packets, flow_of, max_blocks_per_flow, want_left):
@@ -1705,9 +1678,9 @@ class FecRxFlows:
         P, slots, blocks, closes, consumed, offered, pp, fp, left = self._mixed(packets, flow_of, max_blocks_per_flow, want_left)
         sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=packets.device)
         er = torch.empty((slots, self.n), dtype=torch.uint8, device=packets.device)
-        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_push_mixed(
+        T = self._ctx._check(self._fn("push_mixed")(
             self._h, pp, fp, P, _ptr(sym), _ptr(er), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data,
-            offered.ctypes.data, _ptr(left) if want_left else None), "fec_rx_flows_push_mixed")
+            offered.ctypes.data, _ptr(left) if want_left else None), self._what("push_mixed"))
         r = (closes, blocks[:T], sym[:T], er[:T], consumed, offered)
         return r + (left[:P],) if want_left else r
 
@@ -1716,17 +1689,33 @@ class FecRxFlows:
         when asked).  No payload byte is copied to sort the packets: only their indices are partitioned by flow."""
         P, slots, blocks, closes, consumed, offered, pp, fp, left = self._mixed(packets, flow_of, max_blocks_per_flow, want_left)
         fr = self._frames(slots)
-        T = self._ctx._check(self._L.ldpc_amd_fec_rx_flows_decode_mixed(
+        T = self._ctx._check(self._fn("decode_mixed")(
             self._h, code, pp, fp, P, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status),
             _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data,
-            offered.ctypes.data, _ptr(left) if want_left else None), "fec_rx_flows_decode_mixed")
+            offered.ctypes.data, _ptr(left) if want_left else None), self._what("decode_mixed"))
         r = (closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed, offered)
         return r + (left[:P],) if want_left else r
 
     @property
     def unrouted(self):
         """packets of no flow the mixed calls were given so far"""
-        return int(self._L.ldpc_amd_fec_rx_flows_unrouted(self._h))
+        return int(self._fn("unrouted")(self._h))
+
+
+class FecRxFlows(_RxFlows):
+    """nflows FecRxDevice in one object (include/ldpc_erasure_amd_flows.h): one packet array segmented by flow -- flow f owns the
+    packets flow_begin[f] .. flow_begin[f+1]-1 -- is planned for all flows at once and read back once, and every block that closed, of
+    every flow, is decoded in one launch.  Flow f behaves exactly like a FecRxDevice fed its segment with max_blocks =
+    max_blocks_per_flow.  The closed blocks come out dense in flow order: flow 0's in closing order, then flow 1's, ...; flow f's
+    start at closes[:f].sum().  push_mixed / decode_mixed take the packets in arrival order with a flow number each instead
+    (include/ldpc_erasure_amd_flows_mixed.h) and return the same; all four calls mix freely.  Close it before its Context."""
+    _pre = "ldpc_amd_fec_rx_flows_"
+
+    def __init__(self, ctx, nflows, n, k, S):
+        self._ctx, self._L = ctx, ctx._L
+        h = C.c_void_p()
+        ctx._check(self._L.ldpc_amd_fec_rx_flows_create(ctx._h, nflows, n, k, S, C.byref(h)), "fec_rx_flows_create")
+        self._h, self.nflows, self.n, self.k, self.S = h, nflows, n, k, S
 
     def flush(self, flow):
         """None, or (block number, sym torch [n][S], erased torch [n]) of the block the end of flow `flow`'s stream closes."""
@@ -1796,25 +1785,8 @@ class FecRxFlows:
         """int64 [nflows]: packets of each flow that went to no block so far"""
         return np.array([self._L.ldpc_amd_fec_rx_flows_dropped(self._h, f) for f in range(self.nflows)], dtype=np.int64)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.ldpc_amd_fec_rx_flows_destroy(self._h)
-            self._h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FecRxWindowFlows:
+class FecRxWindowFlows(_RxFlows):
     """nflows FecRxWindow in one object (include/ldpc_erasure_amd_rx_window_flows.h), shaped on FecRxFlows: one packet array segmented
     by flow -- flow f owns the packets flow_begin[f] .. flow_begin[f+1]-1 -- is planned for all flows at once (one wavefront per flow)
     and read back once, and every block that closed, of every flow, is decoded in one launch.  Flow f behaves exactly like a
@@ -1824,6 +1796,7 @@ class FecRxWindowFlows:
     rule for a wire interleaved to that depth, FecRxWindowHost(..., depth=depth) per flow (include/ldpc_erasure_amd_interleave_flows.h;
     needs 2 * depth <= window).  rule: the close rule of every flow as a 4-tuple (include/ldpc_erasure_amd_rx_rule.h), None: the
     default rule.  Close it before its Context."""
+    _pre = "ldpc_amd_fec_rxw_flows_"
 
     def __init__(self, ctx, nflows, n, k, S, window=4, ahead_limit=10, depth=1, rule=None):
         self._ctx, self._L = ctx, ctx._L
@@ -1837,11 +1810,6 @@ class FecRxWindowFlows:
             ctx._check(self._L.ldpc_amd_fec_rxw_flows_create_depth(ctx._h, nflows, n, k, S, window, ahead_limit, depth, C.byref(h)),
                        "fec_rxw_flows_create")
         self._h, self.nflows, self.n, self.k, self.S, self.window, self.ahead_limit = h, nflows, n, k, S, window, ahead_limit
-
-    _device = FecRxWindow._device
-    _frames = FecRxWindow._frames
-    _segments = FecRxFlows._segments
-    _mixed = FecRxFlows._mixed
 
     @property
     def depth(self):
@@ -1857,61 +1825,18 @@ class FecRxWindowFlows:
         self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_get_rule(self._h, C.byref(r)), "fec_rxw_flows_get_rule")
         return (r.c_hi, r.later_hi, r.c_lo, r.later_lo)
 
-    def push_many(self, packets, flow_begin, max_blocks_per_flow):
-        """packets: torch uint8 [P][8+S] on the device, flow_begin: nflows + 1 packet indices.  Returns (closes int32 [nflows],
-        blocks int32 [T], sym torch uint8 [T][n][S], erased torch uint8 [T][n], consumed int64 [nflows])."""
-        import torch
-        fb, slots, blocks, closes, consumed, pp = self._segments(packets, flow_begin, max_blocks_per_flow)
-        sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=packets.device)
-        er = torch.empty((slots, self.n), dtype=torch.uint8, device=packets.device)
-        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_push_many(self._h, pp, fb.ctypes.data, _ptr(sym), _ptr(er), blocks.ctypes.data,
-                                                                      closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
-                             "fec_rxw_flows_push_many")
-        return closes, blocks[:T], sym[:T], er[:T], consumed
-
     def decode_many(self, code, packets, flow_begin, max_blocks_per_flow, max_sweeps=10, do_ml=1):
         """push_many + Context.decode_frames of all flows in one call -> (closes int32 [nflows], blocks int32 [T], DecodedFrames of
         the T closed blocks, consumed int64 [nflows]).  Context.fec_rx_window_flows_info() says which form ran.  Keep `packets` alive
         until the context's stream has passed the call."""
-        fb, slots, blocks, closes, consumed, pp = self._segments(packets, flow_begin, max_blocks_per_flow)
-        fr = self._frames(slots)
-        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_decode_many(
-            self._h, code, pp, fb.ctypes.data, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status),
-            _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data),
-            "fec_rxw_flows_decode_many")
-        return closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed
+        return super().decode_many(code, packets, flow_begin, max_blocks_per_flow, max_sweeps, do_ml)
 
     def push_mixed(self, packets, flow_of, max_blocks_per_flow, want_left=False):
         """push_many for packets in arrival order (include/ldpc_erasure_amd_rx_window_flows_mixed.h): packets torch uint8 [P][8+S],
         flow_of torch int32 [P] on the device, flow_of[p] = the flow of packet p (outside 0 .. nflows-1: no flow, ignored and counted
         in `unrouted`).  Returns push_many's tuple for the per-flow segments, then offered int64 [nflows] (packets of each flow), then
         -- want_left -- left torch uint8 [P]: 1 for the packets behind their flow's consumed prefix, to be submitted again."""
-        import torch
-        P, slots, blocks, closes, consumed, offered, pp, fp, left = self._mixed(packets, flow_of, max_blocks_per_flow, want_left)
-        sym = torch.empty((slots, self.n, self.S), dtype=torch.uint8, device=packets.device)
-        er = torch.empty((slots, self.n), dtype=torch.uint8, device=packets.device)
-        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_push_mixed(
-            self._h, pp, fp, P, _ptr(sym), _ptr(er), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data,
-            offered.ctypes.data, _ptr(left) if want_left else None), "fec_rxw_flows_push_mixed")
-        r = (closes, blocks[:T], sym[:T], er[:T], consumed, offered)
-        return r + (left[:P],) if want_left else r
-
-    def decode_mixed(self, code, packets, flow_of, max_blocks_per_flow, max_sweeps=10, do_ml=1, want_left=False):
-        """decode_many for packets in arrival order with a flow number each (push_mixed): decode_many's tuple, then offered (and left
-        when asked).  No payload byte is copied to sort the packets: only their indices are partitioned by flow."""
-        P, slots, blocks, closes, consumed, offered, pp, fp, left = self._mixed(packets, flow_of, max_blocks_per_flow, want_left)
-        fr = self._frames(slots)
-        T = self._ctx._check(self._L.ldpc_amd_fec_rxw_flows_decode_mixed(
-            self._h, code, pp, fp, P, max_sweeps, do_ml, _ptr(fr.out), _ptr(fr.sweeps), _ptr(fr.residual), _ptr(fr.status),
-            _ptr(fr.erased_out), _ptr(fr.residual_src), blocks.ctypes.data, closes.ctypes.data, max_blocks_per_flow, consumed.ctypes.data,
-            offered.ctypes.data, _ptr(left) if want_left else None), "fec_rxw_flows_decode_mixed")
-        r = (closes, blocks[:T], DecodedFrames(*(t[:T] for t in fr)), consumed, offered)
-        return r + (left[:P],) if want_left else r
-
-    @property
-    def unrouted(self):
-        """packets of no flow the mixed calls were given so far"""
-        return int(self._L.ldpc_amd_fec_rxw_flows_unrouted(self._h))
+        return super().push_mixed(packets, flow_of, max_blocks_per_flow, want_left)
 
     def pending(self):
         """WindowFlowsPending(base int32 [nflows] (-1: the flow has not started), cnt int32 [nflows][window]: packets every open slot
@@ -1970,23 +1895,6 @@ class FecRxWindowFlows:
     def dropped(self, flow):
         """packets of flow `flow` that went to no block so far (-1: no such flow)"""
         return int(self._L.ldpc_amd_fec_rxw_flows_dropped(self._h, flow))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.ldpc_amd_fec_rxw_flows_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _FecTxCounter:

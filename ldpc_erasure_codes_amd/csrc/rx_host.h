@@ -5,6 +5,7 @@
 //   1. every workspace of a call is reserved (rx_decode_reserve) before anything moves, so a refusal leaves the receiver where it was;
 //   2. whatever rewrites the staging planes -- the staging update (e), a flush's plane reset -- is launched by the caller BEHIND
 //      rx_decode_slots: the fused decode reads the planes, the composed gather reads them chunk by chunk.
+// The call skeleton of the two multi-flow receivers, in front of and around that tail, is rx_flows_host.h.
 // Everything here has internal linkage: each unit that includes the header gets its own copy.
 // A windowed receiver defines LDPC_AMD_RX_HOST_WINDOWED before the include and gets the window's host mirror too (the scan's
 // result record, rx_window_scan_dev.h, names its words like wire_dev.hip's own record, so that unit cannot see both).
@@ -46,6 +47,19 @@ inline void rx_result_slots(DecodeArgs &d, const RxResults &o, const uint8_t *er
     d.status = o.status ? o.status + first : nullptr;
     d.erased_out = o.erased_out ? o.erased_out + (size_t)first * n : nullptr;
     d.residual_src = o.residual_src ? o.residual_src + first : nullptr;
+}
+
+// the pinned copy of a plan's result records, grown to res_bytes; Rx: any receiver object with res_host, res_host_cap
+template <class Rx>
+int rx_readback_grow(ldpc_amd_ctx *ctx, Rx *rx, size_t res_bytes)
+{
+    if (rx->res_host_cap >= res_bytes) return LDPC_AMD_OK;
+    if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every plan ends with a synchronisation
+    rx->res_host = nullptr;
+    rx->res_host_cap = 0;
+    LDPC_HIP_TRY(ctx, hipHostMalloc((void **)&rx->res_host, res_bytes, hipHostMallocDefault));
+    rx->res_host_cap = res_bytes;
+    return LDPC_AMD_OK;
 }
 
 // the decode calls' arguments, checked before anything is planned; Rx: any receiver object with n, k, S

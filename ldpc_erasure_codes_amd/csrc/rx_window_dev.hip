@@ -249,13 +249,7 @@ int rxw_plan(ldpc_amd_fec_rxw_dev *rx, const char *who, const uint8_t *packets, 
         (rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)max_blocks + (size_t)rx->W) * (size_t)n)) ||
         (rc = scratch_reserve(ctx, rx->res, res_bytes)))
         return rc;
-    if (rx->res_host_cap < res_bytes) {
-        if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every plan ends with a synchronisation
-        rx->res_host = nullptr;
-        rx->res_host_cap = 0;
-        LDPC_HIP_TRY(ctx, hipHostMalloc((void **)&rx->res_host, res_bytes, hipHostMallocDefault));
-        rx->res_host_cap = res_bytes;
-    }
+    if ((rc = rx_readback_grow(ctx, rx, res_bytes))) return rc;
     uint32_t *dense = (uint32_t *)rx->dense.p;
     int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
     if (plen % 4 == 0 && ((uintptr_t)packets & 3) == 0)

@@ -28,7 +28,9 @@
 //   (d), (e), the flush     unchanged;  rxwf_left marks the packets behind every flow's consumed prefix through order[]
 // Flush: planned from the host mirror alone, one int32 plane number per handed-out slot (wire_dev.hip's batch flush).
 // The host code every device receiver needs -- the argument check and the decode tail of the decode calls, the host mirror of a
-// flow's window, the upload of the flush's plane numbers -- is csrc/rx_host.h.
+// flow's window, the upload of the flush's plane numbers -- is csrc/rx_host.h.  The calls themselves -- checks, plan, push, decode,
+// commit, batch flush, create and destroy -- are csrc/rx_flows_host.h's, shared with wire_dev.hip's flows; this unit gives it the
+// kernels and the window's rules as WFlowsPolicy.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -43,8 +45,7 @@
 #include "../../include/ldpc_erasure_amd_rx_window_flows_mixed.h"
 #include "../../include/ldpc_erasure_amd_interleave_flows.h"
 #define LDPC_AMD_RX_HOST_WINDOWED
-#include "rx_host.h"   // and with it rx_window_scan_dev.h
-#include "flows_demux_dev.h"   // the partition of a mixed call, and kMaxFlows
+#include "rx_flows_host.h"   // the multi-flow call skeleton; with it rx_host.h, rx_window_scan_dev.h and flows_demux_dev.h (kMaxFlows)
 
 using namespace ldpc_amd;
 
@@ -362,264 +363,9 @@ namespace {
 
 typedef ldpc_amd_fec_rxw_flows Rx;
 
-// One call's PLAN for all flows: (a) + (b), ONE read-back, the slot bases.  Nothing of any flow's state changes before rxwf_commit.
-struct WFlowsPlan {
-    int T = 0;             // closed blocks of all flows
-    int64_t max_used = 0;  // the longest consumed prefix
-    size_t rec = 0;        // words of one flow's result record
-    // a mixed call (else null / 0): the partition, the flow bases as read back behind the scan records ([nflows + 1], the last one =
-    // the routed packets), the longest remainder behind a consumed prefix
-    const uint32_t *order = nullptr, *base = nullptr;
-    int64_t max_left = 0;
-};
-
 inline RxwMirror rxwf_mirror(Rx *rx, int f)
 {
     return RxwMirror{&rx->base[f], &rx->head[f], &rx->ahead[f], &rx->cnt[(size_t)f * rx->W], &rx->totals[(size_t)f * 5], rx->W};
-}
-
-int rxwf_check_limits(Rx *rx, const char *who, int64_t P, int max_blocks)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (P < 0 || P >= ((int64_t)1 << 31)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need fewer than 2^31 packets in all", who);
-    if (max_blocks < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need max_blocks_per_flow >= 1", who);
-    if ((int64_t)rx->nflows * max_blocks * rx->n >= ((int64_t)1 << 31) - 2)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows * max_blocks_per_flow * n must be below 2^31 - 2", who);
-    return LDPC_AMD_OK;
-}
-
-int rxwf_check_call(Rx *rx, const char *who, const int64_t *flow_begin, int max_blocks, int64_t &P)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (!flow_begin || flow_begin[0] != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin must not be null and must start at 0", who);
-    for (int f = 0; f < rx->nflows; f++)
-        if (flow_begin[f + 1] < flow_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin decreases at flow %d", who, f);
-    P = flow_begin[rx->nflows];
-    return rxwf_check_limits(rx, who, P, max_blocks);
-}
-
-// Where the packets of a call are: segmented by the caller (flow_begin, host) or interleaved with a flow number each (flow_of, device)
-struct WFlowsSrc {
-    bool mixed = false;
-    const int64_t *flow_begin = nullptr;
-    const int32_t *flow_of = nullptr;
-};
-
-// the mixed calls' own arguments, P > 0 (the device is set)
-int rxwf_check_mixed(Rx *rx, const char *who, const int32_t *flow_of, const uint8_t *left)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (!flow_of || !is_device_ptr(ctx, flow_of))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be a device pointer of device %d", who, ctx->device);
-    if ((uintptr_t)flow_of & 3) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be 4-byte aligned", who);
-    if (left && !is_device_ptr(ctx, left)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: left must be a device pointer of device %d", who, ctx->device);
-    return LDPC_AMD_OK;
-}
-
-void rxwf_nothing(const Rx *rx, int *closes, int64_t *consumed, int64_t *offered)
-{
-    if (closes) std::fill(closes, closes + rx->nflows, 0);
-    if (consumed) std::fill(consumed, consumed + rx->nflows, (int64_t)0);
-    if (offered) std::fill(offered, offered + rx->nflows, (int64_t)0);
-}
-
-int rxwf_plan(Rx *rx, const char *who, const uint8_t *packets, const WFlowsSrc &src, int64_t npackets, int max_blocks, WFlowsPlan &pl)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const int n = rx->n, nf = rx->nflows, W = rx->W;
-    const int64_t plen = (int64_t)rx->S + kHdr;
-    const int64_t *flow_begin = src.flow_begin;
-    const bool mixed = src.mixed;
-    pl.rec = (size_t)R_WORDS + (size_t)max_blocks;
-    const size_t res_bytes = sizeof(int32_t) * (pl.rec * (size_t)nf + (mixed ? (size_t)nf + 1 : 0));   // mixed: the flow bases behind the records
-    int rc;
-    if ((rc = scratch_reserve(ctx, rx->dense, sizeof(uint32_t) * (size_t)npackets)) ||
-        (rc = scratch_reserve(ctx, rx->dest, sizeof(int32_t) * (size_t)npackets)) || (rc = scratch_reserve(ctx, rx->res, res_bytes)))
-        return rc;
-    if (mixed && ((rc = scratch_reserve(ctx, rx->order, sizeof(uint32_t) * (size_t)npackets)) || (rc = demux_reserve(ctx, npackets, nf)))) return rc;
-    if (rx->res_host_cap < res_bytes) {
-        if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every plan ends with a synchronisation
-        rx->res_host = nullptr;
-        rx->res_host_cap = 0;
-        LDPC_HIP_TRY(ctx, hipHostMalloc((void **)&rx->res_host, res_bytes, hipHostMallocDefault));
-        rx->res_host_cap = res_bytes;
-    }
-    uint32_t *dense = (uint32_t *)rx->dense.p;
-    int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
-    for (int f = 0; f < nf; f++) {   // (the copy of the previous call's records is behind that call's synchronisation)
-        WFlowIn &in = rx->in_host[f];
-        in.begin = mixed ? 0 : flow_begin[f]; in.len = mixed ? 0 : flow_begin[f + 1] - flow_begin[f];
-        in.base = rx->base[f]; in.ahead = rx->ahead[f];
-        for (int j = 0; j < kMaxW; j++) in.cnt[j] = j < W ? rx->cnt[(size_t)f * W + j] : 0;
-    }
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->in_dev, rx->in_host, sizeof(WFlowIn) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-    // (a) + (b): the plan; a mixed call's on the partition, which also fills in every flow's segment (begin, len) on the device
-    const bool aligned4 = plen % 4 == 0 && ((uintptr_t)packets & 3) == 0;
-    if (mixed) {
-        uint32_t *base = (uint32_t *)res + pl.rec * (size_t)nf, *order = (uint32_t *)rx->order.p;
-        if ((rc = demux_launch(ctx, src.flow_of, npackets, nf, base, rx->in_dev, order))) return rc;
-        if (aligned4)
-            hipLaunchKernelGGL(rxwf_headers_idx<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, (const uint32_t *)order,
-                               (const uint32_t *)base + nf, (int)plen, dense);
-        else
-            hipLaunchKernelGGL(rxwf_headers_idx<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, (const uint32_t *)order,
-                               (const uint32_t *)base + nf, (int)plen, dense);
-        pl.order = order;
-        pl.base = (const uint32_t *)rx->res_host + pl.rec * (size_t)nf;
-    } else if (aligned4)
-        hipLaunchKernelGGL(rxwf_headers<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
-    else
-        hipLaunchKernelGGL(rxwf_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    RxwRule r{n, rx->kd, rx->km, W, rx->A};
-    if (rx->ruled) {
-        const RxwRuleV rv{n, rx->rule.c_hi, rx->rule.later_hi, rx->rule.c_lo, rx->rule.later_lo, W, rx->A};
-        if (rx->D > 1)
-            hipLaunchKernelGGL(rxw_scan_flows_grouped_ruled, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, rv,
-                               rx->D, max_blocks, dest, res);
-        else
-            hipLaunchKernelGGL(rxw_scan_flows_ruled, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, rv, max_blocks,
-                               dest, res);
-    } else if (rx->D > 1)
-        hipLaunchKernelGGL(rxw_scan_flows_grouped, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, r, rx->D,
-                           max_blocks, dest, res);
-    else
-        hipLaunchKernelGGL(rxw_scan_flows, dim3(nf), dim3(64), 0, ctx->stream, (const uint32_t *)dense, (const WFlowIn *)rx->in_dev, r, max_blocks, dest, res);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->res_host, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = check_device_error(ctx))) return rc;
-    int64_t base = 0;
-    for (int f = 0; f < nf; f++) {   // the tables of the kernels behind the plan (their copy of the previous call is behind this synchronisation)
-        const int32_t *h = rx->res_host + (size_t)f * pl.rec;
-        if (h[R_ERR])
-            return set_error(ctx, LDPC_AMD_EHIP, "%s: the plan scan of flow %d hit its iteration cap (internal error); every flow's state is unchanged",
-                             who, f);
-        const int64_t used = word64(h, R_CONSUMED_LO);
-        rx->tab_host[f] = WFlowTab{mixed ? (int64_t)pl.base[f] : flow_begin[f], used, (int)base, h[R_CLOSES], rx->head[f], 0};
-        base += h[R_CLOSES];
-        pl.max_used = std::max(pl.max_used, used);
-        if (mixed) pl.max_left = std::max(pl.max_left, (int64_t)(pl.base[f + 1] - pl.base[f]) - used);
-    }
-    pl.T = (int)base;   // <= nflows * max_blocks < 2^31
-    if ((rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)pl.T + (size_t)W * (size_t)nf) * (size_t)n)) ||
-        (rc = scratch_reserve(ctx, rx->slots, sizeof(int32_t) * (size_t)std::max(pl.T, 1))))
-        return rc;
-    return LDPC_AMD_OK;
-}
-
-// the flow table, the slot map and (c): the winners' table of the call, [(T + W nflows)][n]
-int rxwf_winners_launch(Rx *rx, const WFlowsPlan &pl)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const int nf = rx->nflows;
-    int32_t *win = (int32_t *)rx->win.p;
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->tab_dev, rx->tab_host, sizeof(WFlowTab) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-    if (pl.T > 0) {
-        hipLaunchKernelGGL(rxwf_flow_slots, dim3(nf), dim3(64), 0, ctx->stream, (const WFlowTab *)rx->tab_dev, (int32_t *)rx->slots.p);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-    }
-    LDPC_HIP_TRY(ctx, hipMemsetAsync(win, 0xff, sizeof(int32_t) * ((size_t)pl.T + (size_t)rx->W * (size_t)nf) * (size_t)rx->n, ctx->stream));   // -1: no packet
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pl.max_used + kThreads - 1) / kThreads, std::max(1, 32768 / nf)));
-    if (pl.order)   // a mixed call planned on positions: the table takes the packet indices
-        hipLaunchKernelGGL(rxwf_winners<true>, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p, (const int32_t *)rx->dest.p,
-                           (const WFlowTab *)rx->tab_dev, pl.order, rx->n, rx->W, pl.T, win);
-    else
-        hipLaunchKernelGGL(rxwf_winners<false>, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p, (const int32_t *)rx->dest.p,
-                           (const WFlowTab *)rx->tab_dev, (const uint32_t *)nullptr, rx->n, rx->W, pl.T, win);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    return LDPC_AMD_OK;
-}
-
-// a mixed call's `left` (may be null): zero, then 1 behind every flow's consumed prefix
-int rxwf_left_launch(Rx *rx, const WFlowsPlan &pl, int64_t npackets, uint8_t *left)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (!left) return LDPC_AMD_OK;
-    LDPC_HIP_TRY(ctx, hipMemsetAsync(left, 0, (size_t)npackets, ctx->stream));
-    if (pl.max_left <= 0) return LDPC_AMD_OK;
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pl.max_left + kThreads - 1) / kThreads, std::max(1, 32768 / rx->nflows)));
-    hipLaunchKernelGGL(rxwf_left, dim3(gx, rx->nflows), dim3(kThreads), 0, ctx->stream, (const WFlowTab *)rx->tab_dev, (const WFlowIn *)rx->in_dev,
-                       pl.order, left);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    return LDPC_AMD_OK;
-}
-
-// (d) for the closed slots first .. first + count - 1 (gather) or (e) for the W open blocks of every flow
-template <bool GATHER>
-int rxwf_move_launch(Rx *rx, const WFlowsPlan &pl, const uint8_t *packets, int first, int count, uint8_t *sym, uint8_t *er)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const int n = rx->n, S = rx->S;
-    if (GATHER && count <= 0) return LDPC_AMD_OK;
-    WFlowMoveArgs a{};
-    a.packets = packets; a.plen = (int64_t)S + kHdr; a.win = (const int32_t *)rx->win.p; a.tab = rx->tab_dev;
-    a.slot_flow = (const int32_t *)rx->slots.p; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
-    a.sym_out = sym; a.er_out = er; a.n = n; a.S = S; a.W = rx->W; a.T = pl.T; a.nflows = rx->nflows; a.first = first; a.count = count;
-    const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0 && ((uintptr_t)sym & 15) == 0;
-    const int64_t items = (GATHER ? (int64_t)count : (int64_t)rx->W * rx->nflows) * n * (v16 ? S / 16 : S);
-    if (v16) hipLaunchKernelGGL((rxwf_move<GATHER, true>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((rxwf_move<GATHER, false>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    return LDPC_AMD_OK;
-}
-
-// every flow's mirror (base, head, ahead, cnt, totals) and the host outputs: the last step of a call
-// (a mixed call: offered and the unrouted count too)
-void rxwf_commit(Rx *rx, const WFlowsPlan &pl, int *blocks, int *closes, int64_t *consumed, int64_t npackets, int64_t *offered)
-{
-    if (pl.base) {
-        rx->unrouted += npackets - (int64_t)pl.base[rx->nflows];
-        for (int f = 0; offered && f < rx->nflows; f++) offered[f] = (int64_t)(pl.base[f + 1] - pl.base[f]);
-    }
-    for (int f = 0; f < rx->nflows; f++) {
-        const int32_t *h = rx->res_host + (size_t)f * pl.rec;
-        const WFlowTab &t = rx->tab_host[f];
-        rxw_mirror_commit(rxwf_mirror(rx, f), h, t.closes);
-        if (blocks) memcpy(blocks + t.base, h + R_WORDS, sizeof(int) * (size_t)t.closes);
-        if (closes) closes[f] = t.closes;
-        if (consumed) consumed[f] = t.used;
-    }
-}
-
-// ---- the flush's plan: the host's, from the mirror (ldpc_amd_fec_rxw_dev_flush per listed flow) -------------------------------------
-struct WFlushPlan {
-    std::vector<int> sel;          // the listed flows, in list order
-    std::vector<int> closes;       // blocks handed out per list entry
-    std::vector<int> blocks;       // [T] their wire numbers, in slot order
-    std::vector<int32_t> planes;   // [T] their staging planes, f W + b
-    int T = 0;
-};
-
-int rxwf_flush_plan(const Rx *rx, const char *who, const int32_t *flows, int nsel, WFlushPlan &pl)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (flows) {
-        if (nsel < 0 || nsel > rx->nflows) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need 0 <= nsel <= nflows = %d (got %d)", who, rx->nflows, nsel);
-        std::vector<uint8_t> seen((size_t)rx->nflows, 0);
-        for (int j = 0; j < nsel; j++) {
-            const int f = flows[j];
-            if (f < 0 || f >= rx->nflows) return set_error(ctx, LDPC_AMD_EINVAL, "%s: no flow %d (nflows = %d)", who, f, rx->nflows);
-            if (seen[(size_t)f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow %d is given twice", who, f);
-            seen[(size_t)f] = 1;
-        }
-    } else {
-        nsel = rx->nflows;
-    }
-    pl.sel.resize((size_t)nsel);
-    pl.closes.resize((size_t)nsel);
-    for (int j = 0; j < nsel; j++) {
-        const int f = flows ? flows[j] : j;
-        const int count = rxw_mirror_flush_count(&rx->cnt[(size_t)f * rx->W], rx->W);
-        pl.sel[(size_t)j] = f;
-        pl.closes[(size_t)j] = count;
-        for (int c = 0; c < count; c++) {
-            pl.blocks.push_back((rx->base[f] + c) & 0xff);
-            pl.planes.push_back(f * rx->W + (rx->head[f] + c) % rx->W);
-        }
-    }
-    pl.T = (int)pl.planes.size();   // <= W nflows
-    return LDPC_AMD_OK;
 }
 
 // COPY: slots first .. first + count - 1 -> sym / er, their planes reset in the same launch; else: the planes of those slots reset
@@ -637,16 +383,128 @@ int rxwf_flush_launch(Rx *rx, int first, int count, uint8_t *sym, uint8_t *er)
     return LDPC_AMD_OK;
 }
 
-// the mirror of every listed flow after its flush -- each handed-out block a close -- and the host outputs
-void rxwf_flush_commit(Rx *rx, const WFlushPlan &pl, int *blocks, int *closes)
-{
-    for (size_t j = 0; j < pl.sel.size(); j++) {
-        if (closes) closes[j] = pl.closes[j];
-        if (pl.closes[j] > 0) rxw_mirror_flush(rxwf_mirror(rx, pl.sel[j]), pl.closes[j], nullptr);
+// What the windowed receiver puts into the multi-flow call skeleton (rx_flows_host.h)
+struct WFlowsPolicy {
+    typedef ldpc_amd_fec_rxw_flows Rx;
+    static int planes_per_flow(const Rx *rx) { return rx->W; }
+    static void fill_in(Rx *rx, int f, int64_t begin, int64_t len)
+    {
+        WFlowIn &in = rx->in_host[f];
+        in.begin = begin; in.len = len;
+        in.base = rx->base[f]; in.ahead = rx->ahead[f];
+        for (int j = 0; j < kMaxW; j++) in.cnt[j] = j < rx->W ? rx->cnt[(size_t)f * rx->W + j] : 0;
     }
-    if (blocks && pl.T > 0) memcpy(blocks, pl.blocks.data(), sizeof(int) * (size_t)pl.T);
-}
-
+    static int launch_headers(Rx *rx, bool aligned4, const uint8_t *packets, const int32_t *flow_of, uint32_t *base, uint32_t *order, int64_t np,
+                              int plen, uint32_t *dense)
+    {
+        hipStream_t st = rx->ctx->stream;
+        const int nf = rx->nflows;
+        int rc;
+        if (order && (rc = demux_launch(rx->ctx, flow_of, np, nf, base, rx->in_dev, order))) return rc;
+        const uint32_t *ord = order, *routed = order ? base + nf : nullptr;   // the routed count, as the partition's bases kernel wrote it
+        if (order && aligned4) hipLaunchKernelGGL(rxwf_headers_idx<true>, dim3(grid_for(np)), dim3(kThreads), 0, st, packets, ord, routed, plen, dense);
+        else if (order) hipLaunchKernelGGL(rxwf_headers_idx<false>, dim3(grid_for(np)), dim3(kThreads), 0, st, packets, ord, routed, plen, dense);
+        else if (aligned4) hipLaunchKernelGGL(rxwf_headers<true>, dim3(grid_for(np)), dim3(kThreads), 0, st, packets, np, plen, dense);
+        else hipLaunchKernelGGL(rxwf_headers<false>, dim3(grid_for(np)), dim3(kThreads), 0, st, packets, np, plen, dense);
+        return LDPC_AMD_OK;
+    }
+    // the only step that looks at the depth and at the rule
+    static void launch_scan(Rx *rx, const uint32_t *dense, int max_blocks, int32_t *dest, int32_t *res)
+    {
+        hipStream_t st = rx->ctx->stream;
+        const int nf = rx->nflows, n = rx->n, W = rx->W;
+        const WFlowIn *in = rx->in_dev;
+        RxwRule r{n, rx->kd, rx->km, W, rx->A};
+        if (rx->ruled) {
+            const RxwRuleV rv{n, rx->rule.c_hi, rx->rule.later_hi, rx->rule.c_lo, rx->rule.later_lo, W, rx->A};
+            if (rx->D > 1) hipLaunchKernelGGL(rxw_scan_flows_grouped_ruled, dim3(nf), dim3(64), 0, st, dense, in, rv, rx->D, max_blocks, dest, res);
+            else hipLaunchKernelGGL(rxw_scan_flows_ruled, dim3(nf), dim3(64), 0, st, dense, in, rv, max_blocks, dest, res);
+        } else if (rx->D > 1)
+            hipLaunchKernelGGL(rxw_scan_flows_grouped, dim3(nf), dim3(64), 0, st, dense, in, r, rx->D, max_blocks, dest, res);
+        else
+            hipLaunchKernelGGL(rxw_scan_flows, dim3(nf), dim3(64), 0, st, dense, in, r, max_blocks, dest, res);
+    }
+    static size_t rec_words(int max_blocks) { return (size_t)R_WORDS + (size_t)max_blocks; }
+    static bool err(const int32_t *h) { return h[R_ERR] != 0; }
+    static int closes(const int32_t *h) { return h[R_CLOSES]; }
+    static int64_t consumed(const int32_t *h) { return word64(h, R_CONSUMED_LO); }
+    static WFlowTab tab_entry(const Rx *rx, int f, int64_t begin, int64_t used, int base, int closes)
+    {
+        return WFlowTab{begin, used, base, closes, rx->head[f], 0};
+    }
+    static void launch_slots(Rx *rx)
+    {
+        hipLaunchKernelGGL(rxwf_flow_slots, dim3(rx->nflows), dim3(64), 0, rx->ctx->stream, (const WFlowTab *)rx->tab_dev, (int32_t *)rx->slots.p);
+    }
+    // a mixed call planned on positions: the table takes the packet indices
+    static int launch_winners(Rx *rx, const RxFlowsPlan &pl, unsigned gx, int32_t *win)
+    {
+        ldpc_amd_ctx *ctx = rx->ctx;
+        if (pl.order)
+            hipLaunchKernelGGL(rxwf_winners<true>, dim3(gx, rx->nflows), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p,
+                               (const int32_t *)rx->dest.p, (const WFlowTab *)rx->tab_dev, pl.order, rx->n, rx->W, pl.T, win);
+        else
+            hipLaunchKernelGGL(rxwf_winners<false>, dim3(gx, rx->nflows), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p,
+                               (const int32_t *)rx->dest.p, (const WFlowTab *)rx->tab_dev, (const uint32_t *)nullptr, rx->n, rx->W, pl.T, win);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        return LDPC_AMD_OK;
+    }
+    static void launch_left(Rx *rx, const RxFlowsPlan &pl, unsigned gx, uint8_t *left)
+    {
+        hipLaunchKernelGGL(rxwf_left, dim3(gx, rx->nflows), dim3(kThreads), 0, rx->ctx->stream, (const WFlowTab *)rx->tab_dev,
+                           (const WFlowIn *)rx->in_dev, pl.order, left);
+    }
+    static void launch_move(Rx *rx, const RxFlowsPlan &pl, const uint8_t *packets, bool gather, int first, int count, uint8_t *sym, uint8_t *er,
+                            bool v16, int64_t items)
+    {
+        WFlowMoveArgs a{};
+        a.packets = packets; a.plen = (int64_t)rx->S + kHdr; a.win = (const int32_t *)rx->win.p; a.tab = rx->tab_dev;
+        a.slot_flow = (const int32_t *)rx->slots.p; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
+        a.sym_out = sym; a.er_out = er; a.n = rx->n; a.S = rx->S; a.W = rx->W; a.T = pl.T; a.nflows = rx->nflows; a.first = first; a.count = count;
+        const dim3 grid(grid_for(items)), block(kThreads);
+        hipStream_t st = rx->ctx->stream;
+        if (gather && v16) hipLaunchKernelGGL((rxwf_move<true, true>), grid, block, 0, st, a);
+        else if (gather) hipLaunchKernelGGL((rxwf_move<true, false>), grid, block, 0, st, a);
+        else if (v16) hipLaunchKernelGGL((rxwf_move<false, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((rxwf_move<false, false>), grid, block, 0, st, a);
+    }
+    static void launch_sources(Rx *rx, int T, uint32_t *src, uint8_t *er)
+    {
+        hipLaunchKernelGGL(rxwf_sources, dim3(grid_for((int64_t)T * rx->n)), dim3(kThreads), 0, rx->ctx->stream, (const int32_t *)rx->win.p,
+                           (const uint8_t *)rx->stage_er, (const WFlowTab *)rx->tab_dev, (const int32_t *)rx->slots.p, rx->n, rx->W, T, src, er);
+    }
+    static void commit_flow(Rx *rx, int f, const int32_t *h, int closes) { rxw_mirror_commit(rxwf_mirror(rx, f), h, closes); }
+    static void record_info(ldpc_amd_ctx *ctx, bool fused, int T, int launches, size_t scratch)
+    {
+        ctx->rxwf_info[0] = fused ? 1 : 2; ctx->rxwf_info[1] = T; ctx->rxwf_info[2] = launches; ctx->rxwf_info[3] = (int64_t)scratch;
+    }
+    // ---- the flush (ldpc_amd_fec_rxw_dev_flush per listed flow): every open slot up to the last non-empty one ----
+    static int flush_fill(const Rx *rx, int f, int, RxFlushPlan &pl)
+    {
+        const int count = rxw_mirror_flush_count(&rx->cnt[(size_t)f * rx->W], rx->W);
+        for (int c = 0; c < count; c++) {
+            pl.blocks.push_back((rx->base[f] + c) & 0xff);
+            pl.planes.push_back(f * rx->W + (rx->head[f] + c) % rx->W);
+        }
+        return count;
+    }
+    // (a chunk's planes are reset by the launch that copies them; the fused decode reads them, so their reset stands behind it)
+    static int flush_gather(Rx *rx, int first, int count, uint8_t *sym, uint8_t *er) { return rxwf_flush_launch<true>(rx, first, count, sym, er); }
+    static int flush_after(Rx *rx, bool fused, int T) { return fused ? rxwf_flush_launch<false>(rx, 0, T, nullptr, nullptr) : LDPC_AMD_OK; }
+    static void launch_flush_sources(Rx *rx, int T, uint32_t *src, uint8_t *er)
+    {
+        hipLaunchKernelGGL(rxwf_flush_sources, dim3(grid_for((int64_t)T * rx->n)), dim3(kThreads), 0, rx->ctx->stream, (const int32_t *)rx->fl.dev,
+                           (const uint8_t *)rx->stage_er, rx->n, T, src, er);
+    }
+    static void flush_commit_flow(Rx *rx, int f, int count)   // each handed-out block a close
+    {
+        if (count > 0) rxw_mirror_flush(rxwf_mirror(rx, f), count, nullptr);
+    }
+    static void record_flush(ldpc_amd_ctx *ctx, int path, int T, int, int launches, size_t scratch)   // (flush_many writes no info word)
+    {
+        if (path != 3) record_info(ctx, path == 1, T, launches, scratch);
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -699,44 +557,10 @@ int ldpc_amd_fec_rxw_flows_create_rule(ldpc_amd_ctx *ctx, int nflows, int n, int
     rx->base.assign((size_t)nflows, -1); rx->head.assign((size_t)nflows, 0); rx->ahead.assign((size_t)nflows, 0);
     rx->cnt.assign((size_t)nflows * window, 0);
     rx->totals.assign((size_t)nflows * 5, 0);
-    const size_t planes = (size_t)nflows * window, plane = (size_t)n * S;
-    // (a request beyond the device's memory is not always answered with hipErrorOutOfMemory: a staging plane that cannot be had is ENOMEM)
-    hipError_t e = hipMalloc((void **)&rx->stage_sym, planes * plane);
-    if (e == hipSuccess) e = hipMalloc((void **)&rx->stage_er, planes * (size_t)n);
-    const bool no_planes = e != hipSuccess;
-    if (e == hipSuccess) e = hipMalloc((void **)&rx->in_dev, sizeof(WFlowIn) * (size_t)nflows);
-    if (e == hipSuccess) e = hipMalloc((void **)&rx->tab_dev, sizeof(WFlowTab) * (size_t)nflows);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&rx->in_host, sizeof(WFlowIn) * (size_t)nflows, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&rx->tab_host, sizeof(WFlowTab) * (size_t)nflows, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_sym, 0, planes * plane, ctx->stream);   // payload zero, every symbol erased
-    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_er, 1, planes * (size_t)n, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        ldpc_amd_fec_rxw_flows_destroy(rx);
-        return set_error(ctx, no_planes || e == hipErrorOutOfMemory ? LDPC_AMD_ENOMEM : LDPC_AMD_EHIP, "fec_rxw_flows_create: %s%s",
-                         no_planes ? "the staging planes do not fit: " : "", hipGetErrorString(e));
-    }
-    *out = rx;
-    return LDPC_AMD_OK;
+    return rxf_create_buffers<WFlowsPolicy>(ctx, rx, "fec_rxw_flows_create", out);
 }
 
-void ldpc_amd_fec_rxw_flows_destroy(ldpc_amd_fec_rxw_flows *rx)
-{
-    if (!rx) return;
-    (void)hipSetDevice(rx->ctx->device);
-    (void)hipStreamSynchronize(rx->ctx->stream);   // pending work of this object may still use its buffers
-    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots, &rx->order};
-    for (Scratch *s : sc)
-        if (s->p) (void)hipFree(s->p);
-    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    void *host[] = {rx->in_host, rx->tab_host, rx->res_host};
-    for (void *p : host)
-        if (p) (void)hipHostFree(p);
-    rx_upload_free(rx->fl);
-    delete rx;
-}
+void ldpc_amd_fec_rxw_flows_destroy(ldpc_amd_fec_rxw_flows *rx) { rxf_destroy(rx); }
 
 int ldpc_amd_fec_rxw_flows_stats(const ldpc_amd_fec_rxw_flows *rx, int flow, int64_t totals[5])
 {
@@ -773,127 +597,30 @@ int ldpc_amd_fec_rxw_flows_pending(const ldpc_amd_fec_rxw_flows *rx, int32_t *ba
     return total;
 }
 
-}  // extern "C"
-
-namespace {
-
-// push_many and push_mixed: P is the segmented call's flow_begin[nflows], or the mixed call's argument
-int rxwf_push(Rx *rx, const char *who, const uint8_t *packets, const WFlowsSrc &src, int64_t P, uint8_t *sym_batch, uint8_t *erased_batch,
-              int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed, int64_t *offered, uint8_t *left)
-{
-    if (!rx) return LDPC_AMD_EINVAL;
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const bool mixed = src.mixed;
-    int rc;
-    if ((rc = mixed ? rxwf_check_limits(rx, who, P, max_blocks_per_flow) : rxwf_check_call(rx, who, src.flow_begin, max_blocks_per_flow, P)))
-        return rc;
-    if (!sym_batch || !erased_batch || (P > 0 && !packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must not be null", who);
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((P > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must be device pointers of device %d", who, ctx->device);
-    if (P == 0) {
-        rxwf_nothing(rx, closes, consumed, offered);
-        return 0;
-    }
-    if (mixed && (rc = rxwf_check_mixed(rx, who, src.flow_of, left))) return rc;
-    WFlowsPlan pl;
-    if ((rc = rxwf_plan(rx, who, packets, src, P, max_blocks_per_flow, pl))) return rc;
-    // (c), (d), (e): the data movement, asynchronous
-    if ((rc = rxwf_winners_launch(rx, pl)) || (rc = rxwf_move_launch<true>(rx, pl, packets, 0, pl.T, sym_batch, erased_batch)) ||
-        (rc = rxwf_move_launch<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)) || (rc = rxwf_left_launch(rx, pl, P, left)))
-        return rc;
-    rxwf_commit(rx, pl, blocks, closes, consumed, P, offered);
-    return pl.T;
-}
-
-// push_many + decode_frames in one call (rx_host.h: the decode driver).  FUSED where the decoder can fetch its rows from the packets
-// itself (decode_reads_packets): (d) shrinks to rxwf_sources, the planes of all flows being one `stage` base.  Else COMPOSED: (d)
-// gathers chunk by chunk.  (e) is launched BEHIND the decode in both forms: it overwrites the staging planes of the carried blocks,
-// which the fused decode reads.
-int rxwf_decode(Rx *rx, const char *who, int code, const uint8_t *packets, const WFlowsSrc &src, int64_t P, int max_sweeps, int do_ml, uint8_t *out,
-                int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src, int *blocks, int *closes,
-                int max_blocks_per_flow, int64_t *consumed, int64_t *offered, uint8_t *left)
-{
-    if (!rx) return LDPC_AMD_EINVAL;
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
-    const bool mixed = src.mixed;
-    int rc;
-    if ((rc = mixed ? rxwf_check_limits(rx, who, P, max_blocks_per_flow) : rxwf_check_call(rx, who, src.flow_begin, max_blocks_per_flow, P)))
-        return rc;
-    if (P == 0) {
-        rxwf_nothing(rx, closes, consumed, offered);
-        return 0;
-    }
-    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
-    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, o))) return rc;
-    if (!packets || !is_device_ptr(ctx, packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets must be a device pointer of device %d", who, ctx->device);
-    if (mixed && (rc = rxwf_check_mixed(rx, who, src.flow_of, left))) return rc;
-    const DevCode &cd = ctx->codes[code]->dev;
-    const int n = rx->n, S = rx->S;
-    const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
-    const size_t frame = (size_t)n * S;
-
-    WFlowsPlan pl;
-    if ((rc = rxwf_plan(rx, who, packets, src, P, max_blocks_per_flow, pl))) return rc;
-    const int T = pl.T;
-    const int64_t chunk = rx_chunk(T, frame);
-    size_t scratch = 0;
-    if ((rc = rx_decode_reserve(ctx, T, n, frame, fused, chunk, &scratch))) return rc;
-    if ((rc = rxwf_winners_launch(rx, pl))) return rc;
-    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
-    const PacketRows pin{nullptr, packets, rx->stage_sym, S + kHdr};
-    auto sources = [&](uint32_t *src, uint8_t *er) -> int {
-        hipLaunchKernelGGL(rxwf_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
-                           (const uint8_t *)rx->stage_er, (const WFlowTab *)rx->tab_dev, (const int32_t *)rx->slots.p, n, rx->W, T, src, er);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-        return LDPC_AMD_OK;
-    };
-    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return rxwf_move_launch<true>(rx, pl, packets, first, count, sym, er); };
-    int launches = 0;
-    if ((rc = rx_decode_slots(ctx, d, o, T, chunk, fused, pin, sources, gather, &launches))) return rc;
-    if ((rc = rxwf_move_launch<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
-    if ((rc = rxwf_left_launch(rx, pl, P, left))) return rc;
-    rxwf_commit(rx, pl, blocks, closes, consumed, P, offered);
-    ctx->rxwf_info[0] = fused ? 1 : 2; ctx->rxwf_info[1] = T; ctx->rxwf_info[2] = launches; ctx->rxwf_info[3] = (int64_t)scratch;
-    return T;
-}
-
-}  // namespace
-
-extern "C" {
-
+// ---- the calls: each fills in where its packets are and runs the skeleton (rx_flows_host.h) under its own name ----------------------
 int ldpc_amd_fec_rxw_flows_push_many(ldpc_amd_fec_rxw_flows *rx, const uint8_t *packets, const int64_t *flow_begin, uint8_t *sym_batch,
                                      uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
 {
-    WFlowsSrc src;
-    src.flow_begin = flow_begin;
-    return rxwf_push(rx, "fec_rxw_flows_push_many", packets, src, 0, sym_batch, erased_batch, blocks, closes, max_blocks_per_flow, consumed, nullptr,
-                     nullptr);
+    return rxf_push<WFlowsPolicy>(rx, "fec_rxw_flows_push_many", packets, RxFlowsSrc{false, flow_begin, nullptr}, 0, sym_batch, erased_batch,
+                                  max_blocks_per_flow, RxFlowsOut{blocks, closes, consumed, nullptr, nullptr});
 }
 
 int ldpc_amd_fec_rxw_flows_decode_many(ldpc_amd_fec_rxw_flows *rx, int code, const uint8_t *packets, const int64_t *flow_begin, int max_sweeps,
                                        int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
                                        int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
 {
-    WFlowsSrc src;
-    src.flow_begin = flow_begin;
-    return rxwf_decode(rx, "fec_rxw_flows_decode_many", code, packets, src, 0, max_sweeps, do_ml, out, sweeps, residual, status, erased_out,
-                       residual_src, blocks, closes, max_blocks_per_flow, consumed, nullptr, nullptr);
+    return rxf_decode<WFlowsPolicy>(rx, "fec_rxw_flows_decode_many", code, packets, RxFlowsSrc{false, flow_begin, nullptr}, 0, max_sweeps, do_ml,
+                                    RxResults{out, sweeps, residual, status, erased_out, residual_src}, max_blocks_per_flow,
+                                    RxFlowsOut{blocks, closes, consumed, nullptr, nullptr});
 }
 
-// ---- interleaved packets (include/ldpc_erasure_amd_rx_window_flows_mixed.h) ---------------------------------------------------------
+// interleaved packets (include/ldpc_erasure_amd_rx_window_flows_mixed.h)
 int ldpc_amd_fec_rxw_flows_push_mixed(ldpc_amd_fec_rxw_flows *rx, const uint8_t *packets, const int32_t *flow_of, int64_t P, uint8_t *sym_batch,
                                       uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed,
                                       int64_t *offered, uint8_t *left)
 {
-    WFlowsSrc src;
-    src.mixed = true;
-    src.flow_of = flow_of;
-    return rxwf_push(rx, "fec_rxw_flows_push_mixed", packets, src, P, sym_batch, erased_batch, blocks, closes, max_blocks_per_flow, consumed, offered,
-                     left);
+    return rxf_push<WFlowsPolicy>(rx, "fec_rxw_flows_push_mixed", packets, RxFlowsSrc{true, nullptr, flow_of}, P, sym_batch, erased_batch,
+                                  max_blocks_per_flow, RxFlowsOut{blocks, closes, consumed, offered, left});
 }
 
 int ldpc_amd_fec_rxw_flows_decode_mixed(ldpc_amd_fec_rxw_flows *rx, int code, const uint8_t *packets, const int32_t *flow_of, int64_t P,
@@ -901,11 +628,9 @@ int ldpc_amd_fec_rxw_flows_decode_mixed(ldpc_amd_fec_rxw_flows *rx, int code, co
                                         uint8_t *erased_out, int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow,
                                         int64_t *consumed, int64_t *offered, uint8_t *left)
 {
-    WFlowsSrc src;
-    src.mixed = true;
-    src.flow_of = flow_of;
-    return rxwf_decode(rx, "fec_rxw_flows_decode_mixed", code, packets, src, P, max_sweeps, do_ml, out, sweeps, residual, status, erased_out,
-                       residual_src, blocks, closes, max_blocks_per_flow, consumed, offered, left);
+    return rxf_decode<WFlowsPolicy>(rx, "fec_rxw_flows_decode_mixed", code, packets, RxFlowsSrc{true, nullptr, flow_of}, P, max_sweeps, do_ml,
+                                    RxResults{out, sweeps, residual, status, erased_out, residual_src}, max_blocks_per_flow,
+                                    RxFlowsOut{blocks, closes, consumed, offered, left});
 }
 
 int64_t ldpc_amd_fec_rxw_flows_unrouted(const ldpc_amd_fec_rxw_flows *rx) { return rx ? rx->unrouted : -1; }
@@ -914,71 +639,16 @@ int ldpc_amd_fec_rxw_flows_flush_many(ldpc_amd_fec_rxw_flows *rx, const int32_t 
                                       int *blocks, int *closes)
 {
     if (!rx) return LDPC_AMD_EINVAL;
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const char *who = "fec_rxw_flows_flush_many";
-    WFlushPlan pl;
-    int rc;
-    if ((rc = rxwf_flush_plan(rx, who, flows, nsel, pl))) return rc;
-    if (!sym_batch || !erased_batch) return set_error(ctx, LDPC_AMD_EINVAL, "%s: sym_batch / erased_batch must not be null", who);
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: sym_batch / erased_batch must be device pointers of device %d", who, ctx->device);
-    if (pl.T == 0) {
-        if (closes) std::fill(closes, closes + pl.sel.size(), 0);
-        return 0;
-    }
-    if ((rc = rx_upload_planes(ctx, who, rx->fl, (size_t)rx->W * (size_t)rx->nflows, pl.planes.data(), pl.T)) ||
-        (rc = rxwf_flush_launch<true>(rx, 0, pl.T, sym_batch, erased_batch)))
-        return rc;
-    rxwf_flush_commit(rx, pl, blocks, closes);
-    return pl.T;
+    return rxf_flush_many<WFlowsPolicy>(rx, "fec_rxw_flows_flush_many", flows, nsel, 0, sym_batch, erased_batch, blocks, closes);
 }
 
-// flush_many + decode.  FUSED where the decoder has the packets-in form and S % 16 == 0: every row of every block is staged (or erased),
-// rxwf_flush_sources names it and ONE launch_decode follows the words into the planes; the planes are reset by one launch behind it.
-// Else COMPOSED: a chunk of planes goes to the scratch (and is reset in the same launch) and through the decoder.
 int ldpc_amd_fec_rxw_flows_decode_flush_many(ldpc_amd_fec_rxw_flows *rx, int code, const int32_t *flows, int nsel, int max_sweeps, int do_ml,
                                              uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
                                              int32_t *residual_src, int *blocks, int *closes)
 {
     if (!rx) return LDPC_AMD_EINVAL;
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const char *who = "fec_rxw_flows_decode_flush_many";
-    WFlushPlan pl;
-    int rc;
-    if ((rc = rxwf_flush_plan(rx, who, flows, nsel, pl))) return rc;
-    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
-    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, o))) return rc;
-    const int T = pl.T;
-    if (T == 0) {
-        if (closes) std::fill(closes, closes + pl.sel.size(), 0);
-        return 0;
-    }
-    const DevCode &cd = ctx->codes[code]->dev;
-    const int n = rx->n, S = rx->S;
-    const bool fused = ctx->knobs.rx_pkt != 0 && S % 16 == 0 && decode_reads_packets(ctx, cd, S);
-    const size_t frame = (size_t)n * S;
-    const int64_t chunk = rx_chunk(T, frame);
-    size_t scratch = 0;
-    if ((rc = rx_decode_reserve(ctx, T, n, frame, fused, chunk, &scratch))) return rc;
-    if ((rc = rx_upload_planes(ctx, who, rx->fl, (size_t)rx->W * (size_t)rx->nflows, pl.planes.data(), pl.T))) return rc;
-    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
-    // no word of the table names a packet (rxwf_flush_sources), so the packet base is never added to: any valid aligned address
-    const PacketRows pin{nullptr, rx->stage_sym, rx->stage_sym, S + kHdr};
-    auto sources = [&](uint32_t *src, uint8_t *er) -> int {
-        hipLaunchKernelGGL(rxwf_flush_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl.dev,
-                           (const uint8_t *)rx->stage_er, n, T, src, er);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-        return LDPC_AMD_OK;
-    };
-    // (composed: a chunk's planes are reset by the launch that copies them)
-    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return rxwf_flush_launch<true>(rx, first, count, sym, er); };
-    int launches = 0;
-    if ((rc = rx_decode_slots(ctx, d, o, T, chunk, fused, pin, sources, gather, &launches))) return rc;
-    if (fused && (rc = rxwf_flush_launch<false>(rx, 0, T, nullptr, nullptr))) return rc;   // the planes reset, behind the decode that reads them
-    rxwf_flush_commit(rx, pl, blocks, closes);
-    ctx->rxwf_info[0] = fused ? 1 : 2; ctx->rxwf_info[1] = T; ctx->rxwf_info[2] = launches; ctx->rxwf_info[3] = (int64_t)scratch;
-    return T;
+    return rxf_decode_flush_many<WFlowsPolicy>(rx, "fec_rxw_flows_decode_flush_many", code, flows, nsel, 0, max_sweeps, do_ml,
+                                               RxResults{out, sweeps, residual, status, erased_out, residual_src}, blocks, closes);
 }
 
 int ldpc_amd_fec_rxw_flows_info(ldpc_amd_ctx *ctx, int64_t info[4])

@@ -32,9 +32,8 @@
 #include <new>
 #include <vector>
 
-#include "rx_host.h"
+#include "rx_flows_host.h"   // the multi-flow call skeleton; with it rx_host.h and flows_demux_dev.h
 #include "fec_header_dev.h"
-#include "flows_demux_dev.h"
 #include "../../include/ldpc_erasure_amd_wire_dev.h"
 #include "../../include/ldpc_erasure_amd_sender.h"
 #include "../../include/ldpc_erasure_amd_sender_flows.h"
@@ -1140,13 +1139,7 @@ static int rx_plan(ldpc_amd_fec_rx_dev *rx, const char *who, const uint8_t *pack
         (rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)max_blocks + 2) * (size_t)n)) ||
         (rc = scratch_reserve(ctx, rx->res, res_bytes)))
         return rc;
-    if (rx->res_host_cap < res_bytes) {
-        if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every call ends with a synchronisation
-        rx->res_host = nullptr;
-        rx->res_host_cap = 0;
-        LDPC_HIP_TRY(ctx, hipHostMalloc((void **)&rx->res_host, res_bytes, hipHostMallocDefault));
-        rx->res_host_cap = res_bytes;
-    }
+    if ((rc = rx_readback_grow(ctx, rx, res_bytes))) return rc;
     uint32_t *dense = (uint32_t *)rx->dense.p;
     int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
 
@@ -1371,210 +1364,102 @@ struct ldpc_amd_fec_rx_flows {
     RxPlaneUpload fl;   // the batch flush: the closed slots' planes on the device, [2 nflows]
 };
 
-// One call's PLAN for all flows: (a) + (b), ONE read-back, the slot bases.  Nothing of any flow's state changes before flows_commit.
-struct FlowsPlan {
-    int T = 0;             // closed blocks of all flows
-    int64_t max_used = 0;  // the longest consumed prefix
-    size_t rec = 0;        // words of one flow's result record
-    // a mixed call (else null / 0): the partition, the flow bases as read back behind the scan records ([nflows + 1], the last one =
-    // the routed packets), the longest remainder behind a consumed prefix
-    const uint32_t *order = nullptr, *base = nullptr;
-    int64_t max_left = 0;
-};
-
-// Where the packets of a call are: segmented by the caller (flow_begin, host) or interleaved with a flow number each (flow_of, device)
-struct FlowsSrc {
-    bool mixed = false;
-    const int64_t *flow_begin = nullptr;
-    const int32_t *flow_of = nullptr;
-};
-
-static int flows_check_limits(ldpc_amd_fec_rx_flows *rx, const char *who, int64_t P, int max_blocks)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (P < 0 || P >= ((int64_t)1 << 31)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need fewer than 2^31 packets in all", who);
-    if (max_blocks < 1) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need max_blocks_per_flow >= 1", who);
-    if ((int64_t)rx->nflows * max_blocks * rx->n >= ((int64_t)1 << 31) - 2)
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: nflows * max_blocks_per_flow * n must be below 2^31 - 2", who);
-    return LDPC_AMD_OK;
-}
-
-static int flows_check_call(ldpc_amd_fec_rx_flows *rx, const char *who, const int64_t *flow_begin, int max_blocks, int64_t &P)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (!flow_begin || flow_begin[0] != 0) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin must not be null and must start at 0", who);
-    for (int f = 0; f < rx->nflows; f++)
-        if (flow_begin[f + 1] < flow_begin[f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_begin decreases at flow %d", who, f);
-    P = flow_begin[rx->nflows];
-    return flows_check_limits(rx, who, P, max_blocks);
-}
-
-static void flows_nothing(const ldpc_amd_fec_rx_flows *rx, int *closes, int64_t *consumed, int64_t *offered)
-{
-    if (closes) std::fill(closes, closes + rx->nflows, 0);
-    if (consumed) std::fill(consumed, consumed + rx->nflows, (int64_t)0);
-    if (offered) std::fill(offered, offered + rx->nflows, (int64_t)0);
-}
-
-// the mixed calls' own arguments, P > 0 (the device is set)
-static int flows_check_mixed(ldpc_amd_fec_rx_flows *rx, const char *who, const int32_t *flow_of, const uint8_t *left)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (!flow_of || !is_device_ptr(ctx, flow_of))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be a device pointer of device %d", who, ctx->device);
-    if ((uintptr_t)flow_of & 3) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow_of must be 4-byte aligned", who);
-    if (left && !is_device_ptr(ctx, left)) return set_error(ctx, LDPC_AMD_EINVAL, "%s: left must be a device pointer of device %d", who, ctx->device);
-    return LDPC_AMD_OK;
-}
-
-static int flows_plan(ldpc_amd_fec_rx_flows *rx, const char *who, const uint8_t *packets, const FlowsSrc &src, int64_t npackets,
-                      int max_blocks, FlowsPlan &pl)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const int n = rx->n, nf = rx->nflows;
-    const int64_t plen = (int64_t)rx->S + kHdr;
-    const int64_t *flow_begin = src.flow_begin;
-    const bool mixed = src.mixed;
-    pl.rec = (size_t)R_WORDS + (size_t)max_blocks;
-    const size_t res_bytes = sizeof(int32_t) * (pl.rec * (size_t)nf + (mixed ? (size_t)nf + 1 : 0));   // mixed: the flow bases behind the records
-    int rc;
-    if ((rc = scratch_reserve(ctx, rx->dense, sizeof(uint32_t) * (size_t)npackets)) ||
-        (rc = scratch_reserve(ctx, rx->dest, sizeof(int32_t) * (size_t)npackets)) || (rc = scratch_reserve(ctx, rx->res, res_bytes)))
-        return rc;
-    if (mixed && ((rc = scratch_reserve(ctx, rx->order, sizeof(uint32_t) * (size_t)npackets)) || (rc = demux_reserve(ctx, npackets, nf)))) return rc;
-    if (rx->res_host_cap < res_bytes) {
-        if (rx->res_host) (void)hipHostFree(rx->res_host);   // no copy into it is pending: every plan ends with a synchronisation
-        rx->res_host = nullptr;
-        rx->res_host_cap = 0;
-        LDPC_HIP_TRY(ctx, hipHostMalloc((void **)&rx->res_host, res_bytes, hipHostMallocDefault));
-        rx->res_host_cap = res_bytes;
+// What the two-block receiver puts into the multi-flow call skeleton (rx_flows_host.h)
+struct FlowsPolicy {
+    typedef ldpc_amd_fec_rx_flows Rx;
+    static int planes_per_flow(const Rx *) { return 2; }
+    static void fill_in(Rx *rx, int f, int64_t begin, int64_t len)
+    {
+        rx->in_host[f] = FlowIn{begin, len, rx->cur[f], rx->next[f], rx->ccnt[f], rx->ncnt[f]};
     }
-    uint32_t *dense = (uint32_t *)rx->dense.p;
-    int32_t *dest = (int32_t *)rx->dest.p, *res = (int32_t *)rx->res.p;
-    for (int f = 0; f < nf; f++)   // (the copy of the previous call's records is behind that call's synchronisation)
-        rx->in_host[f] = FlowIn{mixed ? 0 : flow_begin[f], mixed ? 0 : flow_begin[f + 1] - flow_begin[f], rx->cur[f], rx->next[f], rx->ccnt[f],
-                                rx->ncnt[f]};
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->in_dev, rx->in_host, sizeof(FlowIn) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-
-    // (a) + (b): the plan; a mixed call's on the partition, which also fills in every flow's segment (begin, len) on the device
-    const bool aligned4 = plen % 4 == 0 && ((uintptr_t)packets & 3) == 0;
-    if (mixed) {
-        uint32_t *base = (uint32_t *)res + pl.rec * (size_t)nf, *order = (uint32_t *)rx->order.p;
-        if ((rc = demux_launch(ctx, src.flow_of, npackets, nf, base, rx->in_dev, order))) return rc;
-        if (aligned4)
-            hipLaunchKernelGGL(fec_rx_headers_idx<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, (const uint32_t *)order,
-                               (const uint32_t *)base + nf, (int)plen, dense);
-        else
-            hipLaunchKernelGGL(fec_rx_headers_idx<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, (const uint32_t *)order,
-                               (const uint32_t *)base + nf, (int)plen, dense);
-        pl.order = order;
-        pl.base = (const uint32_t *)rx->res_host + pl.rec * (size_t)nf;
-    } else if (aligned4)
-        hipLaunchKernelGGL(fec_rx_headers<true>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
-    else
-        hipLaunchKernelGGL(fec_rx_headers<false>, dim3(grid_for(npackets)), dim3(kThreads), 0, ctx->stream, packets, npackets, (int)plen, dense);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(fec_rx_scan_flows, dim3(nf), dim3(64), 0, ctx->stream, dense, rx->in_dev, n, rx->kd, rx->km, max_blocks, dest, res);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->res_host, res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    LDPC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = check_device_error(ctx))) return rc;
-    int64_t base = 0;
-    for (int f = 0; f < nf; f++) {   // the tables of the kernels behind the plan (their copy of the previous call is behind this synchronisation)
-        const int32_t *h = rx->res_host + (size_t)f * pl.rec;
-        if (h[R_ERR])
-            return set_error(ctx, LDPC_AMD_EHIP, "%s: the plan scan of flow %d hit its iteration cap (internal error); every flow's state is unchanged",
-                             who, f);
-        const int64_t used = (int64_t)(((uint64_t)(uint32_t)h[R_CONSUMED_HI] << 32) | (uint32_t)h[R_CONSUMED_LO]);
-        rx->tab_host[f] = FlowTab{mixed ? (int64_t)pl.base[f] : flow_begin[f], used, (int)base, h[R_CLOSES], rx->cb[f], 0};
-        base += h[R_CLOSES];
-        pl.max_used = std::max(pl.max_used, used);
-        if (mixed) pl.max_left = std::max(pl.max_left, (int64_t)(pl.base[f + 1] - pl.base[f]) - used);
+    static int launch_headers(Rx *rx, bool aligned4, const uint8_t *packets, const int32_t *flow_of, uint32_t *base, uint32_t *order, int64_t np,
+                              int plen, uint32_t *dense)
+    {
+        hipStream_t st = rx->ctx->stream;
+        const int nf = rx->nflows;
+        int rc;
+        if (order && (rc = demux_launch(rx->ctx, flow_of, np, nf, base, rx->in_dev, order))) return rc;
+        const uint32_t *ord = order, *routed = order ? base + nf : nullptr;   // the routed count, as the partition's bases kernel wrote it
+        if (order && aligned4) hipLaunchKernelGGL(fec_rx_headers_idx<true>, dim3(grid_for(np)), dim3(kThreads), 0, st, packets, ord, routed, plen, dense);
+        else if (order) hipLaunchKernelGGL(fec_rx_headers_idx<false>, dim3(grid_for(np)), dim3(kThreads), 0, st, packets, ord, routed, plen, dense);
+        else if (aligned4) hipLaunchKernelGGL(fec_rx_headers<true>, dim3(grid_for(np)), dim3(kThreads), 0, st, packets, np, plen, dense);
+        else hipLaunchKernelGGL(fec_rx_headers<false>, dim3(grid_for(np)), dim3(kThreads), 0, st, packets, np, plen, dense);
+        return LDPC_AMD_OK;
     }
-    pl.T = (int)base;   // <= nflows * max_blocks < 2^31
-    if ((rc = scratch_reserve(ctx, rx->win, sizeof(int32_t) * ((size_t)pl.T + 2 * (size_t)nf) * (size_t)n)) ||
-        (rc = scratch_reserve(ctx, rx->slots, sizeof(int32_t) * (size_t)std::max(pl.T, 1))))
-        return rc;
-    return LDPC_AMD_OK;
-}
-
-// the flow table, the slot map and (c): the winners' table of the call, [(T + 2 nflows)][n]
-static int flows_winners(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const int nf = rx->nflows;
-    int32_t *win = (int32_t *)rx->win.p;
-    LDPC_HIP_TRY(ctx, hipMemcpyAsync(rx->tab_dev, rx->tab_host, sizeof(FlowTab) * (size_t)nf, hipMemcpyHostToDevice, ctx->stream));
-    if (pl.T > 0) {
-        hipLaunchKernelGGL(fec_rx_flow_slots, dim3(nf), dim3(64), 0, ctx->stream, rx->tab_dev, (int32_t *)rx->slots.p);
+    static void launch_scan(Rx *rx, const uint32_t *dense, int max_blocks, int32_t *dest, int32_t *res)
+    {
+        hipLaunchKernelGGL(fec_rx_scan_flows, dim3(rx->nflows), dim3(64), 0, rx->ctx->stream, dense, rx->in_dev, rx->n, rx->kd, rx->km, max_blocks, dest,
+                           res);
+    }
+    static size_t rec_words(int max_blocks) { return (size_t)R_WORDS + (size_t)max_blocks; }
+    static bool err(const int32_t *h) { return h[R_ERR] != 0; }
+    static int closes(const int32_t *h) { return h[R_CLOSES]; }
+    static int64_t consumed(const int32_t *h) { return (int64_t)(((uint64_t)(uint32_t)h[R_CONSUMED_HI] << 32) | (uint32_t)h[R_CONSUMED_LO]); }
+    static FlowTab tab_entry(const Rx *rx, int f, int64_t begin, int64_t used, int base, int closes)
+    {
+        return FlowTab{begin, used, base, closes, rx->cb[f], 0};
+    }
+    static void launch_slots(Rx *rx)
+    {
+        hipLaunchKernelGGL(fec_rx_flow_slots, dim3(rx->nflows), dim3(64), 0, rx->ctx->stream, rx->tab_dev, (int32_t *)rx->slots.p);
+    }
+    static int launch_winners(Rx *rx, const RxFlowsPlan &pl, unsigned gx, int32_t *win)
+    {
+        ldpc_amd_ctx *ctx = rx->ctx;
+        const int nf = rx->nflows;
+        hipLaunchKernelGGL(fec_rx_winners_flows, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p,
+                           (const int32_t *)rx->dest.p, rx->tab_dev, rx->n, pl.T, win);
         LDPC_HIP_TRY(ctx, hipGetLastError());
+        if (pl.order) {   // a mixed call planned on positions: every winner back to its packet index
+            const int64_t cells = ((int64_t)pl.T + 2 * (int64_t)nf) * rx->n;
+            hipLaunchKernelGGL(fec_rx_win_order, dim3(grid_for(cells)), dim3(kThreads), 0, ctx->stream, win, cells, pl.order);
+            LDPC_HIP_TRY(ctx, hipGetLastError());
+        }
+        return LDPC_AMD_OK;
     }
-    LDPC_HIP_TRY(ctx, hipMemsetAsync(win, 0xff, sizeof(int32_t) * ((size_t)pl.T + 2 * (size_t)nf) * (size_t)rx->n, ctx->stream));   // -1: no packet
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pl.max_used + kThreads - 1) / kThreads, std::max(1, 32768 / nf)));
-    hipLaunchKernelGGL(fec_rx_winners_flows, dim3(gx, nf), dim3(kThreads), 0, ctx->stream, (const uint32_t *)rx->dense.p,
-                       (const int32_t *)rx->dest.p, rx->tab_dev, rx->n, pl.T, win);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    if (pl.order) {   // a mixed call planned on positions: every winner back to its packet index
-        const int64_t cells = ((int64_t)pl.T + 2 * (int64_t)nf) * rx->n;
-        hipLaunchKernelGGL(fec_rx_win_order, dim3(grid_for(cells)), dim3(kThreads), 0, ctx->stream, win, cells, pl.order);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
+    static void launch_move(Rx *rx, const RxFlowsPlan &pl, const uint8_t *packets, bool gather, int first, int count, uint8_t *sym, uint8_t *er,
+                            bool v16, int64_t items)
+    {
+        FlowMoveArgs a{};
+        a.packets = packets; a.plen = (int64_t)rx->S + kHdr; a.win = (const int32_t *)rx->win.p; a.tab = rx->tab_dev;
+        a.slot_flow = (const int32_t *)rx->slots.p; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
+        a.sym_out = sym; a.er_out = er; a.n = rx->n; a.S = rx->S; a.T = pl.T; a.nflows = rx->nflows; a.first = first; a.count = count;
+        const dim3 grid(grid_for(items)), block(kThreads);
+        hipStream_t st = rx->ctx->stream;
+        if (gather && v16) hipLaunchKernelGGL((fec_rx_move_flows<true, true>), grid, block, 0, st, a);
+        else if (gather) hipLaunchKernelGGL((fec_rx_move_flows<true, false>), grid, block, 0, st, a);
+        else if (v16) hipLaunchKernelGGL((fec_rx_move_flows<false, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((fec_rx_move_flows<false, false>), grid, block, 0, st, a);
     }
-    return LDPC_AMD_OK;
-}
-
-// (d) for the closed slots first .. first + count - 1 (gather) or (e) for the two open blocks of every flow
-template <bool GATHER>
-static int flows_move(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl, const uint8_t *packets, int first, int count, uint8_t *sym, uint8_t *er)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const int n = rx->n, S = rx->S;
-    FlowMoveArgs a{};
-    a.packets = packets; a.plen = (int64_t)S + kHdr; a.win = (const int32_t *)rx->win.p; a.tab = rx->tab_dev;
-    a.slot_flow = (const int32_t *)rx->slots.p; a.stage_sym = rx->stage_sym; a.stage_er = rx->stage_er;
-    a.sym_out = sym; a.er_out = er; a.n = n; a.S = S; a.T = pl.T; a.nflows = rx->nflows; a.first = first; a.count = count;
-    const bool v16 = S % 16 == 0 && ((uintptr_t)packets & 7) == 0 && ((uintptr_t)sym & 15) == 0;
-    const int64_t q = v16 ? S / 16 : S;
-    const int64_t items = (GATHER ? (int64_t)count : 2 * (int64_t)rx->nflows) * n * q;
-    if (GATHER && count <= 0) return LDPC_AMD_OK;
-    if (v16) hipLaunchKernelGGL((fec_rx_move_flows<GATHER, true>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((fec_rx_move_flows<GATHER, false>), dim3(grid_for(items)), dim3(kThreads), 0, ctx->stream, a);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    return LDPC_AMD_OK;
-}
-
-// a mixed call's `left` (may be null): zero, then 1 behind every flow's consumed prefix
-static int flows_left(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl, int64_t npackets, uint8_t *left)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (!left) return LDPC_AMD_OK;
-    LDPC_HIP_TRY(ctx, hipMemsetAsync(left, 0, (size_t)npackets, ctx->stream));
-    if (pl.max_left <= 0) return LDPC_AMD_OK;
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((pl.max_left + kThreads - 1) / kThreads, std::max(1, 32768 / rx->nflows)));
-    hipLaunchKernelGGL(fec_rx_left_flows, dim3(gx, rx->nflows), dim3(kThreads), 0, ctx->stream, (const FlowTab *)rx->tab_dev,
-                       (const FlowIn *)rx->in_dev, pl.order, left);
-    LDPC_HIP_TRY(ctx, hipGetLastError());
-    return LDPC_AMD_OK;
-}
-
-// (a mixed call: offered and the unrouted count too)
-static void flows_commit(ldpc_amd_fec_rx_flows *rx, const FlowsPlan &pl, int *blocks, int *closes, int64_t *consumed, int64_t npackets,
-                         int64_t *offered)
-{
-    if (pl.base) {
-        rx->unrouted += npackets - (int64_t)pl.base[rx->nflows];
-        for (int f = 0; offered && f < rx->nflows; f++) offered[f] = (int64_t)(pl.base[f + 1] - pl.base[f]);
+    static void launch_left(Rx *rx, const RxFlowsPlan &pl, unsigned gx, uint8_t *left)
+    {
+        hipLaunchKernelGGL(fec_rx_left_flows, dim3(gx, rx->nflows), dim3(kThreads), 0, rx->ctx->stream, (const FlowTab *)rx->tab_dev,
+                           (const FlowIn *)rx->in_dev, pl.order, left);
     }
-    for (int f = 0; f < rx->nflows; f++) {
-        const int32_t *h = rx->res_host + (size_t)f * pl.rec;
-        const FlowTab &t = rx->tab_host[f];
+    static void launch_sources(Rx *rx, int T, uint32_t *rows, uint8_t *er)
+    {
+        hipLaunchKernelGGL(fec_rx_sources_flows, dim3(grid_for((int64_t)T * rx->n)), dim3(kThreads), 0, rx->ctx->stream, (const int32_t *)rx->win.p,
+                           rx->stage_er, rx->tab_dev, (const int32_t *)rx->slots.p, rx->n, T, rows, er);
+    }
+    static void commit_flow(Rx *rx, int f, const int32_t *h, int closes)
+    {
         rx->cur[f] = h[R_CUR]; rx->next[f] = h[R_NEXT]; rx->ccnt[f] = h[R_CCNT]; rx->ncnt[f] = h[R_NCNT];
-        rx->cb[f] ^= t.closes & 1;   // :241, once per close
+        rx->cb[f] ^= closes & 1;   // :241, once per close
         rx->dropped[f] += (int64_t)(((uint64_t)(uint32_t)h[R_DROPPED_HI] << 32) | (uint32_t)h[R_DROPPED_LO]);
-        if (blocks) memcpy(blocks + t.base, h + R_WORDS, sizeof(int) * (size_t)t.closes);
-        if (closes) closes[f] = t.closes;
-        if (consumed) consumed[f] = t.used;
     }
-}
+    static void record_info(ldpc_amd_ctx *ctx, bool fused, int T, int, size_t)
+    {
+        ctx->receiver_path = fused ? 1 : 2;
+        ctx->receiver_blocks = T;
+    }
+    // the batch flush's members: defined with the flush, below
+    static int flush_fill(const Rx *rx, int f, int rounds, RxFlushPlan &pl);
+    static int flush_gather(Rx *rx, int first, int count, uint8_t *sym, uint8_t *er);
+    static int flush_after(Rx *rx, bool fused, int T);
+    static void launch_flush_sources(Rx *rx, int T, uint32_t *src, uint8_t *er);
+    static void flush_commit_flow(Rx *rx, int f, int count);
+    static void record_flush(ldpc_amd_ctx *ctx, int path, int T, int n, int launches, size_t scratch);
+};
 
 extern "C" {
 
@@ -1596,103 +1481,30 @@ int ldpc_amd_fec_rx_flows_create(ldpc_amd_ctx *ctx, int nflows, int n, int k, in
     rx->cur.assign(nflows, -1); rx->next.assign(nflows, -1);
     rx->ccnt.assign(nflows, 0); rx->ncnt.assign(nflows, 0); rx->cb.assign(nflows, 0);
     rx->dropped.assign(nflows, 0);
-    const size_t planes = 2 * (size_t)nflows, plane = (size_t)n * S;
-    // (a request beyond the device's memory is not always answered with hipErrorOutOfMemory: a staging plane that cannot be had is ENOMEM)
-    hipError_t e = hipMalloc((void **)&rx->stage_sym, planes * plane);
-    if (e == hipSuccess) e = hipMalloc((void **)&rx->stage_er, planes * (size_t)n);
-    const bool no_planes = e != hipSuccess;
-    if (e == hipSuccess) e = hipMalloc((void **)&rx->in_dev, sizeof(FlowIn) * (size_t)nflows);
-    if (e == hipSuccess) e = hipMalloc((void **)&rx->tab_dev, sizeof(FlowTab) * (size_t)nflows);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&rx->in_host, sizeof(FlowIn) * (size_t)nflows, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&rx->tab_host, sizeof(FlowTab) * (size_t)nflows, hipHostMallocDefault);
-    // :62-71 all symbols erased until a packet produces them, payload zero
-    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_sym, 0, planes * plane, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(rx->stage_er, 1, planes * (size_t)n, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        ldpc_amd_fec_rx_flows_destroy(rx);
-        return set_error(ctx, no_planes || e == hipErrorOutOfMemory ? LDPC_AMD_ENOMEM : LDPC_AMD_EHIP, "fec_rx_flows_create: %s%s",
-                         no_planes ? "the staging planes do not fit: " : "", hipGetErrorString(e));
-    }
-    *out = rx;
-    return LDPC_AMD_OK;
+    return rxf_create_buffers<FlowsPolicy>(ctx, rx, "fec_rx_flows_create", out);
 }
 
-void ldpc_amd_fec_rx_flows_destroy(ldpc_amd_fec_rx_flows *rx)
-{
-    if (!rx) return;
-    (void)hipSetDevice(rx->ctx->device);
-    (void)hipStreamSynchronize(rx->ctx->stream);   // pending work of this object may still use its buffers
-    Scratch *sc[] = {&rx->dense, &rx->dest, &rx->win, &rx->res, &rx->slots, &rx->order};
-    for (Scratch *s : sc)
-        if (s->p) (void)hipFree(s->p);
-    void *dev[] = {rx->stage_sym, rx->stage_er, rx->in_dev, rx->tab_dev};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    void *host[] = {rx->in_host, rx->tab_host, rx->res_host};
-    for (void *p : host)
-        if (p) (void)hipHostFree(p);
-    rx_upload_free(rx->fl);
-    delete rx;
-}
+void ldpc_amd_fec_rx_flows_destroy(ldpc_amd_fec_rx_flows *rx) { rxf_destroy(rx); }
 
 int64_t ldpc_amd_fec_rx_flows_dropped(const ldpc_amd_fec_rx_flows *rx, int flow)
 {
     return rx && flow >= 0 && flow < rx->nflows ? rx->dropped[flow] : -1;
 }
 
-}  // extern "C"
-
-// push_many and push_mixed: P is the segmented call's flow_begin[nflows], or the mixed call's argument
-static int flows_push(ldpc_amd_fec_rx_flows *rx, const char *who, const uint8_t *packets, const FlowsSrc &src, int64_t P, uint8_t *sym_batch,
-                      uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed, int64_t *offered, uint8_t *left)
-{
-    if (!rx) return LDPC_AMD_EINVAL;
-    ldpc_amd_ctx *ctx = rx->ctx;
-    const bool mixed = src.mixed;
-    int rc;
-    if ((rc = mixed ? flows_check_limits(rx, who, P, max_blocks_per_flow) : flows_check_call(rx, who, src.flow_begin, max_blocks_per_flow, P)))
-        return rc;
-    if (!sym_batch || !erased_batch || (P > 0 && !packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must not be null", who);
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((P > 0 && !is_device_ptr(ctx, packets)) || !is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets / sym_batch / erased_batch must be device pointers of device %d", who, ctx->device);
-    if (P == 0) {
-        flows_nothing(rx, closes, consumed, offered);
-        return 0;
-    }
-    if (mixed && (rc = flows_check_mixed(rx, who, src.flow_of, left))) return rc;
-    FlowsPlan pl;
-    if ((rc = flows_plan(rx, who, packets, src, P, max_blocks_per_flow, pl))) return rc;
-    // (c), (d), (e): the data movement, asynchronous
-    if ((rc = flows_winners(rx, pl)) || (rc = flows_move<true>(rx, pl, packets, 0, pl.T, sym_batch, erased_batch)) ||
-        (rc = flows_move<false>(rx, pl, packets, 0, 0, sym_batch, nullptr)) || (rc = flows_left(rx, pl, P, left)))
-        return rc;
-    flows_commit(rx, pl, blocks, closes, consumed, P, offered);
-    return pl.T;
-}
-
-extern "C" {
-
+// ---- the calls: each fills in where its packets are and runs the skeleton (rx_flows_host.h) under its own name -----------------------
 int ldpc_amd_fec_rx_flows_push_many(ldpc_amd_fec_rx_flows *rx, const uint8_t *packets, const int64_t *flow_begin, uint8_t *sym_batch,
                                     uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
 {
-    FlowsSrc src;
-    src.flow_begin = flow_begin;
-    return flows_push(rx, "fec_rx_flows_push_many", packets, src, 0, sym_batch, erased_batch, blocks, closes, max_blocks_per_flow, consumed, nullptr,
-                      nullptr);
+    return rxf_push<FlowsPolicy>(rx, "fec_rx_flows_push_many", packets, RxFlowsSrc{false, flow_begin, nullptr}, 0, sym_batch, erased_batch,
+                                 max_blocks_per_flow, RxFlowsOut{blocks, closes, consumed, nullptr, nullptr});
 }
 
 int ldpc_amd_fec_rx_flows_push_mixed(ldpc_amd_fec_rx_flows *rx, const uint8_t *packets, const int32_t *flow_of, int64_t P, uint8_t *sym_batch,
                                      uint8_t *erased_batch, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed,
                                      int64_t *offered, uint8_t *left)
 {
-    FlowsSrc src;
-    src.mixed = true;
-    src.flow_of = flow_of;
-    return flows_push(rx, "fec_rx_flows_push_mixed", packets, src, P, sym_batch, erased_batch, blocks, closes, max_blocks_per_flow, consumed, offered,
-                      left);
+    return rxf_push<FlowsPolicy>(rx, "fec_rx_flows_push_mixed", packets, RxFlowsSrc{true, nullptr, flow_of}, P, sym_batch, erased_batch,
+                                 max_blocks_per_flow, RxFlowsOut{blocks, closes, consumed, offered, left});
 }
 
 int64_t ldpc_amd_fec_rx_flows_unrouted(const ldpc_amd_fec_rx_flows *rx) { return rx ? rx->unrouted : -1; }
@@ -1725,69 +1537,13 @@ int ldpc_amd_fec_rx_flows_flush(ldpc_amd_fec_rx_flows *rx, int flow, uint8_t *sy
 
 // ldpc_amd_fec_rx_dev_decode_many for all flows: ONE launch_decode over the T closed slots (composed: one per chunk of slots).  The
 // staging update of all flows is one launch BEHIND the decode, for the reason given there.
-}  // extern "C"
-
-static int flows_decode(ldpc_amd_fec_rx_flows *rx, const char *who, int code, const uint8_t *packets, const FlowsSrc &src, int64_t P, int max_sweeps,
-                        int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out, int32_t *residual_src,
-                        int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed, int64_t *offered, uint8_t *left)
-{
-    if (!rx) return LDPC_AMD_EINVAL;
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (code < 0 || code >= (int)ctx->codes.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown code handle %d", code);
-    const bool mixed = src.mixed;
-    int rc;
-    if ((rc = mixed ? flows_check_limits(rx, who, P, max_blocks_per_flow) : flows_check_call(rx, who, src.flow_begin, max_blocks_per_flow, P)))
-        return rc;
-    if (P == 0) {
-        flows_nothing(rx, closes, consumed, offered);
-        return 0;
-    }
-    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
-    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, o))) return rc;
-    if (!packets || !is_device_ptr(ctx, packets))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: packets must be a device pointer of device %d", who, ctx->device);
-    if (mixed && (rc = flows_check_mixed(rx, who, src.flow_of, left))) return rc;
-    const DevCode &cd = ctx->codes[code]->dev;
-    const int n = rx->n, S = rx->S;
-    const bool fused = ctx->knobs.rx_pkt != 0 && ((uintptr_t)packets & 7) == 0 && decode_reads_packets(ctx, cd, S);
-    const size_t frame = (size_t)n * S;
-
-    FlowsPlan pl;
-    if ((rc = flows_plan(rx, who, packets, src, P, max_blocks_per_flow, pl))) return rc;
-    const int T = pl.T;
-    const int64_t chunk = rx_chunk(T, frame);
-    size_t scratch = 0;
-    if ((rc = rx_decode_reserve(ctx, T, n, frame, fused, chunk, &scratch))) return rc;
-    if ((rc = flows_winners(rx, pl))) return rc;
-    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
-    const PacketRows pin{nullptr, packets, rx->stage_sym, S + kHdr};
-    auto sources = [&](uint32_t *rows, uint8_t *er) -> int {
-        hipLaunchKernelGGL(fec_rx_sources_flows, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
-                           rx->stage_er, rx->tab_dev, (const int32_t *)rx->slots.p, n, T, rows, er);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-        return LDPC_AMD_OK;
-    };
-    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return flows_move<true>(rx, pl, packets, first, count, sym, er); };
-    int launches = 0;
-    if ((rc = rx_decode_slots(ctx, d, o, T, chunk, fused, pin, sources, gather, &launches))) return rc;
-    if ((rc = flows_move<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
-    if ((rc = flows_left(rx, pl, P, left))) return rc;
-    flows_commit(rx, pl, blocks, closes, consumed, P, offered);
-    ctx->receiver_path = fused ? 1 : 2;
-    ctx->receiver_blocks = T;
-    return T;
-}
-
-extern "C" {
-
 int ldpc_amd_fec_rx_flows_decode_many(ldpc_amd_fec_rx_flows *rx, int code, const uint8_t *packets, const int64_t *flow_begin, int max_sweeps,
                                       int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
                                       int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow, int64_t *consumed)
 {
-    FlowsSrc src;
-    src.flow_begin = flow_begin;
-    return flows_decode(rx, "fec_rx_flows_decode_many", code, packets, src, 0, max_sweeps, do_ml, out, sweeps, residual, status, erased_out,
-                        residual_src, blocks, closes, max_blocks_per_flow, consumed, nullptr, nullptr);
+    return rxf_decode<FlowsPolicy>(rx, "fec_rx_flows_decode_many", code, packets, RxFlowsSrc{false, flow_begin, nullptr}, 0, max_sweeps, do_ml,
+                                   RxResults{out, sweeps, residual, status, erased_out, residual_src}, max_blocks_per_flow,
+                                   RxFlowsOut{blocks, closes, consumed, nullptr, nullptr});
 }
 
 int ldpc_amd_fec_rx_flows_decode_mixed(ldpc_amd_fec_rx_flows *rx, int code, const uint8_t *packets, const int32_t *flow_of, int64_t P,
@@ -1795,11 +1551,9 @@ int ldpc_amd_fec_rx_flows_decode_mixed(ldpc_amd_fec_rx_flows *rx, int code, cons
                                        uint8_t *erased_out, int32_t *residual_src, int *blocks, int *closes, int max_blocks_per_flow,
                                        int64_t *consumed, int64_t *offered, uint8_t *left)
 {
-    FlowsSrc src;
-    src.mixed = true;
-    src.flow_of = flow_of;
-    return flows_decode(rx, "fec_rx_flows_decode_mixed", code, packets, src, P, max_sweeps, do_ml, out, sweeps, residual, status, erased_out,
-                        residual_src, blocks, closes, max_blocks_per_flow, consumed, offered, left);
+    return rxf_decode<FlowsPolicy>(rx, "fec_rx_flows_decode_mixed", code, packets, RxFlowsSrc{true, nullptr, flow_of}, P, max_sweeps, do_ml,
+                                   RxResults{out, sweeps, residual, status, erased_out, residual_src}, max_blocks_per_flow,
+                                   RxFlowsOut{blocks, closes, consumed, offered, left});
 }
 
 int ldpc_amd_fec_rx_flows_decode_flush(ldpc_amd_fec_rx_flows *rx, int flow, int code, int max_sweeps, int do_ml, uint8_t *out, int32_t *sweeps,
@@ -1828,22 +1582,16 @@ int ldpc_amd_fec_rx_flows_decode_flush(ldpc_amd_fec_rx_flows *rx, int flow, int 
 // ---- the batch flush (include/ldpc_erasure_amd_flows_flush.h) -------------------------------------------------------------
 // ldpc_amd_fec_rx_flows_flush / _decode_flush for many flows and up to two blocks of each in one call.  The PLAN is the host's: the
 // mirror knows every flow's state, so which blocks close, in which order and from which plane is decided without the device
-// (flush_plan: the rule of ldpc_amd_fec_rx_flows_flush, replayed on a copy of the flow's state).  The DATA MOVEMENT is all-staged --
+// (flush_replay: the rule of ldpc_amd_fec_rx_flows_flush, replayed on a copy of the flow's state).  The DATA MOVEMENT is all-staged --
 // a block that a flush closes got its last packet in an earlier call -- so the decode form is the carried-block case of
-// flows_decode for every row: fec_rx_flush_sources writes a staged (or erased) row-source word per symbol and ONE launch_decode
+// the decode calls for every row: fec_rx_flush_sources writes a staged (or erased) row-source word per symbol and ONE launch_decode
 // follows them into the planes; where the decoder has no packets-in form, fec_rx_flush_gather copies the planes into the context's
-// scratch, chunk by chunk, as flows_decode does.  fec_rx_flush_reset, ONE launch for all closed planes, stands BEHIND the decode,
+// scratch, chunk by chunk, as the decode calls do.  fec_rx_flush_reset, ONE launch for all closed planes, stands BEHIND the decode,
 // which reads them.  Nothing is read back and nothing waits: the mirror is advanced on the host when everything is enqueued.
-struct FlushPlan {
-    std::vector<int> sel;          // the selected flows, in list order
-    std::vector<int> closes;       // blocks that close per list entry
-    std::vector<int> blocks;       // [T] their wire numbers, in slot order
-    std::vector<int32_t> planes;   // [T] their staging planes, f * 2 + b
-    int T = 0;
-};
+// The two calls themselves are rx_flows_host.h's (rxf_flush_many, rxf_decode_flush_many); here are FlowsPolicy's flush members.
 
 // how many blocks `rounds` flushes of flow f close, from its mirror; with out: their numbers and planes
-static int flush_replay(const ldpc_amd_fec_rx_flows *rx, int f, int rounds, FlushPlan *out)
+static int flush_replay(const ldpc_amd_fec_rx_flows *rx, int f, int rounds, RxFlushPlan *out)
 {
     int cur = rx->cur[f], next = rx->next[f], ccnt = rx->ccnt[f], ncnt = rx->ncnt[f], cb = rx->cb[f], c = 0;
     for (; c < rounds; c++) {
@@ -1857,31 +1605,7 @@ static int flush_replay(const ldpc_amd_fec_rx_flows *rx, int f, int rounds, Flus
     return c;
 }
 
-static int flush_plan(const ldpc_amd_fec_rx_flows *rx, const char *who, const int32_t *flows, int nsel, int rounds, FlushPlan &pl)
-{
-    ldpc_amd_ctx *ctx = rx->ctx;
-    if (rounds < 1 || rounds > 2) return set_error(ctx, LDPC_AMD_EINVAL, "%s: rounds must be 1 or 2 (got %d)", who, rounds);
-    if (flows) {
-        if (nsel < 0 || nsel > rx->nflows) return set_error(ctx, LDPC_AMD_EINVAL, "%s: need 0 <= nsel <= nflows = %d (got %d)", who, rx->nflows, nsel);
-        std::vector<uint8_t> seen((size_t)rx->nflows, 0);
-        for (int j = 0; j < nsel; j++) {
-            const int f = flows[j];
-            if (f < 0 || f >= rx->nflows) return set_error(ctx, LDPC_AMD_EINVAL, "%s: no flow %d (nflows = %d)", who, f, rx->nflows);
-            if (seen[(size_t)f]) return set_error(ctx, LDPC_AMD_EINVAL, "%s: flow %d is given twice", who, f);
-            seen[(size_t)f] = 1;
-        }
-    } else {
-        nsel = rx->nflows;
-    }
-    pl.sel.resize((size_t)nsel);
-    pl.closes.resize((size_t)nsel);
-    for (int j = 0; j < nsel; j++) {
-        pl.sel[(size_t)j] = flows ? flows[j] : j;
-        pl.closes[(size_t)j] = flush_replay(rx, pl.sel[(size_t)j], rounds, &pl);
-    }
-    pl.T = (int)pl.planes.size();   // <= 2 nflows
-    return LDPC_AMD_OK;
-}
+int FlowsPolicy::flush_fill(const Rx *rx, int f, int rounds, RxFlushPlan &pl) { return flush_replay(rx, f, rounds, &pl); }
 
 // the piece of the plane kernels: the widest of 16, 4, 1 bytes that divides S and that `p` (null: the planes alone) is aligned to
 static int flush_piece(int S, const void *p)
@@ -1891,7 +1615,7 @@ static int flush_piece(int S, const void *p)
     return 1;
 }
 
-static int flush_gather(ldpc_amd_fec_rx_flows *rx, int first, int count, uint8_t *sym, uint8_t *er)
+int FlowsPolicy::flush_gather(Rx *rx, int first, int count, uint8_t *sym, uint8_t *er)
 {
     ldpc_amd_ctx *ctx = rx->ctx;
     const int n = rx->n, S = rx->S, W = flush_piece(S, sym);
@@ -1904,7 +1628,8 @@ static int flush_gather(ldpc_amd_fec_rx_flows *rx, int first, int count, uint8_t
     return LDPC_AMD_OK;
 }
 
-static int flush_reset(ldpc_amd_fec_rx_flows *rx, int T)
+// ONE launch for all handed-out planes, behind whatever read them: the gather, or the decode (fused or composed)
+int FlowsPolicy::flush_after(Rx *rx, bool, int T)
 {
     ldpc_amd_ctx *ctx = rx->ctx;
     const int n = rx->n, S = rx->S, W = flush_piece(S, nullptr);
@@ -1917,23 +1642,30 @@ static int flush_reset(ldpc_amd_fec_rx_flows *rx, int T)
     return LDPC_AMD_OK;
 }
 
-// the mirror of every selected flow advanced once per closed block (ldpc_amd_fec_rx_flows_flush), the host outputs, the info words
-static void flush_commit(ldpc_amd_fec_rx_flows *rx, const FlushPlan &pl, int *blocks, int *closes, int path, size_t scratch, int launches)
+void FlowsPolicy::launch_flush_sources(Rx *rx, int T, uint32_t *src, uint8_t *er)
 {
-    for (size_t j = 0; j < pl.sel.size(); j++) {
-        const int f = pl.sel[j];
-        for (int c = 0; c < pl.closes[j]; c++) {
-            rx->cur[f] = rx->next[f];
-            rx->next[f] = (rx->next[f] + 1) & 0xff;
-            rx->ccnt[f] = rx->ncnt[f];
-            rx->ncnt[f] = 0;
-            rx->cb[f] ^= 1;
-        }
-        if (closes) closes[j] = pl.closes[j];
+    hipLaunchKernelGGL(fec_rx_flush_sources, dim3(grid_for((int64_t)T * rx->n)), dim3(kThreads), 0, rx->ctx->stream, (const int32_t *)rx->fl.dev,
+                       (const uint8_t *)rx->stage_er, rx->n, T, src, er);
+}
+
+// the mirror of a listed flow advanced once per closed block (ldpc_amd_fec_rx_flows_flush)
+void FlowsPolicy::flush_commit_flow(Rx *rx, int f, int count)
+{
+    for (int c = 0; c < count; c++) {
+        rx->cur[f] = rx->next[f];
+        rx->next[f] = (rx->next[f] + 1) & 0xff;
+        rx->ccnt[f] = rx->ncnt[f];
+        rx->ncnt[f] = 0;
+        rx->cb[f] ^= 1;
     }
-    if (blocks && pl.T > 0) memcpy(blocks, pl.blocks.data(), sizeof(int) * (size_t)pl.T);
-    ldpc_amd_ctx *ctx = rx->ctx;
-    ctx->flush_info[0] = path; ctx->flush_info[1] = pl.T; ctx->flush_info[2] = (int64_t)scratch; ctx->flush_info[3] = launches;
+}
+
+// [2]: the device memory the call used: the plane numbers; with a decode the row flags and the row-source words or the scratch
+void FlowsPolicy::record_flush(ldpc_amd_ctx *ctx, int path, int T, int n, int launches, size_t scratch)
+{
+    size_t bytes = sizeof(int32_t) * (size_t)T;
+    if (path != 3) bytes += (path == 1 ? sizeof(uint32_t) * (size_t)T * n : scratch) + (size_t)T * n;
+    ctx->flush_info[0] = path; ctx->flush_info[1] = T; ctx->flush_info[2] = (int64_t)bytes; ctx->flush_info[3] = launches;
 }
 
 extern "C" {
@@ -1951,72 +1683,30 @@ int ldpc_amd_fec_rx_flows_pending(const ldpc_amd_fec_rx_flows *rx, int32_t *cur_
     return total;
 }
 
+// (the number of rounds is looked at before the list)
+static int flush_check_rounds(const ldpc_amd_fec_rx_flows *rx, const char *who, int rounds)
+{
+    if (!rx) return LDPC_AMD_EINVAL;
+    if (rounds < 1 || rounds > 2) return set_error(rx->ctx, LDPC_AMD_EINVAL, "%s: rounds must be 1 or 2 (got %d)", who, rounds);
+    return LDPC_AMD_OK;
+}
+
 int ldpc_amd_fec_rx_flows_flush_many(ldpc_amd_fec_rx_flows *rx, const int32_t *flows, int nsel, int rounds, uint8_t *sym_batch,
                                      uint8_t *erased_batch, int *blocks, int *closes)
 {
-    if (!rx) return LDPC_AMD_EINVAL;
-    ldpc_amd_ctx *ctx = rx->ctx;
     const char *who = "fec_rx_flows_flush_many";
-    FlushPlan pl;
-    int rc;
-    if ((rc = flush_plan(rx, who, flows, nsel, rounds, pl))) return rc;
-    if (!sym_batch || !erased_batch) return set_error(ctx, LDPC_AMD_EINVAL, "%s: sym_batch / erased_batch must not be null", who);
-    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!is_device_ptr(ctx, sym_batch) || !is_device_ptr(ctx, erased_batch))
-        return set_error(ctx, LDPC_AMD_EINVAL, "%s: sym_batch / erased_batch must be device pointers of device %d", who, ctx->device);
-    if (pl.T == 0) {
-        if (closes) std::fill(closes, closes + pl.sel.size(), 0);
-        return 0;
-    }
-    if ((rc = rx_upload_planes(ctx, who, rx->fl, 2 * (size_t)rx->nflows, pl.planes.data(), pl.T)) ||
-        (rc = flush_gather(rx, 0, pl.T, sym_batch, erased_batch)) || (rc = flush_reset(rx, pl.T)))
-        return rc;
-    flush_commit(rx, pl, blocks, closes, 3, sizeof(int32_t) * (size_t)pl.T, 0);
-    return pl.T;
+    const int rc = flush_check_rounds(rx, who, rounds);
+    return rc ? rc : rxf_flush_many<FlowsPolicy>(rx, who, flows, nsel, rounds, sym_batch, erased_batch, blocks, closes);
 }
 
 int ldpc_amd_fec_rx_flows_decode_flush_many(ldpc_amd_fec_rx_flows *rx, int code, const int32_t *flows, int nsel, int rounds, int max_sweeps,
                                             int do_ml, uint8_t *out, int32_t *sweeps, int32_t *residual, int32_t *status, uint8_t *erased_out,
                                             int32_t *residual_src, int *blocks, int *closes)
 {
-    if (!rx) return LDPC_AMD_EINVAL;
-    ldpc_amd_ctx *ctx = rx->ctx;
     const char *who = "fec_rx_flows_decode_flush_many";
-    FlushPlan pl;
-    int rc;
-    if ((rc = flush_plan(rx, who, flows, nsel, rounds, pl))) return rc;
-    const RxResults o{out, sweeps, residual, status, erased_out, residual_src};
-    if ((rc = rx_decode_check(ctx, rx, who, code, max_sweeps, o))) return rc;
-    const int T = pl.T;
-    if (T == 0) {
-        if (closes) std::fill(closes, closes + pl.sel.size(), 0);
-        return 0;
-    }
-    const DevCode &cd = ctx->codes[code]->dev;
-    const int n = rx->n, S = rx->S;
-    // (word-sized symbols take the composed form: the header says why)
-    const bool fused = ctx->knobs.rx_pkt != 0 && S % 16 == 0 && decode_reads_packets(ctx, cd, S);
-    const size_t frame = (size_t)n * S;
-    const int64_t chunk = rx_chunk(T, frame);
-    size_t scratch = 0;
-    if ((rc = rx_decode_reserve(ctx, T, n, frame, fused, chunk, &scratch))) return rc;
-    if ((rc = rx_upload_planes(ctx, who, rx->fl, 2 * (size_t)rx->nflows, pl.planes.data(), pl.T))) return rc;
-    DecodeArgs d = rx_decode_args(cd, n, S, max_sweeps, do_ml);
-    // no word of the table names a packet (fec_rx_flush_sources), so the packet base is never added to: any valid aligned address
-    const PacketRows pin{nullptr, rx->stage_sym, rx->stage_sym, S + kHdr};
-    auto sources = [&](uint32_t *src, uint8_t *er) -> int {
-        hipLaunchKernelGGL(fec_rx_flush_sources, dim3(grid_for((int64_t)T * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->fl.dev,
-                           (const uint8_t *)rx->stage_er, n, T, src, er);
-        LDPC_HIP_TRY(ctx, hipGetLastError());
-        return LDPC_AMD_OK;
-    };
-    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *er) { return flush_gather(rx, first, count, sym, er); };
-    int launches = 0;
-    if ((rc = rx_decode_slots(ctx, d, o, T, chunk, fused, pin, sources, gather, &launches))) return rc;
-    if ((rc = flush_reset(rx, T))) return rc;
-    flush_commit(rx, pl, blocks, closes, fused ? 1 : 2,
-                 (fused ? sizeof(uint32_t) * (size_t)T * n : scratch) + (size_t)T * n + sizeof(int32_t) * (size_t)T, launches);
-    return T;
+    const int rc = flush_check_rounds(rx, who, rounds);
+    return rc ? rc : rxf_decode_flush_many<FlowsPolicy>(rx, who, code, flows, nsel, rounds, max_sweeps, do_ml,
+                                                        RxResults{out, sweeps, residual, status, erased_out, residual_src}, blocks, closes);
 }
 
 int ldpc_amd_fec_flows_flush_info(ldpc_amd_ctx *ctx, int64_t info[4])
