@@ -1,6 +1,6 @@
 /* ldpc_erasure_amd_rs_wire.h -- Reed-Solomon on the FEC wire: a sender that turns source blocks of a registered RS code into wire
  * packets, straight or block-interleaved, and an RS decode tail on the windowed device receiver.  Everything here is additive: every
- * other entry point keeps its bytes.  Implemented in csrc/rs_wire_dev.hip (the packet encoder kernel), csrc/wire_dev.hip (the sender's
+ * other entry point keeps its bytes.  Implemented in csrc/rs_wire_dev.hip (the packet encoder and the row decoder), csrc/wire_dev.hip (the sender's
  * entry point) and csrc/rx_window_dev.hip (the receiver's), same shared library.
  *
  * Why: the paper's comparison of a long LDPC code with a short RS code on a bursty channel turns on interleaving -- a short RS code
@@ -38,10 +38,36 @@
  * push_many gives; msg, received and status are what ldpc_amd_rs_decode_frames returns for the planes push_many would have handed out
  * (first-k selection, ReedSolomonErasureCodes.m:78-81: a block with fewer than k symbols decodes to zeros, status
  * LDPC_AMD_RS_ST_SHORT).  The receiver must have been created for the RS code's (n,k) -- any window, ahead limit and depth -- else
- * LDPC_AMD_EINVAL.  One form only: the closed blocks are gathered chunk by chunk into the context's received-symbol scratch (at most
- * 256 MiB), each chunk followed by the RS decoder.  Every workspace is reserved before anything moves, and the staging planes are
- * rewritten behind the decode: a refused call leaves the receiver where it was.  RS calls, the LDPC decode calls, push_many and the
- * flushes mix freely on one object.
+ * LDPC_AMD_EINVAL.  Two paths, the same bytes:
+ *   FUSED     no row is copied: the receiver writes one source word per (block, symbol) -- the packet that won the symbol, the row of
+ *             a staging plane, or erased -- and the decoder on rows in place (below) reads the rows where they lie, the W staging
+ *             planes being one `stage` base.  Taken where that decoder applies and wins: 1 <= n - k <= 64, S >= 16 accepted by the
+ *             context's symbol-length rule, packets 8-byte and msg 4-byte aligned, knob RX_PKT not 0 -- less the shapes the composed
+ *             decoder streams already (n - k <= 32 with S a multiple of 256, or a word length from 256 up), where it is the faster.
+ *   COMPOSED  the closed blocks are gathered chunk by chunk into the context's received-symbol scratch (at most 256 MiB), each chunk
+ *             followed by the RS decoder of ldpc_amd_rs_decode_frames.  S = 1 and n - k > 64 are always composed.
+ * ldpc_amd_fec_rxw_dev_rs_decode_flush is never fused, as the LDPC flush of this object is not: its blocks lie complete in their
+ * planes and go through the scratch.  Every workspace is reserved before anything moves, and the staging planes are rewritten behind
+ * the decode: a refused call leaves the receiver where it was.  RS calls, the LDPC decode calls, push_many and the flushes mix freely
+ * on one object.
+ *
+ * THE DECODER ON ROWS IN PLACE.  ldpc_amd_rs_decode_rows_dev (ldpc_erasure_amd_rs_rows.h, included here) is the decoder the fused
+ * receiver runs, on its own: src holds one source word per (block, symbol) -- the payload of packet p, LDPC_AMD_ROW_STAGED | i for row
+ * i of `stage`, or LDPC_AMD_ROW_ERASED.  msg, received and status are what ldpc_amd_rs_decode_frames returns for the frames the words
+ * describe, a word that names a packet >= npackets or a staged row >= nstage_rows taken as erased (no row outside the two arrays is
+ * ever fetched); erased_out, if given, receives the flags after that vetting.  Two words may name the same row.  A plan kernel
+ * selects the first k usable rows of every block, inverts the r x r system of its missing source rows once, on bytes, and writes a
+ * k x r coefficient table; a streaming kernel of the sender's shape then reads every selected row once, where it lies, stores the
+ * source rows and multiplies into r accumulators in registers -- as many as the block misses, by buckets of 8, 16, 24, 32, 48, 64.
+ * The tables live in a context scratch of at most 256 MiB, reserved before anything is enqueued; more blocks than it holds are
+ * decoded in chunks.  nblocks == 0 is LDPC_AMD_OK and touches nothing.  Refusals come before anything is enqueued and leave the
+ * context usable and the outputs untouched:
+ *   LDPC_AMD_ENOCODE  unknown RS handle
+ *   LDPC_AMD_EINVAL   a negative count, S < 1, nblocks * n >= 2^31, npackets or nstage_rows >= 2^31, null or host pointers (packets /
+ *                     stage may be NULL with a count of 0), msg overlapping packets, stage or src
+ *   LDPC_AMD_EUNSUP   a shape the kernel does not take -- S = 1, S refused by the context's symbol-length rule, n - k > 64, packets
+ *                     not 8-byte aligned, stage, msg or src not 4-byte aligned, knob RX_PKT 0.  This call has no composed fallback.
+ * A null context is LDPC_AMD_EINVAL before any device is touched.
  *
  * THE CLOSE RULE ON SHORT BLOCKS.  A receiver made without a rule follows the default rule: it closes a block early when it holds more than k + round(0.2 (n-k)) symbols and later
  * blocks have sent more than 100 packets, or more than k + round(0.8 (n-k)) and more than 10.  For RS(255,192) these are 205 and 242 of
@@ -60,6 +86,7 @@
 
 #include "ldpc_erasure_amd.h"
 #include "ldpc_erasure_amd_interleave.h"
+#include "ldpc_erasure_amd_rs_rows.h"
 #include "ldpc_erasure_amd_rx_window.h"
 
 #ifdef __cplusplus
@@ -91,7 +118,8 @@ int ldpc_amd_fec_rxw_dev_rs_decode_flush(ldpc_amd_fec_rxw_dev *rx, int rs, uint8
                                          uint8_t *erased_batch, int *blocks);
 
 /* info[0]: blocks RS-decoded by the last such call of the context; info[1]: RS decode launches of that call; info[2]: bytes of
- * received-symbol scratch it used; info[3]: reserved, 0. */
+ * scratch it used -- received symbols (composed) or source words and per-block tables (fused); info[3]: its path (0 none yet,
+ * 1 fused, 2 composed). */
 int ldpc_amd_fec_rs_receiver_info(ldpc_amd_ctx *ctx, int64_t info[4]);
 
 #ifdef __cplusplus

@@ -82,6 +82,9 @@ EXPORTS_RS_WIRE = [
     "ldpc_amd_fec_rxw_dev_rs_decode_flush", "ldpc_amd_fec_rs_receiver_info",
 ]
 FEC_CLASS_RS = 2   # LDPC_AMD_FEC_CLASS_RS
+# include/ldpc_erasure_amd_rs_rows.h: the RS decoder on rows in place, and the two constants of a source word
+EXPORTS_RS_ROWS = ["ldpc_amd_rs_decode_rows_dev"]
+ROW_STAGED, ROW_ERASED = 0x80000000, 0xFFFFFFFF   # LDPC_AMD_ROW_STAGED | row of `stage`; LDPC_AMD_ROW_ERASED
 EXPORTS_RECEIVER = ["ldpc_amd_fec_rx_dev_decode_many", "ldpc_amd_fec_rx_dev_decode_flush", "ldpc_amd_fec_receiver_info"]
 RECEIVER_PATHS = ("none", "fused", "composed")
 # every symbol include/ldpc_erasure_amd_words.h declares (word-sized symbols: any S that is a multiple of 4)
@@ -385,6 +388,8 @@ def load_library():
         L.ldpc_amd_fec_rxw_dev_rs_decode_many.argtypes = [vp, i32, vp, i64, vp, vp, vp, vp, vp, i32, C.POINTER(i64)]
         L.ldpc_amd_fec_rxw_dev_rs_decode_flush.argtypes = [vp, i32, vp, vp, vp, vp, vp]
         L.ldpc_amd_fec_rs_receiver_info.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "ldpc_amd_rs_decode_rows_dev"):   # (absent from the older builds tools/ab_lib.py loads)
+        L.ldpc_amd_rs_decode_rows_dev.argtypes = [vp, i32, i32, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp]
     if hasattr(L, "ldpc_amd_fec_tx_flows_ilv_layout"):   # (absent from the older builds tools/ab_lib.py loads)
         L.ldpc_amd_fec_tx_flows_ilv_layout.argtypes = [i32, vp, i32, vp, i32, i32, vp, vp]
         L.ldpc_amd_fec_tx_flows_ilv_layout.restype = i64
@@ -890,6 +895,33 @@ class Context:
                                                       _ptr(status), DEVICE_PTRS if dev else 0), "rs_decode_frames")
         return RsDecodedFrames(msg, received, status)
 
+    def rs_decode_rows(self, rs, src, packets=None, stage=None, out=None, erased_out=None):
+        """The RS decoder on rows in place (include/ldpc_erasure_amd_rs_rows.h).  src: torch uint32 / int32 [B][n] on this context's
+        device, one source word per (block, symbol): p = the payload of packets[p], ROW_STAGED | i = stage[i], ROW_ERASED; packets
+        torch uint8 [P][8+S], stage torch uint8 [R][S] (each may be None).  A word that names a packet >= P or a staged row >= R
+        counts as erased.  -> RsDecodedFrames(msg [B,k,S], received [B] int32, status [B] int32): what rs_decode_frames returns for
+        the frames the words describe.  `out`: the (msg, received, status) to write into; erased_out: torch uint8 [B][n] that
+        receives the flags after vetting.  Asynchronous on the context's stream."""
+        import torch
+        n, k = self.rs_info(rs)
+        B = src.shape[0]
+        assert _is_torch(src) and src.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and tuple(src.shape) == (B, n) and src.is_contiguous()
+        assert packets is not None or stage is not None, "packets or stage: one of them says what S is"
+        S = packets.shape[1] - 8 if packets is not None else stage.shape[1]
+        for a, width in ((packets, 8 + S), (stage, S)):
+            assert a is None or (_is_torch(a) and a.dtype == torch.uint8 and a.ndim == 2 and a.shape[1] == width and a.is_contiguous())
+        if out is None:
+            out = (torch.empty((B, k, S), dtype=torch.uint8, device=src.device),
+                   torch.empty((B,), dtype=torch.int32, device=src.device), torch.empty((B,), dtype=torch.int32, device=src.device))
+        msg, received, status = out
+        assert tuple(msg.shape) == (B, k, S) and msg.is_contiguous() and tuple(received.shape) == (B,) and tuple(status.shape) == (B,)
+        assert erased_out is None or (tuple(erased_out.shape) == (B, n) and erased_out.is_contiguous())
+        self._check(self._L.ldpc_amd_rs_decode_rows_dev(self._h, rs, S, B, _ptr(src), _ptr(packets) if packets is not None else None,
+                                                        0 if packets is None else packets.shape[0], _ptr(stage) if stage is not None else None,
+                                                        0 if stage is None else stage.shape[0], _ptr(msg), _ptr(received), _ptr(status),
+                                                        _ptr(erased_out) if erased_out is not None else None), "rs_decode_rows_dev")
+        return RsDecodedFrames(msg, received, status)
+
     def rs_bad_blocks(self):
         """Blocks of the last rs_decode whose positions were malformed (decoded to zeros).  Synchronises."""
         c = C.c_longlong(0)
@@ -1055,8 +1087,9 @@ class Context:
 
     def fec_rs_receiver_info(self):
         """{"blocks": blocks RS-decoded by the last FecRxWindow.rs_decode_many / rs_decode_flush of this context, "launches": its RS
-        decode launches, "scratch_bytes": received-symbol scratch it used}."""
-        return self._info("fec_rs_receiver_info", C.c_int64, ("blocks", "launches", "scratch_bytes"))
+        decode launches, "scratch_bytes": the scratch it used (received symbols, or source words and per-block tables), "path": "none" |
+        "fused" | "composed"}."""
+        return self._info("fec_rs_receiver_info", C.c_int64, ("blocks", "launches", "scratch_bytes", "path"), RECEIVER_PATHS)
 
     def fec_tx_rs(self, rs, S, depth=1, block0=0):
         """A sender of RS blocks that numbers them across calls and emits them block-interleaved (FecTxRs)."""

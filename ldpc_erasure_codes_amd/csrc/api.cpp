@@ -887,7 +887,7 @@ void ldpc_amd_cleanup(ldpc_amd_ctx *ctx)
     Scratch *all[] = {&ctx->sched, &ctx->mlws, &ctx->mlstate, &ctx->mlops, &ctx->mlrec, &ctx->mllist, &ctx->biglist, &ctx->encctr, &ctx->stage_in, &ctx->stage_er,
                       &ctx->stage_out, &ctx->stage_i32, &ctx->schedpull, &ctx->schedlists, &ctx->rsws, &ctx->rsbad, &ctx->fpga_erased, &ctx->fpga_stats,
                       &ctx->rssel, &ctx->frstatus, &ctx->stage_fr, &ctx->sender_cw, &ctx->rx_sym, &ctx->rx_er, &ctx->rx_src, &ctx->demux_tab, &ctx->txf_desc,
-                      &ctx->dgram_off, &ctx->dgram_len, &ctx->wire_len, &ctx->rsw_tab, &ctx->rsw_coef};
+                      &ctx->dgram_off, &ctx->dgram_len, &ctx->wire_len, &ctx->rsw_tab, &ctx->rsw_coef, &ctx->rsr_plan};
     for (Scratch *s : all) scratch_free(*s);
     for (auto &v : ctx->prof_events)
         for (auto &pr : v) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }

@@ -19,13 +19,13 @@ declare -A DEPS=(
   [api.cpp]="$HERE/builtin_codes_gen.inc"
   [wire.cpp]=""
   [multi.hip]=""
-  [wire_dev.hip]="$HERE/fec_header_dev.h $HERE/rx_host.h $HERE/rx_flows_host.h $HERE/flows_demux_dev.h $ROOT/include/ldpc_erasure_amd_rx_window.h $ROOT/include/ldpc_erasure_amd_interleave.h $ROOT/include/ldpc_erasure_amd_interleave_flows.h $ROOT/include/ldpc_erasure_amd_rx_window_flows.h $ROOT/include/ldpc_erasure_amd_rs_wire.h"
-  [rs_wire_dev.hip]="$HERE/fec_header_dev.h"
+  [wire_dev.hip]="$HERE/fec_header_dev.h $HERE/rx_host.h $HERE/rx_flows_host.h $HERE/flows_demux_dev.h $ROOT/include/ldpc_erasure_amd_rx_window.h $ROOT/include/ldpc_erasure_amd_interleave.h $ROOT/include/ldpc_erasure_amd_interleave_flows.h $ROOT/include/ldpc_erasure_amd_rx_window_flows.h $ROOT/include/ldpc_erasure_amd_rs_wire.h $ROOT/include/ldpc_erasure_amd_rs_rows.h"
+  [rs_wire_dev.hip]="$HERE/fec_header_dev.h $ROOT/include/ldpc_erasure_amd_rs_rows.h"
   [datagram_dev.hip]="$HERE/dgram_scan_dev.h"
   [wire_ragged_dev.hip]="$HERE/dgram_scan_dev.h"
   [link_dev.hip]="$HERE/dgram_scan_dev.h $ROOT/include/ldpc_erasure_amd_link.h"
   [rx_window.cpp]="$ROOT/include/ldpc_erasure_amd_rx_window.h $ROOT/include/ldpc_erasure_amd_rx_rule.h $ROOT/include/ldpc_erasure_amd_interleave.h"
-  [rx_window_dev.hip]="$ROOT/include/ldpc_erasure_amd_rx_window.h $ROOT/include/ldpc_erasure_amd_rx_rule.h $ROOT/include/ldpc_erasure_amd_rs_wire.h $ROOT/include/ldpc_erasure_amd_interleave.h $HERE/rx_window_scan_dev.h $HERE/rx_host.h"
+  [rx_window_dev.hip]="$ROOT/include/ldpc_erasure_amd_rx_window.h $ROOT/include/ldpc_erasure_amd_rx_rule.h $ROOT/include/ldpc_erasure_amd_rs_wire.h $ROOT/include/ldpc_erasure_amd_rs_rows.h $ROOT/include/ldpc_erasure_amd_interleave.h $HERE/rx_window_scan_dev.h $HERE/rx_host.h"
   [rx_window_flows_dev.hip]="$ROOT/include/ldpc_erasure_amd_rx_window.h $ROOT/include/ldpc_erasure_amd_rx_rule.h $ROOT/include/ldpc_erasure_amd_interleave.h $ROOT/include/ldpc_erasure_amd_interleave_flows.h $ROOT/include/ldpc_erasure_amd_rx_window_flows.h $ROOT/include/ldpc_erasure_amd_rx_window_flows_mixed.h $HERE/rx_window_scan_dev.h $HERE/rx_host.h $HERE/rx_flows_host.h $HERE/flows_demux_dev.h"
 )
 pids=()

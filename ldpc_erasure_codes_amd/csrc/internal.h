@@ -274,9 +274,12 @@ struct ldpc_amd_ctx {
     // fec_rs_encode_packets_dev (include/ldpc_erasure_amd_rs_wire.h): the packed-multiply table and the padded coefficients the packet
     // encoder of rs_wire_dev.hip reads (its last call: tx_last[kTxRs])
     ldpc_amd::Scratch rsw_tab, rsw_coef;
-    // fec_rxw_dev_rs_decode_many / _rs_decode_flush (rx_window_dev.hip): blocks, RS decode launches and scratch bytes of the last call
-    // (ldpc_amd_fec_rs_receiver_info)
+    // fec_rxw_dev_rs_decode_many / _rs_decode_flush (rx_window_dev.hip): blocks, RS decode launches, scratch bytes and path (0 none,
+    // 1 fused, 2 composed) of the last call (ldpc_amd_fec_rs_receiver_info)
     int64_t rsrx_info[4] = {0, 0, 0, 0};
+    // the RS decoder on rows in place (rs_wire_dev.hip, launch_rs_decode_rows): per block of one chunk its header, the records of its
+    // selected rows and its coefficient table (at most 256 MiB)
+    ldpc_amd::Scratch rsr_plan;
 };
 
 namespace ldpc_amd {
@@ -369,6 +372,19 @@ int launch_rs_encode(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks
 // take, max_stride * (8 + S) beyond 32 bits.
 int launch_rs_encode_packets(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks, const uint8_t *src, const void *desc, int64_t max_stride,
                              uint8_t *packets);
+// The RS decoder on rows in place (rs_wire_dev.hip; include/ldpc_erasure_amd_rs_rows.h): the rows of block b lie where the words
+// rows.src[b][n] say (PacketRows above; rows.stage holds nstage_rows rows of S bytes, rows.packets npackets packets of rows.plen = 8 + S
+// bytes), a word that points outside either array counts as erased.  msg [nblocks][k][S]; er_out [nblocks][n] the flags after
+// vetting, received and status [nblocks]: each may be nullptr.  First-k selection as launch_rs_decode_frames.
+// rs_decode_rows_takes: the shapes the kernels take -- launch_rs_decode_rows returns kDecodeNotFused, with nothing launched, where it
+// says no.  rs_decode_rows_fused: the one eligibility rule of the receivers -- takes, less the shapes where the composed path is the
+// faster one.  rs_decode_rows_reserve: every workspace nblocks blocks will need (rx_host.h, rule 1), *bytes what one chunk uses.
+constexpr int kDecodeNotFused = 1;
+bool rs_decode_rows_takes(const ldpc_amd_ctx *ctx, const HostRs &rs, int S, const uint8_t *packets, const uint8_t *stage, const uint8_t *msg);
+bool rs_decode_rows_fused(const ldpc_amd_ctx *ctx, const HostRs &rs, int S, const uint8_t *packets, const uint8_t *stage, const uint8_t *msg);
+int rs_decode_rows_reserve(ldpc_amd_ctx *ctx, const HostRs &rs, int64_t nblocks, size_t *bytes);
+int launch_rs_decode_rows(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks, const PacketRows &rows, int64_t npackets,
+                          int64_t nstage_rows, uint8_t *er_out, uint8_t *msg, int32_t *received, int32_t *status, int *launches = nullptr);
 int launch_fpga_stats(ldpc_amd_ctx *ctx, const DevCode &code, int rs_n, int rs_k, int64_t nframes,
                       const uint8_t *erased0, const int32_t *residual_k, unsigned long long *stats /* [2], accumulated */);
 

@@ -1,5 +1,6 @@
 // rs_wire_dev.hip -- the Reed-Solomon sender of the FEC wire (include/ldpc_erasure_amd_rs_wire.h): source blocks -> wire packets in one
-// kernel, every block placed and numbered by the 16-byte descriptor the descriptor-driven senders of wire_dev.hip use.
+// kernel, every block placed and numbered by the 16-byte descriptor the descriptor-driven senders of wire_dev.hip use.  Behind it the
+// decoder of the other end (include/ldpc_erasure_amd_rs_rows.h): the same loop on a per-block table, its rows read where they lie.
 //
 // codeword = source * [I | P] (Matlab/Test_My_RS_Decode.m:48).  rs_encode_kernel (rs_kernels.inc) forms every parity row by reading all k
 // source rows again: (n-k) k row reads per block, and the codewords then go through a packetiser.  Here, as in the streaming phase of
@@ -20,6 +21,7 @@
 #include <algorithm>
 #include <array>
 
+#include "../../include/ldpc_erasure_amd_rs_rows.h"
 #include "fec_header_dev.h"
 #include "internal.h"
 
@@ -155,9 +157,382 @@ void launch_q(ldpc_amd_ctx *ctx, unsigned grid, const RswArgs &a)
     hipLaunchKernelGGL(rs_encode_packets_kernel<Q>, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, a);
 }
 
+// ---- the decoder on rows in place (include/ldpc_erasure_amd_rs_rows.h) ---------------------------------------------------------------
+// msg = the k source rows of a block, from any k of its n rows.  With the first k usable rows selected (ReedSolomonErasureCodes.m:78-81),
+// nsys of them source rows and r = k - nsys repair rows of columns j_0 .. j_{r-1}, and u_0 .. u_{r-1} the missing source positions:
+//     msg[u] = sum over the selected rows t of D[t][u] * row_t,
+//     D[nsys + q][u] = Minv[u][q],   D[t][u] = sum_q Minv[u][q] * P[pos_t][j_q] for a received source row,   M[q][t] = P[u_t][j_q].
+// rs_rows_plan_kernel vets and selects, inverts M on bytes and writes D per block; rs_decode_rows_kernel is then the encoder's loop on
+// another table: one wavefront per (block, 256-byte slice), every selected row read once WHERE IT LIES -- the payload of a packet or a
+// row of the staging planes, by its source word (internal.h, PacketRows) -- a source row stored to msg, and multiplied into the r
+// accumulators.  One pass, no second phase (DESIGN.md 4.4d has the reason and the numbers).
+constexpr int kRMax = 64;                       // parity depth n - k the decoder takes
+constexpr int kRowsThreads = 256;               // threads of a plan workgroup
+constexpr uint8_t kNoLog = 0xFF;                // the plan's logs run 0 .. 254
+constexpr size_t kRowsScratchMax = (size_t)256 << 20;
+
+// the accumulators a block runs with follow ITS r, by buckets: 0 (a copy), <= 8, 16, 24, 32, 48, 64
+__host__ __device__ constexpr int rows_bucket(int r) { return r <= 8 ? 8 : r <= 16 ? 16 : r <= 24 ? 24 : r <= 32 ? 32 : r <= 48 ? 48 : 64; }
+
+// Per block of a chunk: hdr[4] = {nsys, r, usable rows, status}; rec[k + R][2] = {source word, position} of the k selected rows, then
+// {0, position} of the r missing source rows; tab[k][dstride] = D, rows padded with zeros to dstride = rows_bucket(R) bytes.
+struct RowsPlanArgs {
+    int n, k, dstride;
+    int64_t nblocks;
+    const uint32_t *src;    // [nblocks][n] source words
+    int64_t npackets, nstage_rows;
+    const uint8_t *g;       // [k][n] the generator
+    uint32_t *hdr, *rec;
+    uint8_t *tab;
+    uint8_t *er_out;        // [nblocks][n] or nullptr
+    int32_t *received, *status;   // [nblocks] or nullptr
+};
+
+__global__ __launch_bounds__(kRowsThreads) void rs_rows_plan_kernel(RowsPlanArgs a)
+{
+    __shared__ uint8_t lg[256], ex[512], pres[256], fcol[kRMax];
+    __shared__ uint8_t A[kRMax * 2 * kRMax];    // [r][2 r]: [M | I] -> [I | M^-1]
+    __shared__ uint8_t GL[(255 - kRMax) * kRMax];   // [nsys][r], nsys + r = k <= 255, r <= kRMax
+    __shared__ uint16_t selpos[256], upos[kRMax];
+    __shared__ uint32_t selword[256];
+    __shared__ int misc[4];
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    const int n = a.n, k = a.k, R = n - k;
+    if (tid == 0) {   // log / antilog of GF(256), polynomial kPrimPoly
+        int x = 1;
+        for (int i = 0; i < 255; i++) {
+            ex[i] = ex[i + 255] = (uint8_t)x;
+            lg[x] = (uint8_t)i;
+            x <<= 1;
+            if (x & 0x100) x ^= kPrimPoly;
+        }
+        ex[510] = ex[0]; ex[511] = ex[1]; lg[0] = 0;
+    }
+    auto mul = [&](uint8_t x, uint8_t y) -> uint8_t { return (x && y) ? ex[lg[x] + lg[y]] : (uint8_t)0; };
+    const uint64_t below = (1ull << lane) - 1ull;
+    for (int64_t blk = blockIdx.x; blk < a.nblocks; blk += gridDim.x) {
+        __syncthreads();   // (the tables; the block before is through with the shared arrays)
+        pres[tid] = 0;
+        if (tid < 64) {    // vet every word, take the first k usable positions in ascending order (rs_select_kernel's rule)
+            const uint32_t *w = a.src + blk * n;
+            int cnt = 0;
+            for (int j0 = 0; j0 < n; j0 += 64) {
+                const int j = j0 + lane;
+                const uint32_t word = j < n ? w[j] : kRowErased;
+                const uint32_t idx = word & ~kRowStaged;
+                const bool ok = j < n && word != kRowErased && ((word & kRowStaged) ? (int64_t)idx < a.nstage_rows : (int64_t)idx < a.npackets);
+                if (j < n && a.er_out) a.er_out[blk * n + j] = ok ? 0 : 1;
+                const uint64_t mask = __ballot(ok);
+                const int pos = cnt + __popcll(mask & below);
+                if (ok && pos < k) {
+                    selpos[pos] = (uint16_t)j;
+                    selword[pos] = word;
+                }
+                cnt += __popcll(mask);
+            }
+            if (lane == 0) misc[0] = cnt;
+        }
+        __syncthreads();
+        const int cnt = misc[0];
+        uint32_t *hdr = a.hdr + blk * 4;
+        if (cnt < k) {     // short: no solve, the stream kernel stores zeros
+            if (tid == 0) {
+                hdr[0] = 0; hdr[1] = 0; hdr[2] = (uint32_t)cnt; hdr[3] = LDPC_AMD_RS_ST_SHORT;
+                if (a.received) a.received[blk] = cnt;
+                if (a.status) a.status[blk] = LDPC_AMD_RS_ST_SHORT;
+            }
+            continue;
+        }
+        for (int t = tid; t < k; t += kRowsThreads)
+            if (selpos[t] < k) pres[selpos[t]] = 1;
+        __syncthreads();
+        if (tid < 64) {    // the missing source positions, ascending
+            int miss = 0;
+            for (int u0 = 0; u0 < k; u0 += 64) {
+                const int u = u0 + lane;
+                const bool gone = u < k && pres[u] == 0;
+                const uint64_t mask = __ballot(gone);
+                const int pos = miss + __popcll(mask & below);
+                if (gone && pos < kRMax) upos[pos] = (uint16_t)u;
+                miss += __popcll(mask);
+            }
+            if (lane == 0) { misc[1] = miss; misc[2] = 0; }
+        }
+        __syncthreads();
+        const int r = min(misc[1], min(R, kRMax)), nsys = k - r, W2 = 2 * r;   // (r <= R: the k selected rows hold k - nsys repair rows)
+        // selected repair row q is column selpos[nsys + q] of the generator: M[q][t] = g[u_t][that column]
+        for (int i = tid; i < r * W2; i += kRowsThreads) {
+            const int q = i / W2, c = i - q * W2;
+            A[i] = c < r ? a.g[(int)upos[c] * n + selpos[nsys + q]] : (uint8_t)(c - r == q);
+        }
+        for (int c = 0; c < r; c++) {   // Gauss-Jordan, the first non-zero pivot (rs_decode_kernel)
+            __syncthreads();
+            if (tid == 0) {
+                int p = c;
+                while (p < r && A[p * W2 + c] == 0) p++;
+                misc[3] = p < r ? p : -1;
+            }
+            __syncthreads();
+            const int p = misc[3];
+            if (p < 0) {   // singular: not an MDS generator.  The block is handed out as short.
+                if (tid == 0) misc[2] = 1;
+                break;
+            }
+            const uint8_t ipiv = ex[255 - lg[A[p * W2 + c]]];
+            __syncthreads();
+            if (tid < W2) {   // rows p and c change places, the pivot row scaled to a leading one
+                const uint8_t top = A[c * W2 + tid];
+                A[c * W2 + tid] = mul(A[p * W2 + tid], ipiv);
+                if (p != c) A[p * W2 + tid] = top;
+            }
+            __syncthreads();
+            if (tid < r) fcol[tid] = tid == c ? (uint8_t)0 : A[tid * W2 + c];
+            __syncthreads();
+            for (int i = tid; i < r * W2; i += kRowsThreads) {
+                const int row = i / W2, col = i - row * W2;
+                const uint8_t f = fcol[row];
+                if (f) A[i] ^= mul(f, A[c * W2 + col]);
+            }
+        }
+        __syncthreads();
+        const bool singular = misc[2] != 0;
+        if (tid == 0) {
+            hdr[0] = singular ? 0u : (uint32_t)nsys; hdr[1] = singular ? 0u : (uint32_t)r; hdr[2] = (uint32_t)cnt;
+            hdr[3] = singular ? LDPC_AMD_RS_ST_SHORT : LDPC_AMD_RS_ST_DECODED;
+            if (a.received) a.received[blk] = cnt;
+            if (a.status) a.status[blk] = singular ? LDPC_AMD_RS_ST_SHORT : LDPC_AMD_RS_ST_DECODED;
+        }
+        if (singular) continue;
+        uint32_t *rec = a.rec + blk * (int64_t)(k + R) * 2;
+        for (int t = tid; t < k + r; t += kRowsThreads) {
+            rec[2 * t] = t < k ? selword[t] : 0u;
+            rec[2 * t + 1] = t < k ? selpos[t] : upos[t - k];
+        }
+        // D, with every product out of the LDS: the logs of Minv over the left half of A (the identity by now), the logs of the
+        // generator entries P[pos_t][j_q] in GL; kNoLog stands for the log of zero
+        for (int i = tid; i < r * r; i += kRowsThreads) {
+            const int u = i / r, q = i - u * r;
+            const uint8_t m = A[u * W2 + r + q];
+            A[u * W2 + q] = m ? lg[m] : kNoLog;
+        }
+        for (int i = tid; i < nsys * r; i += kRowsThreads) {
+            const int t = i / r, q = i - t * r;
+            const uint8_t c = a.g[(int)selpos[t] * n + selpos[nsys + q]];
+            GL[i] = c ? lg[c] : kNoLog;
+        }
+        __syncthreads();
+        uint8_t *tab = a.tab + blk * (int64_t)k * a.dstride;
+        for (int i = tid; i < nsys * r; i += kRowsThreads) {       // a received source row: D[t][u] = sum_q Minv[u][q] P[pos_t][j_q]
+            const int t = i / r, u = i - t * r;
+            const uint8_t *ml = A + u * W2, *gl = GL + t * r;
+            uint8_t d = 0;
+            for (int q = 0; q < r; q++) {
+                const uint8_t x = ml[q], y = gl[q];
+                if (x != kNoLog && y != kNoLog) d ^= ex[x + y];
+            }
+            tab[t * a.dstride + u] = d;
+        }
+        for (int i = tid; i < r * r; i += kRowsThreads) {          // a selected repair row: D[nsys + q][u] = Minv[u][q]
+            const int q = i / r, u = i - q * r;
+            tab[(nsys + q) * a.dstride + u] = A[u * W2 + r + q];
+        }
+        const int pad = a.dstride - r;                              // the columns past r: zero coefficients
+        for (int i = tid; i < k * pad; i += kRowsThreads) {
+            const int t = i / pad, u = r + (i - t * pad);
+            tab[t * a.dstride + u] = 0;
+        }
+    }
+}
+
+struct RowsArgs {
+    int k, nrec, S, nslices, dstride;   // nrec = k + R records per block
+    int64_t nblocks;
+    const uint32_t *mul3;   // [256][8]
+    const uint32_t *hdr, *rec;
+    const uint8_t *tab;
+    const uint8_t *packets, *stage;   // packets of 8 + S bytes, 8-byte aligned; rows of S bytes, 4-byte aligned
+    uint8_t *msg;                     // [nblocks][k][S], 4-byte aligned
+};
+
+// One decoded block's slice with Q >= r accumulators (Q = 0: every source row arrived, a copy).  Row t + 1 is in flight while row t is
+// multiplied, and the record of row t + 2 -- where it lies -- is on its way from the scalar cache.
+template <int Q>
+__device__ __forceinline__ void rows_block(const RowsArgs &a, cu32 *rec, cu32 *tab, cu32 *mul3, uint8_t *mrow, int nsys, int r, bool active, uint32_t off)
+{
+    const int k = a.k;
+    const uint32_t S = (uint32_t)a.S, plen = S + kHdr;
+    auto row = [&](uint32_t w) {   // w wave-uniform and vetted by the plan: inside its array
+        const uint8_t *p = (w & kRowStaged) ? a.stage + (uint64_t)(w & ~kRowStaged) * S : a.packets + (uint64_t)w * plen + kHdr;
+        return reinterpret_cast<const uint32_t *>(p + off);
+    };
+    uint32_t acc[Q > 0 ? Q : 1];
+#pragma unroll
+    for (int q = 0; q < Q; q++) acc[q] = 0u;
+    const uint32_t cstep = (uint32_t)a.dstride >> 2;
+    const int t1 = k > 1 ? 1 : 0;
+    uint32_t vcur = active ? __builtin_nontemporal_load(row(rec[0])) : 0u;
+    uint32_t pcur = rec[1], wnxt = rec[2 * t1], pnxt = rec[2 * t1 + 1];
+    for (int t = 0; t < k; t++) {
+        // (clamped: the row past the end is the last one again, as in the encoder)
+        const uint32_t vnxt = active ? __builtin_nontemporal_load(row(wnxt)) : 0u;
+        const int t2 = t + 2 < k ? t + 2 : k - 1;
+        const uint32_t w2 = rec[2 * t2], p2 = rec[2 * t2 + 1];
+        if (t < nsys && active) __builtin_nontemporal_store(vcur, reinterpret_cast<uint32_t *>(mrow + (uint64_t)pcur * S));
+        if constexpr (Q > 0) {
+            uint32_t cw[Q / 4];
+#pragma unroll
+            for (int j = 0; j < Q / 4; j++) cw[j] = tab[(uint32_t)t * cstep + j];
+            const Sel3 sel = gfsel(vcur);
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const uint32_t c = (cw[q >> 2] >> (8 * (q & 3))) & 0xffu;
+                acc[q] = gfmac4_sel(acc[q], load_multab(mul3, c), sel);
+            }
+        }
+        vcur = vnxt; pcur = pnxt; wnxt = w2; pnxt = p2;
+    }
+#pragma unroll
+    for (int q = 0; q < Q; q++)
+        if (q < r && active) __builtin_nontemporal_store(acc[q], reinterpret_cast<uint32_t *>(mrow + (uint64_t)rec[2 * (k + q) + 1] * S));
+}
+
+__global__ __launch_bounds__(64 * kWaves) void rs_decode_rows_kernel(RowsArgs a)
+{
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int k = a.k, S = a.S;
+    cu32 *mul3 = as_const(a.mul3);
+    const int64_t nitems = a.nblocks * a.nslices;
+    for (int64_t item = (int64_t)blockIdx.x * kWaves + wave; item < nitems; item += (int64_t)gridDim.x * kWaves) {
+        const int64_t blk = item / a.nslices;
+        const int sl = (int)(item - blk * a.nslices);
+        const uint32_t off = (S >= kSlice ? min((uint32_t)sl * kSlice, (uint32_t)(S - kSlice)) : 0u) + (uint32_t)lane * 4u;
+        const bool active = off < (uint32_t)S;
+        cu32 *hdr = as_const(a.hdr + blk * 4);
+        const int nsys = (int)hdr[0], r = (int)hdr[1];
+        uint8_t *mrow = a.msg + (uint64_t)blk * (uint64_t)k * (uint64_t)S + off;
+        if (hdr[3] != (uint32_t)LDPC_AMD_RS_ST_DECODED) {   // short: zeros over all k rows
+            for (int t = 0; t < k; t++)
+                if (active) __builtin_nontemporal_store(0u, reinterpret_cast<uint32_t *>(mrow + (uint64_t)t * (uint32_t)S));
+            continue;
+        }
+        cu32 *rec = as_const(a.rec + blk * a.nrec * 2);
+        cu32 *tab = as_const(a.tab + blk * (int64_t)k * a.dstride);
+        // wave-uniform: r came through a scalar load
+        if (r == 0) rows_block<0>(a, rec, tab, mul3, mrow, nsys, r, active, off);
+        else if (r <= 8) rows_block<8>(a, rec, tab, mul3, mrow, nsys, r, active, off);
+        else if (r <= 16) rows_block<16>(a, rec, tab, mul3, mrow, nsys, r, active, off);
+        else if (r <= 24) rows_block<24>(a, rec, tab, mul3, mrow, nsys, r, active, off);
+        else if (r <= 32) rows_block<32>(a, rec, tab, mul3, mrow, nsys, r, active, off);
+        else if (r <= 48) rows_block<48>(a, rec, tab, mul3, mrow, nsys, r, active, off);
+        else rows_block<64>(a, rec, tab, mul3, mrow, nsys, r, active, off);
+    }
+}
+
+// the packed-multiply table of the context, uploaded once
+int rsw_table(ldpc_amd_ctx *ctx, const char *who)
+{
+    if (ctx->rsw_tab.p) return LDPC_AMD_OK;
+    static const std::array<uint32_t, 256 * 8> tab = [] {   // built once for the process, never freed: the copy may read it later
+        std::array<uint32_t, 256 * 8> t{};
+        build_mul3_tables(t.data());
+        return t;
+    }();
+    int rc;
+    if ((rc = scratch_reserve(ctx, ctx->rsw_tab, sizeof(tab)))) return rc;
+    if (hipMemcpyAsync(ctx->rsw_tab.p, tab.data(), sizeof(tab), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(ctx->rsw_tab.p);
+        ctx->rsw_tab = Scratch{};
+        return set_error(ctx, LDPC_AMD_EHIP, "%s: the multiply table could not be uploaded", who);
+    }
+    return LDPC_AMD_OK;
+}
+
+// bytes of plan scratch per block, and where the three arrays of a chunk of `count` blocks begin
+struct RowsLayout {
+    size_t per_block, o_rec, o_tab, bytes;
+    int dstride;
+    int64_t chunk;
+};
+RowsLayout rows_layout(const HostRs &rs, int64_t nblocks)
+{
+    const int R = rs.n - rs.k;
+    RowsLayout l{};
+    l.dstride = rows_bucket(R);
+    l.per_block = 16 + (size_t)rs.n * 8 + (size_t)rs.k * l.dstride;
+    l.chunk = std::max<int64_t>(1, std::min<int64_t>(nblocks, (int64_t)((kRowsScratchMax - 512) / l.per_block)));
+    l.o_rec = ((size_t)l.chunk * 16 + 255) & ~(size_t)255;
+    l.o_tab = (l.o_rec + (size_t)l.chunk * rs.n * 8 + 255) & ~(size_t)255;
+    l.bytes = l.o_tab + (size_t)l.chunk * rs.k * l.dstride;
+    return l;
+}
+
 }  // namespace
 
 namespace ldpc_amd {
+
+bool rs_decode_rows_takes(const ldpc_amd_ctx *ctx, const HostRs &rs, int S, const uint8_t *packets, const uint8_t *stage, const uint8_t *msg)
+{
+    const int R = rs.n - rs.k;
+    if (ctx->knobs.rx_pkt == 0 || R < 1 || R > kRMax || rs.n > 256) return false;
+    if (S < 16 || (S & 3) != 0 || !symbol_len_ok(ctx, S)) return false;   // every access is a dword one: the word form needs nothing extra
+    // (row addresses are 64-bit products of a word below 2^31 and 8 + S or S: any array the words can name is addressable)
+    return ((uintptr_t)packets & 7) == 0 && ((uintptr_t)stage & 3) == 0 && ((uintptr_t)msg & 3) == 0;
+}
+
+bool rs_decode_rows_fused(const ldpc_amd_ctx *ctx, const HostRs &rs, int S, const uint8_t *packets, const uint8_t *stage, const uint8_t *msg)
+{
+    // Where launch_rs_decode_frames streams already (rs_decode_packets_kernel: R <= 32, S a multiple of 256 or a word length from 256
+    // up) the fused form would save only the gather, and loses more than that: RS(255,223), S = 1024, 4096 blocks at 10 % loss, rows
+    // in place 2.27 ms against 1.38 + 0.60 ms of gather (profiles/rs_rows_bench.json).  Those shapes stay composed.
+    const int R = rs.n - rs.k;
+    if (R <= 32 && rs.k <= 256 && S >= 256 && ((S % 256) == 0 || symbol_len_words(S)) && S < (1 << 23) && ctx->knobs.rs_generic == 0) return false;
+    return rs_decode_rows_takes(ctx, rs, S, packets, stage, msg);
+}
+
+int rs_decode_rows_reserve(ldpc_amd_ctx *ctx, const HostRs &rs, int64_t nblocks, size_t *bytes)
+{
+    *bytes = 0;
+    if (nblocks <= 0) return LDPC_AMD_OK;
+    int rc;
+    if ((rc = rsw_table(ctx, "rs_decode_rows"))) return rc;
+    return scratch_reserve(ctx, ctx->rsr_plan, *bytes = rows_layout(rs, nblocks).bytes);
+}
+
+int launch_rs_decode_rows(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks, const PacketRows &rows, int64_t npackets,
+                          int64_t nstage_rows, uint8_t *er_out, uint8_t *msg, int32_t *received, int32_t *status, int *launches)
+{
+    if (launches) *launches = 0;
+    if (nblocks <= 0) return LDPC_AMD_OK;
+    if (!rs_decode_rows_takes(ctx, rs, S, rows.packets, rows.stage, msg) || ((uintptr_t)rows.src & 3) != 0) return kDecodeNotFused;
+    int rc;
+    size_t bytes;
+    if ((rc = rs_decode_rows_reserve(ctx, rs, nblocks, &bytes))) return rc;
+    const RowsLayout l = rows_layout(rs, nblocks);
+    uint8_t *ws = (uint8_t *)ctx->rsr_plan.p;
+    const int n = rs.n, k = rs.k;
+    for (int64_t first = 0; first < nblocks; first += l.chunk) {   // the chunks follow one another on the stream: one scratch
+        const int64_t count = std::min(l.chunk, nblocks - first);
+        RowsPlanArgs p{};
+        p.n = n; p.k = k; p.dstride = l.dstride; p.nblocks = count; p.src = rows.src + first * n; p.npackets = npackets; p.nstage_rows = nstage_rows;
+        p.g = rs.d_g; p.hdr = (uint32_t *)ws; p.rec = (uint32_t *)(ws + l.o_rec); p.tab = ws + l.o_tab;
+        p.er_out = er_out ? er_out + first * n : nullptr; p.received = received ? received + first : nullptr; p.status = status ? status + first : nullptr;
+        hipLaunchKernelGGL(rs_rows_plan_kernel, dim3((unsigned)std::min<int64_t>(count, (int64_t)ctx->sm_count * 8)), dim3(kRowsThreads), 0, ctx->stream, p);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        RowsArgs a{};
+        a.k = k; a.nrec = n; a.S = S; a.nslices = (S + kSlice - 1) / kSlice; a.dstride = l.dstride; a.nblocks = count;
+        a.mul3 = (const uint32_t *)ctx->rsw_tab.p; a.hdr = p.hdr; a.rec = p.rec; a.tab = p.tab; a.packets = rows.packets; a.stage = rows.stage;
+        a.msg = msg + (size_t)first * k * S;
+        // persistent, the encoder's grid: at most five workgroups (twenty wavefronts) per CU, striding over the (block, slice) items
+        const int64_t items = count * a.nslices;
+        const unsigned grid = (unsigned)std::min<int64_t>((items + kWaves - 1) / kWaves, (int64_t)ctx->sm_count * 5);
+        hipLaunchKernelGGL(rs_decode_rows_kernel, dim3(grid), dim3(64 * kWaves), 0, ctx->stream, a);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        if (launches) ++*launches;
+    }
+    return LDPC_AMD_OK;
+}
 
 int launch_rs_encode_packets(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t nblocks, const uint8_t *src, const void *desc, int64_t max_stride,
                              uint8_t *packets)
@@ -171,20 +546,7 @@ int launch_rs_encode_packets(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t
     const int q = std::min(kQMax, R <= 32 ? (R + 3) & ~3 : (R + 7) & ~7);   // instantiated: 4, 8, ... 32, 40, 48, 56, 64
     const int qtot = (R + q - 1) / q * q;
     int rc;
-    if (!ctx->rsw_tab.p) {   // the packed-multiply table, once per context
-        static const std::array<uint32_t, 256 * 8> tab = [] {   // built once for the process, never freed: the copy may read it later
-            std::array<uint32_t, 256 * 8> t{};
-            build_mul3_tables(t.data());
-            return t;
-        }();
-        if ((rc = scratch_reserve(ctx, ctx->rsw_tab, sizeof(tab)))) return rc;
-        if (hipMemcpyAsync(ctx->rsw_tab.p, tab.data(), sizeof(tab), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(ctx->rsw_tab.p);
-            ctx->rsw_tab = Scratch{};
-            return set_error(ctx, LDPC_AMD_EHIP, "rs_encode_packets: the multiply table could not be uploaded");
-        }
-    }
+    if ((rc = rsw_table(ctx, "rs_encode_packets"))) return rc;
     if ((rc = scratch_reserve(ctx, ctx->rsw_coef, (size_t)rs.k * qtot))) return rc;
     hipLaunchKernelGGL(rs_wire_coef_kernel, dim3((unsigned)std::min(64, (rs.k * qtot + 255) / 256)), dim3(256), 0, ctx->stream, (const uint8_t *)rs.d_g,
                        rs.n, rs.k, qtot, (uint8_t *)ctx->rsw_coef.p);
@@ -214,3 +576,39 @@ int launch_rs_encode_packets(ldpc_amd_ctx *ctx, const HostRs &rs, int S, int64_t
 }
 
 }  // namespace ldpc_amd
+
+// ---- the decoder alone (include/ldpc_erasure_amd_rs_rows.h): everything is checked before anything is enqueued ---------------------------
+extern "C" int ldpc_amd_rs_decode_rows_dev(ldpc_amd_ctx *ctx, int rs, int S, int64_t nblocks, const uint32_t *src, const uint8_t *packets,
+                                           int64_t npackets, const uint8_t *stage, int64_t nstage_rows, uint8_t *msg, int32_t *received,
+                                           int32_t *status, uint8_t *erased_out)
+{
+    if (!ctx) return LDPC_AMD_EINVAL;
+    if (rs < 0 || rs >= (int)ctx->rs.size()) return set_error(ctx, LDPC_AMD_ENOCODE, "unknown RS handle %d", rs);
+    const HostRs &r = *ctx->rs[rs];
+    if (nblocks < 0 || npackets < 0 || nstage_rows < 0 || S < 1)
+        return set_error(ctx, LDPC_AMD_EINVAL, "rs_decode_rows: need nblocks, npackets, nstage_rows >= 0 and S >= 1");
+    if (nblocks * r.n >= ((int64_t)1 << 31) || nblocks >= ((int64_t)1 << 31))
+        return set_error(ctx, LDPC_AMD_EINVAL, "rs_decode_rows: nblocks * n must be below 2^31");
+    if (npackets >= ((int64_t)1 << 31) || nstage_rows >= ((int64_t)1 << 31))
+        return set_error(ctx, LDPC_AMD_EINVAL, "rs_decode_rows: a source word names packets and staged rows below 2^31");
+    if (nblocks == 0) return LDPC_AMD_OK;
+    if (npackets == 0) packets = nullptr;
+    if (nstage_rows == 0) stage = nullptr;
+    if (S == 1 || r.n - r.k > kRMax) return set_error(ctx, LDPC_AMD_EUNSUP, "rs_decode_rows: S = 1 and n - k > %d have no decoder on rows in place", kRMax);
+    if (!symbol_len_ok(ctx, S)) return refuse_symbol_len(ctx, S, "S must be a multiple of 16 (got %d)");
+    LDPC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const void *need[] = {src, msg, npackets ? packets : msg, nstage_rows ? stage : msg};
+    const void *opt[] = {received, status, erased_out};
+    bool ok = true;
+    for (const void *p : need) ok = ok && p && is_device_ptr(ctx, p);
+    for (const void *p : opt) ok = ok && (!p || is_device_ptr(ctx, p));
+    if (!ok) return set_error(ctx, LDPC_AMD_EINVAL, "rs_decode_rows: src, packets, stage, msg and the result arrays must be device pointers of device %d", ctx->device);
+    const uintptr_t m0 = (uintptr_t)msg, m1 = m0 + (size_t)nblocks * r.k * S;
+    auto overlaps = [&](const void *p, size_t bytes) { return p && (uintptr_t)p < m1 && m0 < (uintptr_t)p + bytes; };
+    if (overlaps(packets, (size_t)npackets * (S + kHdr)) || overlaps(stage, (size_t)nstage_rows * S) || overlaps(src, (size_t)nblocks * r.n * 4))
+        return set_error(ctx, LDPC_AMD_EINVAL, "rs_decode_rows: msg must not overlap packets, stage or src");
+    if (!rs_decode_rows_takes(ctx, r, S, packets, stage, msg) || ((uintptr_t)src & 3) != 0)
+        return set_error(ctx, LDPC_AMD_EUNSUP, "rs_decode_rows: needs packets 8-byte aligned, stage, msg and src 4-byte aligned, and the knob RX_PKT not 0");
+    const int rc = launch_rs_decode_rows(ctx, r, S, nblocks, PacketRows{src, packets, stage, S + kHdr}, npackets, nstage_rows, erased_out, msg, received, status);
+    return rc == kDecodeNotFused ? set_error(ctx, LDPC_AMD_EUNSUP, "rs_decode_rows: no decoder on rows in place for this call") : rc;
+}

@@ -606,8 +606,10 @@ static int rxw_rs_slots(ldpc_amd_ctx *ctx, const HostRs &r, int S, int T, int64_
 
 extern "C" {
 
-// push_many + rs_decode_frames in one call, composed: (d) gathers the closed blocks chunk by chunk into the context's scratch, the RS
-// decoder follows each chunk; (e) behind the decode, as in decode_many.
+// push_many + rs_decode_frames in one call.  FUSED where the RS decoder on rows in place applies (rs_decode_rows_fused): (d) shrinks to
+// rxw_sources, which also writes the flags, and the decoder follows the words into the packets and the W planes, one `stage` base.
+// Else COMPOSED: (d) gathers the closed blocks chunk by chunk into the context's scratch, the RS decoder follows each chunk.  (e) behind
+// the decode in both forms, as in decode_many.
 int ldpc_amd_fec_rxw_dev_rs_decode_many(ldpc_amd_fec_rxw_dev *rx, int rs, const uint8_t *packets, int64_t npackets, uint8_t *msg,
                                         int32_t *received, int32_t *status, uint8_t *erased_batch, int *blocks, int max_blocks,
                                         int64_t *consumed)
@@ -624,27 +626,48 @@ int ldpc_amd_fec_rxw_dev_rs_decode_many(ldpc_amd_fec_rxw_dev *rx, int rs, const 
     if (npackets == 0) return 0;
     if (!packets || !is_device_ptr(ctx, packets))
         return set_error(ctx, LDPC_AMD_EINVAL, "fec_rxw_dev_rs_decode_many: packets must be a device pointer of device %d", ctx->device);
-    const int S = rx->S;
-    const int64_t chunk = rx_chunk(max_blocks, (size_t)rx->n * S);
+    const int n = rx->n, S = rx->S;
+    const bool fused = rs_decode_rows_fused(ctx, *r, S, packets, rx->stage_sym, msg);
+    const int64_t chunk = rx_chunk(max_blocks, (size_t)n * S);
 
     RxwPlan pl;
     if ((rc = rxw_plan(rx, "fec_rxw_dev_rs_decode_many", packets, npackets, max_blocks, pl))) return rc;
     const int closes = pl.closes;
     size_t scratch = 0;
-    if ((rc = rxw_rs_reserve(ctx, *r, S, closes, chunk, erased_batch == nullptr, &scratch))) return rc;
+    if (fused) {   // the flags unless the caller takes them, the source words, the decoder's tables
+        size_t tables = 0;
+        if (closes > 0 && ((!erased_batch && (rc = scratch_reserve(ctx, ctx->rx_er, (size_t)closes * n))) ||
+                           (rc = scratch_reserve(ctx, ctx->rx_src, sizeof(uint32_t) * (size_t)closes * n)) ||
+                           (rc = rs_decode_rows_reserve(ctx, *r, closes, &tables))))
+            return rc;
+        scratch = closes > 0 ? sizeof(uint32_t) * (size_t)closes * n + tables : 0;
+    } else if ((rc = rxw_rs_reserve(ctx, *r, S, closes, chunk, erased_batch == nullptr, &scratch))) {
+        return rc;
+    }
     if ((rc = rxw_winners_launch(rx, pl))) return rc;
     uint8_t *er = erased_batch ? erased_batch : (uint8_t *)ctx->rx_er.p;
-    auto gather = [&](int first, int count, uint8_t *sym, uint8_t *e) { return rxw_move_launch<true>(rx, pl, packets, first, count, sym, e); };
     int launches = 0;
-    if ((rc = rxw_rs_slots(ctx, *r, S, closes, chunk, er, msg, received, status, gather, &launches))) return rc;
+    if (fused && closes > 0) {
+        uint32_t *src = (uint32_t *)ctx->rx_src.p;
+        hipLaunchKernelGGL(rxw_sources, dim3(grid_for((int64_t)closes * n)), dim3(kThreads), 0, ctx->stream, (const int32_t *)rx->win.p,
+                           rx->stage_er, n, rx->W, rx->head, closes, src, er);
+        LDPC_HIP_TRY(ctx, hipGetLastError());
+        // (every word rxw_sources writes lies inside the call's packets or the W planes: the decoder's own flags would be these)
+        if ((rc = launch_rs_decode_rows(ctx, *r, S, closes, PacketRows{src, packets, rx->stage_sym, S + kHdr}, npackets, (int64_t)rx->W * n, nullptr,
+                                        msg, received, status, &launches)))
+            return rc == kDecodeNotFused ? set_error(ctx, LDPC_AMD_EHIP, "fec_rxw_dev_rs_decode_many: the row decoder refused a call it had accepted (internal error)") : rc;
+    } else if (!fused) {
+        auto gather = [&](int first, int count, uint8_t *sym, uint8_t *e) { return rxw_move_launch<true>(rx, pl, packets, first, count, sym, e); };
+        if ((rc = rxw_rs_slots(ctx, *r, S, closes, chunk, er, msg, received, status, gather, &launches))) return rc;
+    }
     if ((rc = rxw_move_launch<false>(rx, pl, packets, 0, 0, nullptr, nullptr))) return rc;   // (e)
     rxw_commit(rx, pl, blocks, consumed);
-    ctx->rsrx_info[0] = closes; ctx->rsrx_info[1] = launches; ctx->rsrx_info[2] = (int64_t)scratch; ctx->rsrx_info[3] = 0;
+    ctx->rsrx_info[0] = closes; ctx->rsrx_info[1] = launches; ctx->rsrx_info[2] = (int64_t)scratch; ctx->rsrx_info[3] = fused ? 1 : 2;
     return closes;
 }
 
-// flush + RS decode: the blocks lie complete in their planes, a chunk of them goes to the scratch (its planes reset by the same launch)
-// and through the RS decoder
+// flush + RS decode, never fused: the blocks lie complete in their planes, a chunk of them goes to the scratch (its planes reset by the
+// same launch) and through the RS decoder
 int ldpc_amd_fec_rxw_dev_rs_decode_flush(ldpc_amd_fec_rxw_dev *rx, int rs, uint8_t *msg, int32_t *received, int32_t *status,
                                          uint8_t *erased_batch, int *blocks)
 {
@@ -664,7 +687,7 @@ int ldpc_amd_fec_rxw_dev_rs_decode_flush(ldpc_amd_fec_rxw_dev *rx, int rs, uint8
     int launches = 0;
     if ((rc = rxw_rs_slots(ctx, *r, S, count, chunk, er, msg, received, status, gather, &launches))) return rc;
     rxw_mirror_flush(rxw_mirror(rx), count, blocks);
-    ctx->rsrx_info[0] = count; ctx->rsrx_info[1] = launches; ctx->rsrx_info[2] = (int64_t)scratch; ctx->rsrx_info[3] = 0;
+    ctx->rsrx_info[0] = count; ctx->rsrx_info[1] = launches; ctx->rsrx_info[2] = (int64_t)scratch; ctx->rsrx_info[3] = 2;
     return count;
 }
 
